@@ -1,12 +1,14 @@
 #!/usr/bin/env python3
-"""bench.py -- NW-head hot path on MI355X.  Contract: see the task statement / DESIGN.md.
+"""bench.py -- NW-head hot path on MI355X.  See DESIGN.md section 6.
 
 One "step" = one query batch (B=256, d=512) predicted against the whole support bank
 ('full' inference, nwhead/nw.py:127-160 with mode='full'): scores -> softmax -> label aggregation ->
 log.  Workload "K3": bank N=50000, d=512, C=200 (BASELINE.json configs[2]); with --gpus G the bank is
 sharded G ways (strong scaling), partials are exchanged with one RCCL all-gather per bucket of steps.
-The north-star shape T (B=256, N=10000, d=512) is measured in the same run on rank 0 and reported in
-the same JSON line under "north_star_T".
+A plain run times exactly --steps steps of K3 and prints the headline JSON line; --dump-outputs DIR writes
+the last timed step's (B, C) log-probabilities to DIR/log_probs.npy.  --full adds, in the same line, the
+single-call latency, the roofline block, the north-star shape T (B=256, N=10000, d=512, "north_star_T")
+and the other workloads, measured on rank 0, and the CPU baseline.
 """
 import argparse
 import json
@@ -451,7 +453,7 @@ def cpu_baseline(B_sample, N, d, C, budget_s=20.0):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=2048)
+    ap.add_argument("--steps", type=int, default=2048, help="timed steps (query batches of --batch queries), exactly")
     ap.add_argument("--warmup", type=int, default=256)
     ap.add_argument("--batch", type=int, default=256)
     ap.add_argument("--bank", type=int, default=50000)
@@ -465,19 +467,18 @@ def main():
                          "launch is 6.1 tiles per CU, i.e. 7 rounds for the work of 6.1")
     ap.add_argument("--min-warmup-ms", type=float, default=40.0,
                     help="the untimed warm-up lasts at least this long (device time): post-idle clock ramp")
-    ap.add_argument("--min-timed-ms", type=float, default=100.0, help="the timed region lasts at least this long")
-    ap.add_argument("--min-launches", type=int, default=100, help="... and at least this many coalesced launches")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--skip-extras", action="store_true", help="only the timed workload (for profiling)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: single-call latency, roofline block, the other "
+                         "workloads and the CPU baseline")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave out the CPU baseline")
+    ap.add_argument("--skip-extras", action="store_true",
+                    help="with --full: leave out the workloads other than K3 (for profiling)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write what the last timed step returned, its (B, C) log-probabilities, to DIR/log_probs.npy")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     args.bucket = max(1, args.bucket)
-    # The timed region is made of WHOLE launches and of at least four of them: --steps is rounded up to a multiple
-    # of the bucket (a ragged last bucket would be a launch shape of its own, and two launches are not a
-    # measurement); `steps` in the JSON line is what was timed, `steps_requested` what was asked for.
-    steps_requested = args.steps
-    args.steps = max(4 * args.bucket, -(-args.steps // args.bucket) * args.bucket)
-    # ... --steps is a MINIMUM: the timed region also lasts at least --min-timed-ms and --min-launches coalesced launches
-    # (fixed below, once a step's duration is known); `steps` in the line is what was timed
     # Library banners (RCCL prints its version block to stdout when the first communicator comes up)
     # must not land next to the JSON line: stdout is pointed at stderr until the line is printed.
     sys.stdout.flush()
@@ -579,15 +580,7 @@ def main():
         run(extra)
         warm_steps += 8 * args.bucket + extra
     warm_steps += args.bucket   # (the bucket in front of the collection)
-    # the timed region: at least --steps steps, --min-launches whole launches and --min-timed-ms of device time
-    want = max(args.steps, args.min_launches * args.bucket, int(args.min_timed_ms / per_step_ms) + 1)
-    want = -(-want // args.bucket) * args.bucket
-    if use_dist:                                       # one count for all ranks
-        cnt = torch.tensor([want], dtype=torch.int64, device=dev)
-        dist.all_reduce(cnt, op=dist.ReduceOp.MAX)
-        want = int(cnt.item())
-    args.steps = want
-    # ... and one untimed rehearsal of the timed call itself (same number of steps, same chunking): whatever the
+    # one untimed rehearsal of the timed call itself (same number of steps, same chunking): whatever the
     # caching allocator or the exchange ring still has to grow for THIS pattern grows here (measured: a 30 ms stall
     # inside an 8.7 ms timed region when the first 32-bucket chunk of a process was the timed one)
     if args.steps * per_step_ms < 2000.0:
@@ -595,17 +588,36 @@ def main():
         warm_steps += args.steps
     barrier()
     t0 = time.perf_counter()
-    run(args.steps)
+    out = run(args.steps)
     barrier()
     dt = time.perf_counter() - t0
     if use_dist:
         tt = torch.tensor([dt], dtype=torch.float64, device=dev)
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         dt = tt.item()
+    if args.dump_outputs and rank == 0:       # every rank holds the same merged output
+        import numpy as np
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, "log_probs.npy"), out.detach().to(torch.float32).cpu().numpy())
 
-    lat_us = measure_latency(bank, qs[0])     # every rank: the sharded call has a collective inside
+    fast = bank.cache is not None and bank.cache.split is not None
     line = None
     if rank == 0:
+        line = {"metric": "query-predictions/sec", "value": args.steps * B / dt, "unit": "query-predictions/s",
+                "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+                "rccl_ranks": world if backend_used == "nccl" else 0, "dist_backend": backend_used,
+                "class_window": bank.CL, "persistent_wgs": bank.persistent_wgs,
+                "warmup_steps_run": warm_steps,
+                "ms_per_step": dt / args.steps * 1e3, "higher_is_better": True, "scaling": "strong",
+                "vs_baseline": None, "dtype": "f32", "operands": "split-fp16x2 (fp32 accumulate)" if fast else "f32",
+                "data": "synthetic",
+                "config": {"workload": f"K3 predict('full'): B={B} queries/step vs bank N={N} d={d} C={C}, "
+                                       f"bank sharded {world}-way, {args.bucket} query batches coalesced per launch"
+                                       + (" and per RCCL all-gather" if world > 1 else ""),
+                           "B": B, "N_support": N, "d": d, "C": C, "parallelism": f"support-shard x{world}"}}
+    if args.full:
+        lat_us = measure_latency(bank, qs[0])     # every rank: the sharded call has a collective inside
+    if rank == 0 and args.full:
         n_shard = hi - lo
         # one launch = one forward over this rank's shard = nw_fused_kernel (+ the small merge kernel)
         # one launch = the partial forward of one bucket (bucket*B queries) over this rank's shard:
@@ -626,7 +638,6 @@ def main():
         lib.nw_debug_tile_timing(0)
         t_sc = tot.value / max(cnt.value, 1) * 1e-6
         flops = 2.0 * Bl * n_shard * d
-        fast = bank.cache is not None and bank.cache.split is not None
         peak = PEAK_SPLIT_F16_TFLOPS if fast else PEAK_F32_MFMA_TFLOPS
         persistent = fast and Bl * n_shard >= 64 * 128 * 1024
         kname = "nw_fused_f16p_kernel" if persistent else "nw_fused_kernel"
@@ -664,22 +675,10 @@ def main():
                 "queries_per_launch": Bl,
                 "alg_bytes_per_launch": alg_bytes(Bl, n_shard, d, C),
                 "alg_GBps": alg_bytes(Bl, n_shard, d, C) / t_all / 1e9}
-        line = {"metric": "query-predictions/sec", "value": args.steps * B / dt, "unit": "query-predictions/s",
-                "n_gpus": world, "steps": args.steps, "steps_requested": steps_requested, "warmup": args.warmup,
-                "rccl_ranks": world if backend_used == "nccl" else 0, "dist_backend": backend_used,
-                "class_window": bank.CL, "persistent_wgs": bank.persistent_wgs,
-                "warmup_steps_run": warm_steps,
-                "ms_per_step": dt / args.steps * 1e3, "higher_is_better": True, "scaling": "strong",
-                "vs_baseline": None, "dtype": "f32", "operands": "split-fp16x2 (fp32 accumulate)" if fast else "f32",
-                "data": "synthetic",
-                "latency_us_single_call_B256": lat_us,
-                "latency_note": "one uncoalesced predict('full') call of B queries against this rank's shard (plus the "
-                                "exchange when sharded); a `step` of the timed region is 1/bucket of a coalesced launch",
-                "config": {"workload": f"K3 predict('full'): B={B} queries/step vs bank N={N} d={d} C={C}, "
-                                       f"bank sharded {world}-way, {args.bucket} query batches coalesced per launch"
-                                       + (" and per RCCL all-gather" if world > 1 else ""),
-                           "B": B, "N_support": N, "d": d, "C": C, "parallelism": f"support-shard x{world}"},
-                "roofline": roof}
+        line.update({"latency_us_single_call_B256": lat_us,
+                     "latency_note": "one uncoalesced predict('full') call of B queries against this rank's shard (plus the "
+                                     "exchange when sharded); a `step` of the timed region is 1/bucket of a coalesced launch",
+                     "roofline": roof})
         if world == 1 and not args.skip_extras:
             line["north_star_T"] = T_ = measure_shape(256, 10000, 512, 200, dev, 100)
             # the north-star shape as a roofline block of its own: the tile kernel at T

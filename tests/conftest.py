@@ -1,6 +1,15 @@
 import os
 import sys
 
+# CPU numerics that do not depend on the host, set before torch loads (spawned workers inherit them): the oracle tests
+# hold torch's fp32 CPU results to the reference's (tests/golden/, generated under the same settings by make_goldens.py)
+# at 1e-6, and MKL's sgemm and ATen's vector kernels round differently per instruction set (an Intel host vs an AMD one,
+# AVX-512 vs AVX2).  One MKL thread (torch's CPU pool follows it): MKL's COMPATIBLE branch splits a product by thread
+# count, so with several threads the same rows computed in differently shaped calls differ in their last bits.
+os.environ["MKL_CBWR"] = "COMPATIBLE"
+os.environ["MKL_NUM_THREADS"] = "1"
+os.environ["ATEN_CPU_CAPABILITY"] = "avx2"
+
 import numpy as np
 import pytest
 import torch

@@ -18,6 +18,10 @@ import sys
 import types
 
 sys.dont_write_bytecode = True
+# the host-independent CPU numerics tests/conftest.py runs the suite under (before torch loads)
+os.environ["MKL_CBWR"] = "COMPATIBLE"
+os.environ["MKL_NUM_THREADS"] = "1"
+os.environ["ATEN_CPU_CAPABILITY"] = "avx2"
 REF = os.environ.get("NWHEAD_REFERENCE", "/root/reference")
 OUT = os.path.dirname(os.path.abspath(__file__))
 
@@ -349,7 +353,6 @@ def g9():
 
 
 if __name__ == "__main__":
-    torch.set_num_threads(4)
     only = sys.argv[1:]
     for fn in (g1, g2, g3, g4, g5, g6, g6b, g7, g8, g9):
         if not only or fn.__name__ in only:

@@ -5,7 +5,7 @@ old=$1; n=${2:-3}
 for i in $(seq $n); do
   for which in old new; do
     if [ $which = old ]; then export NW_HIP_LIB=$old; else unset NW_HIP_LIB; fi
-    timeout -k 10 200 python bench.py --no-cpu-baseline --skip-extras 2>/dev/null > /tmp/ab.json || exit 1
+    timeout -k 10 200 python bench.py --full --steps 2600 --no-cpu-baseline --skip-extras 2>/dev/null > /tmp/ab.json || exit 1
     python - <<PY
 import json
 d=json.load(open("/tmp/ab.json")); r=d["roofline"]

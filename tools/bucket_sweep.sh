@@ -3,7 +3,7 @@
 for b in $1; do
   for nc in "50000 200" "25000 100" "12500 50" "6250 25"; do
     set -- $nc
-    timeout -k 10 200 python bench.py --bucket $b --bank $1 --classes $2 --steps 832 --warmup 128 --no-cpu-baseline --skip-extras 2>/dev/null > /tmp/bs.json
+    timeout -k 10 200 python bench.py --bucket $b --bank $1 --classes $2 --steps $((100 * b)) --warmup 128 --full --no-cpu-baseline --skip-extras 2>/dev/null > /tmp/bs.json
     python - <<PY
 import json
 d=json.load(open("/tmp/bs.json")); r=d["roofline"]
