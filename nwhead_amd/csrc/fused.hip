@@ -85,7 +85,7 @@ int tile_timer_read(double* total_us, int64_t* launches) {
 
 int persistent_variant() {
     const int x = knob(KNOB_PVAR);
-    return (x >= 0 && x <= 2) ? x : -1;  // -1: chosen per launch
+    return (x >= 0 && x <= 3) ? x : -1;  // -1: chosen per launch
 }
 
 int persistent_qgroup() {

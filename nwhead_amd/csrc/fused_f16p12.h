@@ -1,0 +1,507 @@
+// fused_f16p12.h -- persistent split-fp16 fused forward, 256-query tiles: EIGHT multiplying waves and FOUR loader waves
+// (gfx950 / MI355X only).
+//
+// nw_fused_f16p_kernel<8, KIND, false, 2> (fused_f16p.h) with the tile twice as tall and the multiplying waves doubled:
+//   * workgroup tile 256 queries x 128 supports, 768 threads: waves 0-7 multiply 32 queries x 128 supports each (the
+//     consumer wave of fused_f16p.h), waves 8-11 fill LDS.  Two multiplying waves per SIMD cover each other's stalls, the
+//     epilogue issues from two waves per SIMD, there is one barrier per 96 MFMAs of a SIMD instead of per 48, and the LDS
+//     fill moves 25 % fewer bytes per flop.  No multiplying wave issues an LDS-DMA;
+//   * three waves per SIMD leave 168 registers per wave: 64 accumulators, 32 for the query fragments (double-buffered:
+//     this stage's and the next one's) and 32 for the support fragments, a rolling window of two pairs of 16-row blocks.
+//     The last pair of a stage is multiplied BEHIND the stage's barrier, under the first LDS reads of the next stage, so
+//     the matrix pipe has work while every wave of the workgroup waits for its first fragments;
+//   * 48 KB stages in a ring of three: during stage k the consumers read buffer k only, stage k+1 has landed at barrier
+//     k-1, and the loaders issue stage k+2 right behind barrier k-1 into the buffer that barrier released (every read of
+//     it was waited for in front of the barrier), waiting for all but the youngest stage as in fused_f16p.h;
+//   * the same arithmetic, element for element: per accumulator the products al x bh, ah x bl, ah x bh of a stage in this
+//     order, k chunks rotated by the support tile, support tiles of 128 rows, workspace layout and run tables unchanged.
+// Requires d / 32 >= 3 (the header of a tile rides with its first stage, two stages ahead).
+#pragma once
+#include "fused_f16p.h"
+
+namespace nw {
+namespace {
+
+struct P12 {
+    static constexpr int RS = 8, QB = 2, NCW = 8, NLW = 4;
+    static constexpr int THREADS = 64 * (NCW + NLW);       // 768
+    static constexpr int BS = 16 * RS;                     // 128 supports
+    static constexpr int BQP = 16 * QB * NCW;              // 256 queries
+    static constexpr int ROWS = BQP + BS;                  // rows of a stage image
+    static constexpr int TILE_F4 = ROWS * ROW_F4;
+    static constexpr int STAGE_BYTES = TILE_F4 * 16;       // 48 KB
+    static constexpr int NB = 3;                           // ring depth
+    static constexpr int AHEAD = NB - 1;                   // stages in flight per loader wave
+    static constexpr int NT = ROWS / 8;                    // 1 KB pieces per stage
+    static constexpr int NI = NT / NLW;                    // ... per loader wave
+    static constexpr int NQI = BQP / 8 / NLW;              // of them query pieces (the first ones)
+    static constexpr int N64 = BS / 64;                    // 64-entry pieces per support-side header array
+    static constexpr int NH = BS;                          // entries per support-side header array
+    static constexpr int HDR_F = 3 * NH + 2 * BQP;         // sn2 | ssc | runid | qn2[BQP] | qsc[BQP]
+    static constexpr int NP = 3 * N64 + 2 * (BQP / 64);    // header pieces (256 B each)
+    static constexpr int HPW = (NP + NLW - 1) / NLW;       // ... per loader wave
+    static constexpr int NHB = 3;                          // header buffers (tile index mod 3, as in fused_f16p.h)
+    static constexpr size_t HDR_BYTES = (size_t)NHB * HDR_F * 4;
+    static constexpr size_t LDS_BYTES = HDR_BYTES + (size_t)NB * STAGE_BYTES;
+    static_assert(NT % NLW == 0 && (BQP / 8) % NLW == 0, "even split of the pieces");
+    static_assert(HDR_BYTES % 16 == 0 && LDS_BYTES <= 160 * 1024, "LDS of one CU");
+    static_assert(NI + HPW < 64, "vmcnt is a 6-bit field");
+};
+
+// epilogue_p<8, KIND, 2, 8> (fused_f16p.h) for a wave that has 168 registers: the same operations on the same values, but
+// the support factors are made per 16-row block and the scores of both query blocks are formed while the accumulators
+// die, so that never more than 64 accumulator / score registers and one block's factors are live together.
+template <int KIND>
+__device__ __forceinline__ void epilogue_p12(f32x4 (&acc)[P12::QB][P12::RS], const float* hdr, int nrun, int2 bnd,
+                                             float scale, float* __restrict__ ws_m,
+                                             float* __restrict__ ws_den, float* __restrict__ ws_num, int B, int N,
+                                             int q0, int s0, int st, int wave, int lane
+#ifdef NW_DIAG_FUSED
+                                             , unsigned long long (&diag_)[8], unsigned long long& last_
+#endif
+                                             ) {
+    using P = P12;
+    constexpr int RS = P::RS, QB = P::QB, BS = P::BS;
+    constexpr bool NEED_NORM = (KIND != NW_SCORE_DOT);
+    typedef float f32x2 __attribute__((ext_vector_type(2)));
+    const float* sn2 = hdr;
+    const float* ssc = hdr + P::NH;
+    const int* runid = reinterpret_cast<const int*>(hdr + 2 * P::NH);
+    const float* qn2 = hdr + 3 * P::NH;
+    const float* qsc_s = qn2 + P::BQP;
+    const int i = lane & 15, g = lane >> 4;
+    using SF = ScoreFactors<KIND>;
+    float Cq[QB], Bq[QB];
+#pragma unroll
+    for (int j = 0; j < QB; ++j) {
+        const int qrow = 16 * (QB * wave + j) + i;
+        SF::query(NEED_NORM ? qn2[qrow] : 0.f, qsc_s[qrow], scale, Cq[j], Bq[j]);
+    }
+    NW_PSTAMP(1);
+    float sc[QB][RS][4];
+#pragma unroll
+    for (int r = 0; r < RS; ++r) {
+        const float4 n4 = NEED_NORM ? *reinterpret_cast<const float4*>(sn2 + 16 * r + 4 * g) : make_float4(0.f, 0.f, 0.f, 0.f);
+        const float4 s4 = *reinterpret_cast<const float4*>(ssc + 16 * r + 4 * g);
+        float4 K4, B4;
+        SF::support(n4.x, s4.x, K4.x, B4.x);
+        SF::support(n4.y, s4.y, K4.y, B4.y);
+        SF::support(n4.z, s4.z, K4.z, B4.z);
+        SF::support(n4.w, s4.w, K4.w, B4.w);
+        // Bit for bit as epilogue_p is compiled: there hipcc contracts Base's last product with "+ Bq" into one fma for the
+        // wave's FIRST query block (the factors are made in its basic block) and adds the rounded product for the second one
+        float4 B4r = B4;
+        asm volatile("" : "+v"(B4r.x), "+v"(B4r.y), "+v"(B4r.z), "+v"(B4r.w));
+#pragma unroll
+        for (int j = 0; j < QB; ++j) {  // x = acc * (K * Cq) + (Base + Bq): three packed fp32 ops per pair
+            const f32x2 cq = {Cq[j], Cq[j]}, bq = {Bq[j], Bq[j]};
+            const float4 Bj = (j == 0) ? B4 : B4r;
+            const f32x2 d01 = __builtin_elementwise_fma(f32x2{acc[j][r][0], acc[j][r][1]}, f32x2{K4.x, K4.y} * cq,
+                                                        f32x2{Bj.x, Bj.y} + bq);
+            const f32x2 d23 = __builtin_elementwise_fma(f32x2{acc[j][r][2], acc[j][r][3]}, f32x2{K4.z, K4.w} * cq,
+                                                        f32x2{Bj.z, Bj.w} + bq);
+            // distance kernels: sc = +distance (u = -sc), extremum = minimum; the others: sc = u, maximum
+            sc[j][r][0] = SF::finish_abs(d01.x);
+            sc[j][r][1] = SF::finish_abs(d01.y);
+            sc[j][r][2] = SF::finish_abs(d23.x);
+            sc[j][r][3] = SF::finish_abs(d23.y);
+            // made HERE, in the place of the accumulators they are made of (hipcc otherwise sinks the second query block's
+            // scores behind the first one's run sums and keeps its accumulators and every block's factors until then)
+            asm volatile("" : "+v"(sc[j][r][0]), "+v"(sc[j][r][1]), "+v"(sc[j][r][2]), "+v"(sc[j][r][3]));
+        }
+        __builtin_amdgcn_sched_barrier(0);
+    }
+    NW_PSTAMP(2);
+#pragma unroll
+    for (int j = 0; j < QB; ++j) {
+        const int qrow = 16 * (QB * wave + j) + i;
+        const int b = q0 + qrow;
+        float (&sj)[RS][4] = sc[j];
+        constexpr float WORST = SF::DIST ? INFINITY : -INFINITY;
+        if (s0 + BS > N) {  // only the last support tile has rows past the bank
+            const int lim = N - s0 - 4 * g;  // rows of the bank left from this lane group's first row on
+#pragma unroll
+            for (int r = 0; r < RS; ++r)
+#pragma unroll
+                for (int e = 0; e < 4; ++e)
+                    if (16 * r + e >= lim) sj[r][e] = WORST;
+        }
+        // tile-local extremum: independent chains, then the wave's four lane groups
+        auto best = [](float a, float b) { return SF::DIST ? fminf(a, b) : fmaxf(a, b); };
+        float mx[4] = {WORST, WORST, WORST, WORST};
+#pragma unroll
+        for (int r = 0; r < RS; ++r) mx[r & 3] = best(mx[r & 3], best(best(sj[r][0], sj[r][1]), best(sj[r][2], sj[r][3])));
+        float ext = best(best(mx[0], mx[1]), best(mx[2], mx[3]));
+        ext = SF::DIST ? group4_min(ext) : group4_max(ext);
+        const float mloc = SF::DIST ? -ext : ext;  // the tile maximum of u
+#pragma unroll
+        for (int r = 0; r < RS; ++r)
+#pragma unroll
+            for (int e = 0; e < 4; ++e)  // 2^(u - max); 2^-inf = 0 for padded rows
+                sj[r][e] = __builtin_amdgcn_exp2f(SF::DIST ? ext - sj[r][e] : sj[r][e] - ext);
+        NW_PSTAMP(3);
+        // ---- run sums: as epilogue_p (whole 16-row blocks with a scalar 0 / 1 weight, the blocks a run boundary cuts
+        // per element; more than three runs through the indicator MFMAs)
+        float dloc;
+        auto red4 = [](float x) { return group4_sum(x); };
+        if (nrun <= 3) {
+            float S0[2] = {0.f, 0.f}, S1[2] = {0.f, 0.f}, S2[2] = {0.f, 0.f};
+            if (nrun == 1) {
+#pragma unroll
+                for (int r = 0; r < RS; ++r) {
+                    S0[r & 1] += (sj[r][0] + sj[r][1]) + (sj[r][2] + sj[r][3]);
+                }
+            } else {
+                const int b1 = bnd.x, b2 = (nrun == 3) ? bnd.y : BS;
+                const float L1 = (float)(b1 - 4 * g);
+                const float M2 = 1.f - (float)(b2 - 4 * g);
+#pragma unroll
+                for (int r = 0; r < RS; ++r) {
+                    const int lo = 16 * r, hi = 16 * r + 16;
+                    const bool in0 = hi <= b1, in2 = lo >= b2, in1 = lo >= b1 && hi <= b2;
+                    const float quad = (sj[r][0] + sj[r][1]) + (sj[r][2] + sj[r][3]);
+                    S0[r & 1] = __builtin_fmaf(in0 ? 1.f : 0.f, quad, S0[r & 1]);
+                    S1[r & 1] = __builtin_fmaf(in1 ? 1.f : 0.f, quad, S1[r & 1]);
+                    S2[r & 1] = __builtin_fmaf(in2 ? 1.f : 0.f, quad, S2[r & 1]);
+                    if (!(in0 || in1 || in2)) {
+#pragma unroll
+                        for (int e = 0; e < 4; ++e) {
+                            const float c = (float)(16 * r + e), ev = sj[r][e];
+                            const float w1 = __builtin_amdgcn_fmed3f(L1 - c, 0.f, 1.f);  // [t <  b1]
+                            const float u2 = __builtin_amdgcn_fmed3f(c + M2, 0.f, 1.f);  // [t >= b2]
+                            S0[e & 1] = __builtin_fmaf(w1, ev, S0[e & 1]);
+                            S2[e & 1] = __builtin_fmaf(u2, ev, S2[e & 1]);
+                            S1[e & 1] = __builtin_fmaf((1.f - w1) - u2, ev, S1[e & 1]);  // exact 0 / 1
+                        }
+                    }
+                }
+            }
+            const float s0v = red4(S0[0] + S0[1]);
+            float s1v = 0.f, s2v = 0.f;
+            if (nrun >= 2) s1v = red4(S1[0] + S1[1]);
+            if (nrun == 3) s2v = red4(S2[0] + S2[1]);
+            dloc = (s0v + s1v) + s2v;
+            if (g == 0 && b < B) {
+                ws_num[((size_t)st * BS) * B + b] = s0v;
+                if (nrun >= 2) ws_num[((size_t)st * BS + 1) * B + b] = s1v;
+                if (nrun == 3) ws_num[((size_t)st * BS + 2) * B + b] = s2v;
+            }
+        } else {
+            float dl[4] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+            for (int r = 0; r < RS; ++r) dl[r & 3] += (sj[r][0] + sj[r][1]) + (sj[r][2] + sj[r][3]);
+            dloc = red4((dl[0] + dl[1]) + (dl[2] + dl[3]));
+            // run sums on the matrix cores: indicator (A operand) x E (already in B-operand layout)
+            for (int run_base = 0; run_base < nrun; run_base += 16) {
+                f32x4 Pm = {0.f, 0.f, 0.f, 0.f};
+                const int want = run_base + i;
+#pragma unroll
+                for (int r = 0; r < RS; ++r) {
+                    const int4 rid = *reinterpret_cast<const int4*>(runid + 16 * r + 4 * g);
+                    Pm = __builtin_amdgcn_mfma_f32_16x16x4f32(rid.x == want ? 1.f : 0.f, sj[r][0], Pm, 0, 0, 0);
+                    Pm = __builtin_amdgcn_mfma_f32_16x16x4f32(rid.y == want ? 1.f : 0.f, sj[r][1], Pm, 0, 0, 0);
+                    Pm = __builtin_amdgcn_mfma_f32_16x16x4f32(rid.z == want ? 1.f : 0.f, sj[r][2], Pm, 0, 0, 0);
+                    Pm = __builtin_amdgcn_mfma_f32_16x16x4f32(rid.w == want ? 1.f : 0.f, sj[r][3], Pm, 0, 0, 0);
+                }
+                if (b < B) {
+#pragma unroll
+                    for (int jj = 0; jj < 4; ++jj) {
+                        const int run = run_base + 4 * g + jj;
+                        if (run < nrun) ws_num[((size_t)st * BS + run) * B + b] = Pm[jj];
+                    }
+                }
+            }
+        }
+        NW_PSTAMP(4);
+        if (g == 0 && b < B) {
+            ws_m[(size_t)st * B + b] = mloc;
+            ws_den[(size_t)st * B + b] = dloc;
+        }
+        NW_PSTAMP(5);
+    }
+}
+
+template <int KIND>
+__global__ __launch_bounds__(P12::THREADS, 3) void nw_fused_f16p_kernel_w12(
+    const float* __restrict__ q, const float* __restrict__ s, const float* __restrict__ s_norm2,
+    const float* __restrict__ s_scale, const float* __restrict__ q_norm2, const float* __restrict__ q_scale,
+    const float* __restrict__ logit_scale, const int* __restrict__ ws_runid, const int* __restrict__ ws_nrun,
+    const int* __restrict__ ws_bnd, float* __restrict__ ws_m, float* __restrict__ ws_den, float* __restrict__ ws_num, int B,
+    int N, int d, int n_stiles, int n_qtiles, int qg) {
+    using P = P12;
+    constexpr int RS = P::RS, QB = P::QB, BS = P::BS, BQP = P::BQP, NI = P::NI, NB = P::NB, NLW = P::NLW;
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    float* hdr0 = reinterpret_cast<float*>(smem);  // NHB header buffers of HDR_F floats, by tile index mod NHB
+    float4* stage = reinterpret_cast<float4*>(smem + P::HDR_BYTES);
+
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int nk = d / BK;
+    // ---- tile order: as nw_fused_f16p_kernel (XCD-local lists, groups of qg query tiles, support-tile major)
+    const int xcd = blockIdx.x & 7, cu = blockIdx.x >> 3, n_cu = gridDim.x >> 3;
+    const int ns_x = n_stiles >> 3;
+    const int n_full = ns_x * n_qtiles;
+    const int rem = n_stiles & 7;
+    const int nq_x = (n_qtiles - xcd + 7) >> 3;
+    const int n_local = n_full + rem * nq_x;
+    const int grp_tiles = qg * ns_x;
+    auto decode = [&](int L, int& qt, int& st) {
+        if (L >= n_full) {
+            const int r = L - n_full, j = r / nq_x;
+            st = 8 * ns_x + j;
+            qt = xcd + 8 * (r - j * nq_x);
+            return;
+        }
+        const int gi_ = L / grp_tiles, r = L - gi_ * grp_tiles;
+        const int g_ = min(qg, n_qtiles - gi_ * qg);
+        const int stl = r / g_;
+        qt = gi_ * qg + (r - stl * g_);
+        st = stl * 8 + xcd;
+    };
+
+    if (wave >= P::NCW) {
+        // ================================ LOADER ================================
+        const int lw = wave - P::NCW;
+        unsigned voff[NI];
+        int iT = cu, ikt = 0, irot = 0, ipar = 0;  // issue cursor: (tile of this XCD's list, stage), header buffer
+        int iq0 = 0, is0 = 0, ist = 0;
+        int gs = 0;                                // ring slot of the stage under the cursor
+        auto set_tile = [&](int T) {
+            int qt, st;
+            decode(T, qt, st);
+            iq0 = qt * BQP;
+            is0 = st * BS;
+            ist = st;
+            irot = st % nk;
+#pragma unroll
+            for (int m = 0; m < NI; ++m) {
+                const int R = 8 * (lw + NLW * m) + (lane >> 3);       // row of the stage image: queries, then supports
+                const int lslot = (lane & 7) ^ ((R >> 1) & 7);        // swizzle on the source side (an LDS-DMA writes linearly)
+                // relative to the tile's first rows (64-bit bases in issue_next): no 4 GB limit on the bank
+                const int rel = (m < P::NQI) ? min(iq0 + R, B - 1) - iq0 : min(is0 + R - BQP, N - 1) - is0;
+                voff[m] = ((unsigned)rel * (unsigned)d + lslot * 4) * 4u;
+            }
+        };
+        auto dma4 = [&](const void* src, float* dst) {  // one dword per lane -> dst[lane]
+            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src,
+                                             (__attribute__((address_space(3))) void*)dst, 4, 0, 0);
+        };
+        // header pieces of the tile under the issue cursor: HPW per loader wave (piece ids past the last one repeat the
+        // last piece: same bytes to the same place)
+        auto issue_header = [&]() {
+            float* h = hdr0 + ipar * P::HDR_F;
+#pragma unroll
+            for (int k = 0; k < P::HPW; ++k) {
+                const int pc = min(lw + NLW * k, P::NP - 1);
+                if (pc < 3 * P::N64) {
+                    const int arr = pc / P::N64, c = pc - arr * P::N64;
+                    const int row = is0 + 64 * c + lane;
+                    float* dst = h + arr * P::NH + 64 * c;
+                    if (arr == 0) dma4(s_norm2 + min(row, N - 1), dst);
+                    else if (arr == 1) dma4(s_scale + min(row, N - 1), dst);
+                    else dma4(ws_runid + (size_t)ist * BS + 64 * c + lane, dst);  // padded by 64 entries
+                } else {
+                    const int qp = pc - 3 * P::N64, arr = qp / (BQP / 64), c = qp - arr * (BQP / 64);  // qn2 pieces, then qsc pieces
+                    const int row = min(iq0 + 64 * c + lane, B - 1);
+                    dma4((arr == 0 ? q_norm2 : q_scale) + row, h + 3 * P::NH + arr * BQP + 64 * c);
+                }
+            }
+        };
+        bool young_hdr = false;  // does the youngest issued stage carry header pieces?
+        auto issue_next = [&]() {  // returns false once every stage of every tile has been issued
+            if (iT >= n_local) return false;
+            int kc = ikt + irot;
+            if (kc >= nk) kc -= nk;
+            float4* buf = stage + gs * P::TILE_F4;
+            const char* qb = reinterpret_cast<const char*>(q + (size_t)iq0 * d) + (size_t)kc * BK * 4;
+            const char* sb = reinterpret_cast<const char*>(s + (size_t)is0 * d) + (size_t)kc * BK * 4;
+#ifndef NW_ABL_NODMA
+#pragma unroll
+            for (int m = 0; m < NI; ++m) {
+                const char* g = ((m < P::NQI) ? qb : sb) + voff[m];
+                __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)g,
+                                                 (__attribute__((address_space(3))) void*)(buf + 64 * (lw + NLW * m)), 16, 0, 0);
+            }
+#else   // timing experiment: nothing is filled (results wrong)
+            (void)qb; (void)sb; (void)buf;
+#endif
+            young_hdr = (ikt == 0);
+            if (young_hdr) issue_header();  // after the stage's own pieces: they are waited for last
+            gs = (gs + 1 == NB) ? 0 : gs + 1;
+            if (++ikt == nk) {
+                ikt = 0;
+                ipar = (ipar + 1 == P::NHB) ? 0 : ipar + 1;
+                iT += n_cu;
+                if (iT < n_local) set_tile(iT);
+            }
+            return true;
+        };
+        auto wait_landed = [&](bool issued) {  // everything but the youngest stage of this wave has landed
+#ifdef NW_ABL_NODMA
+            if (!issued) wait_vmcnt<0>();
+            else if (young_hdr) wait_vmcnt<P::HPW>();
+            else wait_vmcnt<0>();
+#else
+            if (!issued) wait_vmcnt<0>();
+            else if (young_hdr) wait_vmcnt<NI + P::HPW>();
+            else wait_vmcnt<NI>();
+#endif
+        };
+        if (iT < n_local) set_tile(iT);
+        bool more = true;
+#pragma unroll
+        for (int k0 = 0; k0 < P::AHEAD; ++k0) more = issue_next();
+        wait_landed(more);
+        tile_barrier();  // P: all but the youngest issued stage (and the first tile's header) have landed
+        for (int T = cu; T < n_local; T += n_cu) {
+            for (int kt = 0; kt < nk; ++kt) {
+                more = issue_next();
+                wait_landed(more);
+                tile_barrier();
+            }
+        }
+    } else {
+        // ================================ CONSUMER ================================
+        const int i = lane & 15, g = lane >> 4;
+        const int rsw = (i >> 1) & 7;
+        const int sh = g ^ rsw, sl = (4 + g) ^ rsw;  // 16-byte slots of the high / low halves, swizzled by the row
+        const int qoff = (16 * QB * wave + i) * ROW_F4, soff = (BQP + i) * ROW_F4;
+        struct QF { float4 bh[QB], bl[QB]; };   // query fragments of one stage
+        struct SW { float4 al[2], ah[2]; };     // support fragments of one pair of 16-row blocks
+        constexpr int NW_ = RS / 2;             // pairs per stage
+        auto rd_q = [&](QF& f, const float4* S) {
+#pragma unroll
+            for (int j = 0; j < QB; ++j) {
+                f.bh[j] = S[qoff + 16 * j * ROW_F4 + sh];
+                f.bl[j] = S[qoff + 16 * j * ROW_F4 + sl];
+            }
+        };
+        auto rd_w = [&](SW& w, const float4* S, int p) {
+#pragma unroll
+            for (int x = 0; x < 2; ++x) {
+                w.al[x] = S[soff + 16 * (2 * p + x) * ROW_F4 + sl];
+                w.ah[x] = S[soff + 16 * (2 * p + x) * ROW_F4 + sh];
+            }
+        };
+        auto mm = [](const float4& a, const float4& b, f32x4 c) {
+            return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(half8, a), __builtin_bit_cast(half8, b), c, 0, 0, 0);
+        };
+        auto pin = []() { __builtin_amdgcn_sched_barrier(0); };
+        f32x4 acc[QB][RS];
+        // the twelve MFMAs of pair p: four independent accumulator chains, per accumulator al x bh, ah x bl, ah x bh
+        auto mm_w = [&](const SW& w, const QF& f, int p) {
+#pragma unroll
+            for (int x = 0; x < 2; ++x)
+#pragma unroll
+                for (int j = 0; j < QB; ++j) acc[j][2 * p + x] = mm(w.al[x], f.bh[j], acc[j][2 * p + x]);
+#pragma unroll
+            for (int x = 0; x < 2; ++x)
+#pragma unroll
+                for (int j = 0; j < QB; ++j) acc[j][2 * p + x] = mm(w.ah[x], f.bl[j], acc[j][2 * p + x]);
+#pragma unroll
+            for (int x = 0; x < 2; ++x)
+#pragma unroll
+                for (int j = 0; j < QB; ++j) acc[j][2 * p + x] = mm(w.ah[x], f.bh[j], acc[j][2 * p + x]);
+            __builtin_amdgcn_sched_barrier(0);
+        };
+        SW wa, wb;
+        // One stage.  fp = the previous stage's query fragments, fc = this stage's (read here).  The last pair of the
+        // previous stage (in wb) is multiplied under this stage's first reads; this stage's last pair is left in wb.
+        auto run_stage = [&](const QF& fp, QF& fc, int slot, auto first) {
+            constexpr bool FIRST = decltype(first)::value;
+#ifdef NW_ABL_NORD   // timing experiment: no fragment reads in the loop (the fragments of a tile's first stage are reused)
+            constexpr bool RD = FIRST;
+#else
+            constexpr bool RD = true;
+#endif
+            const float4* S = stage + slot * P::TILE_F4;
+            if (RD) { rd_q(fc, S); rd_w(wa, S, 0); }
+            pin();
+            if (!FIRST) mm_w(wb, fp, NW_ - 1);
+#pragma unroll
+            for (int p = 0; p + 1 < NW_; ++p) {
+                if (RD) rd_w((p & 1) ? wa : wb, S, p + 1);
+                pin();
+                mm_w((p & 1) ? wb : wa, fc, p);
+            }
+            static_assert(NW_ % 2 == 0, "the last pair of a stage sits in wb");
+            tile_barrier();  // every read of this stage's buffer has returned: the loaders may refill it
+        };
+        using Yes = std::integral_constant<bool, true>;
+        using No = std::integral_constant<bool, false>;
+
+        // exp(logit_scale) once per launch, in a scalar register (made per tile, hipcc parks the constants of expf in vector
+        // registers across the main loop)
+        float scale = 1.f;
+        if (KIND == NW_SCORE_CLIP)
+            scale = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, expf(*logit_scale))));
+        tile_barrier();  // P
+        int gi = 0;     // ring slot of the current tile's first stage
+        int par = 0;     // header buffer of the current tile
+        auto next_slot = [&]() {
+            const int b = gi;
+            gi = (gi + 1 == NB) ? 0 : gi + 1;
+            return b;
+        };
+#ifdef NW_DIAG_FUSED
+        unsigned long long diag_[8] = {0, 0, 0, 0, 0, 0, 0, 0}, last_ = __builtin_amdgcn_s_memtime();
+        const unsigned long long first_ = last_, first_rt_ = __builtin_amdgcn_s_memrealtime();
+#endif
+        for (int T = cu; T < n_local; T += n_cu) {
+            int qt, st;
+            decode(T, qt, st);
+            const int q0 = qt * BQP, s0 = st * BS;
+            const int nrun = ws_nrun[st];  // wave-uniform: scalar loads, used after the main loop
+            const int2 bnd = *reinterpret_cast<const int2*>(ws_bnd + 2 * (size_t)st);  // first rows of runs 1 and 2
+#pragma unroll
+            for (int j = 0; j < QB; ++j)
+#pragma unroll
+                for (int r = 0; r < RS; ++r) acc[j][r] = f32x4{0.f, 0.f, 0.f, 0.f};
+            QF f0, f1;
+#ifdef NW_ABL_NORD
+            rd_q(f1, stage + gi * P::TILE_F4);
+#endif
+            run_stage(f1, f0, next_slot(), Yes{});
+            int kt = 1;
+            for (; kt + 1 < nk; kt += 2) {
+                run_stage(f0, f1, next_slot(), No{});
+                run_stage(f1, f0, next_slot(), No{});
+            }
+            if (kt < nk) {
+                run_stage(f0, f1, next_slot(), No{});
+                mm_w(wb, f1, NW_ - 1);
+            } else {
+                mm_w(wb, f0, NW_ - 1);
+            }
+            NW_PSTAMP(0);
+#ifndef NW_ABL_NOEPI
+            epilogue_p12<KIND>(acc, hdr0 + par * P::HDR_F, nrun, bnd, scale, ws_m, ws_den, ws_num, B, N, q0, s0, st, wave,
+                               lane
+#ifdef NW_DIAG_FUSED
+                               , diag_, last_
+#endif
+                               );
+#else
+            {  // ablation build: keep every accumulator chain alive
+                f32x4 sum_ = {0.f, 0.f, 0.f, 0.f};
+                for (int j = 0; j < QB; ++j)
+                    for (int r = 0; r < RS; ++r) sum_ += acc[j][r];
+                if (sum_[0] + sum_[1] + sum_[2] + sum_[3] == 12345.678f) ws_m[tid] = sum_[0] + nrun + bnd.x;
+            }
+#endif
+            par = (par + 1 == P::NHB) ? 0 : par + 1;
+            NW_PSTAMP(6);
+        }
+#ifdef NW_DIAG_FUSED
+        if (tid == 0 && blockIdx.x < 1024) {
+            for (int k = 0; k < 7; ++k) nw_diag_p[8 * blockIdx.x + k] = diag_[k];
+            nw_diag_p[8 * blockIdx.x + 7] = last_ - first_;
+            nw_diag_rt[2 * blockIdx.x] = first_rt_;
+            nw_diag_rt[2 * blockIdx.x + 1] = __builtin_amdgcn_s_memrealtime();
+        }
+#endif
+    }
+}
+
+}  // namespace
+}  // namespace nw

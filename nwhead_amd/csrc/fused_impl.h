@@ -33,7 +33,7 @@ bool env_flag(const char* name);
 int tile_timer_start(hipStream_t st);          // diagnostics (nw_debug_tile_timing): -1 when disabled
 void tile_timer_stop(int slot, hipStream_t st);
 int persistent_qgroup();  // query tiles kept L2-resident per XCD by the persistent kernel (NW_QG)
-int persistent_variant();  // NW_PVAR = 0: 64-query tiles, one workgroup per CU; 1: two per CU; 2: 128-query tiles; unset: -1
+int persistent_variant();  // NW_PVAR = 0: 64-query tiles, one workgroup per CU; 1: two per CU; 2: 128-query tiles; 3: 256-query tiles; unset: -1
 
 namespace {
 
@@ -470,9 +470,7 @@ int launch_fused_kind(const float* q, const float* s, const int64_t* sy, const f
 
 }  // namespace nw
 #include "fused_f16p.h"
-#ifdef NW_WITH_P8   // tools/bench_fused.hip only: the eight-multiplying-wave experiment (tools/experiments/fused_f16p8.h)
-#include "fused_f16p8.h"
-#endif
+#include "fused_f16p12.h"
 namespace nw {
 namespace {
 template <int RS, int KIND>
@@ -486,28 +484,30 @@ int launch_f16p(const float* q, const float* s, const int64_t* sy, const float* 
         // of the sharded path (ShardedBank leaves one CU per XCD when there is more than one rank)
         const int wg_cap = fwd_opts().persistent_wgs & ~7;
         if (wg_cap >= 8 && wg_cap < cus) cus = wg_cap;
-        // 0: 64-query tiles, one workgroup per CU; 1: two per CU; 2: 128-query tiles.  Measured at B = 2048,
-        // N = 50000, d = 512 (tools/bench_fused.hip, same device): 387 / 353 / 337 us.  128-query tiles
-        // unless their padding costs more than 15 % of the rows (then two 64-query workgroups per CU).
+        // 0: 64-query tiles, one workgroup per CU; 1: two per CU; 2: 128-query tiles; 3: 256-query tiles on eight
+        // multiplying waves (fused_f16p12.h, tiles of 128 supports only).  Measured at B = 2048, N = 50000, d = 512
+        // (tools/bench_fused.hip, same device): 387 / 353 / 337 us for 0 / 1 / 2.  The tallest tile whose padding costs no
+        // more than 15 % of the rows (else two 64-query workgroups per CU).
         int variant = persistent_variant();
-        if (variant < 0) variant = ((B + 127) / 128 * 128 <= 1.15 * ((B + 63) / 64 * 64)) ? 2 : 1;
+        if (variant < 0) {
+            const double rows64 = 1.15 * ((B + 63) / 64 * 64);
+            variant = (RS == 8 && (B + 255) / 256 * 256 <= rows64) ? 3 : ((B + 127) / 128 * 128 <= rows64) ? 2 : 1;
+        }
         (void)n_qtiles;
-#ifdef NW_WITH_P8   // NW_PVAR=3 in tools/bench_fused.hip: 256-query tiles, eight multiplying waves (measured slower)
         if constexpr (RS == 8) {
             if (variant == 3) {
-                static const bool attr = hipFuncSetAttribute(reinterpret_cast<const void*>(nw_fused_f16p8_kernel<KIND>),
-                                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)P8::LDS_BYTES) == hipSuccess;
+                static const bool attr = hipFuncSetAttribute(reinterpret_cast<const void*>(nw_fused_f16p_kernel_w12<KIND>),
+                                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)P12::LDS_BYTES) == hipSuccess;
                 (void)attr;
                 int qgrp = persistent_qgroup() / 2;   // the same bytes of queries resident per XCD as with 128-query tiles
                 if (qgrp < 1) qgrp = 1;
-                hipLaunchKernelGGL((nw_fused_f16p8_kernel<KIND>), dim3(cus), dim3(TILE_THREADS), P8::LDS_BYTES, st, q, s, s_norm2,
-                                   s_scale, q_norm2, q_scale, ls, ws.runid, ws.nrun, ws.bnd, ws.m, ws.den, ws.num, B, N, d, n_stiles,
-                                   (B + P8::BQP - 1) / P8::BQP, qgrp);
+                hipLaunchKernelGGL((nw_fused_f16p_kernel_w12<KIND>), dim3(cus), dim3(P12::THREADS), P12::LDS_BYTES, st, q, s,
+                                   s_norm2, s_scale, q_norm2, q_scale, ls, ws.runid, ws.nrun, ws.bnd, ws.m, ws.den, ws.num, B, N, d,
+                                   n_stiles, (B + P12::BQP - 1) / P12::BQP, qgrp);
                 NW_CHECK_LAUNCH();
                 return NW_OK;
             }
         }
-#endif
         if (variant > 2) variant = 2;
 #define NW_LAUNCH_P(TWO_, QB_, GRID_, NBUF_)                                                                      \
     do {                                                                                                          \

@@ -1,4 +1,6 @@
 // Diagnostic harness: phase stamps of nw_fused_kernel (build with -DNW_DIAG_FUSED).
+// Persistent kernels (argv[5] = 2): NW_PVAR=0 / 1 / 2 pick the variants of fused_f16p.h, NW_PVAR=3 the 256-query kernel of
+// fused_f16p12.h (-DNW_BENCH_RS=8); both take -DNW_ABL_NODMA / -DNW_ABL_NORD / -DNW_ABL_NOEPI.
 #include <hip/hip_runtime.h>
 #include <cstdio>
 #include <cstdlib>
