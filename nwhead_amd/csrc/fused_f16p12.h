@@ -112,96 +112,131 @@ __device__ __forceinline__ void epilogue_p12(f32x4 (&acc)[P12::QB][P12::RS], con
         __builtin_amdgcn_sched_barrier(0);
     }
     NW_PSTAMP(2);
+    // Both query blocks go through every phase together (extrema, lane-group reductions, exp2, run sums, reductions): the
+    // swaps of one block lie under the other's hazard padding.  Each value's own operation order is that of epilogue_p.
+    constexpr float WORST = SF::DIST ? INFINITY : -INFINITY;
+    if (s0 + BS > N) {  // only the last support tile has rows past the bank
+        const int lim = N - s0 - 4 * g;  // rows of the bank left from this lane group's first row on
 #pragma unroll
-    for (int j = 0; j < QB; ++j) {
-        const int qrow = 16 * (QB * wave + j) + i;
-        const int b = q0 + qrow;
-        float (&sj)[RS][4] = sc[j];
-        constexpr float WORST = SF::DIST ? INFINITY : -INFINITY;
-        if (s0 + BS > N) {  // only the last support tile has rows past the bank
-            const int lim = N - s0 - 4 * g;  // rows of the bank left from this lane group's first row on
+        for (int j = 0; j < QB; ++j)
 #pragma unroll
             for (int r = 0; r < RS; ++r)
 #pragma unroll
                 for (int e = 0; e < 4; ++e)
-                    if (16 * r + e >= lim) sj[r][e] = WORST;
-        }
-        // tile-local extremum: independent chains, then the wave's four lane groups
-        auto best = [](float a, float b) { return SF::DIST ? fminf(a, b) : fmaxf(a, b); };
-        float mx[4] = {WORST, WORST, WORST, WORST};
+                    if (16 * r + e >= lim) sc[j][r][e] = WORST;
+    }
+    // tile-local extremum: four independent chains per block, then the wave's four lane groups.  Minimum and maximum are
+    // exact, so any grouping gives epilogue_p's bits: three-input steps (v_min3 / v_max3_f32), eight values in four of them.
+    auto best = [](float a, float b) { return SF::DIST ? fminf(a, b) : fmaxf(a, b); };
+    auto best3 = [&](float a, float b, float c) { return best(best(a, b), c); };
+    static_assert(RS == 8, "chain k takes the 16-row blocks k and k + 4");
+    float ext[QB];
 #pragma unroll
-        for (int r = 0; r < RS; ++r) mx[r & 3] = best(mx[r & 3], best(best(sj[r][0], sj[r][1]), best(sj[r][2], sj[r][3])));
-        float ext = best(best(mx[0], mx[1]), best(mx[2], mx[3]));
-        ext = SF::DIST ? group4_min(ext) : group4_max(ext);
-        const float mloc = SF::DIST ? -ext : ext;  // the tile maximum of u
+    for (int j = 0; j < QB; ++j) {
+        float mx[4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) mx[k] = best3(sc[j][k][0], sc[j][k][1], sc[j][k][2]);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) mx[k] = best3(mx[k], sc[j][k][3], sc[j][k + 4][0]);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) mx[k] = best3(mx[k], sc[j][k + 4][1], sc[j][k + 4][2]);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) mx[k] = best(mx[k], sc[j][k + 4][3]);
+        ext[j] = best(best3(mx[0], mx[1], mx[2]), mx[3]);
+    }
+    group4_each(ext, best);
+    float mloc[QB], dloc[QB], s0v[QB], s1v[QB] = {0.f, 0.f}, s2v[QB] = {0.f, 0.f};
+#pragma unroll
+    for (int j = 0; j < QB; ++j) {
+        mloc[j] = SF::DIST ? -ext[j] : ext[j];  // the tile maximum of u
 #pragma unroll
         for (int r = 0; r < RS; ++r)
 #pragma unroll
             for (int e = 0; e < 4; ++e)  // 2^(u - max); 2^-inf = 0 for padded rows
-                sj[r][e] = __builtin_amdgcn_exp2f(SF::DIST ? ext - sj[r][e] : sj[r][e] - ext);
-        NW_PSTAMP(3);
-        // ---- run sums: as epilogue_p (whole 16-row blocks with a scalar 0 / 1 weight, the blocks a run boundary cuts
-        // per element; more than three runs through the indicator MFMAs)
-        float dloc;
-        auto red4 = [](float x) { return group4_sum(x); };
-        if (nrun <= 3) {
-            float S0[2] = {0.f, 0.f}, S1[2] = {0.f, 0.f}, S2[2] = {0.f, 0.f};
-            if (nrun == 1) {
+                sc[j][r][e] = __builtin_amdgcn_exp2f(SF::DIST ? ext[j] - sc[j][r][e] : sc[j][r][e] - ext[j]);
+    }
+    NW_PSTAMP(3);
+    // ---- run sums: as epilogue_p (whole 16-row blocks with a scalar 0 / 1 weight, the blocks a run boundary cuts
+    // per element; more than three runs through the indicator MFMAs)
+    auto add = [](float a, float b) { return a + b; };
+    if (nrun <= 3) {
+        float S0[QB][2] = {{0.f, 0.f}, {0.f, 0.f}}, S1[QB][2] = {{0.f, 0.f}, {0.f, 0.f}}, S2[QB][2] = {{0.f, 0.f}, {0.f, 0.f}};
+        if (nrun == 1) {
 #pragma unroll
-                for (int r = 0; r < RS; ++r) {
-                    S0[r & 1] += (sj[r][0] + sj[r][1]) + (sj[r][2] + sj[r][3]);
+            for (int r = 0; r < RS; ++r)
+#pragma unroll
+                for (int j = 0; j < QB; ++j) S0[j][r & 1] += (sc[j][r][0] + sc[j][r][1]) + (sc[j][r][2] + sc[j][r][3]);
+        } else {
+            const int b1 = bnd.x, b2 = (nrun == 3) ? bnd.y : BS;
+            const float L1 = (float)(b1 - 4 * g);
+            const float M2 = 1.f - (float)(b2 - 4 * g);
+#pragma unroll
+            for (int r = 0; r < RS; ++r) {
+                const int lo = 16 * r, hi = 16 * r + 16;
+                const bool in0 = hi <= b1, in2 = lo >= b2, in1 = lo >= b1 && hi <= b2;
+#pragma unroll
+                for (int j = 0; j < QB; ++j) {
+                    const float quad = (sc[j][r][0] + sc[j][r][1]) + (sc[j][r][2] + sc[j][r][3]);
+                    S0[j][r & 1] = __builtin_fmaf(in0 ? 1.f : 0.f, quad, S0[j][r & 1]);
+                    S1[j][r & 1] = __builtin_fmaf(in1 ? 1.f : 0.f, quad, S1[j][r & 1]);
+                    S2[j][r & 1] = __builtin_fmaf(in2 ? 1.f : 0.f, quad, S2[j][r & 1]);
                 }
-            } else {
-                const int b1 = bnd.x, b2 = (nrun == 3) ? bnd.y : BS;
-                const float L1 = (float)(b1 - 4 * g);
-                const float M2 = 1.f - (float)(b2 - 4 * g);
+                if (!(in0 || in1 || in2)) {
 #pragma unroll
-                for (int r = 0; r < RS; ++r) {
-                    const int lo = 16 * r, hi = 16 * r + 16;
-                    const bool in0 = hi <= b1, in2 = lo >= b2, in1 = lo >= b1 && hi <= b2;
-                    const float quad = (sj[r][0] + sj[r][1]) + (sj[r][2] + sj[r][3]);
-                    S0[r & 1] = __builtin_fmaf(in0 ? 1.f : 0.f, quad, S0[r & 1]);
-                    S1[r & 1] = __builtin_fmaf(in1 ? 1.f : 0.f, quad, S1[r & 1]);
-                    S2[r & 1] = __builtin_fmaf(in2 ? 1.f : 0.f, quad, S2[r & 1]);
-                    if (!(in0 || in1 || in2)) {
+                    for (int e = 0; e < 4; ++e) {
+                        const float c = (float)(16 * r + e);
+                        const float w1 = __builtin_amdgcn_fmed3f(L1 - c, 0.f, 1.f);  // [t <  b1]
+                        const float u2 = __builtin_amdgcn_fmed3f(c + M2, 0.f, 1.f);  // [t >= b2]
 #pragma unroll
-                        for (int e = 0; e < 4; ++e) {
-                            const float c = (float)(16 * r + e), ev = sj[r][e];
-                            const float w1 = __builtin_amdgcn_fmed3f(L1 - c, 0.f, 1.f);  // [t <  b1]
-                            const float u2 = __builtin_amdgcn_fmed3f(c + M2, 0.f, 1.f);  // [t >= b2]
-                            S0[e & 1] = __builtin_fmaf(w1, ev, S0[e & 1]);
-                            S2[e & 1] = __builtin_fmaf(u2, ev, S2[e & 1]);
-                            S1[e & 1] = __builtin_fmaf((1.f - w1) - u2, ev, S1[e & 1]);  // exact 0 / 1
+                        for (int j = 0; j < QB; ++j) {
+                            const float ev = sc[j][r][e];
+                            S0[j][e & 1] = __builtin_fmaf(w1, ev, S0[j][e & 1]);
+                            S2[j][e & 1] = __builtin_fmaf(u2, ev, S2[j][e & 1]);
+                            S1[j][e & 1] = __builtin_fmaf((1.f - w1) - u2, ev, S1[j][e & 1]);  // exact 0 / 1
                         }
                     }
                 }
             }
-            const float s0v = red4(S0[0] + S0[1]);
-            float s1v = 0.f, s2v = 0.f;
-            if (nrun >= 2) s1v = red4(S1[0] + S1[1]);
-            if (nrun == 3) s2v = red4(S2[0] + S2[1]);
-            dloc = (s0v + s1v) + s2v;
-            if (g == 0 && b < B) {
-                ws_num[((size_t)st * BS) * B + b] = s0v;
-                if (nrun >= 2) ws_num[((size_t)st * BS + 1) * B + b] = s1v;
-                if (nrun == 3) ws_num[((size_t)st * BS + 2) * B + b] = s2v;
-            }
+        }
+        if (nrun == 1) {
+            float v[QB] = {S0[0][0] + S0[0][1], S0[1][0] + S0[1][1]};
+            group4_each(v, add);
+            s0v[0] = v[0], s0v[1] = v[1];
+        } else if (nrun == 2) {
+            float v[2 * QB] = {S0[0][0] + S0[0][1], S0[1][0] + S0[1][1], S1[0][0] + S1[0][1], S1[1][0] + S1[1][1]};
+            group4_each(v, add);
+            s0v[0] = v[0], s0v[1] = v[1], s1v[0] = v[2], s1v[1] = v[3];
         } else {
+            float v[3 * QB] = {S0[0][0] + S0[0][1], S0[1][0] + S0[1][1], S1[0][0] + S1[0][1],
+                               S1[1][0] + S1[1][1], S2[0][0] + S2[0][1], S2[1][0] + S2[1][1]};
+            group4_each(v, add);
+            s0v[0] = v[0], s0v[1] = v[1], s1v[0] = v[2], s1v[1] = v[3], s2v[0] = v[4], s2v[1] = v[5];
+        }
+#pragma unroll
+        for (int j = 0; j < QB; ++j) dloc[j] = (s0v[j] + s1v[j]) + s2v[j];
+    } else {
+#pragma unroll
+        for (int j = 0; j < QB; ++j) {
             float dl[4] = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-            for (int r = 0; r < RS; ++r) dl[r & 3] += (sj[r][0] + sj[r][1]) + (sj[r][2] + sj[r][3]);
-            dloc = red4((dl[0] + dl[1]) + (dl[2] + dl[3]));
-            // run sums on the matrix cores: indicator (A operand) x E (already in B-operand layout)
+            for (int r = 0; r < RS; ++r) dl[r & 3] += (sc[j][r][0] + sc[j][r][1]) + (sc[j][r][2] + sc[j][r][3]);
+            dloc[j] = (dl[0] + dl[1]) + (dl[2] + dl[3]);
+        }
+        group4_each(dloc, add);
+        // run sums on the matrix cores: indicator (A operand) x E (already in B-operand layout)
+#pragma unroll
+        for (int j = 0; j < QB; ++j) {
+            const int b = q0 + 16 * (QB * wave + j) + i;
             for (int run_base = 0; run_base < nrun; run_base += 16) {
                 f32x4 Pm = {0.f, 0.f, 0.f, 0.f};
                 const int want = run_base + i;
 #pragma unroll
                 for (int r = 0; r < RS; ++r) {
                     const int4 rid = *reinterpret_cast<const int4*>(runid + 16 * r + 4 * g);
-                    Pm = __builtin_amdgcn_mfma_f32_16x16x4f32(rid.x == want ? 1.f : 0.f, sj[r][0], Pm, 0, 0, 0);
-                    Pm = __builtin_amdgcn_mfma_f32_16x16x4f32(rid.y == want ? 1.f : 0.f, sj[r][1], Pm, 0, 0, 0);
-                    Pm = __builtin_amdgcn_mfma_f32_16x16x4f32(rid.z == want ? 1.f : 0.f, sj[r][2], Pm, 0, 0, 0);
-                    Pm = __builtin_amdgcn_mfma_f32_16x16x4f32(rid.w == want ? 1.f : 0.f, sj[r][3], Pm, 0, 0, 0);
+                    Pm = __builtin_amdgcn_mfma_f32_16x16x4f32(rid.x == want ? 1.f : 0.f, sc[j][r][0], Pm, 0, 0, 0);
+                    Pm = __builtin_amdgcn_mfma_f32_16x16x4f32(rid.y == want ? 1.f : 0.f, sc[j][r][1], Pm, 0, 0, 0);
+                    Pm = __builtin_amdgcn_mfma_f32_16x16x4f32(rid.z == want ? 1.f : 0.f, sc[j][r][2], Pm, 0, 0, 0);
+                    Pm = __builtin_amdgcn_mfma_f32_16x16x4f32(rid.w == want ? 1.f : 0.f, sc[j][r][3], Pm, 0, 0, 0);
                 }
                 if (b < B) {
 #pragma unroll
@@ -212,13 +247,27 @@ __device__ __forceinline__ void epilogue_p12(f32x4 (&acc)[P12::QB][P12::RS], con
                 }
             }
         }
-        NW_PSTAMP(4);
-        if (g == 0 && b < B) {
-            ws_m[(size_t)st * B + b] = mloc;
-            ws_den[(size_t)st * B + b] = dloc;
-        }
-        NW_PSTAMP(5);
     }
+    NW_PSTAMP(4);
+    // ---- partial stores.  After group4_* the four lane groups of a wave hold the same bits (both halves of a swap add /
+    // compare the same two operands), and the wave's two query blocks are 32 consecutive b: lane group g carries block
+    // g & 1 of array g >> 1, so one full-wave store writes two 128-byte segments where 16-lane stores wrote four of 64.
+    static_assert(QB == 2, "lane groups 0 / 1 carry query blocks 0 / 1, groups 2 / 3 the same blocks of the next array");
+    int ln = lane;  // made per tile: hoisted out of the tile loop, the selected pointers and offsets cost the main loop registers
+    asm volatile("" : "+v"(ln));
+    const int b = q0 + 16 * QB * wave + (ln & 31);
+    const bool blk1 = ln & 16, arr1 = ln & 32;
+    const size_t tb = (size_t)st * B + b, nb = (size_t)st * BS * B + b;  // in ws_m / ws_den, in ws_num (run 0)
+    if (b < B) {
+        const float mv = blk1 ? mloc[1] : mloc[0], dv = blk1 ? dloc[1] : dloc[0];
+        (arr1 ? ws_den : ws_m)[tb] = arr1 ? dv : mv;
+        if (nrun <= 3) {  // run sums 0 and 1 in one store, the third run's from half a wave
+            const float n0 = blk1 ? s0v[1] : s0v[0], n1 = blk1 ? s1v[1] : s1v[0], n2 = blk1 ? s2v[1] : s2v[0];
+            if (!arr1 || nrun >= 2) ws_num[nb + (arr1 ? B : 0)] = arr1 ? n1 : n0;
+            if (!arr1 && nrun == 3) ws_num[nb + 2 * (size_t)B] = n2;
+        }
+    }
+    NW_PSTAMP(5);
 }
 
 template <int KIND>

@@ -189,6 +189,23 @@ __device__ __forceinline__ float group4_min(float x) {
     return fminf(__uint_as_float(r[0]), __uint_as_float(r[1]));
 }
 
+// group4_sum / group4_min / group4_max of NV independent values at once (op = the two-input add / min / max): per value the
+// same two steps on the same operands, but the swaps of all values are issued together, so that the VALU-write -> permlane
+// hazard padding and the swap latency of one value lie under the others' instructions.
+template <int NV, typename Op>
+__device__ __forceinline__ void group4_each(float (&v)[NV], Op op) {
+    typedef unsigned u2_ __attribute__((ext_vector_type(2)));
+    u2_ r[NV];
+#pragma unroll
+    for (int k = 0; k < NV; ++k) r[k] = __builtin_amdgcn_permlane32_swap(__float_as_uint(v[k]), __float_as_uint(v[k]), false, false);
+#pragma unroll
+    for (int k = 0; k < NV; ++k) v[k] = op(__uint_as_float(r[k][0]), __uint_as_float(r[k][1]));
+#pragma unroll
+    for (int k = 0; k < NV; ++k) r[k] = __builtin_amdgcn_permlane16_swap(__float_as_uint(v[k]), __float_as_uint(v[k]), false, false);
+#pragma unroll
+    for (int k = 0; k < NV; ++k) v[k] = op(__uint_as_float(r[k][0]), __uint_as_float(r[k][1]));
+}
+
 // score from (dot, |q|^2, |s|^2); shared by the MFMA and the generic kernels
 template <int KIND>
 __device__ __forceinline__ float score_from_dot(float dot, float qn2, float sn2, float scale) {
