@@ -16,6 +16,8 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+import ws_poison
+
 pytestmark = pytest.mark.gpu
 
 RTOL, ATOL = 1e-5, 3e-5
@@ -91,13 +93,21 @@ def test_k3_eight_shards_with_class_windows_equal_unsharded(dev, ops, k3, B):
 
 @pytest.mark.parametrize("B", [256, 4096])
 def test_k3_forward_is_bit_reproducible(dev, ops, k3, B):
-    """Same inputs, two launches: identical bits (the merge sums in a fixed order; no float atomics)."""
+    """Same inputs, two launches: identical bits (the merge sums in a fixed order; no float atomics).  The scratch
+    buffer is poisoned before every launch: the second one must not inherit what the first one stored."""
+    need = ws_poison.fwd_workspace_bytes(B, k3["sd"].shape[0], k3["sd"].shape[1], k3["C"])
+    assert ws_poison.poison_cached_workspaces(need, dev) >= need
     a = ops.nw_head(k3["qd"][:B], k3["sd"], k3["syd"], k3["C"], support_cache=k3["bank"]).clone()
     junk = torch.randn(1 << 22, device=dev).sum()              # other work in between
+    assert ws_poison.poison_cached_workspaces(need, dev) >= need
     b = ops.nw_head(k3["qd"][:B], k3["sd"], k3["syd"], k3["C"], support_cache=k3["bank"])
+    assert torch.isfinite(a).all() and torch.isfinite(b).all()
     assert torch.equal(a, b), (a - b).abs().max()
+    assert ws_poison.poison_cached_workspaces(need, dev) >= need
     pa = ops.nw_partials(k3["qd"][:B], k3["sd"], k3["syd"], k3["C"], support_cache=k3["bank"]).clone()
+    assert ws_poison.poison_cached_workspaces(need, dev) >= need
     pb = ops.nw_partials(k3["qd"][:B], k3["sd"], k3["syd"], k3["C"], support_cache=k3["bank"])
+    assert torch.isfinite(pa).all() and torch.isfinite(pb).all()
     assert torch.equal(pa, pb)
     del junk
 
@@ -108,11 +118,18 @@ def test_reproducible_with_unsorted_labels_and_small_shapes(dev, ops):
     for B, N, d, C in ((300, 5000, 64, 37), (64, 1000, 512, 200), (8, 20, 32, 5), (700, 3000, 36, 1000)):
         q, s = torch.randn(B, d, generator=g).to(dev), torch.randn(N, d, generator=g).to(dev)
         sy = torch.randint(0, C, (N,), generator=g).to(dev)
+        need = ws_poison.fwd_workspace_bytes(B, N, d, C)       # (the scratch buffer is poisoned before every launch)
+        assert ws_poison.poison_cached_workspaces(need, dev) >= need
         a = ops.nw_head(q, s, sy, C).clone()
+        assert ws_poison.poison_cached_workspaces(need, dev) >= need
         assert torch.equal(a, ops.nw_head(q, s, sy, C))
+        assert torch.isfinite(a).all()
+        assert ws_poison.poison_cached_workspaces(need, dev) >= need
         a, wa = ops.nw_head(q, s, sy, C, return_weights=True)
         a, wa = a.clone(), wa.clone()
+        assert ws_poison.poison_cached_workspaces(need, dev) >= need
         b, wb = ops.nw_head(q, s, sy, C, return_weights=True)
+        assert torch.isfinite(a).all() and torch.isfinite(wa).all()
         assert torch.equal(a, b) and torch.equal(wa, wb)
 
 

@@ -12,6 +12,7 @@ import torch
 import torch.nn.functional as F
 
 from conftest import T, load_golden
+import ws_poison
 
 pytestmark = pytest.mark.gpu
 
@@ -341,7 +342,8 @@ def test_class_window_merge(dev, ops):
 
 
 @pytest.mark.parametrize("B,N,d,C,kind,sorted_labels", [
-    (1000, 9000, 64, 37, "euclidean", False),     # nk = 2 < pipeline depth, ragged B and N, ~128 runs per tile
+    (1000, 9000, 64, 37, "euclidean", False),     # d < 96: the one-workgroup-per-tile kernel (the persistent one needs three
+                                                  # 32-column stages per tile); ragged B and N, ~128 runs per tile
     (520, 16500, 512, 200, "cosine", True),       # the bench's d, class-sorted bank (1-2 runs per tile)
     (1030, 8200, 96, 11, "dotproduct", True),
     (640, 14000, 128, 150, "euclidean", True),    # ~93 rows per class: 2-3 runs per 128-row tile (VALU run sums)
@@ -362,15 +364,23 @@ def test_persistent_many_tiles(dev, ops, O, B, N, d, C, kind, sorted_labels):
     cache = ops.SplitBank(s)
     assert cache.split is not None
     ls = _ls(dev) if kind == "clip" else None
+    # (the scratch buffer is never cleared: poisoned, so that a store the kernel forgets is not filled in by an earlier call)
+    need = ws_poison.fwd_workspace_bytes(B, N, d, C)
+    assert ws_poison.poison_cached_workspaces(need, dev) >= need
     out = ops.nw_head(q, s, sy, C, kind, ls, support_cache=cache)
+    assert torch.isfinite(out).all()
     ref = O.nw_head_f64(q.cpu(), s.cpu(), sy.cpu(), C, kind)
     smax = O.scores_f64(q[:64].cpu(), s.cpu(), kind, O.CLIP_LOGIT_SCALE_INIT).abs().max().item()
     atol = max(3e-5, 3e-6 * smax)
     close(out, ref.numpy(), rtol=RTOL, atol=atol)
     # partials of two halves of the bank, merged == the whole
     h = N // 2
-    rows = torch.stack([ops.nw_partials(q, s[:h], sy[:h], C, kind, ls, support_cache=ops.SplitBank(s[:h])).view(-1),
-                        ops.nw_partials(q, s[h:], sy[h:], C, kind, ls, support_cache=ops.SplitBank(s[h:])).view(-1)])
+    rows = []
+    for a, b in ((0, h), (h, N)):
+        assert ws_poison.poison_cached_workspaces() >= need
+        rows.append(ops.nw_partials(q, s[a:b], sy[a:b], C, kind, ls, support_cache=ops.SplitBank(s[a:b])).view(-1))
+    rows = torch.stack(rows)
+    assert torch.isfinite(rows).all()
     close(ops.nw_merge(rows, B, C), ref.numpy(), rtol=RTOL, atol=atol)
 
 

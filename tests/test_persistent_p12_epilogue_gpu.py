@@ -18,6 +18,8 @@ import numpy as np
 import pytest
 import torch
 
+import ws_poison
+
 pytestmark = pytest.mark.gpu
 
 KINDS = ("euclidean", "hypersphere_euclidean", "cosine", "dotproduct", "clip")
@@ -123,12 +125,17 @@ def test_p12_epilogue_log_probs_equal_p2(dev, ops, pvar, kind, B, N, labels):
     cache = ops.SplitBank(s)
     assert cache.split is not None
     ls = _logit_scale(kind, dev)
+    # both variants lay the scratch buffer out alike: without the poison a store that one forgets is filled in by the other
+    need = ws_poison.fwd_workspace_bytes(B, N, D, C)
     pvar(2)
+    assert ws_poison.poison_cached_workspaces(need, dev) >= need
     out2 = ops.nw_head(q, s, sy, C, kind, ls, support_cache=cache).clone()
     pvar(3)
+    assert ws_poison.poison_cached_workspaces(need, dev) >= need
     out3 = ops.nw_head(q, s, sy, C, kind, ls, support_cache=cache).clone()
     torch.cuda.synchronize()
     assert out2.shape == (B, C) and not torch.isnan(out2).any()
+    assert torch.isfinite(out2).all() and torch.isfinite(out3).all()
     assert torch.equal(out3, out2), f"max |diff| {(out3 - out2).abs().max().item():.3e}"
 
 
@@ -141,8 +148,13 @@ def test_p12_epilogue_packed_partials_equal_p2(dev, pvar, kind, B, N):
     bank = ShardedBank(s, sy, C, kind, _logit_scale(kind, dev))
     assert bank.cache is not None and bank.cache.split is not None
     rows = {}
+    need = ws_poison.fwd_workspace_bytes(B, N, D, bank.CL)
     for v in (2, 3):
         pvar(v)
+        # the bank's own scratch buffer (kept from call to call, never cleared) is the one in use; the shared one is poisoned
+        # too so that nothing can come from it, and may rightly be empty here: its byte count is not asserted
+        bank._ws = ws_poison.poisoned_workspace(need, dev)
+        ws_poison.poison_cached_workspaces()
         packed = torch.full((bank.row_len(B),), -7.0, dtype=torch.float32, device=dev)
         bank._partial(packed, q)
         torch.cuda.synchronize()
@@ -150,6 +162,7 @@ def test_p12_epilogue_packed_partials_equal_p2(dev, pvar, kind, B, N):
     m2, den2, num2 = rows[2][:B], rows[2][B:2 * B], rows[2][2 * B:]
     m3, den3, num3 = rows[3][:B], rows[3][B:2 * B], rows[3][2 * B:]
     assert not torch.isnan(rows[2]).any() and (den2 > 0).all() and (num2 >= 0).all()
+    assert torch.isfinite(rows[2]).all() and torch.isfinite(rows[3]).all()
     assert torch.equal(m3, m2), f"m: {(m3 != m2).sum().item()} of {B} differ"
     assert torch.equal(den3, den2), f"den: {(den3 != den2).sum().item()} of {B} differ"
     assert torch.equal(num3, num2), f"num: {(num3 != num2).sum().item()} of {B * C} differ"

@@ -12,6 +12,8 @@ import numpy as np
 import pytest
 import torch
 
+import ws_poison
+
 pytestmark = pytest.mark.gpu
 
 KINDS = ("euclidean", "hypersphere_euclidean", "cosine", "dotproduct", "clip")
@@ -77,11 +79,16 @@ def test_p12_equals_p2_and_oracle(dev, ops, O, pvar, kind, sorted_labels, B, N, 
     cache = ops.SplitBank(s)
     assert cache.split is not None
     ls = torch.tensor(float(np.log(1 / 0.07)), dtype=torch.float32, device=dev) if kind == "clip" else None
+    # both variants lay the scratch buffer out alike: without the poison a store that one forgets is filled in by the other
+    need = ws_poison.fwd_workspace_bytes(B, N, d, C)
     pvar(2)
+    assert ws_poison.poison_cached_workspaces(need, dev) >= need
     out2 = ops.nw_head(q, s, sy, C, kind, ls, support_cache=cache).clone()
     pvar(3)
+    assert ws_poison.poison_cached_workspaces(need, dev) >= need
     out3 = ops.nw_head(q, s, sy, C, kind, ls, support_cache=cache).clone()
     torch.cuda.synchronize()
+    assert torch.isfinite(out2).all() and torch.isfinite(out3).all()
     assert torch.equal(out3, out2), f"max |diff| {(out3 - out2).abs().max().item():.3e}"
     ref = _oracle_rows(O, q, s, sy, kind, 16 if N * d > 4_000_000 else 256)
     smax = O.scores_f64(q[:64], s, kind, O.CLIP_LOGIT_SCALE_INIT).abs().max().item()
