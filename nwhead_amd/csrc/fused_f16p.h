@@ -13,6 +13,8 @@
 //   * the runs of equal labels are found ONCE per launch by nw_run_tables_kernel (fused.hip) instead
 //     of once per (query tile, support tile) workgroup;
 //   * barriers: one per stage, executed by both roles, nothing else.
+// The configuration, the tile order and the loader role are persistent_pipe.h's (shared with the 256-query kernel
+// of fused_f16p12.h); this file holds the consumer role: the main loops and the tile epilogue.
 // Tile shape, LDS stage image and MFMA stream are those of nw_fused_kernel<RS, KIND, false, MODE_F16>.
 // Requires d / 32 >= 3: the header of tile T+2 is issued 3 stages before tile T+1 ends, i.e. (three
 // stages per tile) possibly while the consumers still run the epilogue of tile T -- hence three header
@@ -24,44 +26,15 @@
 // TFLOP/s-equivalent is the power-limited pace of this instruction mix, not 833.
 #pragma once
 #include "fused_impl.h"
+#include "persistent_pipe.h"
 
 namespace nw {
 namespace {
 
-#ifdef NW_DIAG_FUSED  // diagnostic build only (tools/bench_fused.hip): per-workgroup phase totals
-__device__ unsigned long long nw_diag_p[8 * 1024];
-__device__ unsigned long long nw_diag_rt[2 * 1024];   // s_memrealtime (100 MHz) at the first / last stamp of a workgroup
-#define NW_PSTAMP(k)                                                                         \
-    do {                                                                                     \
-        unsigned long long now_;                                                             \
-        __builtin_amdgcn_sched_barrier(0);                                                   \
-        asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(now_)::"memory");         \
-        __builtin_amdgcn_sched_barrier(0);                                                   \
-        diag_[k] += now_ - last_;                                                            \
-        last_ = now_;                                                                        \
-    } while (0)
-#else
-#define NW_PSTAMP(k)
-#endif
-
 // QB = query blocks (of 16 rows) per consumer wave: the tile is 64*QB queries x 16*RS supports.
-template <int RS, int QB>
-struct PCfg {
-    static constexpr int BS = 16 * RS;
-    static constexpr int BQP = 64 * QB;                 // query rows per tile
-    static constexpr int N64 = (BS + 63) / 64;          // 64-row DMA pieces per support-side header array
-    static constexpr int NH = N64 * 64;                 // entries per support-side array in LDS
-    static constexpr int HDR_F = 3 * NH + 2 * BQP;      // sn2 | ssc | runid | qn2[BQP] | qsc[BQP]
-    static constexpr int NP = 3 * N64 + 2 * QB;         // header pieces (256 B each)
-    static constexpr int HPW = (NP + NLOAD - 1) / NLOAD;  // ... per loader wave
-    static constexpr int TILE_F4 = (BQP + BS) * ROW_F4; // one stage: 128 B per row
-    static constexpr int NT = (BQP + BS) / 8;           // stage DMA pieces (1 KB = 8 rows)
-    static constexpr int NI = (NT + NLOAD - 1) / NLOAD; // ... per loader wave (waves lw < NT % NLOAD, or all)
-    static constexpr int NI_LO = NT / NLOAD;
-    static constexpr int NHB = 3;                       // header buffers
-    static constexpr size_t HDR_BYTES = NHB * (size_t)HDR_F * 4;
-    static_assert(HDR_BYTES % 16 == 0, "stage buffers must stay 16-byte aligned");
-};
+// TWO = two workgroups per CU: a ring of three stage buffers instead of four.
+template <int RS, int QB, bool TWO = false>
+struct PCfg : PipeCfg<16 * RS, 64 * QB, NCONS, NLOAD, TWO ? 3 : 4> {};
 
 // Epilogue of one tile for the consumer waves: scores -> tile-local softmax statistics -> run sums.
 // Same arithmetic as fused_epilogue<.., MODE_F16> (fused_impl.h); the header comes from LDS only.
@@ -243,9 +216,6 @@ __device__ __forceinline__ void epilogue_p(f32x4 (&acc)[QB][RS], const float* hd
 // QB = 2     : 128-query tiles (one workgroup per CU, single-buffered fragments): per flop 1/3 fewer
 //              bytes through the LDS fill and 44 % fewer LDS read bytes than the 64-query tile -- on
 //              this power-limited loop (header comment) energy per flop is what sets the pace.
-#if defined(NW_ABL_QREG) && !defined(NW_ABL_NOQ)
-#define NW_ABL_NOQ
-#endif
 template <int RS, int KIND, bool TWO, int QB>
 __global__ __launch_bounds__(TILE_THREADS, TWO ? 4 : 2) void nw_fused_f16p_kernel(
     const float* __restrict__ q, const float* __restrict__ s, const float* __restrict__ s_norm2,
@@ -253,17 +223,11 @@ __global__ __launch_bounds__(TILE_THREADS, TWO ? 4 : 2) void nw_fused_f16p_kerne
     const float* __restrict__ logit_scale, const int* __restrict__ ws_runid, const int* __restrict__ ws_nrun, const int* __restrict__ ws_bnd,
     float* __restrict__ ws_m, float* __restrict__ ws_den, float* __restrict__ ws_num, int B, int N, int d,
     int n_stiles, int n_qtiles, int qg) {
-    using P = PCfg<RS, QB>;
-    constexpr int BS = P::BS, BQP = P::BQP, TILE_F4 = P::TILE_F4, NI = P::NI, NI_LO = P::NI_LO, NT = P::NT;
+    using P = PCfg<RS, QB, TWO>;
+    constexpr int BS = P::BS, BQP = P::BQP, TILE_F4 = P::TILE_F4, NB = P::NB;
     constexpr bool SINGLE = TWO || QB > 1;  // single-buffered fragments
     static_assert(!(TWO && QB > 1), "two 128-query workgroups do not fit the LDS of a CU");
-    static_assert(BQP % (8 * NLOAD) == 0, "query and support pieces must not share a loader round");
-    constexpr int NB = TWO ? 3 : 4;  // ring depth
-#ifdef NW_ABL_AHEAD   // timing experiment (tools/bench_fused.hip): fewer stages in flight
-    constexpr int AHEAD = NW_ABL_AHEAD;
-#else
-    constexpr int AHEAD = NB - 1;    // stages in flight per loader wave
-#endif
+    static_assert(P::THREADS == TILE_THREADS, "launch bounds");
     static_assert(RS > 5, "the persistent kernel is built for the tall tiles");
     extern __shared__ __attribute__((aligned(16))) char smem[];
     float* hdr0 = reinterpret_cast<float*>(smem);  // NHB header buffers of HDR_F floats, by tile index mod NHB
@@ -272,160 +236,12 @@ __global__ __launch_bounds__(TILE_THREADS, TWO ? 4 : 2) void nw_fused_f16p_kerne
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int nk = d / BK;
-    // ---- tile order.  Workgroup b runs on XCD b % 8 (round-robin dispatch, one workgroup per CU), and
-    // every XCD has its own 4 MiB L2, so each XCD walks its OWN list of tiles in an order that keeps
-    // its working set in that L2: XCD x owns the support tiles st = x (mod 8); its list is cut into
-    // groups of `qg` query tiles (kept resident: qg * BQP * 2 KB at d = 512), and inside a group runs support-tile
-    // major, so the n_cu workgroups of the XCD are on ~n_cu/qg support tiles x qg query tiles at any
-    // time.
-    // The support tiles beyond the last full round of 8 (n_stiles % 8 of them) are dealt by QUERY tile
-    // (qt = x mod 8) instead, so every XCD gets the same number of tiles to within n_stiles % 8: with 49
-    // support tiles (a shard of the K3 bank at 8 ranks) one XCD would otherwise walk 7 and seven XCDs 6.
-    const int xcd = blockIdx.x & 7, cu = blockIdx.x >> 3, n_cu = gridDim.x >> 3;
-    const int ns_x = n_stiles >> 3;              // full rounds: support tiles st = stl * 8 + x
-    const int n_full = ns_x * n_qtiles;
-    const int rem = n_stiles & 7;                // leftover support tiles 8 * ns_x .. n_stiles - 1
-    const int nq_x = (n_qtiles - xcd + 7) >> 3;  // query tiles of this XCD in the leftover part
-    const int n_local = n_full + rem * nq_x;     // tiles of this XCD
-    const int grp_tiles = qg * ns_x;
-    auto decode = [&](int L, int& qt, int& st) {
-        if (L >= n_full) {                       // leftover part, support-tile major
-            const int r = L - n_full, j = r / nq_x;
-            st = 8 * ns_x + j;
-            qt = xcd + 8 * (r - j * nq_x);
-            return;
-        }
-        const int gi = L / grp_tiles, r = L - gi * grp_tiles;
-        const int g = min(qg, n_qtiles - gi * qg);
-        const int stl = r / g;
-        qt = gi * qg + (r - stl * g);
-        st = stl * 8 + xcd;
-    };
+    const PersistentTiles tiles(blockIdx.x, gridDim.x, n_stiles, n_qtiles, qg);  // tile order: persistent_pipe.h
+    const int cu = tiles.cu, n_cu = tiles.n_cu, n_local = tiles.n_local;
 
-    if (wave >= NCONS) {
-        // ================================ LOADER ================================
-        const int lw = wave - NCONS;
-        const bool long_wave = (NI == NI_LO) || (lw < NT % NLOAD);
-        unsigned voff[NI];
-        int iT = cu, ikt = 0, irot = 0, ipar = 0;  // issue cursor: (tile of this XCD's list, stage), header buffer
-        int iq0 = 0, is0 = 0, ist = 0;
-        int gs = 0;                                // stages issued so far (ring position)
-        auto set_tile = [&](int T) {
-            int qt, st;
-            decode(T, qt, st);
-            iq0 = qt * BQP;
-            is0 = st * BS;
-            ist = st;
-            irot = st % nk;
-#pragma unroll
-            for (int m = 0; m < NI; ++m) {
-                const int R = 8 * (lw + NLOAD * m) + (lane >> 3);
-                const int lslot = (lane & 7) ^ ((R >> 1) & 7);
-                // relative to the tile's first rows (64-bit bases in issue_next): no 4 GB limit on the bank
-                const int rel = (8 * NLOAD * m < BQP) ? min(iq0 + R, B - 1) - iq0 : min(is0 + R - BQP, N - 1) - is0;
-                voff[m] = ((unsigned)rel * (unsigned)d + lslot * 4) * 4u;
-            }
-        };
-        auto dma4 = [&](const void* src, float* dst) {  // one dword per lane -> dst[lane]
-            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src,
-                                             (__attribute__((address_space(3))) void*)dst, 4, 0, 0);
-        };
-        // header pieces of the tile under the issue cursor: HPW per loader wave (piece ids past the
-        // last one repeat the last piece: same bytes to the same place)
-        auto issue_header = [&]() {
-            float* h = hdr0 + ipar * P::HDR_F;
-#pragma unroll
-            for (int k = 0; k < P::HPW; ++k) {
-                const int pc = min(lw + NLOAD * k, P::NP - 1);
-                if (pc < 3 * P::N64) {
-                    const int arr = pc / P::N64, c = pc - arr * P::N64;
-                    const int row = is0 + 64 * c + lane;
-                    float* dst = h + arr * P::NH + 64 * c;
-                    if (arr == 0) dma4(s_norm2 + min(row, N - 1), dst);
-                    else if (arr == 1) dma4(s_scale + min(row, N - 1), dst);
-                    else dma4(ws_runid + (size_t)ist * BS + 64 * c + lane, dst);  // padded by 64 entries
-                } else {
-                    const int qp = pc - 3 * P::N64, arr = qp / QB, c = qp - arr * QB;  // qn2 pieces, then qsc pieces
-                    const int row = min(iq0 + 64 * c + lane, B - 1);
-                    dma4((arr == 0 ? q_norm2 : q_scale) + row, h + 3 * P::NH + arr * BQP + 64 * c);
-                }
-            }
-        };
-        bool young_hdr = false;  // does the youngest issued stage carry header pieces?
-        auto issue_next = [&]() {  // returns false once every stage of every tile has been issued
-            if (iT >= n_local) return false;
-            int kc = ikt + irot;
-            if (kc >= nk) kc -= nk;
-            float4* buf = stage + ((unsigned)gs % NB) * TILE_F4;
-            const char* qb = reinterpret_cast<const char*>(q + (size_t)iq0 * d) + (size_t)kc * BK * 4;
-            const char* sb = reinterpret_cast<const char*>(s + (size_t)is0 * d) + (size_t)kc * BK * 4;
-#ifndef NW_ABL_NODMA
-#pragma unroll
-#endif
-            for (int m = 0; m < NI; ++m) {
-                if (NI != NI_LO && m == NI - 1 && lw + NLOAD * m >= NT) break;
-#if defined(NW_ABL_NOQ)   // timing experiment: the query rows are not filled (results wrong, half of the LDS-DMA bytes gone)
-                if (8 * NLOAD * m < BQP) continue;
-#endif
-#ifdef NW_ABL_NOS   // ... or the support rows are not
-                if (8 * NLOAD * m >= BQP) continue;
-#endif
-                const char* g = ((8 * NLOAD * m < BQP) ? qb : sb) + voff[m];
-#ifndef NW_ABL_NODMA
-                __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)g,
-                                                 (__attribute__((address_space(3))) void*)(buf + 64 * (lw + NLOAD * m)),
-                                                 16, 0, 0);
-#else
-                (void)g; (void)buf;
-#endif
-            }
-            young_hdr = (ikt == 0);
-            if (young_hdr) issue_header();  // after the stage's own pieces: they are waited for last
-            ++gs;
-            if (++ikt == nk) {
-                ikt = 0;
-                ipar = (ipar + 1 == P::NHB) ? 0 : ipar + 1;
-                iT += n_cu;
-                if (iT < n_local) set_tile(iT);
-            }
-            return true;
-        };
-        auto wait_landed = [&](bool issued) {  // everything but the youngest stage of this wave has landed
-#ifdef NW_ABL_AHEAD   // (with fewer stages in flight the youngest must have landed too: the consumers read one stage ahead)
-            if (AHEAD < NB - 1) { wait_vmcnt<0>(); return; }
-#endif
-#if defined(NW_ABL_NOQ) || defined(NW_ABL_NOS)
-            {
-                constexpr int NQP = BQP / (8 * NLOAD);
-#ifdef NW_ABL_NOQ
-                constexpr int NP_ = NI - NQP;
-#else
-                constexpr int NP_ = NQP;
-#endif
-                static_assert(NI == NI_LO, "ablation builds: even split of the pieces");
-                if (!issued) wait_vmcnt<0>();
-                else if (young_hdr) wait_vmcnt<NP_ + P::HPW>();
-                else wait_vmcnt<NP_>();
-                return;
-            }
-#endif
-            if (!issued) wait_vmcnt<0>();
-            else if (long_wave) { if (young_hdr) wait_vmcnt<NI + P::HPW>(); else wait_vmcnt<NI>(); }
-            else { if (young_hdr) wait_vmcnt<NI_LO + P::HPW>(); else wait_vmcnt<NI_LO>(); }
-        };
-        if (iT < n_local) set_tile(iT);
-        bool more = true;
-#pragma unroll
-        for (int k0 = 0; k0 < AHEAD; ++k0) more = issue_next();
-        wait_landed(more);
-        tile_barrier();  // P: all but the youngest issued stage (and the first tile's header) have landed
-        for (int T = cu; T < n_local; T += n_cu) {
-            for (int kt = 0; kt < nk; ++kt) {
-                more = issue_next();
-                wait_landed(more);
-                tile_barrier();
-            }
-        }
+    if (wave >= P::NCW) {
+        persistent_loader<P>(tiles, wave - P::NCW, lane, hdr0, stage, q, s, s_norm2, s_scale, q_norm2, q_scale, ws_runid, B, N,
+                             d);
     } else {
         // ================================ CONSUMER ================================
         const int i = lane & 15, g = lane >> 4;
@@ -486,7 +302,7 @@ __global__ __launch_bounds__(TILE_THREADS, TWO ? 4 : 2) void nw_fused_f16p_kerne
 #endif
         for (int T = cu; T < n_local; T += n_cu) {
             int qt, st;
-            decode(T, qt, st);
+            tiles.decode(T, qt, st);
             const int q0 = qt * BQP, s0 = st * BS;
             const int nrun = ws_nrun[st];  // wave-uniform: scalar loads, used after the main loop
             const int2 bnd = *reinterpret_cast<const int2*>(ws_bnd + 2 * (size_t)st);  // first rows of runs 1 and 2
@@ -521,37 +337,6 @@ __global__ __launch_bounds__(TILE_THREADS, TWO ? 4 : 2) void nw_fused_f16p_kerne
                 auto pin = []() { __builtin_amdgcn_sched_barrier(0); };
                 // one stage: ac = this stage's F1, an = the next stage's (filled here), b = this stage's F2 on
                 // entry, the next stage's on exit
-#ifdef NW_ABL_QREG   // timing experiment: the wave's own query rows, global -> VGPR, two stages ahead (values unused)
-                const char* qtile_ = reinterpret_cast<const char*>(q + (size_t)q0 * d);
-                unsigned qlane_[QB];
-#pragma unroll
-                for (int j = 0; j < QB; ++j)
-                    qlane_[j] = ((unsigned)(min(q0 + 16 * (QB * wave + j) + i, B - 1) - q0) * (unsigned)d + 4 * g) * 4u;
-                const int krot_ = st % nk;
-                auto qload_ = [&](float4 (&X)[2 * QB], int kt_) {
-                    int kc = min(kt_, nk - 1) + krot_;
-                    if (kc >= nk) kc -= nk;
-                    const char* b_ = qtile_ + (size_t)kc * (BK * 4);
-#pragma unroll
-                    for (int j = 0; j < QB; ++j) {
-                        X[2 * j] = *reinterpret_cast<const float4*>(b_ + qlane_[j]);
-                        X[2 * j + 1] = *reinterpret_cast<const float4*>(b_ + qlane_[j] + 64);
-                    }
-                };
-                float4 qx0_[2 * QB], qx1_[2 * QB];
-                qload_(qx0_, 0);
-                qload_(qx1_, 1);
-                int kt_abs_ = 0;
-#define NW_QREG_STEP(X)                                                                                   \
-    do {                                                                                                  \
-        _Pragma("unroll") for (int e_ = 0; e_ < 2 * QB; ++e_) asm volatile("" ::"v"(__builtin_bit_cast(f32x4, X[e_])));             \
-        qload_(X, kt_abs_ + 2);                                                                           \
-        ++kt_abs_;                                                                                        \
-        pin();                                                                                            \
-    } while (0)
-#else
-#define NW_QREG_STEP(X)
-#endif
                 auto run_stage = [&](const F1& ac, F1& an, F2& b, int buf_next, auto has_next) {
 #ifdef NW_ABL_NORD   // timing experiment: no fragment reads in the loop (the first stage's fragments are reused)
                     constexpr bool NXT = false;
@@ -617,26 +402,20 @@ __global__ __launch_bounds__(TILE_THREADS, TWO ? 4 : 2) void nw_fused_f16p_kerne
                 }
                 int kt = 0;
                 for (; kt + 2 < nk; kt += 2) {
-                    NW_QREG_STEP(qx0_);
                     run_stage(a0, a1, b0, gi + kt + 1, Yes{});
                     tile_barrier_nowait();
-                    NW_QREG_STEP(qx1_);
                     run_stage(a1, a0, b0, gi + kt + 2, Yes{});
                     tile_barrier_nowait();
                 }
                 if (kt + 2 == nk) {
-                    NW_QREG_STEP(qx0_);
                     run_stage(a0, a1, b0, gi + kt + 1, Yes{});
                     tile_barrier_nowait();
-                    NW_QREG_STEP(qx1_);
                     run_stage(a1, a0, b0, 0, No{});
                     tile_barrier_nowait();
                 } else {
-                    NW_QREG_STEP(qx0_);
                     run_stage(a0, a1, b0, 0, No{});
                     tile_barrier_nowait();
                 }
-#undef NW_QREG_STEP
             } else if constexpr (SINGLE) {
                 Frag f0;
                 for (int kt = 0; kt < nk; ++kt) {
@@ -675,23 +454,13 @@ __global__ __launch_bounds__(TILE_THREADS, TWO ? 4 : 2) void nw_fused_f16p_kerne
 #endif
                                  );
 #else
-            {  // ablation build: keep every accumulator chain alive
-                f32x4 sum_ = {0.f, 0.f, 0.f, 0.f};
-                for (int j = 0; j < QB; ++j)
-                    for (int r = 0; r < RS; ++r) sum_ += acc[j][r];
-                if (sum_[0] + sum_[1] + sum_[2] + sum_[3] == 12345.678f) ws_m[tid] = sum_[0] + nrun + bnd.x;
-            }
+            keep_acc_alive(acc, ws_m, nrun, bnd);
 #endif
             par = (par + 1 == P::NHB) ? 0 : par + 1;
             NW_PSTAMP(6);
         }
 #ifdef NW_DIAG_FUSED
-        if (tid == 0 && blockIdx.x < 1024) {
-            for (int k = 0; k < 7; ++k) nw_diag_p[8 * blockIdx.x + k] = diag_[k];
-            nw_diag_p[8 * blockIdx.x + 7] = last_ - first_;
-            nw_diag_rt[2 * blockIdx.x] = first_rt_;
-            nw_diag_rt[2 * blockIdx.x + 1] = __builtin_amdgcn_s_memrealtime();
-        }
+        diag_write_out(diag_, last_, first_, first_rt_);
 #endif
     }
 }

@@ -12,9 +12,10 @@
 //     the matrix pipe has work while every wave of the workgroup waits for its first fragments;
 //   * 48 KB stages in a ring of three: during stage k the consumers read buffer k only, stage k+1 has landed at barrier
 //     k-1, and the loaders issue stage k+2 right behind barrier k-1 into the buffer that barrier released (every read of
-//     it was waited for in front of the barrier), waiting for all but the youngest stage as in fused_f16p.h;
+//     it was waited for in front of the barrier), waiting for all but the youngest stage;
 //   * the same arithmetic, element for element: per accumulator the products al x bh, ah x bl, ah x bh of a stage in this
 //     order, k chunks rotated by the support tile, support tiles of 128 rows, workspace layout and run tables unchanged.
+// Configuration interface, tile order and loader role: persistent_pipe.h, shared with fused_f16p.h.
 // Requires d / 32 >= 3 (the header of a tile rides with its first stage, two stages ahead).
 #pragma once
 #include "fused_f16p.h"
@@ -22,30 +23,9 @@
 namespace nw {
 namespace {
 
-struct P12 {
-    static constexpr int RS = 8, QB = 2, NCW = 8, NLW = 4;
-    static constexpr int THREADS = 64 * (NCW + NLW);       // 768
-    static constexpr int BS = 16 * RS;                     // 128 supports
-    static constexpr int BQP = 16 * QB * NCW;              // 256 queries
-    static constexpr int ROWS = BQP + BS;                  // rows of a stage image
-    static constexpr int TILE_F4 = ROWS * ROW_F4;
-    static constexpr int STAGE_BYTES = TILE_F4 * 16;       // 48 KB
-    static constexpr int NB = 3;                           // ring depth
-    static constexpr int AHEAD = NB - 1;                   // stages in flight per loader wave
-    static constexpr int NT = ROWS / 8;                    // 1 KB pieces per stage
-    static constexpr int NI = NT / NLW;                    // ... per loader wave
-    static constexpr int NQI = BQP / 8 / NLW;              // of them query pieces (the first ones)
-    static constexpr int N64 = BS / 64;                    // 64-entry pieces per support-side header array
-    static constexpr int NH = BS;                          // entries per support-side header array
-    static constexpr int HDR_F = 3 * NH + 2 * BQP;         // sn2 | ssc | runid | qn2[BQP] | qsc[BQP]
-    static constexpr int NP = 3 * N64 + 2 * (BQP / 64);    // header pieces (256 B each)
-    static constexpr int HPW = (NP + NLW - 1) / NLW;       // ... per loader wave
-    static constexpr int NHB = 3;                          // header buffers (tile index mod 3, as in fused_f16p.h)
-    static constexpr size_t HDR_BYTES = (size_t)NHB * HDR_F * 4;
-    static constexpr size_t LDS_BYTES = HDR_BYTES + (size_t)NB * STAGE_BYTES;
-    static_assert(NT % NLW == 0 && (BQP / 8) % NLW == 0, "even split of the pieces");
-    static_assert(HDR_BYTES % 16 == 0 && LDS_BYTES <= 160 * 1024, "LDS of one CU");
-    static_assert(NI + HPW < 64, "vmcnt is a 6-bit field");
+struct P12 : PipeCfg<128, 256, 8, 4, 3> {
+    static constexpr int RS = BS / 16, QB = BQP / (16 * NCW);
+    static_assert(LDS_BYTES <= 160 * 1024, "LDS of one CU");
 };
 
 // epilogue_p<8, KIND, 2, 8> (fused_f16p.h) for a wave that has 168 registers: the same operations on the same values, but
@@ -278,7 +258,7 @@ __global__ __launch_bounds__(P12::THREADS, 3) void nw_fused_f16p_kernel_w12(
     const int* __restrict__ ws_bnd, float* __restrict__ ws_m, float* __restrict__ ws_den, float* __restrict__ ws_num, int B,
     int N, int d, int n_stiles, int n_qtiles, int qg) {
     using P = P12;
-    constexpr int RS = P::RS, QB = P::QB, BS = P::BS, BQP = P::BQP, NI = P::NI, NB = P::NB, NLW = P::NLW;
+    constexpr int RS = P::RS, QB = P::QB, BS = P::BS, BQP = P::BQP, NB = P::NB;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     float* hdr0 = reinterpret_cast<float*>(smem);  // NHB header buffers of HDR_F floats, by tile index mod NHB
     float4* stage = reinterpret_cast<float4*>(smem + P::HDR_BYTES);
@@ -286,129 +266,12 @@ __global__ __launch_bounds__(P12::THREADS, 3) void nw_fused_f16p_kernel_w12(
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int nk = d / BK;
-    // ---- tile order: as nw_fused_f16p_kernel (XCD-local lists, groups of qg query tiles, support-tile major)
-    const int xcd = blockIdx.x & 7, cu = blockIdx.x >> 3, n_cu = gridDim.x >> 3;
-    const int ns_x = n_stiles >> 3;
-    const int n_full = ns_x * n_qtiles;
-    const int rem = n_stiles & 7;
-    const int nq_x = (n_qtiles - xcd + 7) >> 3;
-    const int n_local = n_full + rem * nq_x;
-    const int grp_tiles = qg * ns_x;
-    auto decode = [&](int L, int& qt, int& st) {
-        if (L >= n_full) {
-            const int r = L - n_full, j = r / nq_x;
-            st = 8 * ns_x + j;
-            qt = xcd + 8 * (r - j * nq_x);
-            return;
-        }
-        const int gi_ = L / grp_tiles, r = L - gi_ * grp_tiles;
-        const int g_ = min(qg, n_qtiles - gi_ * qg);
-        const int stl = r / g_;
-        qt = gi_ * qg + (r - stl * g_);
-        st = stl * 8 + xcd;
-    };
+    const PersistentTiles tiles(blockIdx.x, gridDim.x, n_stiles, n_qtiles, qg);  // tile order: persistent_pipe.h
+    const int cu = tiles.cu, n_cu = tiles.n_cu, n_local = tiles.n_local;
 
     if (wave >= P::NCW) {
-        // ================================ LOADER ================================
-        const int lw = wave - P::NCW;
-        unsigned voff[NI];
-        int iT = cu, ikt = 0, irot = 0, ipar = 0;  // issue cursor: (tile of this XCD's list, stage), header buffer
-        int iq0 = 0, is0 = 0, ist = 0;
-        int gs = 0;                                // ring slot of the stage under the cursor
-        auto set_tile = [&](int T) {
-            int qt, st;
-            decode(T, qt, st);
-            iq0 = qt * BQP;
-            is0 = st * BS;
-            ist = st;
-            irot = st % nk;
-#pragma unroll
-            for (int m = 0; m < NI; ++m) {
-                const int R = 8 * (lw + NLW * m) + (lane >> 3);       // row of the stage image: queries, then supports
-                const int lslot = (lane & 7) ^ ((R >> 1) & 7);        // swizzle on the source side (an LDS-DMA writes linearly)
-                // relative to the tile's first rows (64-bit bases in issue_next): no 4 GB limit on the bank
-                const int rel = (m < P::NQI) ? min(iq0 + R, B - 1) - iq0 : min(is0 + R - BQP, N - 1) - is0;
-                voff[m] = ((unsigned)rel * (unsigned)d + lslot * 4) * 4u;
-            }
-        };
-        auto dma4 = [&](const void* src, float* dst) {  // one dword per lane -> dst[lane]
-            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src,
-                                             (__attribute__((address_space(3))) void*)dst, 4, 0, 0);
-        };
-        // header pieces of the tile under the issue cursor: HPW per loader wave (piece ids past the last one repeat the
-        // last piece: same bytes to the same place)
-        auto issue_header = [&]() {
-            float* h = hdr0 + ipar * P::HDR_F;
-#pragma unroll
-            for (int k = 0; k < P::HPW; ++k) {
-                const int pc = min(lw + NLW * k, P::NP - 1);
-                if (pc < 3 * P::N64) {
-                    const int arr = pc / P::N64, c = pc - arr * P::N64;
-                    const int row = is0 + 64 * c + lane;
-                    float* dst = h + arr * P::NH + 64 * c;
-                    if (arr == 0) dma4(s_norm2 + min(row, N - 1), dst);
-                    else if (arr == 1) dma4(s_scale + min(row, N - 1), dst);
-                    else dma4(ws_runid + (size_t)ist * BS + 64 * c + lane, dst);  // padded by 64 entries
-                } else {
-                    const int qp = pc - 3 * P::N64, arr = qp / (BQP / 64), c = qp - arr * (BQP / 64);  // qn2 pieces, then qsc pieces
-                    const int row = min(iq0 + 64 * c + lane, B - 1);
-                    dma4((arr == 0 ? q_norm2 : q_scale) + row, h + 3 * P::NH + arr * BQP + 64 * c);
-                }
-            }
-        };
-        bool young_hdr = false;  // does the youngest issued stage carry header pieces?
-        auto issue_next = [&]() {  // returns false once every stage of every tile has been issued
-            if (iT >= n_local) return false;
-            int kc = ikt + irot;
-            if (kc >= nk) kc -= nk;
-            float4* buf = stage + gs * P::TILE_F4;
-            const char* qb = reinterpret_cast<const char*>(q + (size_t)iq0 * d) + (size_t)kc * BK * 4;
-            const char* sb = reinterpret_cast<const char*>(s + (size_t)is0 * d) + (size_t)kc * BK * 4;
-#ifndef NW_ABL_NODMA
-#pragma unroll
-            for (int m = 0; m < NI; ++m) {
-                const char* g = ((m < P::NQI) ? qb : sb) + voff[m];
-                __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)g,
-                                                 (__attribute__((address_space(3))) void*)(buf + 64 * (lw + NLW * m)), 16, 0, 0);
-            }
-#else   // timing experiment: nothing is filled (results wrong)
-            (void)qb; (void)sb; (void)buf;
-#endif
-            young_hdr = (ikt == 0);
-            if (young_hdr) issue_header();  // after the stage's own pieces: they are waited for last
-            gs = (gs + 1 == NB) ? 0 : gs + 1;
-            if (++ikt == nk) {
-                ikt = 0;
-                ipar = (ipar + 1 == P::NHB) ? 0 : ipar + 1;
-                iT += n_cu;
-                if (iT < n_local) set_tile(iT);
-            }
-            return true;
-        };
-        auto wait_landed = [&](bool issued) {  // everything but the youngest stage of this wave has landed
-#ifdef NW_ABL_NODMA
-            if (!issued) wait_vmcnt<0>();
-            else if (young_hdr) wait_vmcnt<P::HPW>();
-            else wait_vmcnt<0>();
-#else
-            if (!issued) wait_vmcnt<0>();
-            else if (young_hdr) wait_vmcnt<NI + P::HPW>();
-            else wait_vmcnt<NI>();
-#endif
-        };
-        if (iT < n_local) set_tile(iT);
-        bool more = true;
-#pragma unroll
-        for (int k0 = 0; k0 < P::AHEAD; ++k0) more = issue_next();
-        wait_landed(more);
-        tile_barrier();  // P: all but the youngest issued stage (and the first tile's header) have landed
-        for (int T = cu; T < n_local; T += n_cu) {
-            for (int kt = 0; kt < nk; ++kt) {
-                more = issue_next();
-                wait_landed(more);
-                tile_barrier();
-            }
-        }
+        persistent_loader<P>(tiles, wave - P::NCW, lane, hdr0, stage, q, s, s_norm2, s_scale, q_norm2, q_scale, ws_runid, B, N,
+                             d);
     } else {
         // ================================ CONSUMER ================================
         const int i = lane & 15, g = lane >> 4;
@@ -498,7 +361,7 @@ __global__ __launch_bounds__(P12::THREADS, 3) void nw_fused_f16p_kernel_w12(
 #endif
         for (int T = cu; T < n_local; T += n_cu) {
             int qt, st;
-            decode(T, qt, st);
+            tiles.decode(T, qt, st);
             const int q0 = qt * BQP, s0 = st * BS;
             const int nrun = ws_nrun[st];  // wave-uniform: scalar loads, used after the main loop
             const int2 bnd = *reinterpret_cast<const int2*>(ws_bnd + 2 * (size_t)st);  // first rows of runs 1 and 2
@@ -531,23 +394,13 @@ __global__ __launch_bounds__(P12::THREADS, 3) void nw_fused_f16p_kernel_w12(
 #endif
                                );
 #else
-            {  // ablation build: keep every accumulator chain alive
-                f32x4 sum_ = {0.f, 0.f, 0.f, 0.f};
-                for (int j = 0; j < QB; ++j)
-                    for (int r = 0; r < RS; ++r) sum_ += acc[j][r];
-                if (sum_[0] + sum_[1] + sum_[2] + sum_[3] == 12345.678f) ws_m[tid] = sum_[0] + nrun + bnd.x;
-            }
+            keep_acc_alive(acc, ws_m, nrun, bnd);
 #endif
             par = (par + 1 == P::NHB) ? 0 : par + 1;
             NW_PSTAMP(6);
         }
 #ifdef NW_DIAG_FUSED
-        if (tid == 0 && blockIdx.x < 1024) {
-            for (int k = 0; k < 7; ++k) nw_diag_p[8 * blockIdx.x + k] = diag_[k];
-            nw_diag_p[8 * blockIdx.x + 7] = last_ - first_;
-            nw_diag_rt[2 * blockIdx.x] = first_rt_;
-            nw_diag_rt[2 * blockIdx.x + 1] = __builtin_amdgcn_s_memrealtime();
-        }
+        diag_write_out(diag_, last_, first_, first_rt_);
 #endif
     }
 }

@@ -509,22 +509,18 @@ int launch_f16p(const float* q, const float* s, const int64_t* sy, const float* 
             }
         }
         if (variant > 2) variant = 2;
-#define NW_LAUNCH_P(TWO_, QB_, GRID_, NBUF_)                                                                      \
-    do {                                                                                                          \
-        using PC_ = PCfg<RS, QB_>;                                                                                \
-        const size_t lds_ = PC_::HDR_BYTES + (size_t)(NBUF_) * PC_::TILE_F4 * 16;                                 \
-        hipLaunchKernelGGL((nw_fused_f16p_kernel<RS, KIND, TWO_, QB_>), dim3(GRID_), dim3(TILE_THREADS), lds_, st, \
-                           q, s, s_norm2, s_scale, q_norm2, q_scale, ls, ws.runid, ws.nrun, ws.bnd, ws.m, ws.den, ws.num,  \
-                           B, N, d, n_stiles, (B + 64 * (QB_) - 1) / (64 * (QB_)), persistent_qgroup());          \
-    } while (0)
-        constexpr size_t lds_q2 = PCfg<RS, 2>::HDR_BYTES + (size_t)4 * PCfg<RS, 2>::TILE_F4 * 16;
-        constexpr size_t lds_two = PCfg<RS, 1>::HDR_BYTES + (size_t)3 * PCfg<RS, 1>::TILE_F4 * 16;
+#define NW_LAUNCH_P(TWO_, QB_, GRID_)                                                                             \
+    hipLaunchKernelGGL((nw_fused_f16p_kernel<RS, KIND, TWO_, QB_>), dim3(GRID_), dim3(TILE_THREADS),              \
+                       (PCfg<RS, QB_, TWO_>::LDS_BYTES), st, q, s, s_norm2, s_scale, q_norm2, q_scale, ls, ws.runid, \
+                       ws.nrun, ws.bnd, ws.m, ws.den, ws.num, B, N, d, n_stiles, (B + 64 * (QB_) - 1) / (64 * (QB_)), \
+                       persistent_qgroup())
+        constexpr size_t lds_q2 = PCfg<RS, 2, false>::LDS_BYTES, lds_two = PCfg<RS, 1, true>::LDS_BYTES;
         if (variant == 2 && lds_q2 <= 160 * 1024) {
-            NW_LAUNCH_P(false, 2, cus, 4);
+            NW_LAUNCH_P(false, 2, cus);
         } else if (variant == 1 && lds_two <= 80 * 1024) {
-            NW_LAUNCH_P(true, 1, 2 * cus, 3);
+            NW_LAUNCH_P(true, 1, 2 * cus);
         } else {
-            NW_LAUNCH_P(false, 1, cus, 4);
+            NW_LAUNCH_P(false, 1, cus);
         }
 #undef NW_LAUNCH_P
         NW_CHECK_LAUNCH();

@@ -1,6 +1,6 @@
-"""A Python model of the tile order of the persistent split-fp16 kernels (decode() in nwhead_amd/csrc/fused_f16p.h and
-fused_f16p12.h) and of the launcher's workgroup count (launch_f16p in fused_impl.h), and the shapes of the order edges that
-test_persistent_schedule_gpu.py derives from them.  A plain helper module: test_persistent_schedule_model.py checks the
+"""A Python model of the tile order of the persistent split-fp16 kernels (PersistentTiles::decode() in
+nwhead_amd/csrc/persistent_pipe.h, used by fused_f16p.h and fused_f16p12.h) and of the launcher's workgroup count
+(launch_f16p in fused_impl.h), and the shapes of the order edges that test_persistent_schedule_gpu.py derives from them.  A plain helper module: test_persistent_schedule_model.py checks the
 model on the CPU, the GPU tests use it to state what their shapes mean.
 """
 
@@ -15,7 +15,7 @@ def n_local(n_stiles, n_qtiles, xcd):
 
 
 def decode(L, xcd, n_stiles, n_qtiles, qg):
-    """decode() of nw_fused_f16p_kernel / nw_fused_f16p_kernel_w12: entry L of XCD xcd's list -> (qt, st)."""
+    """PersistentTiles::decode() (persistent_pipe.h, both persistent kernels): entry L of XCD xcd's list -> (qt, st)."""
     ns_x = n_stiles >> 3
     n_full = ns_x * n_qtiles
     nq_x = (n_qtiles - xcd + 7) >> 3

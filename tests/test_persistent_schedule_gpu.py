@@ -3,8 +3,8 @@ from its defaults, every call through a scratch buffer filled with 0xFF (tests/w
 
 Which workgroup runs which tile, in which ring slot and header buffer, follows from n_cu = workgroups / 8 (the
 `persistent_wgs` option, which ShardedBank sets to CUs - 8 on every multi-rank run), the query-group size (NW_QG; pvar 3
-takes half of it), n_stiles / 8 and n_stiles % 8, n_qtiles, and nk = d / 32 (decode(), set_tile(), issue_next() and the
-consumer loop of both files).  The tests:
+takes half of it), n_stiles / 8 and n_stiles % 8, n_qtiles, and nk = d / 32 (PersistentTiles::decode() and, in
+persistent_loader(), set_tile() and issue_next() of persistent_pipe.h; the consumer loop of both files).  The tests:
 
   a  schedule invariance: per-tile arithmetic depends on (qt, st) only (the k rotation is st % nk) and the merge adds in a
      fixed order, so every (persistent_wgs, NW_QG) setting gives the default setting's BITS;
