@@ -85,6 +85,16 @@ int nw_row_norm2_f32(const float *x, float *n2, int64_t rows, int64_t d, void *s
 int nw_split_rows_f16x2(const float *x, float *out_split, float *row_scale, float *row_norm2,
                         int64_t rows, int64_t d, void *stream);
 
+/* Half-precision form of a dense (rows,d) fp32 matrix, d % 64 == 0 (NW_ERR_UNSUPPORTED otherwise): the operand of
+ * nw_fwd_opts.operand_form = 1.  The scale rule is nw_split_rows_f16x2's (e = 14 - frexp exponent of the row's largest
+ * magnitude, at most 126; 0 for an all-zero row or a non-finite maximum), but only the rounded value is kept:
+ *   out_rows  (rows,d) fp16, dense, row-major: h = fp16(x * 2^e), round to nearest even;
+ *   row_scale (rows,) = 2^-e;   row_norm2 (rows,) = sum_k (h_k * 2^-e)^2 in fp32: the norms of the ROUNDED rows.
+ * Half the bytes of the split form and one fp16 product per term instead of three; the head computed from these
+ * operands is the exact head of the rounded features h * 2^-e (relative rounding 2^-11 per element). */
+int nw_pack_rows_f16(const float *x, uint16_t *out_rows, float *row_scale, float *row_norm2,
+                     int64_t rows, int64_t d, void *stream);
+
 /* ---------------------------------------------------------------------------------------------
  * Forward.  Replaces NWHead.forward nwhead/nw.py:266-289:
  *     one_hot(sy) -> kernel scores -> softmax over supports -> bmm with one-hot -> log(. + 1e-12)
@@ -115,12 +125,23 @@ int nw_split_rows_f16x2(const float *x, float *out_split, float *row_scale, floa
  *               header -- and it builds the tables itself, as without the option)
  *   persistent_wgs  workgroups of the persistent tile kernel, a multiple of 8; 0 = one per CU.  Sharded inference passes
  *               CUs - 8 (one CU per XCD left to the concurrent RCCL kernel)
- *   force_split nonzero: the split-fp16 path whenever the bank is prepared, also below ~2e8 multiply-adds */
+ *   force_split nonzero: the split-fp16 path whenever the bank is prepared, also below ~2e8 multiply-adds
+ *   operand_form (the field older headers call `reserved`; same offset, same struct size)
+ *               0  s_split holds split rows (nw_split_rows_f16x2), as described above;
+ *               1  s_split holds the half-precision rows of nw_pack_rows_f16, s_scale and s_norm2 come from the same
+ *                  call (all three required): the optional reduced-precision head of 'full' inference.  The queries are
+ *                  rounded the same way inside the call, and the result is the head of the ROUNDED queries and supports
+ *                  at the accuracy of the split path -- two fp16 MFMAs per 64 terms instead of three per 32, at every
+ *                  size, on the 256-query persistent kernel.  Honoured by nw_fwd_f32 (out, lse_out) and
+ *                  nw_fwd_partial_f32; NW_ERR_UNSUPPORTED, before anything is launched, for scores_out / weights_out,
+ *                  batched supports or labels, d % 64 != 0, d < 192, a shape the tile kernels do not take (N <= 25;
+ *                  nw_fwd_workspace_bytes covers every other one) and for nw_fwd_influence_f32
+ *               any other value: NW_ERR_INVALID_ARG */
 typedef struct nw_fwd_opts {
     uint32_t struct_size;
     int32_t persistent_wgs;
     int32_t force_split;
-    int32_t reserved;
+    int32_t operand_form;
     const void *tables;
     size_t tables_bytes;
     const int64_t *tables_sy;

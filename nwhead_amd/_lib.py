@@ -29,6 +29,7 @@ SIGNATURES = {
     "nw_fwd_workspace_bytes": (_sz, [_i64, _i64, _i64, _i64]),
     "nw_row_norm2_f32": (_int, [_p, _p, _i64, _i64, _p]),
     "nw_split_rows_f16x2": (_int, [_p, _p, _p, _p, _i64, _i64, _p]),
+    "nw_pack_rows_f16": (_int, [_p, _p, _p, _p, _i64, _i64, _p]),
     "nw_fwd_f32": (_int, [_p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _sz, _i64, _i64, _i64, _i64, _int, _p, _int, _int, _p, _p]),
     "nw_fwd_partial_f32": (_int, [_p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _sz, _i64, _i64, _i64, _i64, _int, _p, _p, _p]),
     "nw_merge_finalize_f32": (_int, [_p, _p, _p, _p, _i64, _i64, _i64, _i64, _i64, _i64, _p, _i64, _p]),
@@ -152,7 +153,7 @@ class ConvBnStat(C.Structure):
 class FwdOpts(C.Structure):
     """nw_fwd_opts (include/nwhead_hip.h): the options of ONE forward call."""
     _fields_ = [("struct_size", C.c_uint32), ("persistent_wgs", C.c_int32), ("force_split", C.c_int32),
-                ("reserved", C.c_int32), ("tables", C.c_void_p), ("tables_bytes", C.c_size_t),
+                ("operand_form", C.c_int32), ("tables", C.c_void_p), ("tables_bytes", C.c_size_t),
                 ("tables_sy", C.c_void_p), ("tables_N", C.c_int64)]
 
 
@@ -182,10 +183,11 @@ def force_split():
     return os.environ.get("NW_SPLIT_ALWAYS", "") == "1"
 
 
-def fwd_opts(tables=None, tables_bytes=0, persistent_wgs=0, tables_sy=None, tables_n=-1):
-    """An nw_fwd_opts for one forward call (a ctypes object: keep it alive across the call)."""
-    return FwdOpts(C.sizeof(FwdOpts), int(persistent_wgs), int(force_split()), 0, tables, int(tables_bytes), tables_sy,
-                   int(tables_n))
+def fwd_opts(tables=None, tables_bytes=0, persistent_wgs=0, tables_sy=None, tables_n=-1, operand_form=0):
+    """An nw_fwd_opts for one forward call (a ctypes object: keep it alive across the call).  operand_form: 0 = the call's
+    s_split holds split rows, 1 = half-precision rows (nw_pack_rows_f16)."""
+    return FwdOpts(C.sizeof(FwdOpts), int(persistent_wgs), int(force_split()), int(operand_form), tables, int(tables_bytes),
+                   tables_sy, int(tables_n))
 
 
 def check(status: int, what: str):

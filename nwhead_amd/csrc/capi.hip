@@ -41,6 +41,7 @@ struct OptsGuard {   // the call's options are visible to the launch code of thi
         if (o && o->struct_size >= offsetof(nw_fwd_opts, tables)) {
             f.persistent_wgs = o->persistent_wgs;
             f.force_split = o->force_split;
+            f.operand_form = o->operand_form;
         }
         if (o && o->struct_size >= sizeof(nw_fwd_opts)) {
             f.tables = static_cast<const char*>(o->tables);
@@ -53,6 +54,20 @@ struct OptsGuard {   // the call's options are visible to the launch code of thi
     ~OptsGuard() { nw::tl_fwd_opts = saved; }
 };
 }  // namespace
+
+// nw_fwd_opts.operand_form = 1 (half-precision rows of nw_pack_rows_f16 in s_split): what the call must look like, checked
+// before anything is launched.  NW_OK: take launch_fused_half.
+static int half_form_check(const float* q, const float* s, const float* s_norm2, const float* s_split, const float* s_scale,
+                           const void* per_pair_out, int batched, int64_t B, int64_t N, int64_t d, int64_t C) {
+    if (per_pair_out || batched) return NW_ERR_UNSUPPORTED;          // scores / weights, per-query supports or labels
+    if (!nw::half_form_shape_ok(d)) return NW_ERR_UNSUPPORTED;
+    if (B == 0 || N == 0 || C == 0) return NW_OK;                    // nothing to multiply: the common code answers
+    if (!s_split || !s_scale || !s_norm2) return NW_ERR_INVALID_ARG;
+    if ((reinterpret_cast<uintptr_t>(s_split) | reinterpret_cast<uintptr_t>(q)) & 15) return NW_ERR_INVALID_ARG;
+    if (!nw::fused_eligible(q, s_split, B, N, d, C)) return NW_ERR_UNSUPPORTED;   // N <= 25, sizes past the tile kernels
+    (void)s;
+    return NW_OK;
+}
 
 extern "C" int nw_debug_set(const char* name, int value) {
     if (!name) return NW_ERR_INVALID_ARG;
@@ -140,6 +155,18 @@ extern "C" int nw_fwd_f32(const float* q, const float* s, const int64_t* sy, con
     if (N > 0 && (!q || !s || !sy)) return NW_ERR_INVALID_ARG;
     if (kind == NW_SCORE_CLIP && !logit_scale_dev) return NW_ERR_INVALID_ARG;
     if (labels_batched && !sup_batched) return NW_ERR_INVALID_ARG;
+    const int form = nw::fwd_opts().operand_form;
+    if (form != 0 && form != 1) return NW_ERR_INVALID_ARG;
+    if (form == 1) {
+        const int rc = half_form_check(q, s, s_norm2, s_split, s_scale, scores_out ? scores_out : weights_out,
+                                       sup_batched || labels_batched, B, N, d, C);
+        if (rc != NW_OK) return rc;
+        if (N > 0 && C > 0) {
+            if (!workspace || workspace_bytes < nw_fwd_workspace_bytes(B, N, d, C)) return NW_ERR_WORKSPACE;
+            return nw::launch_fused_half(q, s_split, sy, s_norm2, s_scale, logit_scale_dev, out, lse_out, nullptr, nullptr,
+                                         nullptr, workspace, workspace_bytes, B, N, d, C, kind, st);
+        }
+    }
     // Softmax weights on request: the fused kernel writes the scores where the weights go and one in-place pass
     // normalises them with the merge's log-sum-exp (w = exp(score - lse)); the two-kernel fallback below streams
     // the (B,N) matrix five times.
@@ -196,8 +223,17 @@ extern "C" int nw_fwd_partial_f32(const float* q, const float* s, const int64_t*
     if (!m || !den || (!num && C > 0)) return NW_ERR_INVALID_ARG;
     if (N > 0 && (!q || !s || !sy)) return NW_ERR_INVALID_ARG;
     if (kind == NW_SCORE_CLIP && !logit_scale_dev) return NW_ERR_INVALID_ARG;
+    const int form = nw::fwd_opts().operand_form;
+    if (form != 0 && form != 1) return NW_ERR_INVALID_ARG;
+    if (form == 1) {
+        const int rc = half_form_check(q, s, s_norm2, s_split, s_scale, nullptr, 0, B, N, d, C);
+        if (rc != NW_OK) return rc;
+    }
     float* scores = static_cast<float*>(workspace);
     if (N > 0 && (!workspace || workspace_bytes < nw_fwd_workspace_bytes(B, N, d, C))) return NW_ERR_WORKSPACE;
+    if (form == 1 && N > 0 && C > 0)
+        return nw::launch_fused_half(q, s_split, sy, s_norm2, s_scale, logit_scale_dev, nullptr, nullptr, m, den, num,
+                                     workspace, workspace_bytes, B, N, d, C, kind, st);
     if (N > 0 && C > 0 && nw::fused_eligible(q, s, B, N, d, C)) {
         if (s_split && s_scale && s_norm2 && d % 32 == 0 && split_pays(B, N, d) &&
             ((reinterpret_cast<uintptr_t>(s_split) | reinterpret_cast<uintptr_t>(q)) & 15) == 0) {
@@ -245,6 +281,7 @@ extern "C" int nw_fwd_influence_f32(const float* q, const float* s, const int64_
     OptsGuard opts_guard(opts);
     hipStream_t st = static_cast<hipStream_t>(stream);
     if (B < 0 || N < 0 || d < 0 || C < 0) return NW_ERR_INVALID_ARG;
+    if (nw::fwd_opts().operand_form != 0) return NW_ERR_UNSUPPORTED;   // influences need the score matrix: split or fp32 operands
     if (B == 0) return NW_OK;
     if (N == 0 || C == 0)   // no supports: log(0 + 1e-12) and nothing to score
         return nw_fwd_f32(q, s, sy, s_norm2, s_split, s_scale, out, nullptr, lse_out, nullptr, workspace, workspace_bytes,

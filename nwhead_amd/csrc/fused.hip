@@ -25,7 +25,10 @@ namespace nw {
     extern template int launch_fused_kind<K>(const float*, const float*, const int64_t*, const float*,   \
                                              const float*,                                               \
                                              const float*, float*, float*, float*, float*, float*,       \
-                                             float*, void*, size_t, int, int, int, int, hipStream_t);
+                                             float*, void*, size_t, int, int, int, int, hipStream_t); \
+    extern template int launch_fused_half_kind<K>(const float*, const void*, const int64_t*, const float*, const float*, \
+                                                  const float*, float*, float*, float*, float*, float*, void*, size_t,   \
+                                                  int, int, int, int, hipStream_t);
 NW_EXTERN_FUSED_KIND(NW_SCORE_EUCLIDEAN)
 NW_EXTERN_FUSED_KIND(NW_SCORE_HYPERSPHERE)
 NW_EXTERN_FUSED_KIND(NW_SCORE_COSINE)
@@ -455,8 +458,8 @@ int env_rs() {
 }  // namespace
 
 // The query-split area sits behind the fused area, at the tail of nw_fwd_workspace_bytes (capi.hip sizes it).
-int split_queries_into_workspace(const float* q, void* workspace, size_t workspace_bytes, int64_t B, int64_t N, int64_t d,
-                                 int64_t C, float** rows, float** scale, float** norm2, hipStream_t st) {
+int query_area_of_workspace(void* workspace, size_t workspace_bytes, int64_t B, int64_t N, int64_t d, int64_t C, float** rows,
+                            float** scale, float** norm2) {
     const size_t total = nw_fwd_workspace_bytes(B, N, d, C);
     if (!workspace || workspace_bytes < total) return NW_ERR_WORKSPACE;
     const size_t a = al256((size_t)B * (size_t)d * sizeof(float)), b = al256((size_t)B * sizeof(float));
@@ -464,6 +467,13 @@ int split_queries_into_workspace(const float* q, void* workspace, size_t workspa
     *rows = reinterpret_cast<float*>(base);
     *scale = reinterpret_cast<float*>(base + a);
     *norm2 = reinterpret_cast<float*>(base + a + b);
+    return NW_OK;
+}
+
+int split_queries_into_workspace(const float* q, void* workspace, size_t workspace_bytes, int64_t B, int64_t N, int64_t d,
+                                 int64_t C, float** rows, float** scale, float** norm2, hipStream_t st) {
+    const int rc = query_area_of_workspace(workspace, workspace_bytes, B, N, d, C, rows, scale, norm2);
+    if (rc != NW_OK) return rc;
     return launch_split_rows(q, *rows, *scale, *norm2, B, d, st);
 }
 
@@ -598,7 +608,15 @@ size_t fused_workspace_bytes(int64_t B, int64_t N, int64_t d, int64_t C) {
         const size_t n = fused_layout(B, n_stiles, 16 * rs, nullptr, nullptr, C);
         need = n > need ? n : need;
     }
+    if (half_form_shape_ok(d)) {  // nw_fwd_opts.operand_form = 1 runs on tiles of 128 supports at every size
+        const size_t n = fused_layout(B, (N + BANK_BS - 1) / BANK_BS, BANK_BS, nullptr, nullptr, C);
+        need = n > need ? n : need;
+    }
     return need;
+}
+
+bool half_form_shape_ok(int64_t d) {   // whole 64-k stages, at least three of them (fused_f16p12.h), tile-relative offsets
+    return d % 64 == 0 && d >= 192 && d <= (1 << 20);
 }
 
 bool fused_eligible(const float* q, const float* s, int64_t B, int64_t N, int64_t d, int64_t C) {
@@ -615,6 +633,22 @@ int launch_fused(const float* q, const float* s, const int64_t* sy, const float*
                  hipStream_t st) {
 #define NW_KIND_CASE(K) \
     case K: return launch_fused_kind<K>(q, s, sy, s_norm2, s_scale, ls, out, scores, lse, m, den, num, workspace, workspace_bytes, (int)B, (int)N, (int)d, (int)C, st)
+    switch (kind) {
+        NW_KIND_CASE(NW_SCORE_EUCLIDEAN);
+        NW_KIND_CASE(NW_SCORE_HYPERSPHERE);
+        NW_KIND_CASE(NW_SCORE_COSINE);
+        NW_KIND_CASE(NW_SCORE_DOT);
+        NW_KIND_CASE(NW_SCORE_CLIP);
+        default: return NW_ERR_UNSUPPORTED;
+    }
+#undef NW_KIND_CASE
+}
+
+int launch_fused_half(const float* q, const void* s_rows, const int64_t* sy, const float* s_norm2, const float* s_scale,
+                      const float* ls, float* out, float* lse, float* m, float* den, float* num, void* workspace,
+                      size_t workspace_bytes, int64_t B, int64_t N, int64_t d, int64_t C, int kind, hipStream_t st) {
+#define NW_KIND_CASE(K) \
+    case K: return launch_fused_half_kind<K>(q, s_rows, sy, s_norm2, s_scale, ls, out, lse, m, den, num, workspace, workspace_bytes, (int)B, (int)N, (int)d, (int)C, st)
     switch (kind) {
         NW_KIND_CASE(NW_SCORE_EUCLIDEAN);
         NW_KIND_CASE(NW_SCORE_HYPERSPHERE);

@@ -17,6 +17,11 @@
 //     order, k chunks rotated by the support tile, support tiles of 128 rows, workspace layout and run tables unchanged.
 // Configuration interface, tile order and loader role: persistent_pipe.h, shared with fused_f16p.h.
 // Requires d / 32 >= 3 (the header of a tile rides with its first stage, two stages ahead).
+//
+// HALF = true (nw_fwd_opts.operand_form = 1): q and s are PLAIN fp16 rows (nw_pack_rows_f16) and `d` is their row stride
+// in floats, half the embedding width.  Nothing but the multiply step differs: a 128-byte stage row is then 64
+// consecutive k instead of [32 h | 32 l], the same two 16-byte slots per lane are k 8g .. 8g + 7 and 32 + 8g .. 32 + 8g + 7,
+// and an accumulator takes two products per stage (k ascending) where the split form takes three for half the k.
 #pragma once
 #include "fused_f16p.h"
 
@@ -250,7 +255,7 @@ __device__ __forceinline__ void epilogue_p12(f32x4 (&acc)[P12::QB][P12::RS], con
     NW_PSTAMP(5);
 }
 
-template <int KIND>
+template <int KIND, bool HALF = false>
 __global__ __launch_bounds__(P12::THREADS, 3) void nw_fused_f16p_kernel_w12(
     const float* __restrict__ q, const float* __restrict__ s, const float* __restrict__ s_norm2,
     const float* __restrict__ s_scale, const float* __restrict__ q_norm2, const float* __restrict__ q_scale,
@@ -301,19 +306,31 @@ __global__ __launch_bounds__(P12::THREADS, 3) void nw_fused_f16p_kernel_w12(
         auto pin = []() { __builtin_amdgcn_sched_barrier(0); };
         f32x4 acc[QB][RS];
         // the twelve MFMAs of pair p: four independent accumulator chains, per accumulator al x bh, ah x bl, ah x bh
+        // (HALF: eight, per accumulator lo x lo, hi x hi)
         auto mm_w = [&](const SW& w, const QF& f, int p) {
+            if constexpr (HALF) {  // plain fp16 rows: slot `sh` holds k 0 .. 31 of the stage's 64, slot `sl` k 32 .. 63
 #pragma unroll
-            for (int x = 0; x < 2; ++x)
+                for (int x = 0; x < 2; ++x)
 #pragma unroll
-                for (int j = 0; j < QB; ++j) acc[j][2 * p + x] = mm(w.al[x], f.bh[j], acc[j][2 * p + x]);
+                    for (int j = 0; j < QB; ++j) acc[j][2 * p + x] = mm(w.ah[x], f.bh[j], acc[j][2 * p + x]);
 #pragma unroll
-            for (int x = 0; x < 2; ++x)
+                for (int x = 0; x < 2; ++x)
 #pragma unroll
-                for (int j = 0; j < QB; ++j) acc[j][2 * p + x] = mm(w.ah[x], f.bl[j], acc[j][2 * p + x]);
+                    for (int j = 0; j < QB; ++j) acc[j][2 * p + x] = mm(w.al[x], f.bl[j], acc[j][2 * p + x]);
+            } else {
 #pragma unroll
-            for (int x = 0; x < 2; ++x)
+                for (int x = 0; x < 2; ++x)
 #pragma unroll
-                for (int j = 0; j < QB; ++j) acc[j][2 * p + x] = mm(w.ah[x], f.bh[j], acc[j][2 * p + x]);
+                    for (int j = 0; j < QB; ++j) acc[j][2 * p + x] = mm(w.al[x], f.bh[j], acc[j][2 * p + x]);
+#pragma unroll
+                for (int x = 0; x < 2; ++x)
+#pragma unroll
+                    for (int j = 0; j < QB; ++j) acc[j][2 * p + x] = mm(w.ah[x], f.bl[j], acc[j][2 * p + x]);
+#pragma unroll
+                for (int x = 0; x < 2; ++x)
+#pragma unroll
+                    for (int j = 0; j < QB; ++j) acc[j][2 * p + x] = mm(w.ah[x], f.bh[j], acc[j][2 * p + x]);
+            }
             __builtin_amdgcn_sched_barrier(0);
         };
         SW wa, wb;

@@ -28,6 +28,9 @@ int launch_merge_runs(const FusedWs& ws, float* out, float* lse, float* m, float
 // split form of the query batch in the tail of the forward workspace (fused.hip)
 int split_queries_into_workspace(const float* q, void* workspace, size_t workspace_bytes, int64_t B, int64_t N, int64_t d,
                                  int64_t C, float** rows, float** scale, float** norm2, hipStream_t st);
+// that area itself: rows (B * d floats), scales, norms
+int query_area_of_workspace(void* workspace, size_t workspace_bytes, int64_t B, int64_t N, int64_t d, int64_t C, float** rows,
+                            float** scale, float** norm2);
 int device_cu_count();
 bool env_flag(const char* name);
 int tile_timer_start(hipStream_t st);          // diagnostics (nw_debug_tile_timing): -1 when disabled
@@ -529,10 +532,54 @@ int launch_f16p(const float* q, const float* s, const int64_t* sy, const float* 
 }
 }  // namespace
 
+// The head on half-precision operands (nw_fwd_opts.operand_form = 1): always nw_fused_f16p_kernel_w12<KIND, true> on tiles of
+// 128 supports, whatever the size -- the tile-count rule of launch_fused_rs is a speed heuristic, and this form has no
+// other kernel.  s_rows / s_scale / s_norm2: nw_pack_rows_f16 of the bank; the queries are packed here, into the query
+// area at the tail of the workspace.  Run tables, workspace layout and merge are those of the split path.
+template <int KIND>
+int launch_fused_half_kind(const float* q, const void* s_rows, const int64_t* sy, const float* s_norm2, const float* s_scale,
+                           const float* ls, float* out, float* lse, float* m, float* den, float* num, void* workspace,
+                           size_t workspace_bytes, int B, int N, int d, int C, hipStream_t st) {
+    using P = P12;
+    constexpr int BS = P::BS;
+    const int n_stiles = (N + BS - 1) / BS;
+    FusedWs ws;
+    const size_t need = fused_layout(B, n_stiles, BS, static_cast<char*>(workspace), &ws, C);
+    if (!workspace || workspace_bytes < need) return NW_ERR_WORKSPACE;
+    if (!bank_tables_take(sy, N, C, n_stiles, BS, &ws)) {
+        const int rc = launch_run_tables(ws, sy, N, C, n_stiles, BS, st);
+        if (rc != NW_OK) return rc;
+    }
+    float *qr, *qsc, *qn;
+    int rc = query_area_of_workspace(workspace, workspace_bytes, B, N, d, C, &qr, &qsc, &qn);
+    if (rc != NW_OK) return rc;
+    rc = launch_pack_rows_f16(q, qr, qsc, qn, B, d, st);
+    if (rc != NW_OK) return rc;
+    int cus = device_cu_count() & ~7;
+    const int wg_cap = fwd_opts().persistent_wgs & ~7;
+    if (wg_cap >= 8 && wg_cap < cus) cus = wg_cap;
+    static const bool attr = hipFuncSetAttribute(reinterpret_cast<const void*>(nw_fused_f16p_kernel_w12<KIND, true>),
+                                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)P::LDS_BYTES) == hipSuccess;
+    (void)attr;
+    int qgrp = persistent_qgroup() / 2;
+    if (qgrp < 1) qgrp = 1;
+    const int timer_slot = tile_timer_start(st);
+    // d / 2: the row stride of the fp16 rows in floats -- the loader and the stage count follow from it
+    hipLaunchKernelGGL((nw_fused_f16p_kernel_w12<KIND, true>), dim3(cus), dim3(P::THREADS), P::LDS_BYTES, st, qr,
+                       static_cast<const float*>(s_rows), s_norm2, s_scale, qn, qsc, ls, ws.runid, ws.nrun, ws.bnd, ws.m, ws.den,
+                       ws.num, B, N, d / 2, n_stiles, (B + P::BQP - 1) / P::BQP, qgrp);
+    tile_timer_stop(timer_slot, st);
+    NW_CHECK_LAUNCH();
+    return launch_merge_runs(ws, out, lse, m, den, num, B, C, n_stiles, BS, st);
+}
+
 #define NW_INSTANTIATE_FUSED_KIND(K)                                                                   \
     template int launch_fused_kind<K>(const float*, const float*, const int64_t*, const float*,        \
                                       const float*,                                                    \
                                       const float*, float*, float*, float*, float*, float*, float*,    \
-                                      void*, size_t, int, int, int, int, hipStream_t);
+                                      void*, size_t, int, int, int, int, hipStream_t);                 \
+    template int launch_fused_half_kind<K>(const float*, const void*, const int64_t*, const float*, const float*,      \
+                                           const float*, float*, float*, float*, float*, float*, void*, size_t, int,   \
+                                           int, int, int, hipStream_t);
 
 }  // namespace nw

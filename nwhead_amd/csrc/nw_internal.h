@@ -72,6 +72,7 @@ struct FwdOpts {
     int64_t tables_N = -1;
     int persistent_wgs = 0;         // workgroups of the persistent tile kernel (0: one per CU)
     int force_split = 0;            // split-fp16 path at every size
+    int operand_form = 0;           // 0: s_split holds split rows; 1: plain fp16 rows (nw_pack_rows_f16)
 };
 const FwdOpts& fwd_opts();
 // Diagnostic knobs (nw_debug_set; timing experiments, never needed in normal use).  KNOB_UNSET when not set.  The library
@@ -92,6 +93,14 @@ int pick_rs(int64_t B, int64_t N, int64_t d, bool f16 = false);
 bool fused_eligible(const float* q, const float* s, int64_t B, int64_t N, int64_t d, int64_t C);
 size_t fused_workspace_bytes(int64_t B, int64_t N, int64_t d, int64_t C = 0);
 int launch_split_rows(const float* x, float* out, float* scale, float* norm2, int64_t rows, int64_t d,
+                      hipStream_t st);
+// split.hip: fp32 rows -> dense fp16 rows, row scales and the norms of the ROUNDED rows (nw_pack_rows_f16)
+int launch_pack_rows_f16(const float* x, void* out, float* scale, float* norm2, int64_t rows, int64_t d, hipStream_t st);
+// the head on half-precision operands (nw_fwd_opts.operand_form = 1): s_rows / s_scale / s_norm2 from nw_pack_rows_f16
+bool half_form_shape_ok(int64_t d);
+int launch_fused_half(const float* q, const void* s_rows, const int64_t* sy, const float* s_norm2, const float* s_scale,
+                      const float* logit_scale_dev, float* out, float* lse, float* m, float* den, float* num,
+                      void* workspace, size_t workspace_bytes, int64_t B, int64_t N, int64_t d, int64_t C, int kind,
                       hipStream_t st);
 int launch_fused(const float* q, const float* s, const int64_t* sy, const float* s_norm2,
                  const float* s_scale,

@@ -125,6 +125,101 @@ extern "C" int nw_split_rows_f16x2(const float* x, float* out_split, float* row_
 }
 
 // ------------------------------------------------------------------------------------------------------------------
+// fp32 rows -> plain fp16 rows (nw_pack_rows_f16): the operand of the half-precision head (nw_fwd_opts.operand_form = 1).
+// The scale rule of nw_split_rows_kernel, but only h = fp16(x * 2^e) is kept, as a dense (rows, d) fp16 matrix, and
+// norm2[r] = sum_k (h_k * 2^-e)^2: the norms of the ROUNDED rows, so that the head of these operands is the exact head of
+// the rounded features.  One wave per row; 4*d bytes in, 2*d out.
+namespace nw {
+namespace {
+
+__global__ __launch_bounds__(256) void nw_pack_rows_f16_kernel(const float* __restrict__ x, _Float16* __restrict__ out,
+                                                                float* __restrict__ scale, float* __restrict__ norm2,
+                                                                int64_t rows, int64_t d) {
+    const int64_t r = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    const int lane = threadIdx.x & 63;
+    if (r >= rows) return;
+    const float4* src = reinterpret_cast<const float4*>(x + r * d);
+    const int64_t n4 = d / 4;
+    constexpr int KEEP = 8;   // rows up to 2048 floats stay in registers between the maximum and the rounding
+    const bool in_regs = n4 <= 64 * KEEP;
+    float4 keep[KEEP];
+    float mx = 0.f;
+    auto amax4 = [](float m, const float4 v) {
+        return fmaxf(fmaxf(m, fmaxf(fabsf(v.x), fabsf(v.y))), fmaxf(fabsf(v.z), fabsf(v.w)));
+    };
+    if (in_regs) {
+#pragma unroll
+        for (int u = 0; u < KEEP; ++u) {
+            const int64_t c = lane + 64 * u;
+            keep[u] = (c < n4) ? src[c] : make_float4(0.f, 0.f, 0.f, 0.f);
+        }
+#pragma unroll
+        for (int u = 0; u < KEEP; ++u) mx = amax4(mx, keep[u]);
+    } else {
+        for (int64_t c = lane; c < n4; c += 64) mx = amax4(mx, src[c]);
+    }
+    mx = wave_max(mx);
+    int e = 0;
+    if (mx > 0.f && mx < INFINITY) {
+        frexpf(mx, &e);
+        e = 14 - e;
+        if (e > 126) e = 126;
+    }
+    const float up = ldexpf(1.f, e), down = ldexpf(1.f, -e);
+    typedef _Float16 half4 __attribute__((ext_vector_type(4)));
+    half4* dst = reinterpret_cast<half4*>(out + r * d);
+    float n2 = 0.f;
+    auto emit = [&](int64_t c, const float4 v) {
+        const float sv[4] = {v.x * up, v.y * up, v.z * up, v.w * up};
+        half4 h;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            h[k] = (_Float16)sv[k];
+            const float back = (float)h[k] * down;
+            n2 = __builtin_fmaf(back, back, n2);
+        }
+        dst[c] = h;
+    };
+    if (in_regs) {
+#pragma unroll
+        for (int u = 0; u < KEEP; ++u) {
+            const int64_t c = lane + 64 * u;
+            if (c < n4) emit(c, keep[u]);
+        }
+    } else {
+        for (int64_t c = lane; c < n4; c += 64) emit(c, src[c]);
+    }
+    n2 = wave_sum(n2);
+    if (lane == 0) {
+        scale[r] = down;
+        norm2[r] = n2;
+    }
+}
+
+}  // namespace
+
+int launch_pack_rows_f16(const float* x, void* out, float* scale, float* norm2, int64_t rows, int64_t d, hipStream_t st) {
+    if (rows <= 0) return NW_OK;
+    if ((rows + 3) / 4 > 0x7fffffffLL) return NW_ERR_INVALID_ARG;
+    hipLaunchKernelGGL(nw_pack_rows_f16_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, st, x,
+                       static_cast<_Float16*>(out), scale, norm2, rows, d);
+    NW_CHECK_LAUNCH();
+    return NW_OK;
+}
+
+}  // namespace nw
+
+extern "C" int nw_pack_rows_f16(const float* x, uint16_t* out_rows, float* row_scale, float* row_norm2, int64_t rows,
+                                int64_t d, void* stream) {
+    if (rows < 0 || d < 0) return NW_ERR_INVALID_ARG;
+    if (d % 64 != 0) return NW_ERR_UNSUPPORTED;
+    if (rows == 0) return NW_OK;
+    if (!x || !out_rows || !row_scale || !row_norm2) return NW_ERR_INVALID_ARG;
+    if ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(out_rows)) & 15) return NW_ERR_INVALID_ARG;
+    return nw::launch_pack_rows_f16(x, out_rows, row_scale, row_norm2, rows, d, static_cast<hipStream_t>(stream));
+}
+
+// ------------------------------------------------------------------------------------------------------------------
 // All convolution weights of a network -> the split-row operands of conv_nhwc.hip, in ONE launch per optimizer step
 // (the weights change every step; per convolution this was a permute, a flip and two split launches).
 // A job reads a torch (Cout, Cin, KH, KW) contiguous weight and writes one operand:

@@ -57,8 +57,13 @@ class NWNet(nn.Module):
                  kernel_type='euclidean', train_type='random', n_way=None, n_shot=1,
                  n_shot_random=1, n_shot_full=100, n_shot_cluster=1, n_neighbors=10,
                  env_array=None, debug_mode=False, device='cuda:0', return_mask=False, cluster_backend='auto',
-                 loader_workers=0, pin_memory=False, knn_per_query=False):
+                 loader_workers=0, pin_memory=False, knn_per_query=False, full_precision="fp32"):
         super().__init__()
+        # not in the reference: "fp16" serves predict(x, 'full') from a half-precision bank (ops.SplitBank(precision="fp16"):
+        # bank and query features rounded to fp16, half the bytes, a third of the matrix-core work); "fp32" is the parity path
+        if full_precision not in ("fp32", "fp16"):
+            raise ValueError(f"full_precision must be 'fp32' or 'fp16', got {full_precision!r}")
+        self.full_precision = full_precision
         self.knn_per_query = bool(knn_per_query)  # not in the reference: 'knn' / 'hnsw' modes give every query ITS OWN neighbours
         self.cluster_backend = cluster_backend   # not in the reference: where 'cluster' mode's k-means runs (utils.compute_clusters)
         # not in the reference either (its bank loaders are single-process, support.py:164-165): DataLoader workers and
@@ -158,7 +163,8 @@ class NWNet(nn.Module):
         info = self._compute_all_support_feats()
         self.sharded_bank = None                     # predict('full') serves the bank built here
         self.full_feat, self.full_y = info[0], info[1]
-        self.full_cache = ops.SplitBank(self.full_feat, labels=self.full_y)   # norms + split-fp16 rows for predict('full')
+        # norms + split-fp16 (or fp16) rows for predict('full')
+        self.full_cache = ops.SplitBank(self.full_feat, labels=self.full_y, precision=self.full_precision)
         self.full_norm2 = self.full_cache.norm2
         self.support_eval.build_infer_iters(*info)
         self.support_eval.knn.bank = self.support_eval.hnsw.bank = self.full_cache   # neighbour search over the same bank
@@ -194,7 +200,8 @@ class NWNet(nn.Module):
         feat = torch.cat(feats) if feats else torch.empty(0, d, device=self.device)
         y = torch.cat(labels) if labels else torch.empty(0, dtype=torch.int64, device=self.device)
         self.sharded_bank = ShardedBank(feat, y, self.n_classes, self.kernel.kind, self.kernel._logit_scale(),
-                                        group=group, partial_fn=partial_fn, merge_fn=merge_fn)
+                                        group=group, partial_fn=partial_fn, merge_fn=merge_fn,
+                                        precision=self.full_precision)
         return self.sharded_bank
 
     def predict(self, x, mode='random'):
@@ -214,7 +221,7 @@ class NWNet(nn.Module):
             sfeat, sy = sfeat.to(x.device), sy.to(x.device)
             cache = getattr(self, 'full_cache', None)
             if cache is None or not cache.matches(sfeat):   # the bank was replaced or updated since precompute()
-                cache = self.full_cache = ops.SplitBank(sfeat, labels=sy)
+                cache = self.full_cache = ops.SplitBank(sfeat, labels=sy, precision=self.full_precision)
             out = self.nwhead(qfeat, sfeat, sy, support_cache=cache)
         else:
             out = self.nwhead(qfeat, sfeat.to(x.device), sy.to(x.device))

@@ -100,12 +100,12 @@ _WS_CACHE = {}
 _OPTS = {}
 
 
-def _default_opts(persistent_wgs=0):
+def _default_opts(persistent_wgs=0, operand_form=0):
     """The nw_fwd_opts of a call without cached run tables (kept alive here; NW_SPLIT_ALWAYS read when first needed)."""
-    key = (int(persistent_wgs), _lib.force_split())
+    key = (int(persistent_wgs), _lib.force_split(), int(operand_form))
     op = _OPTS.get(key)
     if op is None:
-        op = _OPTS[key] = _lib.fwd_opts(persistent_wgs=persistent_wgs)
+        op = _OPTS[key] = _lib.fwd_opts(persistent_wgs=persistent_wgs, operand_form=operand_form)
     return C_addr(op)
 
 
@@ -200,9 +200,21 @@ class SplitBank:
     per RUN of equal consecutive labels, so a class-sorted bank (what precompute() builds) costs 1-2 sums
     per tile and an unsorted one a sum per row (measured 1862 vs 322 us at B=2048, N=50000).  The output
     does not depend on the order of the supports, so when unsorted labels are given the bank keeps a
-    class-sorted copy (``sorted_rows`` / ``sorted_labels``, stable order) and nw_head runs on that."""
+    class-sorted copy (``sorted_rows`` / ``sorted_labels``, stable order) and nw_head runs on that.
 
-    def __init__(self, s, labels=None):
+    ``precision="fp16"``: the optional reduced-precision bank.  Instead of split rows it holds the rows ROUNDED to fp16
+    with a power-of-two scale per row (nw_pack_rows_f16: ``packed``, ``packed_scale``, ``packed_norm2`` -- the norms of the
+    rounded rows): half the bytes, one fp16 product per term instead of three.  nw_head / nw_partials without gradients
+    and without ``return_weights`` then compute the exact head of the rounded features (queries are rounded the same way
+    inside the call; relative rounding 2^-11 per element).  The width is zero-padded to max(192, next multiple of 64);
+    ``split`` stays None and ``norm2`` holds the norms of the ORIGINAL rows, so every other use of the bank (training
+    steps, weights, scores, influences) runs as with a norms-only bank.  A bank of 25 rows or fewer, which no tile kernel
+    takes, keeps norms only."""
+
+    def __init__(self, s, labels=None, precision="fp32"):
+        if precision not in ("fp32", "fp16"):
+            raise ValueError(f"precision must be 'fp32' or 'fp16', got {precision!r}")
+        self.precision = precision
         _need_hip(s, labels)
         lib = _lib.load()
         sc = _f32c(s)
@@ -215,7 +227,12 @@ class SplitBank:
                 raise ValueError("support labels must be non-negative class indices (F.one_hot, nw.py:276, raises too)")
             self.label_max = hi                # nw_head refuses n_classes <= label_max, like F.one_hot
         self.pad, self.rows = 0, None
-        if sc.dim() == 2 and sc.shape[1] % 32 and sc.shape[1] >= 64 and sc.shape[0] > 0:
+        half = precision == "fp16" and sc.dim() == 2 and sc.shape[0] > 25
+        if half:
+            self.pad = max(192, -(-sc.shape[1] // 64) * 64) - sc.shape[1]
+            if self.pad:
+                sc = self.rows = torch.nn.functional.pad(sc, (0, self.pad))
+        elif precision == "fp32" and sc.dim() == 2 and sc.shape[1] % 32 and sc.shape[1] >= 64 and sc.shape[0] > 0:
             self.pad = (-sc.shape[1]) % 32
             sc = self.rows = torch.nn.functional.pad(sc, (0, self.pad))     # what the kernels read instead of `s`
         self.sorted_rows = self.sorted_labels = None
@@ -229,7 +246,16 @@ class SplitBank:
         N, d = sc.shape
         self.shape = (N, d)
         self.split = self.scale = None
-        if d % 32 == 0 and N > 0:
+        self.packed = self.packed_scale = self.packed_norm2 = None
+        if half:
+            self.packed = torch.empty(N, d, dtype=torch.float16, device=sc.device)
+            self.packed_scale = torch.empty(N, dtype=torch.float32, device=sc.device)
+            self.packed_norm2 = torch.empty(N, dtype=torch.float32, device=sc.device)
+            with torch.cuda.device(sc.device):
+                _lib.check(lib.nw_pack_rows_f16(_ptr(sc), _ptr(self.packed), _ptr(self.packed_scale), _ptr(self.packed_norm2),
+                                                N, d, _stream(sc)), "nw_pack_rows_f16")
+            self.norm2 = row_norm2(sc)
+        elif precision == "fp32" and d % 32 == 0 and N > 0:
             self.split = torch.empty_like(sc)
             self.scale = torch.empty(N, dtype=torch.float32, device=sc.device)
             self.norm2 = torch.empty(N, dtype=torch.float32, device=sc.device)
@@ -241,7 +267,7 @@ class SplitBank:
         self.tables = self._tables_src = None
         self.tables_label_max = -1
         self._opts = {}
-        if labels is not None and labels.dim() == 1 and self.split is not None:
+        if labels is not None and labels.dim() == 1 and (self.split is not None or self.packed is not None):
             self.build_tables(self.sorted_labels if self.sorted_labels is not None else labels)
 
     def build_tables(self, labels):
@@ -265,25 +291,34 @@ class SplitBank:
                        "nw_bank_tables_build")
         self.tables, self._tables_src, self._opts = tables, _sig(labels), {}
 
-    def call_opts(self, sy, n_classes, persistent_wgs=0, sy_call=None):
+    def call_opts(self, sy, n_classes, persistent_wgs=0, sy_call=None, operand_form=0):
         """Address of the nw_fwd_opts for a forward call with labels ``sy``: names the cached run tables when ``sy`` is the
         label tensor they were built from (same storage, unmodified) -- the object stays alive in this bank.  ``sy_call``:
         the int64 tensor whose address the call passes as its labels (``sy`` itself unless it had to be converted); the
-        library uses the tables only for that address and row count."""
+        library uses the tables only for that address and row count.  ``operand_form``: 1 when the call passes this
+        bank's ``packed`` rows (nw_fwd_opts.operand_form)."""
         if self.tables is not None and _sig(sy) == self._tables_src:
             syc = sy if sy_call is None else sy_call
             if self.tables_label_max >= int(n_classes):
                 raise ValueError(f"support label {self.tables_label_max} is outside [0, n_classes={int(n_classes)}) "
                                  "(the reference's F.one_hot, nw.py:276, raises)")
-            key = (int(persistent_wgs), _lib.force_split(), syc.data_ptr(), syc.numel())
+            key = (int(persistent_wgs), _lib.force_split(), syc.data_ptr(), syc.numel(), int(operand_form))
             op = self._opts.get(key)
             if op is None:
                 if len(self._opts) > 64:
                     self._opts.clear()
                 op = self._opts[key] = _lib.fwd_opts(self.tables.data_ptr(), self.tables.numel(), persistent_wgs,
-                                                     syc.data_ptr(), syc.numel())
+                                                     syc.data_ptr(), syc.numel(), operand_form)
             return C_addr(op)
-        return _default_opts(persistent_wgs)
+        return _default_opts(persistent_wgs, operand_form)
+
+    def half_operands(self, d):
+        """(norm2, rows, scale) of the fp16 form for a call whose queries are ``d`` wide, or None when this bank has none."""
+        if self.packed is None:
+            return None
+        if d != self.shape[1]:
+            raise ValueError(f"queries of width {d} against an fp16 bank of (padded) width {self.shape[1]}")
+        return self.packed_norm2, self.packed, self.packed_scale
 
     def matches(self, s):
         """True when `s` is the very tensor (storage, shape, no in-place update since) this bank was prepared from."""
@@ -304,8 +339,8 @@ def _resolve_sorted_bank(s, sy, cache, per_position_outputs=False):
 
 
 def _apply_bank_padding(q, s, cache):
-    """A bank of a width that is not a multiple of 32 holds zero-padded rows (SplitBank.rows / .sorted_rows): pad the
-    queries alike and read the bank's rows instead of the caller's tensor."""
+    """A bank of a width that is not a multiple of 32 (fp16 banks: of 64, or below 192) holds zero-padded rows
+    (SplitBank.rows / .sorted_rows): pad the queries alike and read the bank's rows instead of the caller's tensor."""
     if cache is None or not cache.pad:
         return q, s
     q = torch.nn.functional.pad(q, (0, cache.pad))
@@ -353,6 +388,11 @@ class _NWHeadFn(torch.autograd.Function):
                 _lib.check(lib.nw_split_rows_f16x2(_ptr(sc), _ptr(ssplit), _ptr(sscale), _ptr(sn2), N, d, _stream(qc)),
                            "nw_split_rows_f16x2")
         out = torch.empty(B, n_classes, dtype=torch.float32, device=dev)
+        form = 0
+        if cache is not None and not need_bwd and not want_weights and not sup_b:
+            half = cache.half_operands(d)
+            if half is not None:     # an fp16 bank: the head of the rounded features (nw_fwd_opts.operand_form = 1)
+                (sn2, ssplit, sscale), form = half, 1
         scores = torch.empty(B, N, dtype=torch.float32, device=dev) if need_bwd else None
         lse = torch.empty(B, dtype=torch.float32, device=dev) if need_bwd else None
         weights = torch.empty(B, N, dtype=torch.float32, device=dev) if want_weights else None
@@ -360,7 +400,7 @@ class _NWHeadFn(torch.autograd.Function):
         ws_bytes = _fwd_ws_bytes(lib, B, N, d, n_classes)
         st = _stream(qc)
         ws = _workspace(ws_bytes, dev, st) if ws_bytes else None
-        opts = cache.call_opts(sy, n_classes, sy_call=syc) if cache is not None else _default_opts()
+        opts = cache.call_opts(sy, n_classes, sy_call=syc, operand_form=form) if cache is not None else _default_opts()
         with _OnDevice(dev):
             rc = lib.nw_fwd_f32(_ptr(qc), _ptr(sc), _ptr(syc), _ptr(sn2), _ptr(ssplit), _ptr(sscale), _ptr(out),
                                 _ptr(scores), _ptr(lse),
@@ -404,7 +444,8 @@ def nw_head(q, s, sy, n_classes, kind="euclidean", logit_scale=None, return_weig
             support_norm2=None, support_cache=None, validate_labels=False):
     """NWHead.forward(x, sx, sy) -> (B,C) log-probs (and the (B,N) softmax weights on request).
     support_norm2: optional cached ``row_norm2(s)`` for a shared (N,d) support.
-    support_cache: optional ``SplitBank(s)`` (norms + split-fp16 rows: the fast 'full' inference path).
+    support_cache: optional ``SplitBank(s)`` (norms + split-fp16 rows: the fast 'full' inference path; built with
+    precision="fp16": the reduced-precision head of the rounded features, see SplitBank).
     validate_labels: the reference's F.one_hot (nw.py:276) REFUSES labels outside [0, n_classes); the kernels skip such
     supports silently (banks with labels check once, when they are built).  True: check here and raise F.one_hot's
     RuntimeError -- one device round trip per call, which is why it is opt-in (NWHead.validate_labels; NWNet's debug_mode
@@ -468,7 +509,7 @@ def nw_head(q, s, sy, n_classes, kind="euclidean", logit_scale=None, return_weig
 
 def nw_partials(q, s, sy, n_classes, kind="euclidean", logit_scale=None, support_cache=None):
     """This rank's (m, den, num) over its shard of the bank; no grad.  ``support_cache``: the
-    shard's SplitBank (split-fp16 fast path)."""
+    shard's SplitBank (split-fp16 fast path; an fp16 bank: the partials of the rounded features)."""
     _need_hip(q, s, sy, logit_scale)
     lib = _lib.load()
     qc, sc = _f32c(q), _f32c(s)
@@ -499,12 +540,17 @@ def nw_partials_into(packed, qc, sc, syc, n_classes, kind="euclidean", logit_sca
         ws = _workspace(ws_bytes, qc.device)
     ls = None if logit_scale is None else _f32c(logit_scale)
     ssplit = sscale = None
+    form = 0
     if cache is not None:
         if cache.sorted_rows is not None and sc.data_ptr() != cache.sorted_rows.data_ptr():
             raise ValueError("this SplitBank holds a class-sorted copy of its support: pass cache.sorted_rows / "
                              "cache.sorted_labels (or call nw_partials, which does)")
         sn2, ssplit, sscale = cache.norm2, cache.split, cache.scale
-    opts = cache.call_opts(syc, C, persistent_wgs, sy_call=syc) if cache is not None else _default_opts(persistent_wgs)
+        half = cache.half_operands(d)
+        if half is not None:
+            (sn2, ssplit, sscale), form = half, 1
+    opts = (cache.call_opts(syc, C, persistent_wgs, sy_call=syc, operand_form=form) if cache is not None
+            else _default_opts(persistent_wgs))
     with torch.cuda.device(qc.device):
         _lib.check(lib.nw_fwd_partial_f32(_ptr(qc), _ptr(sc), _ptr(syc), _ptr(sn2), _ptr(ssplit), _ptr(sscale),
                                           _ptr(m), _ptr(den), _ptr(num),

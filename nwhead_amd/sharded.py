@@ -40,8 +40,9 @@ def _coalesce(chunk):
 
 class ShardedBank:
     def __init__(self, feat_shard, y_shard, n_classes, kind="euclidean", logit_scale=None, group=None,
-                 partial_fn=None, merge_fn=None, persistent_wgs=None):
-        """persistent_wgs: workgroups of the persistent tile kernel (nw_fwd_opts.persistent_wgs, a multiple of 8; 0 = one per
+                 partial_fn=None, merge_fn=None, persistent_wgs=None, precision="fp32"):
+        """precision: "fp32" (split-fp16 rows, fp32-grade) or "fp16" (the reduced-precision bank of ops.SplitBank).
+        persistent_wgs: workgroups of the persistent tile kernel (nw_fwd_opts.persistent_wgs, a multiple of 8; 0 = one per
         CU).  Default: with more than one rank, all CUs but one per XCD (count - 8) -- the all-gather of bucket i runs
         under the kernels of bucket i + 1, and a kernel that holds one 160 KB-LDS workgroup on EVERY CU would leave RCCL's
         kernel nowhere to run until it ends; with one rank, one per CU."""
@@ -75,16 +76,16 @@ class ShardedBank:
                 self.class_lo = allb[:, 0].clamp(0, max(self.C - 1, 0)).contiguous()
                 self.y_local = (self.y - lo).contiguous()
         # the shard never changes: prepare it once (squared norms + split-fp16 rows, ops.SplitBank)
-        self.cache = ops.SplitBank(self.feat) if (partial_fn is None and self.feat.is_cuda) else None
+        self.cache = ops.SplitBank(self.feat, precision=precision) if (partial_fn is None and self.feat.is_cuda) else None
         self.norm2 = self.cache.norm2 if self.cache is not None else None
-        if self.cache is not None and self.cache.split is not None:
+        if self.cache is not None and (self.cache.split is not None or self.cache.packed is not None):
             self.cache.build_tables(self.y_local)   # the labels every call of this shard passes (self.y when there is one rank)
 
     # ---- HIP compute hooks (the product path)
     def _hip_partial(self, packed_row, q):
         N, d = self.feat.shape
         if self.cache is not None and self.cache.pad:
-            d = self.cache.shape[1]              # a shard of a width that is not a multiple of 32: the bank's padded rows
+            d = self.cache.shape[1]              # a shard whose bank holds zero-padded rows (ops.SplitBank.pad)
         B = q.shape[0]
         need = ops._lib.load().nw_fwd_workspace_bytes(B, N, d, self.CL)
         if self._ws is None or self._ws.numel() < need:
