@@ -278,6 +278,34 @@ int nw_topk_f32(const float *scores, int64_t *idx_out, float *val_out,
                 int64_t B, int64_t N, int64_t k, void *stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * The k best supports per query over a PREPARED bank, without the (B,N) score matrix.  Replaces the
+ * score matrix + descending argsort + cut to k columns of the reference's neighbour modes
+ * (KNN.__call__, nwhead/utils.py:185-193; NWNet.get_neighbors, nwhead/nw.py:245-249) for banks where
+ * that matrix is the cost: every tile of the split-fp16 tile kernel selects its k best scores in its
+ * epilogue, a second kernel takes the k best of every query's candidates.
+ *   q         (B,d) fp32 queries
+ *   s_split / s_scale / s_norm2   the bank as nw_split_rows_f16x2 leaves it ((N,d), (N,), (N,))
+ *   idx_out   (B,k) int64 bank rows, best score first, equal scores in ascending row order
+ *   val_out   optional (B,k) fp32: their scores (either zero is returned as +0.0)
+ * The scores are, bit for bit, those nw_fwd_f32 writes to scores_out from the same split operands,
+ * and the order is nw_topk_f32's: the result equals nw_topk_f32 of that matrix.
+ * 1 <= k <= min(N, 32), d % 32 == 0, N > 25 (the tile kernels' regime); anything else returns
+ * NW_ERR_UNSUPPORTED (callers go through nw_topk_f32), for which nw_knn_workspace_bytes returns 0.
+ * q, s_split and workspace 16-byte aligned.  Like every entry: no allocation, no synchronisation,
+ * no environment.  nw_knn_workspace_bytes is non-decreasing in B, N and k; to be so it visits the
+ * smaller shapes, up to a millisecond of host time: ask once per shape and keep the answer.
+ * ------------------------------------------------------------------------------------------- */
+size_t nw_knn_workspace_bytes(int64_t B, int64_t N, int64_t d, int64_t k);
+int nw_knn_f32(const float *q, const float *s_split, const float *s_scale, const float *s_norm2,
+               int64_t *idx_out, float *val_out, void *workspace, size_t workspace_bytes,
+               int64_t B, int64_t N, int64_t d, int64_t k, int kind, const float *logit_scale_dev,
+               void *stream);
+/* Whether nw_fwd_f32 / nw_fwd_partial_f32 with split operands (s_split, d % 32 == 0) and no force_split
+ * option run the split-fp16 tile kernel at this shape (1) or the fp32 one (0): the size rule alone.  For
+ * callers that promise the bits of that call's scores_out, like nw_knn_f32's. */
+int nw_scores_use_split(int64_t B, int64_t N, int64_t d);
+
+/* ---------------------------------------------------------------------------------------------
  * Eval-mode BatchNorm (+ ReLU) of the pre-activation backbones as one pass: out = max(x * scale[c] +
  * shift[c], 0).  Replaces the BatchNorm2d -> ReLU pairs in front of the convolutions of
  * model/densenet.py:33-60 (_DenseLayer norm1/relu1), :82-91 (_Transition) and :139 + :160 (norm5 + relu)

@@ -12,8 +12,9 @@ inline bool bad_kind(int kind) { return kind < NW_SCORE_EUCLIDEAN || kind > NW_S
 // Below ~2e8 multiply-adds the fp32-MFMA path with cached norms was the shorter one while the split-fp16 path
 // had a query-split launch in front (measured then: B=64 N=1000 d=512 19.7 vs 29.8 us; B=256 N=10000 d=512
 // 36.1 vs 23.9 us).  nw_fwd_opts.force_split takes the split path at every size.
+extern "C" int nw_scores_use_split(int64_t B, int64_t N, int64_t d);   // the size rule, for callers that must follow it
 static bool split_pays(int64_t B, int64_t N, int64_t d) {
-    return nw::fwd_opts().force_split || (double)B * (double)N * (double)d >= 2.0e8;
+    return nw::fwd_opts().force_split || nw_scores_use_split(B, N, d) != 0;
 }
 
 namespace nw {
@@ -265,6 +266,27 @@ extern "C" int nw_topk_f32(const float* scores, int64_t* idx_out, float* val_out
                            void* stream) {
     if (B < 0 || N < 0 || (B > 0 && (!scores || !idx_out))) return NW_ERR_INVALID_ARG;
     return nw::launch_topk(scores, idx_out, val_out, B, N, k, static_cast<hipStream_t>(stream));
+}
+
+extern "C" int nw_scores_use_split(int64_t B, int64_t N, int64_t d) {
+    return B > 0 && N > 0 && d > 0 && (double)B * (double)N * (double)d >= 2.0e8;
+}
+
+extern "C" size_t nw_knn_workspace_bytes(int64_t B, int64_t N, int64_t d, int64_t k) {
+    return nw::knn_workspace_bytes(B, N, d, k);
+}
+
+extern "C" int nw_knn_f32(const float* q, const float* s_split, const float* s_scale, const float* s_norm2, int64_t* idx_out,
+                          float* val_out, void* workspace, size_t workspace_bytes, int64_t B, int64_t N, int64_t d,
+                          int64_t k, int kind, const float* logit_scale_dev, void* stream) {
+    if (B < 0 || N < 0 || d < 0) return NW_ERR_INVALID_ARG;
+    if (bad_kind(kind)) return NW_ERR_UNSUPPORTED;
+    if (B > 0 && (!q || !s_split || !s_scale || !s_norm2 || !idx_out)) return NW_ERR_INVALID_ARG;
+    if (kind == NW_SCORE_CLIP && !logit_scale_dev) return NW_ERR_INVALID_ARG;
+    if ((reinterpret_cast<uintptr_t>(s_split) | reinterpret_cast<uintptr_t>(q) | reinterpret_cast<uintptr_t>(workspace)) & 15)
+        return NW_ERR_INVALID_ARG;
+    return nw::launch_knn(q, s_split, s_scale, s_norm2, idx_out, val_out, workspace, workspace_bytes, B, N, d, k, kind,
+                          logit_scale_dev, static_cast<hipStream_t>(stream));
 }
 
 extern "C" int nw_debug_tile_timing(int enable) { return nw::tile_timer_enable(enable != 0); }

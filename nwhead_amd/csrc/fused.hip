@@ -25,7 +25,7 @@ namespace nw {
     extern template int launch_fused_kind<K>(const float*, const float*, const int64_t*, const float*,   \
                                              const float*,                                               \
                                              const float*, float*, float*, float*, float*, float*,       \
-                                             float*, void*, size_t, int, int, int, int, hipStream_t); \
+                                             float*, void*, size_t, int, int, int, int, hipStream_t, const CandOut*); \
     extern template int launch_fused_half_kind<K>(const float*, const void*, const int64_t*, const float*, const float*, \
                                                   const float*, float*, float*, float*, float*, float*, void*, size_t,   \
                                                   int, int, int, int, hipStream_t);
@@ -632,7 +632,7 @@ int launch_fused(const float* q, const float* s, const int64_t* sy, const float*
                  size_t workspace_bytes, int64_t B, int64_t N, int64_t d, int64_t C, int kind,
                  hipStream_t st) {
 #define NW_KIND_CASE(K) \
-    case K: return launch_fused_kind<K>(q, s, sy, s_norm2, s_scale, ls, out, scores, lse, m, den, num, workspace, workspace_bytes, (int)B, (int)N, (int)d, (int)C, st)
+    case K: return launch_fused_kind<K>(q, s, sy, s_norm2, s_scale, ls, out, scores, lse, m, den, num, workspace, workspace_bytes, (int)B, (int)N, (int)d, (int)C, st, nullptr)
     switch (kind) {
         NW_KIND_CASE(NW_SCORE_EUCLIDEAN);
         NW_KIND_CASE(NW_SCORE_HYPERSPHERE);
@@ -658,6 +658,91 @@ int launch_fused_half(const float* q, const void* s_rows, const int64_t* sy, con
         default: return NW_ERR_UNSUPPORTED;
     }
 #undef NW_KIND_CASE
+}
+
+// ---- nearest-neighbour search without the (B,N) score matrix (nw_knn_f32): the tile kernel's candidate output
+// (fused_impl.h, OUT_CAND) under the launch decision of the score-writing call, then the k best of every query's
+// candidates (topk.hip).
+namespace {
+struct KnnWs {
+    CandOut cand;
+    int64_t n_stiles;
+    int kcp;
+};
+bool knn_shape_ok(int64_t B, int64_t N, int64_t d, int64_t k) {
+    return B >= 0 && N > 25 && d >= BK && d % BK == 0 && k >= 1 && k <= 32 && k <= N && B < (1 << 30) && N < (1 << 30) &&
+           d <= (1 << 20);   // (d: the loaders' tile-relative offsets, as in launch_fused_rs)
+}
+size_t knn_layout(int64_t B, int64_t N, int64_t d, int64_t k, char* base, KnnWs* out) {
+    const int BS = 16 * pick_rs(B, N, d, true);   // the tile height of the score-writing call of this shape
+    KnnWs w;
+    w.n_stiles = (N + BS - 1) / BS;
+    w.kcp = cand_slots((int)k, BS);
+    size_t off = 0;
+    auto take = [&](size_t bytes) {
+        char* p = base ? base + off : nullptr;
+        off += al256(bytes);
+        return p;
+    };
+    const size_t slots = (size_t)B * (size_t)w.n_stiles * (size_t)w.kcp;
+    w.cand.key = reinterpret_cast<unsigned*>(take(slots * 4));
+    w.cand.row = reinterpret_cast<int*>(take(slots * 4));
+    w.cand.q_rows = reinterpret_cast<float*>(take((size_t)B * (size_t)d * 4));
+    w.cand.q_scale = reinterpret_cast<float*>(take((size_t)B * 4));
+    w.cand.q_norm2 = reinterpret_cast<float*>(take((size_t)B * 4));
+    w.cand.k = (int)k;
+    if (out) *out = w;
+    return off;
+}
+}  // namespace
+
+// What the call needs, made non-decreasing in B, N and k: the tile height follows the shape (pick_rs), and a larger shape
+// on taller tiles can need LESS than a smaller one on short tiles -- so the answer is the largest need over the shapes
+// up to (B, N).  Only shapes below the large-grid rule of pick_rs (fewer than 1024 tiles of 128 rows: there the height
+// is fixed and the need grows with the shape) have to be visited, one N per 16 rows and one B per 64 queries.
+size_t knn_workspace_bytes(int64_t B, int64_t N, int64_t d, int64_t k) {
+    if (!knn_shape_ok(B, N, d, k) || B == 0) return 0;
+    if (pick_rs(B, N, d, true) > 10) return 0;   // (the tile_rs knob at 12: no candidate form, launch_fused_rs refuses)
+    size_t need = knn_layout(B, N, d, k, nullptr, nullptr);
+    const int64_t nq = (B + BQ - 1) / BQ;
+    for (int64_t qt = 1; qt <= nq && qt < 1024; ++qt) {
+        const int64_t Bq = qt * BQ < B ? qt * BQ : B;
+        for (int64_t n = 17; n <= N && qt * ((n + 127) / 128) < 1024; n += 16) {   // n: the least N of its 16 rows
+            const int64_t nn = n > 26 ? n : 26;
+            if (nn > N || k > nn) continue;
+            const size_t x = knn_layout(Bq, nn, d, k, nullptr, nullptr);
+            need = x > need ? x : need;
+        }
+    }
+    return need;
+}
+
+int launch_knn(const float* q, const float* s_split, const float* s_scale, const float* s_norm2, int64_t* idx, float* vals,
+               void* workspace, size_t workspace_bytes, int64_t B, int64_t N, int64_t d, int64_t k, int kind, const float* ls,
+               hipStream_t st) {
+    if (!knn_shape_ok(B, N, d, k)) return NW_ERR_UNSUPPORTED;
+    if (B == 0) return NW_OK;
+    KnnWs w;
+    const size_t need = knn_layout(B, N, d, k, static_cast<char*>(workspace), &w);
+    if (!workspace || workspace_bytes < need) return NW_ERR_WORKSPACE;
+    if (w.n_stiles * w.kcp >= (1ll << 31)) return NW_ERR_UNSUPPORTED;
+    int rc;
+#define NW_KIND_CASE(K)                                                                                                     \
+    case K:                                                                                                                 \
+        rc = launch_fused_kind<K>(q, s_split, nullptr, s_norm2, s_scale, ls, nullptr, nullptr, nullptr, nullptr, nullptr,   \
+                                  nullptr, nullptr, 0, (int)B, (int)N, (int)d, 1, st, &w.cand);                             \
+        break
+    switch (kind) {
+        NW_KIND_CASE(NW_SCORE_EUCLIDEAN);
+        NW_KIND_CASE(NW_SCORE_HYPERSPHERE);
+        NW_KIND_CASE(NW_SCORE_COSINE);
+        NW_KIND_CASE(NW_SCORE_DOT);
+        NW_KIND_CASE(NW_SCORE_CLIP);
+        default: return NW_ERR_UNSUPPORTED;
+    }
+#undef NW_KIND_CASE
+    if (rc != NW_OK) return rc;
+    return launch_topk_candidates(w.cand.key, w.cand.row, idx, vals, B, w.n_stiles * w.kcp, k, st);
 }
 
 }  // namespace nw

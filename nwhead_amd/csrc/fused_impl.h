@@ -31,6 +31,17 @@ int split_queries_into_workspace(const float* q, void* workspace, size_t workspa
 // that area itself: rows (B * d floats), scales, norms
 int query_area_of_workspace(void* workspace, size_t workspace_bytes, int64_t B, int64_t N, int64_t d, int64_t C, float** rows,
                             float** scale, float** norm2);
+// Candidate output of the tile kernel (nw_knn_f32): instead of softmax partials every (query, support tile) pair leaves
+// its kc = min(k, tile rows) best scores, best first, ties in ascending bank-row order, as ordered_bits keys (0: empty slot)
+// and bank rows: key / row [b][st][j], j < kcp = kc rounded up to 4.  q_rows / q_scale / q_norm2: room for the split form
+// of the queries when the launch decision asks for the split launch.
+struct CandOut {
+    unsigned* key;
+    int* row;
+    int k;
+    float *q_rows, *q_scale, *q_norm2;
+};
+__host__ __device__ inline int cand_slots(int k, int BS) { return ((k < BS ? k : BS) + 3) & ~3; }
 int device_cu_count();
 bool env_flag(const char* name);
 int tile_timer_start(hipStream_t st);          // diagnostics (nw_debug_tile_timing): -1 when disabled
@@ -55,6 +66,9 @@ namespace {
 //    and the single-buffered loop ran 750 cycles per stage against 530: 18.5-19.4 us against 16.4.)
 enum { MODE_REG = 0, MODE_DMA = 1, MODE_DMA_SN = 2, MODE_F16 = 3, MODE_F16Q = 4 };
 constexpr bool mode_is_f16(int m) { return m == MODE_F16 || m == MODE_F16Q; }
+// What a tile leaves behind besides (OUT_NONE, OUT_SCORES) or instead of (OUT_CAND) its softmax partials: nothing, its
+// block of the (B,N) score matrix, or its best k scores per query (CandOut; split operands only, no labels, no merge).
+enum { OUT_NONE = 0, OUT_SCORES = 1, OUT_CAND = 2 };
 
 // Runs of equal consecutive labels inside one support tile, by ONE wave (3 rows per lane): fills
 // runid[t] (run of tile row t), runlab[run] (its class, -1 = padding / out-of-range label), nrun_s[0] =
@@ -98,6 +112,67 @@ __device__ __forceinline__ void load_tile_labels(const int64_t* __restrict__ sy,
     }
 }
 
+// OUT_CAND: the tile's kc best scores of every query column, selected from the registers of the epilogue.  A query column
+// is the four lanes g = 0..3 (lanes i, i+16, i+32, i+48), lane (i, g) holding tile rows 16r + 4g + e.  The keys are
+// ordered_bits of the floats the score writer WOULD store (sc * ln2: the product is only weakly monotone in sc, so
+// selecting on sc would break a rounding tie differently), rows past the bank are 0 = "no element".  One round per
+// candidate: in-lane maximum, maximum over the four lanes, the LOWEST tile row among the keys equal to it (in-lane first,
+// then over the lanes), knock that one element out.  Four rounds fill one slot in each of the column's four lanes, which
+// the whole wave then stores at once (16 bytes per query).
+template <int RS>
+__device__ __forceinline__ void tile_candidates(const float (&sc)[RS][4], unsigned* __restrict__ cand_key,
+                                                int* __restrict__ cand_row, int B, int N, int b, int s0, int g, int st,
+                                                int n_stiles, int k) {
+    constexpr int BS = 16 * RS;
+    constexpr float LN2 = 0.693147180559945309417f;
+    constexpr unsigned NOPOS = 1u << 20;
+    unsigned key[RS][4];
+#pragma unroll
+    for (int r = 0; r < RS; ++r)
+#pragma unroll
+        for (int e = 0; e < 4; ++e) key[r][e] = ordered_bits(sc[r][e] * LN2);
+    if (s0 + BS > N) {
+#pragma unroll
+        for (int r = 0; r < RS; ++r)
+#pragma unroll
+            for (int e = 0; e < 4; ++e)
+                if (s0 + 16 * r + 4 * g + e >= N) key[r][e] = 0u;
+    }
+    const int kc = k < BS ? k : BS, kcp = cand_slots(k, BS);
+    const size_t base = ((size_t)b * n_stiles + st) * kcp + g;
+    for (int j0 = 0; j0 < kcp; j0 += 4) {
+        unsigned okey = 0u;
+        int orow = 0;
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            if (j0 + u >= kc) break;  // (the same for every lane)
+            unsigned m = 0u;
+#pragma unroll
+            for (int r = 0; r < RS; ++r) m = max(max(m, key[r][0]), max(key[r][1], max(key[r][2], key[r][3])));
+            m = group4_max_u32(m);
+            unsigned pos = NOPOS;   // 16r + e of this lane's lowest row holding m
+#pragma unroll
+            for (int r = RS - 1; r >= 0; --r)
+#pragma unroll
+                for (int e = 3; e >= 0; --e) pos = key[r][e] == m ? (unsigned)(16 * r + e) : pos;
+            const unsigned win = group4_min_u32(pos + 4u * g);   // tile row of the winner (every key 0: some empty row)
+            const unsigned mine = win - 4u * g;
+#pragma unroll
+            for (int r = 0; r < RS; ++r)
+#pragma unroll
+                for (int e = 0; e < 4; ++e) key[r][e] = (unsigned)(16 * r + e) == mine ? 0u : key[r][e];
+            if (g == u) {
+                okey = m;
+                orow = s0 + (int)win;
+            }
+        }
+        if (b < B) {
+            cand_key[base + j0] = okey;
+            cand_row[base + j0] = orow;
+        }
+    }
+}
+
 #ifdef NW_DIAG_FUSED   // diagnostic build only (tools/bench_fused.hip): phase stamps go to `scores`
 #define NW_FSTAMP(k) if (threadIdx.x == 0) reinterpret_cast<unsigned long long*>(scores)[8 * blockIdx.x + (k)] = __builtin_amdgcn_s_memtime()
 #else
@@ -105,14 +180,16 @@ __device__ __forceinline__ void load_tile_labels(const int64_t* __restrict__ sy,
 #endif
 // The epilogue of one tile: scores -> tile-local softmax statistics -> run sums -> workspace.
 // Called by all threads of the workgroup (loader waves only take part in the run-table copy).
-template <int RS, int KIND, bool WRITE_SCORES, int MODE>
+// OUT_CAND: `scores` / `ws_lab` are CandOut's key / row arrays, n_stiles and k come behind; nothing else is written.
+template <int RS, int KIND, int OUT, int MODE>
 __device__ __forceinline__ void fused_epilogue(
     f32x4 (&acc)[RS], const float* qn2, const float* sn2, const float* ssc, const int* runid,
     const int* runlab, const int* nrun_s, const float* qsc_s,
     const float* __restrict__ logit_scale, float* __restrict__ scores, float* __restrict__ ws_m,
     float* __restrict__ ws_den, int* __restrict__ ws_nrun, int* __restrict__ ws_lab,
-    float* __restrict__ ws_num, int B, int N, int q0, int s0, int qt, int st) {
+    float* __restrict__ ws_num, int B, int N, int q0, int s0, int qt, int st, int n_stiles = 0, int k = 0) {
     constexpr int BS = 16 * RS;
+    constexpr bool WRITE_SCORES = OUT == OUT_SCORES;
     constexpr bool NEED_NORM = (KIND != NW_SCORE_DOT);
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
     const int i = lane & 15, g = lane >> 4;
@@ -158,6 +235,10 @@ __device__ __forceinline__ void fused_epilogue(
                 for (int e = 0; e < 4; ++e)
                     if (s0 + 16 * r + 4 * g + e >= N) sc[r][e] = -INFINITY;
         }
+        if constexpr (OUT == OUT_CAND) {
+            tile_candidates<RS>(sc, reinterpret_cast<unsigned*>(scores), ws_lab, B, N, b, s0, g, st, n_stiles, k);
+            return;
+        }
 #pragma unroll
         for (int r = 0; r < RS; ++r) mloc = fmaxf(mloc, fmaxf(fmaxf(sc[r][0], sc[r][1]), fmaxf(sc[r][2], sc[r][3])));
         if (WRITE_SCORES && b < B) {  // natural units for the caller (backward, neighbour search)
@@ -180,6 +261,7 @@ __device__ __forceinline__ void fused_epilogue(
         // tile-local max over the wave's 16 query columns: lanes i, i+16, i+32, i+48 hold one query
         mloc = group4_max(mloc);
     }
+    if constexpr (OUT == OUT_CAND) return;   // (the loader waves)
     NW_FSTAMP(3);
 
     // ---- 2^(u - mu) and its sums over the runs of equal labels, on the matrix cores:
@@ -283,7 +365,8 @@ __device__ __forceinline__ void fused_epilogue(
 }
 
 
-template <int RS, int KIND, bool WRITE_SCORES, int MODE>
+// OUT_CAND: sy is not read, `scores` / `ws_lab` are CandOut's key / row arrays and `C` carries k.
+template <int RS, int KIND, int OUT, int MODE>
 __global__ __launch_bounds__(TILE_THREADS, (RS <= 5 ? 4 : 2)) void nw_fused_kernel(
     const float* __restrict__ q, const float* __restrict__ s, const int64_t* __restrict__ sy,
     const float* __restrict__ s_norm2, const float* __restrict__ s_scale, const float* __restrict__ q_norm2,
@@ -328,7 +411,7 @@ __global__ __launch_bounds__(TILE_THREADS, (RS <= 5 ? 4 : 2)) void nw_fused_kern
         for (int t = tid; t < BQ; t += TILE_THREADS) qsc_s[t] = q_scale[min(q0 + t, B - 1)];
     }
     // ---- runs of equal consecutive labels inside this support tile (one wave)
-    if (wave == 0) {
+    if (OUT != OUT_CAND && wave == 0) {
         int lab[3];
         load_tile_labels<BS>(sy, s0, N, C, lane, lab);
         run_scan_wave<BS>(lab, lane, runid, runlab, nrun_s);
@@ -357,8 +440,8 @@ __global__ __launch_bounds__(TILE_THREADS, (RS <= 5 ? 4 : 2)) void nw_fused_kern
     }
 
     NW_FSTAMP(2);
-    fused_epilogue<RS, KIND, WRITE_SCORES, MODE>(acc, qn2, sn2, ssc, runid, runlab, nrun_s, qsc_s, logit_scale,
-                                                 scores, ws_m, ws_den, ws_nrun, ws_lab, ws_num, B, N, q0, s0, qt, st);
+    fused_epilogue<RS, KIND, OUT, MODE>(acc, qn2, sn2, ssc, runid, runlab, nrun_s, qsc_s, logit_scale,
+                                        scores, ws_m, ws_den, ws_nrun, ws_lab, ws_num, B, N, q0, s0, qt, st, n_stiles, C);
     NW_FSTAMP(6);
 }
 
@@ -378,14 +461,16 @@ int launch_fused_rs(const float* q, const float* s, const int64_t* sy, const flo
                     const float* s_scale,
                     const float* ls, float* out, float* scores, float* lse, float* m, float* den,
                     float* num, void* workspace, size_t workspace_bytes, int B, int N, int d, int C,
-                    hipStream_t st) {
+                    hipStream_t st, const CandOut* cand = nullptr) {
     const float *q_norm2 = nullptr, *q_scale = nullptr;
     constexpr int BS = 16 * RS;
     const int n_stiles = (N + BS - 1) / BS;
     const int n_qtiles = (B + BQ - 1) / BQ;
-    FusedWs ws;
-    const size_t need = fused_layout(B, n_stiles, BS, static_cast<char*>(workspace), &ws, C);
-    if (!workspace || workspace_bytes < need) return NW_ERR_WORKSPACE;
+    FusedWs ws = {};
+    if (!cand) {   // (candidate output: the caller's CandOut is all the kernel writes)
+        const size_t need = fused_layout(B, n_stiles, BS, static_cast<char*>(workspace), &ws, C);
+        if (!workspace || workspace_bytes < need) return NW_ERR_WORKSPACE;
+    }
     const int grid = padded_grid(n_stiles, n_qtiles);
     // RS = 5 exists for the LDS-DMA modes only (two workgroups per CU); the register-staged loaders
     // need an even split of the tile rows
@@ -399,7 +484,7 @@ int launch_fused_rs(const float* q, const float* s, const int64_t* sy, const flo
                        n_stiles, n_qtiles)
     // many tiles per CU on split operands: the persistent kernel (fused_f16p.h).  RS = 8 is the tallest
     // tile whose build stays under 256 VGPRs.
-    const bool persistent = s_scale && !scores && RS > 5 && (RS == 8 || env_flag("NW_PERSISTENT_ANY_RS")) &&
+    const bool persistent = s_scale && !scores && !cand && RS > 5 && (RS == 8 || env_flag("NW_PERSISTENT_ANY_RS")) &&
                             grid >= 4 * device_cu_count() && d >= 3 * BK && !env_flag("NW_NO_PERSISTENT");
     if (persistent) {  // runs of equal labels per support tile: once per launch (ws.runid / nrun / lab / bnd)
         if (!bank_tables_take(sy, N, C, n_stiles, 16 * RS, &ws)) {
@@ -417,32 +502,51 @@ int launch_fused_rs(const float* q, const float* s, const int64_t* sy, const flo
         const bool raw_ok = force_split == 0 || (force_split < 0 && 2 * grid <= 3 * device_cu_count());
         if (persistent || !raw_ok) {
             float *qr, *qsc, *qn;
-            const int rc = split_queries_into_workspace(q, workspace, workspace_bytes, B, N, d, C, &qr, &qsc, &qn, st);
+            int rc;
+            if (cand) rc = launch_split_rows(q, qr = cand->q_rows, qsc = cand->q_scale, qn = cand->q_norm2, B, d, st);
+            else rc = split_queries_into_workspace(q, workspace, workspace_bytes, B, N, d, C, &qr, &qsc, &qn, st);
             if (rc != NW_OK) return rc;
             q = qr;
             q_scale = qsc;
             q_norm2 = qn;
         }
     }
+    if (cand) {   // the launch of the score-writing call of this shape (tile height, raw or split queries, grid), OUT_CAND
+        if (!s_scale) return NW_ERR_INVALID_ARG;
+        // (RS = 12 on split operands exists only under the tile_rs knob and spills there: no candidate form of it)
+        if constexpr (RS == 12) {
+            return NW_ERR_UNSUPPORTED;
+        } else {
+#define NW_LAUNCH_CAND(MODE_)                                                                                              \
+    hipLaunchKernelGGL((nw_fused_kernel<RS, KIND, OUT_CAND, MODE_>), dim3(grid), dim3(TILE_THREADS), lds_dma, st, q, s,    \
+                       (const int64_t*)nullptr, s_norm2, s_scale, q_norm2, q_scale, ls, reinterpret_cast<float*>(cand->key), \
+                       (float*)nullptr, (float*)nullptr, (int*)nullptr, cand->row, (float*)nullptr, B, N, d, cand->k,       \
+                       n_stiles, n_qtiles)
+            if (!q_scale) NW_LAUNCH_CAND(MODE_F16Q); else NW_LAUNCH_CAND(MODE_F16);
+#undef NW_LAUNCH_CAND
+            NW_CHECK_LAUNCH();
+            return NW_OK;
+        }
+    }
     const int timer_slot = tile_timer_start(st);
     if (s_scale) {
         if (!q_scale) {
-            if (scores) NW_LAUNCH(true, MODE_F16Q, lds_dma); else NW_LAUNCH(false, MODE_F16Q, lds_dma);
+            if (scores) NW_LAUNCH(OUT_SCORES, MODE_F16Q, lds_dma); else NW_LAUNCH(OUT_NONE, MODE_F16Q, lds_dma);
         } else if (scores) {
-            NW_LAUNCH(true, MODE_F16, lds_dma);
+            NW_LAUNCH(OUT_SCORES, MODE_F16, lds_dma);
         } else if (persistent) {
             const int rc = launch_f16p<RS, KIND>(q, s, sy, s_norm2, s_scale, q_norm2, q_scale, ls, ws, B, N, d, C,
                                                  n_stiles, n_qtiles, st);
             if (rc != NW_OK) return rc;
         } else {
-            NW_LAUNCH(false, MODE_F16, lds_dma);
+            NW_LAUNCH(OUT_NONE, MODE_F16, lds_dma);
         }
     } else if (dma && s_norm2 && KIND != NW_SCORE_DOT) {
-        if (scores) NW_LAUNCH(true, MODE_DMA_SN, lds_dma); else NW_LAUNCH(false, MODE_DMA_SN, lds_dma);
+        if (scores) NW_LAUNCH(OUT_SCORES, MODE_DMA_SN, lds_dma); else NW_LAUNCH(OUT_NONE, MODE_DMA_SN, lds_dma);
     } else if (dma) {
-        if (scores) NW_LAUNCH(true, MODE_DMA, lds_dma); else NW_LAUNCH(false, MODE_DMA, lds_dma);
+        if (scores) NW_LAUNCH(OUT_SCORES, MODE_DMA, lds_dma); else NW_LAUNCH(OUT_NONE, MODE_DMA, lds_dma);
     } else {
-        if (scores) NW_LAUNCH(true, MODE_REG, lds_reg); else NW_LAUNCH(false, MODE_REG, lds_reg);
+        if (scores) NW_LAUNCH(OUT_SCORES, MODE_REG, lds_reg); else NW_LAUNCH(OUT_NONE, MODE_REG, lds_reg);
     }
 #undef NW_LAUNCH
     tile_timer_stop(timer_slot, st);
@@ -456,9 +560,10 @@ template <int KIND>
 int launch_fused_kind(const float* q, const float* s, const int64_t* sy, const float* s_norm2,
                       const float* s_scale,
                       const float* ls, float* out, float* scores, float* lse, float* m, float* den,
-                      float* num, void* workspace, size_t wsb, int B, int N, int d, int C, hipStream_t st) {
+                      float* num, void* workspace, size_t wsb, int B, int N, int d, int C, hipStream_t st,
+                      const CandOut* cand) {
 #define NW_RS_CASE(R) \
-    case R: return launch_fused_rs<R, KIND>(q, s, sy, s_norm2, s_scale, ls, out, scores, lse, m, den, num, workspace, wsb, B, N, d, C, st)
+    case R: return launch_fused_rs<R, KIND>(q, s, sy, s_norm2, s_scale, ls, out, scores, lse, m, den, num, workspace, wsb, B, N, d, C, st, cand)
     switch (pick_rs(B, N, d, s_scale != nullptr)) {
         NW_RS_CASE(2);
         NW_RS_CASE(4);
@@ -466,7 +571,7 @@ int launch_fused_kind(const float* q, const float* s, const int64_t* sy, const f
         NW_RS_CASE(6);
         NW_RS_CASE(8);
         NW_RS_CASE(10);
-        default: return launch_fused_rs<12, KIND>(q, s, sy, s_norm2, s_scale, ls, out, scores, lse, m, den, num, workspace, wsb, B, N, d, C, st);
+        default: return launch_fused_rs<12, KIND>(q, s, sy, s_norm2, s_scale, ls, out, scores, lse, m, den, num, workspace, wsb, B, N, d, C, st, cand);
     }
 #undef NW_RS_CASE
 }
@@ -577,7 +682,7 @@ int launch_fused_half_kind(const float* q, const void* s_rows, const int64_t* sy
     template int launch_fused_kind<K>(const float*, const float*, const int64_t*, const float*,        \
                                       const float*,                                                    \
                                       const float*, float*, float*, float*, float*, float*, float*,    \
-                                      void*, size_t, int, int, int, int, hipStream_t);                 \
+                                      void*, size_t, int, int, int, int, hipStream_t, const CandOut*); \
     template int launch_fused_half_kind<K>(const float*, const void*, const int64_t*, const float*, const float*,      \
                                            const float*, float*, float*, float*, float*, float*, void*, size_t, int,   \
                                            int, int, int, hipStream_t);

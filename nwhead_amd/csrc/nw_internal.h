@@ -87,6 +87,15 @@ int knob(int id);
 
 // fused forward (fused.hip)
 int launch_topk(const float* scores, int64_t* idx, float* vals, int64_t B, int64_t N, int64_t k, hipStream_t st);  // topk.hip
+// the k best of M candidates per query: keys = ordered_bits of the scores (0: empty slot), rows = their bank rows; equal
+// keys must stand in ascending row order (topk.hip)
+int launch_topk_candidates(const unsigned* keys, const int* rows, int64_t* idx, float* vals, int64_t B, int64_t M, int64_t k,
+                           hipStream_t st);
+// fused.hip: nearest-neighbour search over a prepared bank without the (B,N) score matrix (nw_knn_f32)
+size_t knn_workspace_bytes(int64_t B, int64_t N, int64_t d, int64_t k);
+int launch_knn(const float* q, const float* s_split, const float* s_scale, const float* s_norm2, int64_t* idx, float* vals,
+               void* workspace, size_t workspace_bytes, int64_t B, int64_t N, int64_t d, int64_t k, int kind,
+               const float* logit_scale_dev, hipStream_t st);
 int tile_timer_enable(bool on);
 int tile_timer_read(double* total_us, int64_t* launches);
 int pick_rs(int64_t B, int64_t N, int64_t d, bool f16 = false);
@@ -213,6 +222,35 @@ __device__ __forceinline__ void group4_each(float (&v)[NV], Op op) {
     for (int k = 0; k < NV; ++k) r[k] = __builtin_amdgcn_permlane16_swap(__float_as_uint(v[k]), __float_as_uint(v[k]), false, false);
 #pragma unroll
     for (int k = 0; k < NV; ++k) v[k] = op(__uint_as_float(r[k][0]), __uint_as_float(r[k][1]));
+}
+
+// group4_max / group4_min of unsigned values (the candidate selection of the tile epilogue works on ordered_bits keys)
+__device__ __forceinline__ unsigned group4_max_u32(unsigned x) {
+    typedef unsigned u2_ __attribute__((ext_vector_type(2)));
+    u2_ r = __builtin_amdgcn_permlane32_swap(x, x, false, false);
+    x = max(r[0], r[1]);
+    r = __builtin_amdgcn_permlane16_swap(x, x, false, false);
+    return max(r[0], r[1]);
+}
+__device__ __forceinline__ unsigned group4_min_u32(unsigned x) {
+    typedef unsigned u2_ __attribute__((ext_vector_type(2)));
+    u2_ r = __builtin_amdgcn_permlane32_swap(x, x, false, false);
+    x = min(r[0], r[1]);
+    r = __builtin_amdgcn_permlane16_swap(x, x, false, false);
+    return min(r[0], r[1]);
+}
+
+// Order-preserving uint image of a float: larger float <=> larger uint, NaN on top.  0 is the image of no float (the
+// smallest, -inf, is 0x007fffff): the selection kernels use it for "not an element".
+__device__ __forceinline__ unsigned ordered_bits(float f) {
+    unsigned b = __float_as_uint(f);
+    if ((b & 0x7fffffffu) > 0x7f800000u) return 0xffffffffu;  // every NaN, either sign: one image above +inf (torch's order)
+    if ((b << 1) == 0) b = 0;  // -0.0 == +0.0: one image, so that their order is the index order
+    return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
+}
+// ... and back (the NaN image gives a quiet NaN, the one image of the zeros +0.0)
+__device__ __forceinline__ float ordered_bits_to_float(unsigned u) {
+    return __uint_as_float((u & 0x80000000u) ? (u ^ 0x80000000u) : ~u);
 }
 
 // score from (dot, |q|^2, |s|^2); shared by the MFMA and the generic kernels

@@ -16,6 +16,11 @@
 //   3. bitonic sort of the (at most 1024) survivors in LDS by (value desc, index asc).
 // Rows of up to 65536 scores are read from memory ONCE and stay in registers (16 or 64 per thread); longer rows are
 // re-read in every pass (five reads).
+//
+// MAPPED (nw_knn_f32): the row holds the CANDIDATES of the fused tile kernel's selection epilogue instead of scores --
+// ordered_bits keys (0: an empty slot) with a column -> bank-row map.  Equal keys stand in ascending bank-row order along
+// the row, so the same stable rule gives (score descending, bank row ascending); outputs are the mapped rows and the
+// floats of the keys.
 #include "nw_internal.h"
 
 namespace nw {
@@ -24,22 +29,16 @@ namespace {
 constexpr int TK_THREADS = 1024;
 constexpr int TK_MAXK = 1024;
 
-__device__ __forceinline__ unsigned ordered_bits(float f) {  // larger float <=> larger uint; NaN on top
-    unsigned b = __float_as_uint(f);
-    if ((b & 0x7fffffffu) > 0x7f800000u) return 0xffffffffu;  // every NaN, either sign: one image above +inf (torch's order)
-    if ((b << 1) == 0) b = 0;  // -0.0 == +0.0: one image, so that their order is the index order
-    return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
-}
-
 constexpr int TK_U = 8;       // independent loads in flight per thread in the histogram passes (long rows: 254 -> ... us at N = 50000 from 4)
 // REGS > 0: the row is read from memory ONCE.  Wave w owns the contiguous segment [w seg, (w + 1) seg) of the row
 // (seg a multiple of 64, 16 seg >= N) and keeps it in registers, element e of lane l = w seg + 64 e + l (coalesced
 // loads); the histogram passes and the ordered compaction (ranks from ballots inside the wave, wave bases from one
 // LDS round) all work from those registers.  REGS = 0 (N > 65536): the row is re-read in every pass.
-template <int REGS>
+template <int REGS, bool MAPPED = false>
 __global__ __launch_bounds__(TK_THREADS) void nw_topk_kernel(const float* __restrict__ scores,
                                                              int64_t* __restrict__ idx_out,
-                                                             float* __restrict__ val_out, int N, int k) {
+                                                             float* __restrict__ val_out, int N, int k,
+                                                             const int* __restrict__ row_map) {
     constexpr bool CACHED = REGS > 0;
     constexpr int TK_REGS = CACHED ? REGS : TK_U;
     __shared__ unsigned hist[256];
@@ -49,6 +48,16 @@ __global__ __launch_bounds__(TK_THREADS) void nw_topk_kernel(const float* __rest
     __shared__ int cand_i[TK_MAXK];
     const int tid = threadIdx.x, lane = tid & 63;
     const float* row = scores + (size_t)blockIdx.x * N;
+    auto key_at = [&](int i) { return MAPPED ? reinterpret_cast<const unsigned*>(row)[i] : ordered_bits(row[i]); };
+    auto emit = [&](int slot, int ix) {
+        if (MAPPED) {
+            idx_out[(size_t)blockIdx.x * k + slot] = row_map[(size_t)blockIdx.x * N + ix];
+            if (val_out) val_out[(size_t)blockIdx.x * k + slot] = ordered_bits_to_float(key_at(ix));
+        } else {
+            idx_out[(size_t)blockIdx.x * k + slot] = ix;
+            if (val_out) val_out[(size_t)blockIdx.x * k + slot] = row[ix];
+        }
+    };
 
     // ---- 1. radix select of the k-th largest
     if (tid == 0) {
@@ -62,7 +71,7 @@ __global__ __launch_bounds__(TK_THREADS) void nw_topk_kernel(const float* __rest
 #pragma unroll
         for (int e = 0; e < TK_REGS; ++e) {   // coalesced, independent loads; the only pass over memory
             const int i = wv * seg + 64 * e + lane;
-            ureg[e] = (64 * e < seg && i < N) ? ordered_bits(row[i]) : 0u;
+            ureg[e] = (64 * e < seg && i < N) ? key_at(i) : 0u;
         }
     }
     for (int pass = 0; pass < 4; ++pass) {
@@ -102,7 +111,7 @@ __global__ __launch_bounds__(TK_THREADS) void nw_topk_kernel(const float* __rest
                 for (int e = 0; e < TK_U; ++e) {  // coalesced, independent: TK_U loads in flight
                     const int i = i0 + e * TK_THREADS + tid;
                     ok[e] = i < N;
-                    u4[e] = ok[e] ? ordered_bits(row[i]) : 0u;
+                    u4[e] = ok[e] ? key_at(i) : 0u;
                 }
 #pragma unroll
                 for (int e = 0; e < TK_U; ++e) count(u4[e], ok[e]);
@@ -188,7 +197,7 @@ __global__ __launch_bounds__(TK_THREADS) void nw_topk_kernel(const float* __rest
     const int lo = min(tid * per, N), hi = min(lo + per, N);
     unsigned cg = 0, ce = 0;
     for (int i = lo; i < hi; ++i) {
-        const unsigned u = ordered_bits(row[i]);
+        const unsigned u = key_at(i);
         cg += u > T;
         ce += u == T;
     }
@@ -214,7 +223,7 @@ __global__ __launch_bounds__(TK_THREADS) void nw_topk_kernel(const float* __rest
         oe += scan_eq[w];
     }
     for (int i = lo; i < hi; ++i) {
-        const unsigned u = ordered_bits(row[i]);
+        const unsigned u = key_at(i);
         if (u > T) {
             cand_u[og] = u;
             cand_i[og] = i;
@@ -258,10 +267,7 @@ __global__ __launch_bounds__(TK_THREADS) void nw_topk_kernel(const float* __rest
                         ix = io;
                     }
                 }
-            if (tid < k) {
-                idx_out[(size_t)blockIdx.x * k + tid] = ix;
-                if (val_out) val_out[(size_t)blockIdx.x * k + tid] = row[ix];
-            }
+            if (tid < k) emit(tid, ix);
         }
         return;
     }
@@ -280,10 +286,7 @@ __global__ __launch_bounds__(TK_THREADS) void nw_topk_kernel(const float* __rest
             __syncthreads();
         }
     }
-    for (int x = tid; x < k; x += TK_THREADS) {
-        idx_out[(size_t)blockIdx.x * k + x] = cand_i[x];
-        if (val_out) val_out[(size_t)blockIdx.x * k + x] = row[cand_i[x]];
-    }
+    for (int x = tid; x < k; x += TK_THREADS) emit(x, cand_i[x]);
 }
 
 }  // namespace
@@ -292,13 +295,29 @@ int launch_topk(const float* scores, int64_t* idx, float* vals, int64_t B, int64
     if (k < 1 || k > N || k > TK_MAXK || N >= (1ll << 31) || B >= (1ll << 31)) return NW_ERR_UNSUPPORTED;
     if (B == 0) return NW_OK;
     if (N <= 16 * TK_THREADS)
-        hipLaunchKernelGGL((nw_topk_kernel<16>), dim3((unsigned)B), dim3(TK_THREADS), 0, st, scores, idx, vals, (int)N, (int)k);
+        hipLaunchKernelGGL((nw_topk_kernel<16>), dim3((unsigned)B), dim3(TK_THREADS), 0, st, scores, idx, vals, (int)N, (int)k, (const int*)nullptr);
     else if (N <= 32 * TK_THREADS)
-        hipLaunchKernelGGL((nw_topk_kernel<32>), dim3((unsigned)B), dim3(TK_THREADS), 0, st, scores, idx, vals, (int)N, (int)k);
+        hipLaunchKernelGGL((nw_topk_kernel<32>), dim3((unsigned)B), dim3(TK_THREADS), 0, st, scores, idx, vals, (int)N, (int)k, (const int*)nullptr);
     else if (N <= 64 * TK_THREADS)
-        hipLaunchKernelGGL((nw_topk_kernel<64>), dim3((unsigned)B), dim3(TK_THREADS), 0, st, scores, idx, vals, (int)N, (int)k);
+        hipLaunchKernelGGL((nw_topk_kernel<64>), dim3((unsigned)B), dim3(TK_THREADS), 0, st, scores, idx, vals, (int)N, (int)k, (const int*)nullptr);
     else
-        hipLaunchKernelGGL((nw_topk_kernel<0>), dim3((unsigned)B), dim3(TK_THREADS), 0, st, scores, idx, vals, (int)N, (int)k);
+        hipLaunchKernelGGL((nw_topk_kernel<0>), dim3((unsigned)B), dim3(TK_THREADS), 0, st, scores, idx, vals, (int)N, (int)k, (const int*)nullptr);
+    NW_CHECK_LAUNCH();
+    return NW_OK;
+}
+
+int launch_topk_candidates(const unsigned* keys, const int* rows, int64_t* idx, float* vals, int64_t B, int64_t M, int64_t k,
+                           hipStream_t st) {
+    if (k < 1 || k > M || k > TK_MAXK || M >= (1ll << 31) || B >= (1ll << 31)) return NW_ERR_UNSUPPORTED;
+    if (B == 0) return NW_OK;
+    const float* kf = reinterpret_cast<const float*>(keys);
+#define NW_TOPK_MAPPED(R_) \
+    hipLaunchKernelGGL((nw_topk_kernel<R_, true>), dim3((unsigned)B), dim3(TK_THREADS), 0, st, kf, idx, vals, (int)M, (int)k, rows)
+    if (M <= 16 * TK_THREADS) NW_TOPK_MAPPED(16);
+    else if (M <= 32 * TK_THREADS) NW_TOPK_MAPPED(32);
+    else if (M <= 64 * TK_THREADS) NW_TOPK_MAPPED(64);
+    else NW_TOPK_MAPPED(0);
+#undef NW_TOPK_MAPPED
     NW_CHECK_LAUNCH();
     return NW_OK;
 }

@@ -229,11 +229,23 @@ class NWNet(nn.Module):
             return out, torch.full((len(x),), True)
         return out
 
-    def get_neighbors(self, x):
-        """Support indices ordered from nearest to farthest under the configured kernel."""
+    def get_neighbors(self, x, k=None):
+        """Support indices ordered from nearest to farthest under the configured kernel.  k (not in the reference): only the
+        k nearest, (B, k), 1 <= k <= N -- for k <= 32 over precompute()'s bank (N % 4 == 0) without the (B, N) score matrix
+        where that pays (ops.nw_knn, ops.knn_fused_pays)."""
         qfeat = self._eval_featurizer()(x).detach()
+        N = self.full_feat.shape[0]
+        if k is not None:
+            k = int(k)
+            if not 1 <= k <= N:
+                raise ops.NWHipError(f"get_neighbors: k = {k} outside [1, N = {N}]")
+            bank = getattr(self, 'full_cache', None)
+            if k <= 32 and N % 4 == 0 and isinstance(self.kernel, _ScoreModule) and bank is not None and qfeat.is_cuda \
+                    and self.full_feat.is_cuda and bank.matches(self.full_feat) and ops.knn_fused_pays(qfeat.shape[0], N):
+                return ops.nw_knn(qfeat, bank, k, self.kernel.kind, self.kernel._logit_scale(), support=self.full_feat)
         scores = self.kernel(qfeat, self.full_feat.to(qfeat.device))
-        return torch.argsort(scores, dim=-1, descending=True)
+        order = torch.argsort(scores, dim=-1, descending=True)
+        return order if k is None else order[:, :k]
 
     # ------------------------------------------------------------------ training step
     def forward(self, x, y, metadata=None, support_data=None):

@@ -118,6 +118,13 @@ class KNN:
 
     def indices(self, x):
         data = self.data.to(x.device)
+        k = min(self.n_neighbors, data.shape[0])
+        if (self.bank is not None and data.is_cuda and 1 <= k <= 32 and data.dim() == 2 and data.shape[0] % 4 == 0
+                and ops.knn_fused_pays(x.shape[0], data.shape[0])):
+            # no (B, N) score matrix: the tiles of the score kernel select (ops.nw_knn).  N % 4 == 0: the lines below then
+            # rank the bank route's scores, whose rows nw_knn returns bit for bit; for other N they rank the fp32 scores
+            # kernel's, which the fused search does not reproduce to the last bit.
+            return ops.nw_knn(x, self.bank, k, "euclidean", support=data)
         scores = ops.nw_scores(x, data, "euclidean", support_cache=self.bank if data.is_cuda else None)
         k = min(self.n_neighbors, scores.shape[1])
         # descending score == ascending distance; ties resolve like a stable argsort would

@@ -177,6 +177,62 @@ def nw_topk(scores, k, return_values=False):
     return (idx, vals) if return_values else idx
 
 
+KNN_FUSED_MIN_SCORE_BYTES = 1 << 30
+
+
+def knn_fused_pays(B, N):
+    """Whether the callers that used to go through the score matrix (KNN.indices, NWNet.get_neighbors) take nw_knn for B
+    queries against N rows: from a (B, N) fp32 score matrix of KNN_FUSED_MIN_SCORE_BYTES on."""
+    return 4 * int(B) * int(N) >= KNN_FUSED_MIN_SCORE_BYTES
+
+
+def nw_knn(q, bank, k, kind="euclidean", logit_scale=None, return_values=False, support=None):
+    """q:(B,d), bank: the SplitBank of an (N,d) support -> (B,k) int64 rows of the tensor the bank was prepared from, best
+    score first, equal scores in ascending row order (with return_values: also their (B,k) scores).  The neighbour search
+    of nwhead/utils.py:185-193 and nwhead/nw.py:245-249 over a resident bank WITHOUT the (B,N) score matrix: the tiles of
+    the split-fp16 kernel select their k best scores themselves (nw_knn_f32).
+
+    The result is that of ``nw_topk(nw_scores(q, support, kind, logit_scale, support_cache=bank), k)``, and that route is
+    taken as it stands -- it needs ``support``, the tensor the bank was prepared from -- when
+    the bank has no split rows (a norms-only or fp16 bank), holds a class-sorted copy (built from unsorted labels), when
+    k > 32, and for shapes whose bank-route scores come from the fp32 tile kernel (below 2e8 multiply-adds, unless
+    NW_SPLIT_ALWAYS=1): the rows and values are the same either way.  (A bank whose N is no multiple of 4 has no
+    bank-route scores; its fused search ranks the split kernel's scores, which lie within the same 3e-5 of the exact ones.)"""
+    _need_hip(q, logit_scale, support)
+    if not isinstance(bank, SplitBank):
+        raise TypeError("nw_knn searches a prepared bank: pass ops.SplitBank(support)")
+    lib = _lib.load()
+    q = _f32c(q)
+    B, d0 = q.shape
+    k = int(k)
+    N = bank.shape[0] if support is None else support.shape[-2]
+    if k < 1 or k > N:
+        raise NWHipError(f"nw_knn: k = {k} outside [1, N = {N}] (nw_topk refuses it too)")
+    dp = d0 + bank.pad
+    # (nw_scores_use_split: the library's own rule for which tile kernel the bank-route score call of this shape runs)
+    fused = (bank.split is not None and bank.sorted_rows is None and k <= 32 and N > 25 and B > 0 and dp == bank.shape[1]
+             and N == bank.shape[0] and (support is None or (support.dim() == 2 and bank.matches(support)))
+             and (_lib.force_split() or bool(lib.nw_scores_use_split(B, N, dp))))
+    if not fused:
+        if support is None:
+            raise ValueError("nw_knn: this search goes through the score matrix and needs `support`, the tensor the bank was "
+                             "prepared from")
+        return nw_topk(nw_scores(q, support, kind, logit_scale, support_cache=bank), k, return_values=return_values)
+    q, _ = _apply_bank_padding(q, bank.split, bank)
+    ls = None if logit_scale is None else _f32c(logit_scale)
+    idx = torch.empty(B, k, dtype=torch.int64, device=q.device)
+    vals = torch.empty(B, k, dtype=torch.float32, device=q.device) if return_values else None
+    key = ("knn", B, N, dp, k)
+    ws_bytes = _WS_BYTES.get(key)
+    if ws_bytes is None:
+        ws_bytes = _WS_BYTES[key] = lib.nw_knn_workspace_bytes(B, N, dp, k)
+    ws = _workspace(ws_bytes, q.device)
+    with _OnDevice(q.device):
+        _lib.check(lib.nw_knn_f32(_ptr(q), _ptr(bank.split), _ptr(bank.scale), _ptr(bank.norm2), _ptr(idx), _ptr(vals),
+                                  _ptr(ws), ws_bytes, B, N, dp, k, _kind_id(kind), _ptr(ls), _stream(q)), "nw_knn_f32")
+    return (idx, vals) if return_values else idx
+
+
 def row_norm2(x):
     """Squared L2 norm of every row of a (rows,d) fp32 HIP tensor -> (rows,).  Cache this for a support
     bank that does not change between calls and pass it as ``support_norm2``."""
