@@ -687,6 +687,24 @@ int nw_debug_tile_timing(int enable);
  * the NW_<NAME> environment variables once, when it loads the library; the library itself never reads the environment. */
 int nw_debug_set(const char *name, int value);
 int nw_debug_tile_timing_read(double *total_us, int64_t *launches);
+/* The launch decision of the fused head for one call, as the library would take it (plan_fused, csrc/fused.hip): no launch,
+ * no device needed.  form: 0 fp32 supports, 1 split rows, 2 half-precision rows.  outputs: 0 log-probabilities or partials,
+ * 1 the same plus scores, 2 the k best candidates per query (nw_knn_f32).  norms: support norms supplied.  cus: CU count to
+ * plan for, 0 = the current device's (256 when there is none), at most 2^20.  Returns NW_OK when *plan was filled; plan->status is what
+ * the launch itself would return for the combination.  mode: 0 register-staged fp32, 1 LDS-DMA fp32, 2 LDS-DMA fp32 with
+ * the caller's norms, 3 split operands, 4 split supports and raw queries; out: as `outputs`.  variant / workgroups / qgroup
+ * describe the persistent kernel and are 0 without it. */
+typedef struct nw_fwd_plan {
+    int32_t status;
+    int32_t rs, bs, n_stiles, n_qtiles, grid;   /* tile height in 16-row blocks and in rows; support / 64-query tiles; workgroups */
+    int32_t mode, out;
+    int32_t dma, persistent, variant, workgroups, qgroup;
+    int32_t split_queries, run_tables;          /* a query split / pack launch, run tables before the tile kernel */
+    int32_t reserved;
+    uint64_t lds_bytes;                         /* dynamic LDS of the tile kernel */
+} nw_fwd_plan;
+int nw_debug_fwd_plan(int64_t B, int64_t N, int64_t d, int64_t C, int form, int outputs, int k, int norms, int kind,
+                      int persistent_wgs, int cus, nw_fwd_plan *plan);
 
 #ifdef __cplusplus
 }

@@ -101,6 +101,7 @@ SIGNATURES = {
     "nw_debug_set": (_int, [C.c_char_p, _int]),
     "nw_debug_tile_timing": (_int, [_int]),
     "nw_debug_tile_timing_read": (_int, [C.POINTER(C.c_double), C.POINTER(C.c_int64)]),
+    "nw_debug_fwd_plan": (_int, [_i64, _i64, _i64, _i64, _int, _int, _int, _int, _int, _int, _int, _p]),
 }
 
 _lib = None
@@ -158,6 +159,25 @@ class FwdOpts(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("persistent_wgs", C.c_int32), ("force_split", C.c_int32),
                 ("operand_form", C.c_int32), ("tables", C.c_void_p), ("tables_bytes", C.c_size_t),
                 ("tables_sy", C.c_void_p), ("tables_N", C.c_int64)]
+
+
+class FwdPlan(C.Structure):
+    """nw_fwd_plan (include/nwhead_hip.h): the launch decision of the fused head for one call."""
+    _fields_ = [(k, C.c_int32) for k in ("status", "rs", "bs", "n_stiles", "n_qtiles", "grid", "mode", "out", "dma", "persistent",
+                                         "variant", "workgroups", "qgroup", "split_queries", "run_tables", "reserved")] + \
+               [("lds_bytes", C.c_uint64)]
+
+
+FORMS = {"fp32": 0, "split": 1, "half": 2}
+OUTPUTS = {"log_probs": 0, "scores": 1, "candidates": 2}
+
+
+def fwd_plan(B, N, d, C_, form="split", outputs="log_probs", k=0, norms=True, kind="euclidean", persistent_wgs=0, cus=0):
+    """The library's launch decision for one forward call (nw_debug_fwd_plan): no launch, no device needed."""
+    p = FwdPlan()
+    check(load().nw_debug_fwd_plan(B, N, d, C_, FORMS[form], OUTPUTS[outputs], k, int(norms), SCORE_KINDS[kind],
+                                   persistent_wgs, cus, C.byref(p)), "nw_debug_fwd_plan")
+    return p
 
 
 # Environment switches of the Python layer (the C library never reads the environment).  NW_SPLIT_ALWAYS travels in every

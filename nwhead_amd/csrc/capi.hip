@@ -3,6 +3,7 @@
 #include <cstdlib>
 #include <string.h>
 #include "nw_internal.h"
+#include "fused_plan.h"
 
 namespace {
 inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
@@ -15,6 +16,13 @@ inline bool bad_kind(int kind) { return kind < NW_SCORE_EUCLIDEAN || kind > NW_S
 extern "C" int nw_scores_use_split(int64_t B, int64_t N, int64_t d);   // the size rule, for callers that must follow it
 static bool split_pays(int64_t B, int64_t N, int64_t d) {
     return nw::fwd_opts().force_split || nw_scores_use_split(B, N, d) != 0;
+}
+// Whether a call with this bank takes the split operands: the bank has them, the shape fits them, they pay (or are
+// forced), and both operands are aligned.
+static bool takes_split(const float* q, const float* s_split, const float* s_scale, const float* s_norm2, int64_t B, int64_t N,
+                        int64_t d) {
+    return s_split && s_scale && s_norm2 && d % 32 == 0 && split_pays(B, N, d) &&
+           ((reinterpret_cast<uintptr_t>(s_split) | reinterpret_cast<uintptr_t>(q)) & 15) == 0;
 }
 
 namespace nw {
@@ -57,7 +65,7 @@ struct OptsGuard {   // the call's options are visible to the launch code of thi
 }  // namespace
 
 // nw_fwd_opts.operand_form = 1 (half-precision rows of nw_pack_rows_f16 in s_split): what the call must look like, checked
-// before anything is launched.  NW_OK: take launch_fused_half.
+// before anything is launched.  NW_OK: take the FORM_HALF launch.
 static int half_form_check(const float* q, const float* s, const float* s_norm2, const float* s_split, const float* s_scale,
                            const void* per_pair_out, int batched, int64_t B, int64_t N, int64_t d, int64_t C) {
     if (per_pair_out || batched) return NW_ERR_UNSUPPORTED;          // scores / weights, per-query supports or labels
@@ -78,6 +86,19 @@ extern "C" int nw_debug_set(const char* name, int value) {
             return NW_OK;
         }
     return NW_ERR_INVALID_ARG;
+}
+
+extern "C" int nw_debug_fwd_plan(int64_t B, int64_t N, int64_t d, int64_t C, int form, int outputs, int k, int norms, int kind,
+                                 int persistent_wgs, int cus, nw_fwd_plan* plan) {
+    if (!plan || B < 0 || N < 0 || d < 0 || C < 0 || k < 0 || cus < 0 || cus > (1 << 20)) return NW_ERR_INVALID_ARG;
+    if (form < nw::FORM_F32 || form > nw::FORM_HALF || outputs < nw::OUT_NONE || outputs > nw::OUT_CAND) return NW_ERR_INVALID_ARG;
+    if (bad_kind(kind)) return NW_ERR_UNSUPPORTED;
+    nw::FwdOpts o;
+    o.persistent_wgs = persistent_wgs;
+    const nw::FusedPlan p = nw::plan_fused(B, N, d, C, form, outputs, k, norms != 0, kind == NW_SCORE_DOT, cus, o);
+    *plan = {p.status, p.rs, p.BS, p.n_stiles, p.n_qtiles, p.grid, p.mode, p.out, p.dma, p.persistent, p.variant, p.workgroups,
+             p.qgroup, p.split_queries, p.run_tables, 0, (uint64_t)p.lds_bytes};
+    return NW_OK;
 }
 
 extern "C" int nw_abi_version(void) { return NW_ABI_VERSION; }
@@ -158,14 +179,17 @@ extern "C" int nw_fwd_f32(const float* q, const float* s, const int64_t* sy, con
     if (labels_batched && !sup_batched) return NW_ERR_INVALID_ARG;
     const int form = nw::fwd_opts().operand_form;
     if (form != 0 && form != 1) return NW_ERR_INVALID_ARG;
+    // the fused launch's operands: fp32 supports; the split / half-precision routes below swap the bank's rows in
+    nw::FusedArgs a = {q, s, sy, s_norm2, nullptr, logit_scale_dev, out, scores_out, lse_out, nullptr, nullptr, nullptr,
+                       workspace, workspace_bytes, (int)B, (int)N, (int)d, (int)C, st, nullptr};
     if (form == 1) {
         const int rc = half_form_check(q, s, s_norm2, s_split, s_scale, scores_out ? scores_out : weights_out,
                                        sup_batched || labels_batched, B, N, d, C);
         if (rc != NW_OK) return rc;
         if (N > 0 && C > 0) {
             if (!workspace || workspace_bytes < nw_fwd_workspace_bytes(B, N, d, C)) return NW_ERR_WORKSPACE;
-            return nw::launch_fused_half(q, s_split, sy, s_norm2, s_scale, logit_scale_dev, out, lse_out, nullptr, nullptr,
-                                         nullptr, workspace, workspace_bytes, B, N, d, C, kind, st);
+            a.s = s_split, a.s_scale = s_scale;
+            return nw::launch_fused(a, nw::FORM_HALF, kind);
         }
     }
     // Softmax weights on request: the fused kernel writes the scores where the weights go and one in-place pass
@@ -184,14 +208,9 @@ extern "C" int nw_fwd_f32(const float* q, const float* s, const int64_t* sy, con
             if (rc != NW_OK) return rc;
             return nw::launch_weights_from_scores(sc_buf, lse, weights_out, B, N, st);
         }
-        if (s_split && s_scale && s_norm2 && d % 32 == 0 && split_pays(B, N, d) &&
-            ((reinterpret_cast<uintptr_t>(s_split) | reinterpret_cast<uintptr_t>(q)) & 15) == 0) {
-            return nw::launch_fused(q, s_split, sy, s_norm2, s_scale, logit_scale_dev,
-                                    out, scores_out, lse_out, nullptr, nullptr, nullptr, workspace,
-                                    workspace_bytes, B, N, d, C, kind, st);
-        }
-        return nw::launch_fused(q, s, sy, s_norm2, nullptr, logit_scale_dev, out, scores_out,
-                                lse_out, nullptr, nullptr, nullptr, workspace, workspace_bytes, B, N, d, C, kind, st);
+        if (!takes_split(q, s_split, s_scale, s_norm2, B, N, d)) return nw::launch_fused(a, nw::FORM_F32, kind);
+        a.s = s_split, a.s_scale = s_scale;
+        return nw::launch_fused(a, nw::FORM_SPLIT, kind);
     }
     float* scores = scores_out;
     if (!scores && N > 0) {
@@ -232,18 +251,16 @@ extern "C" int nw_fwd_partial_f32(const float* q, const float* s, const int64_t*
     }
     float* scores = static_cast<float*>(workspace);
     if (N > 0 && (!workspace || workspace_bytes < nw_fwd_workspace_bytes(B, N, d, C))) return NW_ERR_WORKSPACE;
-    if (form == 1 && N > 0 && C > 0)
-        return nw::launch_fused_half(q, s_split, sy, s_norm2, s_scale, logit_scale_dev, nullptr, nullptr, m, den, num,
-                                     workspace, workspace_bytes, B, N, d, C, kind, st);
+    nw::FusedArgs a = {q, s, sy, s_norm2, nullptr, logit_scale_dev, nullptr, nullptr, nullptr, m, den, num,
+                       workspace, workspace_bytes, (int)B, (int)N, (int)d, (int)C, st, nullptr};
+    if (form == 1 && N > 0 && C > 0) {
+        a.s = s_split, a.s_scale = s_scale;
+        return nw::launch_fused(a, nw::FORM_HALF, kind);
+    }
     if (N > 0 && C > 0 && nw::fused_eligible(q, s, B, N, d, C)) {
-        if (s_split && s_scale && s_norm2 && d % 32 == 0 && split_pays(B, N, d) &&
-            ((reinterpret_cast<uintptr_t>(s_split) | reinterpret_cast<uintptr_t>(q)) & 15) == 0) {
-            return nw::launch_fused(q, s_split, sy, s_norm2, s_scale, logit_scale_dev,
-                                    nullptr, nullptr, nullptr, m, den, num, workspace, workspace_bytes, B, N, d,
-                                    C, kind, st);
-        }
-        return nw::launch_fused(q, s, sy, s_norm2, nullptr, logit_scale_dev, nullptr, nullptr,
-                                nullptr, m, den, num, workspace, workspace_bytes, B, N, d, C, kind, st);
+        if (!takes_split(q, s_split, s_scale, s_norm2, B, N, d)) return nw::launch_fused(a, nw::FORM_F32, kind);
+        a.s = s_split, a.s_scale = s_scale;
+        return nw::launch_fused(a, nw::FORM_SPLIT, kind);
     }
     int rc = nw::launch_scores(q, s, scores, B, N, d, kind, logit_scale_dev, 0, st);
     if (rc != NW_OK) return rc;

@@ -16,24 +16,12 @@
 #include <utility>
 #include <vector>
 #include "fused_impl.h"
-#include <cstring>
 
 namespace nw {
 
 // instantiated in fused_k0.hip .. fused_k4.hip
-#define NW_EXTERN_FUSED_KIND(K)                                                                          \
-    extern template int launch_fused_kind<K>(const float*, const float*, const int64_t*, const float*,   \
-                                             const float*,                                               \
-                                             const float*, float*, float*, float*, float*, float*,       \
-                                             float*, void*, size_t, int, int, int, int, hipStream_t, const CandOut*); \
-    extern template int launch_fused_half_kind<K>(const float*, const void*, const int64_t*, const float*, const float*, \
-                                                  const float*, float*, float*, float*, float*, float*, void*, size_t,   \
-                                                  int, int, int, int, hipStream_t);
-NW_EXTERN_FUSED_KIND(NW_SCORE_EUCLIDEAN)
-NW_EXTERN_FUSED_KIND(NW_SCORE_HYPERSPHERE)
-NW_EXTERN_FUSED_KIND(NW_SCORE_COSINE)
-NW_EXTERN_FUSED_KIND(NW_SCORE_DOT)
-NW_EXTERN_FUSED_KIND(NW_SCORE_CLIP)
+#define NW_EXTERN_FUSED_KIND(K) extern template int launch_fused_kind<K>(const FusedArgs&, const FusedPlan&);
+NW_FOR_EACH_KIND(NW_EXTERN_FUSED_KIND)
 #undef NW_EXTERN_FUSED_KIND
 
 // ---- diagnostics: device time of the tile kernel alone (nw_debug_tile_timing*, include/nwhead_hip.h)
@@ -86,16 +74,8 @@ int tile_timer_read(double* total_us, int64_t* launches) {
     return NW_OK;
 }
 
-int persistent_variant() {
-    const int x = knob(KNOB_PVAR);
-    return (x >= 0 && x <= 3) ? x : -1;  // -1: chosen per launch
-}
-
-int persistent_qgroup() {
-    const int x = knob(KNOB_QG);
-    return (x >= 1 && x <= 64) ? x : 8;
-}
-
+namespace {
+// The device property and the on/off knobs the launch decision reads (plan_fused; the run merge keeps its two switches).
 int device_cu_count() {
     static int n = [] {
         int dev = 0, v = 0;
@@ -105,14 +85,8 @@ int device_cu_count() {
     }();
     return n;
 }
-bool env_flag(const char* name) {   // (named after the variables the Python layer forwards: diagnostic knobs)
-    static const struct { const char* n; int k; } map[] = {
-        {"NW_MERGE_PER_QUERY", KNOB_MERGE_PER_QUERY}, {"NW_MERGE_NO_GLOBAL_TABLES", KNOB_MERGE_NO_GLOBAL_TABLES},
-        {"NW_PERSISTENT_ANY_RS", KNOB_PERSISTENT_ANY_RS}, {"NW_NO_PERSISTENT", KNOB_NO_PERSISTENT}};
-    for (const auto& m : map)
-        if (!strcmp(m.n, name)) return knob(m.k) == 1;
-    return false;
-}
+bool env_flag(int k) { return knob(k) == 1; }
+}  // namespace
 
 inline size_t al256(size_t x) { return (x + 255) & ~(size_t)255; }
 
@@ -470,13 +444,6 @@ int query_area_of_workspace(void* workspace, size_t workspace_bytes, int64_t B, 
     return NW_OK;
 }
 
-int split_queries_into_workspace(const float* q, void* workspace, size_t workspace_bytes, int64_t B, int64_t N, int64_t d,
-                                 int64_t C, float** rows, float** scale, float** norm2, hipStream_t st) {
-    const int rc = query_area_of_workspace(workspace, workspace_bytes, B, N, d, C, rows, scale, norm2);
-    if (rc != NW_OK) return rc;
-    return launch_split_rows(q, *rows, *scale, *norm2, B, d, st);
-}
-
 int launch_run_tables(const FusedWs& ws, const int64_t* sy, int N, int C, int n_stiles, int BS, hipStream_t st) {
     if (BS > 192) return NW_ERR_UNSUPPORTED;  // three rows per lane
     hipLaunchKernelGGL(nw_run_tables_kernel, dim3(n_stiles), dim3(64), 0, st, sy, N, C, BS, ws.runid, ws.nrun, ws.lab, ws.bnd);
@@ -533,7 +500,7 @@ int launch_merge_runs(const FusedWs& ws, float* out, float* lse, float* m, float
     if (force_mq == 1 || force_mq == 16 || force_mq == 32) {
         mq = force_mq;
         if (lds_bytes(mq, true) > cap) mq = 1;
-    } else if (B >= 512 && !env_flag("NW_MERGE_PER_QUERY")) {
+    } else if (B >= 512 && !env_flag(KNOB_MERGE_PER_QUERY)) {
         mq = n_stiles >= 128 ? 16 : 32;
         if (lds_bytes(mq, true) > cap) mq = 16;
         if (lds_bytes(mq, true) > cap) mq = 1;
@@ -547,7 +514,7 @@ int launch_merge_runs(const FusedWs& ws, float* out, float* lse, float* m, float
     if (!tables) {
         // more classes than LDS holds tables for (C > ~4200): the tables go to the workspace, built once per launch
         // (measured at C = 5000: 4.9 ms per call at T when every class scanned every tile, 35 ms at B = 4096, N = 50000)
-        if (ws.ctab && !env_flag("NW_MERGE_NO_GLOBAL_TABLES")) {
+        if (ws.ctab && !env_flag(KNOB_MERGE_NO_GLOBAL_TABLES)) {
             hipLaunchKernelGGL(nw_class_tables_kernel, dim3(1), dim3(1024), 0, st, ws.nrun, ws.lab, n_stiles, BS, C, ws.ctab);
             if (out) NW_MERGE(false, 1, 2); else NW_MERGE(true, 1, 2);
         } else {
@@ -600,23 +567,133 @@ int pick_rs(int64_t B, int64_t N, int64_t d, bool f16) {
     return best_rs;
 }
 
+bool half_form_shape_ok(int64_t d) {   // whole 64-k stages, at least three of them (fused_f16p12.h), tile-relative offsets
+    return d % 64 == 0 && d >= 192 && d <= (1 << 20);
+}
+
+namespace {
+struct TileLds {   // dynamic LDS of the tile kernels at one tile height
+    size_t reg, dma;           // nw_fused_kernel: register-staged / LDS-DMA loaders
+    size_t p64, p64x2, p128;   // nw_fused_f16p_kernel: variants 0, 1, 2 (RS > 5)
+};
+template <int RS>
+constexpr TileLds tile_lds() {
+    if constexpr (RS > 5)
+        return {FUSED_HDR + TileCfg<RS>::STAGE_BYTES, FUSED_HDR + DmaCfg<RS>::STAGE_BYTES, PCfg<RS, 1, false>::LDS_BYTES,
+                PCfg<RS, 1, true>::LDS_BYTES, PCfg<RS, 2, false>::LDS_BYTES};
+    else
+        return {FUSED_HDR + TileCfg<RS>::STAGE_BYTES, FUSED_HDR + DmaCfg<RS>::STAGE_BYTES, 0, 0, 0};
+}
+TileLds tile_lds_of(int rs) {
+    return rs == 2 ? tile_lds<2>() : rs == 4 ? tile_lds<4>() : rs == 5 ? tile_lds<5>() : rs == 6 ? tile_lds<6>()
+         : rs == 8 ? tile_lds<8>() : rs == 10 ? tile_lds<10>() : tile_lds<12>();
+}
+}  // namespace
+
+FusedPlan plan_tiles(int64_t B, int64_t N, int64_t d, int form) {
+    FusedPlan p = {};
+    p.form = form;
+    // nw_fwd_opts.operand_form = 1 runs on tiles of 128 supports at every size: the tile-count rule of pick_rs is a speed
+    // heuristic, and that form has no other kernel
+    p.rs = form == FORM_HALF ? BANK_BS / 16 : pick_rs(B, N, d, form == FORM_SPLIT);
+    p.BS = 16 * p.rs;
+    const int64_t n_stiles = (N + p.BS - 1) / p.BS, n_qtiles = (B + BQ - 1) / BQ;
+    const int64_t grid = (n_stiles + 7) / 8 * 8 * n_qtiles;   // padded_grid
+    // More tiles than a launch has workgroups: refused for every form, the persistent kernels included (new with the plan:
+    // the launchers let the int grid overflow and launched; such a shape needs terabytes of workspace and cannot be served).
+    if (grid > 0x7fffffff) p.status = NW_ERR_UNSUPPORTED;
+    else p.n_stiles = (int)n_stiles, p.n_qtiles = (int)n_qtiles, p.grid = (int)grid;
+    return p;
+}
+
+FusedPlan plan_fused(int64_t B, int64_t N, int64_t d, int64_t C, int form, int out, int k, bool norms, bool dot, int cus,
+                     const FwdOpts& opts) {
+    (void)C; (void)k;   // (neither moves the decision today: the class count sizes the merge, k the candidate slots)
+    if (B < 0 || N < 0 || d < 0 || B >= (1 << 30) || N >= (1 << 30) || d >= (1 << 30)) {   // (fused_eligible's limits)
+        FusedPlan none = {};
+        return none.status = NW_ERR_UNSUPPORTED, none;
+    }
+    FusedPlan p = plan_tiles(B, N, d, form);
+    if (p.status != NW_OK) return p;
+    auto refuse = [&p](int status) { p.status = status; return p; };
+    if (cus <= 0) cus = device_cu_count();
+    const TileLds lds = tile_lds_of(p.rs);
+    const bool split = form == FORM_SPLIT;
+    p.out = out;
+    p.dma = (d % BK) == 0 && (uint64_t)(BQ + p.BS) * 2 * d * 4 < 0xffffffffull;  // per-lane offsets are tile-relative
+    if (form == FORM_HALF) {
+        if (out != OUT_NONE || !half_form_shape_ok(d)) return refuse(NW_ERR_UNSUPPORTED);
+        p.persistent = true;
+    } else {
+        // RS = 5 exists for the LDS-DMA modes only (two workgroups per CU); the register-staged loaders need an even split
+        // of the tile rows
+        if (!p.dma && (p.rs & 1)) return refuse(NW_ERR_UNSUPPORTED);
+        // many tiles per CU on split operands: the persistent kernel (fused_f16p.h).  RS = 8 is the tallest tile whose
+        // build stays under 256 VGPRs.
+        p.persistent = split && out == OUT_NONE && p.rs > 5 && (p.rs == 8 || env_flag(KNOB_PERSISTENT_ANY_RS)) &&
+                       p.grid >= 4 * (int64_t)cus && d >= 3 * BK && !env_flag(KNOB_NO_PERSISTENT);
+    }
+    p.run_tables = p.persistent;   // runs of equal labels per support tile: once per launch, or the bank's
+    if (p.run_tables && p.BS > 192) return refuse(NW_ERR_UNSUPPORTED);   // nw_run_tables_kernel: three rows per lane
+    // split-fp16 operands: the caller has checked d % 32 == 0 and supplied the bank's norms
+    if (split && (!p.dma || !norms)) return refuse(NW_ERR_INVALID_ARG);
+    if (out == OUT_CAND && !split) return refuse(NW_ERR_INVALID_ARG);
+    // (RS = 12 on split operands exists only under the tile_rs knob and spills there: no candidate form of it)
+    if (out == OUT_CAND && p.rs == 12) return refuse(NW_ERR_UNSUPPORTED);
+    if (p.persistent) {
+        p.mode = MODE_F16;
+        p.split_queries = true;
+        int wgs = cus & ~7;  // the same number of workgroups on every XCD
+        // nw_fwd_opts.persistent_wgs: fewer workgroups than CUs (a multiple of 8), to leave CUs to a concurrent RCCL kernel
+        // of the sharded path (ShardedBank leaves one CU per XCD when there is more than one rank)
+        const int wg_cap = opts.persistent_wgs & ~7;
+        if (wg_cap >= 8 && wg_cap < wgs) wgs = wg_cap;
+        // 0: 64-query tiles, one workgroup per CU; 1: two per CU; 2: 128-query tiles; 3: 256-query tiles on eight
+        // multiplying waves (fused_f16p12.h, tiles of 128 supports only).  Measured at B = 2048, N = 50000, d = 512
+        // (tools/bench_fused.hip, same device): 387 / 353 / 337 us for 0 / 1 / 2.  The tallest tile whose padding costs no
+        // more than 15 % of the rows (else two 64-query workgroups per CU).
+        int variant = form == FORM_HALF ? 3 : knob(KNOB_PVAR);   // NW_PVAR forces one of 0-3
+        if (variant < 0 || variant > 3) {
+            const double rows64 = 1.15 * ((B + 63) / 64 * 64);
+            variant = (p.rs == 8 && (B + 255) / 256 * 256 <= rows64) ? 3 : ((B + 127) / 128 * 128 <= rows64) ? 2 : 1;
+        }
+        if (variant == 3 && p.rs != 8) variant = 2;
+        if (variant == 2 && lds.p128 > 160 * 1024) variant = 0;   // the LDS of one CU / of half a CU
+        if (variant == 1 && lds.p64x2 > 80 * 1024) variant = 0;
+        p.variant = variant;
+        p.workgroups = variant == 1 ? 2 * wgs : wgs;
+        // query tiles kept L2-resident per XCD (NW_QG = 1..64, else 8); variant 3: the same bytes of queries as with
+        // 128-query tiles
+        const int qg = (knob(KNOB_QG) >= 1 && knob(KNOB_QG) <= 64) ? knob(KNOB_QG) : 8;
+        p.qgroup = variant != 3 ? qg : qg >= 2 ? qg / 2 : 1;
+        p.lds_bytes = variant == 3 ? (size_t)P12::LDS_BYTES : variant == 2 ? lds.p128 : variant == 1 ? lds.p64x2 : lds.p64;
+        return p;
+    }
+    if (split) {
+        // Raw queries (MODE_F16Q) cost every workgroup a pass over its 64 query rows and the split in its loop
+        // (~5.4 k cycles at T); the split launch costs ~4.4 us + a kernel boundary once.  Measured per forward
+        // (N = 10000, d = 512; raw / split launch): B = 256 20.2 / 21.8 us, 512 40.6 / 40.1, 768 52.7 / 50.4, 1000
+        // 62.4 / 62.3: raw up to 1.5 workgroups per CU.  NW_SPLIT_QUERIES=1 / 0 forces either.
+        const int force_split = knob(KNOB_SPLIT_QUERIES) == KNOB_UNSET ? -1 : knob(KNOB_SPLIT_QUERIES);
+        const bool raw_ok = force_split == 0 || (force_split < 0 && 2 * (int64_t)p.grid <= 3 * (int64_t)cus);
+        p.split_queries = !raw_ok;
+        p.mode = raw_ok ? MODE_F16Q : MODE_F16;
+    } else {
+        p.mode = !p.dma ? MODE_REG : (norms && !dot) ? MODE_DMA_SN : MODE_DMA;   // cached norms: nothing to add for DOT
+    }
+    p.lds_bytes = p.mode == MODE_REG ? lds.reg : lds.dma;
+    return p;
+}
+
 size_t fused_workspace_bytes(int64_t B, int64_t N, int64_t d, int64_t C) {
     size_t need = 0;
-    for (int f16 = 0; f16 < 2; ++f16) {  // either operand form may be chosen at launch
-        const int rs = pick_rs(B, N, d, f16 != 0);
-        const int64_t n_stiles = (N + 16 * rs - 1) / (16 * rs);
-        const size_t n = fused_layout(B, n_stiles, 16 * rs, nullptr, nullptr, C);
-        need = n > need ? n : need;
-    }
-    if (half_form_shape_ok(d)) {  // nw_fwd_opts.operand_form = 1 runs on tiles of 128 supports at every size
-        const size_t n = fused_layout(B, (N + BANK_BS - 1) / BANK_BS, BANK_BS, nullptr, nullptr, C);
+    for (int form : {FORM_F32, FORM_SPLIT, FORM_HALF}) {  // any operand form may be chosen at launch
+        if (form == FORM_HALF && !half_form_shape_ok(d)) continue;
+        const int BS = plan_tiles(B, N, d, form).BS;
+        const size_t n = fused_layout(B, (N + BS - 1) / BS, BS, nullptr, nullptr, C);
         need = n > need ? n : need;
     }
     return need;
-}
-
-bool half_form_shape_ok(int64_t d) {   // whole 64-k stages, at least three of them (fused_f16p12.h), tile-relative offsets
-    return d % 64 == 0 && d >= 192 && d <= (1 << 20);
 }
 
 bool fused_eligible(const float* q, const float* s, int64_t B, int64_t N, int64_t d, int64_t C) {
@@ -625,36 +702,13 @@ bool fused_eligible(const float* q, const float* s, int64_t B, int64_t N, int64_
            d < (1 << 30) && C < (1 << 30) && (8 + C) * 4 <= 160 * 1024;
 }
 
-// out != nullptr: final log-probabilities (+ optional scores / lse); out == nullptr: (m, den, num).
-int launch_fused(const float* q, const float* s, const int64_t* sy, const float* s_norm2,
-                 const float* s_scale, const float* ls, float* out,
-                 float* scores, float* lse, float* m, float* den, float* num, void* workspace,
-                 size_t workspace_bytes, int64_t B, int64_t N, int64_t d, int64_t C, int kind,
-                 hipStream_t st) {
-#define NW_KIND_CASE(K) \
-    case K: return launch_fused_kind<K>(q, s, sy, s_norm2, s_scale, ls, out, scores, lse, m, den, num, workspace, workspace_bytes, (int)B, (int)N, (int)d, (int)C, st, nullptr)
+int launch_fused(const FusedArgs& a, int form, int kind) {
+    const int out = a.cand ? OUT_CAND : a.scores ? OUT_SCORES : OUT_NONE;
+    const FusedPlan p = plan_fused(a.B, a.N, a.d, a.C, form, out, a.cand ? a.cand->k : 0, a.s_norm2 != nullptr,
+                                   kind == NW_SCORE_DOT, 0, fwd_opts());
+#define NW_KIND_CASE(K) case K: return launch_fused_kind<K>(a, p);
     switch (kind) {
-        NW_KIND_CASE(NW_SCORE_EUCLIDEAN);
-        NW_KIND_CASE(NW_SCORE_HYPERSPHERE);
-        NW_KIND_CASE(NW_SCORE_COSINE);
-        NW_KIND_CASE(NW_SCORE_DOT);
-        NW_KIND_CASE(NW_SCORE_CLIP);
-        default: return NW_ERR_UNSUPPORTED;
-    }
-#undef NW_KIND_CASE
-}
-
-int launch_fused_half(const float* q, const void* s_rows, const int64_t* sy, const float* s_norm2, const float* s_scale,
-                      const float* ls, float* out, float* lse, float* m, float* den, float* num, void* workspace,
-                      size_t workspace_bytes, int64_t B, int64_t N, int64_t d, int64_t C, int kind, hipStream_t st) {
-#define NW_KIND_CASE(K) \
-    case K: return launch_fused_half_kind<K>(q, s_rows, sy, s_norm2, s_scale, ls, out, lse, m, den, num, workspace, workspace_bytes, (int)B, (int)N, (int)d, (int)C, st)
-    switch (kind) {
-        NW_KIND_CASE(NW_SCORE_EUCLIDEAN);
-        NW_KIND_CASE(NW_SCORE_HYPERSPHERE);
-        NW_KIND_CASE(NW_SCORE_COSINE);
-        NW_KIND_CASE(NW_SCORE_DOT);
-        NW_KIND_CASE(NW_SCORE_CLIP);
+        NW_FOR_EACH_KIND(NW_KIND_CASE)
         default: return NW_ERR_UNSUPPORTED;
     }
 #undef NW_KIND_CASE
@@ -671,10 +725,10 @@ struct KnnWs {
 };
 bool knn_shape_ok(int64_t B, int64_t N, int64_t d, int64_t k) {
     return B >= 0 && N > 25 && d >= BK && d % BK == 0 && k >= 1 && k <= 32 && k <= N && B < (1 << 30) && N < (1 << 30) &&
-           d <= (1 << 20);   // (d: the loaders' tile-relative offsets, as in launch_fused_rs)
+           d <= (1 << 20);   // (d: the loaders' tile-relative offsets, as in plan_fused)
 }
-size_t knn_layout(int64_t B, int64_t N, int64_t d, int64_t k, char* base, KnnWs* out) {
-    const int BS = 16 * pick_rs(B, N, d, true);   // the tile height of the score-writing call of this shape
+// BS: the tile height of the score-writing call of this shape (16 * pick_rs on split operands)
+size_t knn_layout(int64_t B, int64_t N, int64_t d, int64_t k, int BS, char* base, KnnWs* out) {
     KnnWs w;
     w.n_stiles = (N + BS - 1) / BS;
     w.kcp = cand_slots((int)k, BS);
@@ -699,18 +753,19 @@ size_t knn_layout(int64_t B, int64_t N, int64_t d, int64_t k, char* base, KnnWs*
 // What the call needs, made non-decreasing in B, N and k: the tile height follows the shape (pick_rs), and a larger shape
 // on taller tiles can need LESS than a smaller one on short tiles -- so the answer is the largest need over the shapes
 // up to (B, N).  Only shapes below the large-grid rule of pick_rs (fewer than 1024 tiles of 128 rows: there the height
-// is fixed and the need grows with the shape) have to be visited, one N per 16 rows and one B per 64 queries.
+// is fixed and the need grows with the shape) have to be visited, one N per 16 rows and one B per 64 queries.  (The height
+// rule alone is asked here, ~10^5 times for a large shape: no plans.)
 size_t knn_workspace_bytes(int64_t B, int64_t N, int64_t d, int64_t k) {
     if (!knn_shape_ok(B, N, d, k) || B == 0) return 0;
-    if (pick_rs(B, N, d, true) > 10) return 0;   // (the tile_rs knob at 12: no candidate form, launch_fused_rs refuses)
-    size_t need = knn_layout(B, N, d, k, nullptr, nullptr);
+    if (pick_rs(B, N, d, true) > 10) return 0;   // (the tile_rs knob at 12: no candidate form, plan_fused refuses)
+    size_t need = knn_layout(B, N, d, k, 16 * pick_rs(B, N, d, true), nullptr, nullptr);
     const int64_t nq = (B + BQ - 1) / BQ;
     for (int64_t qt = 1; qt <= nq && qt < 1024; ++qt) {
         const int64_t Bq = qt * BQ < B ? qt * BQ : B;
         for (int64_t n = 17; n <= N && qt * ((n + 127) / 128) < 1024; n += 16) {   // n: the least N of its 16 rows
             const int64_t nn = n > 26 ? n : 26;
             if (nn > N || k > nn) continue;
-            const size_t x = knn_layout(Bq, nn, d, k, nullptr, nullptr);
+            const size_t x = knn_layout(Bq, nn, d, k, 16 * pick_rs(Bq, nn, d, true), nullptr, nullptr);
             need = x > need ? x : need;
         }
     }
@@ -723,24 +778,13 @@ int launch_knn(const float* q, const float* s_split, const float* s_scale, const
     if (!knn_shape_ok(B, N, d, k)) return NW_ERR_UNSUPPORTED;
     if (B == 0) return NW_OK;
     KnnWs w;
-    const size_t need = knn_layout(B, N, d, k, static_cast<char*>(workspace), &w);
+    const size_t need = knn_layout(B, N, d, k, plan_tiles(B, N, d, FORM_SPLIT).BS, static_cast<char*>(workspace), &w);
     if (!workspace || workspace_bytes < need) return NW_ERR_WORKSPACE;
     if (w.n_stiles * w.kcp >= (1ll << 31)) return NW_ERR_UNSUPPORTED;
-    int rc;
-#define NW_KIND_CASE(K)                                                                                                     \
-    case K:                                                                                                                 \
-        rc = launch_fused_kind<K>(q, s_split, nullptr, s_norm2, s_scale, ls, nullptr, nullptr, nullptr, nullptr, nullptr,   \
-                                  nullptr, nullptr, 0, (int)B, (int)N, (int)d, 1, st, &w.cand);                             \
-        break
-    switch (kind) {
-        NW_KIND_CASE(NW_SCORE_EUCLIDEAN);
-        NW_KIND_CASE(NW_SCORE_HYPERSPHERE);
-        NW_KIND_CASE(NW_SCORE_COSINE);
-        NW_KIND_CASE(NW_SCORE_DOT);
-        NW_KIND_CASE(NW_SCORE_CLIP);
-        default: return NW_ERR_UNSUPPORTED;
-    }
-#undef NW_KIND_CASE
+    FusedArgs a = {};   // no labels, no outputs, no workspace but the CandOut
+    a.q = q, a.s = s_split, a.s_norm2 = s_norm2, a.s_scale = s_scale, a.ls = ls;
+    a.B = (int)B, a.N = (int)N, a.d = (int)d, a.C = 1, a.st = st, a.cand = &w.cand;
+    const int rc = launch_fused(a, FORM_SPLIT, kind);
     if (rc != NW_OK) return rc;
     return launch_topk_candidates(w.cand.key, w.cand.row, idx, vals, B, w.n_stiles * w.kcp, k, st);
 }

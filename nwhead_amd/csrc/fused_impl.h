@@ -5,6 +5,7 @@
 #include "tile_core.h"
 #include "tile_dma.h"
 #include "tile_f16.h"
+#include "fused_plan.h"
 
 namespace nw {
 
@@ -25,10 +26,7 @@ int launch_run_tables(const FusedWs& ws, const int64_t* sy, int N, int C, int n_
 bool bank_tables_take(const int64_t* sy, int N, int C, int n_stiles, int BS, FusedWs* ws);   // the caller's cached tables, if named for this call
 int launch_merge_runs(const FusedWs& ws, float* out, float* lse, float* m, float* den, float* num,
                       int B, int C, int n_stiles, int BS, hipStream_t st);
-// split form of the query batch in the tail of the forward workspace (fused.hip)
-int split_queries_into_workspace(const float* q, void* workspace, size_t workspace_bytes, int64_t B, int64_t N, int64_t d,
-                                 int64_t C, float** rows, float** scale, float** norm2, hipStream_t st);
-// that area itself: rows (B * d floats), scales, norms
+// the query area in the tail of the forward workspace (fused.hip): rows (B * d floats), scales, norms of the split / packed queries
 int query_area_of_workspace(void* workspace, size_t workspace_bytes, int64_t B, int64_t N, int64_t d, int64_t C, float** rows,
                             float** scale, float** norm2);
 // Candidate output of the tile kernel (nw_knn_f32): instead of softmax partials every (query, support tile) pair leaves
@@ -42,33 +40,10 @@ struct CandOut {
     float *q_rows, *q_scale, *q_norm2;
 };
 __host__ __device__ inline int cand_slots(int k, int BS) { return ((k < BS ? k : BS) + 3) & ~3; }
-int device_cu_count();
-bool env_flag(const char* name);
 int tile_timer_start(hipStream_t st);          // diagnostics (nw_debug_tile_timing): -1 when disabled
 void tile_timer_stop(int slot, hipStream_t st);
-int persistent_qgroup();  // query tiles kept L2-resident per XCD by the persistent kernel (NW_QG)
-int persistent_variant();  // NW_PVAR = 0: 64-query tiles, one workgroup per CU; 1: two per CU; 2: 128-query tiles; 3: 256-query tiles; unset: -1
 
 namespace {
-
-// MODE_REG : register-staged loaders (tile_core.h), any d % 4 == 0; loaders compute both norms
-// MODE_DMA : LDS-DMA loaders (tile_dma.h), d % 32 == 0; consumers compute both norms
-// MODE_DMA_SN : LDS-DMA loaders, support norms supplied by the caller (cached bank)
-// MODE_F16 : LDS-DMA loaders, split-fp16 operands on the fp16 matrix cores (tile_f16.h): q and s are
-//            SPLIT rows, norms and row scales of both are supplied
-// MODE_F16Q: as MODE_F16, but q holds the caller's RAW fp32 rows: the consumer waves compute the row scales and
-//            norms in their prologue and split their query fragments in registers (tile_f16.h, QRAW) -- the
-//            one-workgroup-per-tile kernel of small grids (T) runs without a query-split launch in front
-//   (Measured and dropped, T shape: the query fragments RESIDENT in the consumer waves -- high halves in 64 VGPRs, low
-//    halves parked in LDS, only support rows in the stage ring, one set of support fragments refilled block by block.
-//    29 % fewer bytes through the loop's L2 -> LDS stream, but getting the rows into operand shape cost 11.5 k cycles
-//    per workgroup (fragment-shaped global loads, or sixteen 8 KB DMA steps each paying a third of the DMA latency)
-//    and the single-buffered loop ran 750 cycles per stage against 530: 18.5-19.4 us against 16.4.)
-enum { MODE_REG = 0, MODE_DMA = 1, MODE_DMA_SN = 2, MODE_F16 = 3, MODE_F16Q = 4 };
-constexpr bool mode_is_f16(int m) { return m == MODE_F16 || m == MODE_F16Q; }
-// What a tile leaves behind besides (OUT_NONE, OUT_SCORES) or instead of (OUT_CAND) its softmax partials: nothing, its
-// block of the (B,N) score matrix, or its best k scores per query (CandOut; split operands only, no labels, no merge).
-enum { OUT_NONE = 0, OUT_SCORES = 1, OUT_CAND = 2 };
 
 // Runs of equal consecutive labels inside one support tile, by ONE wave (3 rows per lane): fills
 // runid[t] (run of tile row t), runlab[run] (its class, -1 = padding / out-of-range label), nrun_s[0] =
@@ -448,132 +423,98 @@ __global__ __launch_bounds__(TILE_THREADS, (RS <= 5 ? 4 : 2)) void nw_fused_kern
 
 constexpr size_t FUSED_HDR = (128 + 4 * RUN_CAP + 4) * 4;
 
-template <int RS, int KIND>
-int launch_f16p(const float* q, const float* s, const int64_t* sy, const float* s_norm2, const float* s_scale,
-                const float* q_norm2, const float* q_scale, const float* ls, const FusedWs& ws, int B, int N,
-                int d, int C, int n_stiles, int n_qtiles, hipStream_t st);
+// The queries as the tile kernel reads them: the caller's raw rows (norm2 = scale = nullptr), or their split / packed form.
+struct QueryRows {
+    const float *rows, *norm2, *scale;
+};
 
-// q: the caller's RAW fp32 queries.  s_scale != nullptr: s holds the SPLIT rows of a prepared bank (d % 32 == 0,
-// s_norm2 given).  The persistent kernel and the score-writing variant take split queries: the split launch
-// (nw_split_rows_kernel into the tail of the workspace) happens here, only for them.
 template <int RS, int KIND>
-int launch_fused_rs(const float* q, const float* s, const int64_t* sy, const float* s_norm2,
-                    const float* s_scale,
-                    const float* ls, float* out, float* scores, float* lse, float* m, float* den,
-                    float* num, void* workspace, size_t workspace_bytes, int B, int N, int d, int C,
-                    hipStream_t st, const CandOut* cand = nullptr) {
-    const float *q_norm2 = nullptr, *q_scale = nullptr;
+int launch_f16p(const FusedArgs& a, const FusedPlan& p, const QueryRows& q, const FusedWs& ws);
+
+// Executes a plan of plan_fused (fused.hip) on tiles of RS blocks: workspace layout, the optional run-table launch and
+// query-split / pack launch (into the query area at the tail of the workspace, or into the CandOut), one tile kernel, the
+// run merge.  Which of them, and with which grid and LDS, is the plan's business; nothing is decided here.
+template <int RS, int KIND>
+int launch_fused_rs(const FusedArgs& a, const FusedPlan& p) {
     constexpr int BS = 16 * RS;
-    const int n_stiles = (N + BS - 1) / BS;
-    const int n_qtiles = (B + BQ - 1) / BQ;
+    const CandOut* cand = a.cand;
+    hipStream_t st = a.st;
     FusedWs ws = {};
     if (!cand) {   // (candidate output: the caller's CandOut is all the kernel writes)
-        const size_t need = fused_layout(B, n_stiles, BS, static_cast<char*>(workspace), &ws, C);
-        if (!workspace || workspace_bytes < need) return NW_ERR_WORKSPACE;
+        const size_t need = fused_layout(a.B, p.n_stiles, BS, static_cast<char*>(a.workspace), &ws, a.C);
+        if (!a.workspace || a.workspace_bytes < need) return NW_ERR_WORKSPACE;
     }
-    const int grid = padded_grid(n_stiles, n_qtiles);
-    // RS = 5 exists for the LDS-DMA modes only (two workgroups per CU); the register-staged loaders
-    // need an even split of the tile rows
-    const bool dma = (d % BK) == 0 && (uint64_t)(BQ + BS) * 2 * d * 4 < 0xffffffffull;  // per-lane offsets are tile-relative
-    if (!dma && (RS & 1)) return NW_ERR_UNSUPPORTED;
-    const size_t lds_reg = FUSED_HDR + TileCfg<RS>::STAGE_BYTES, lds_dma = FUSED_HDR + DmaCfg<RS>::STAGE_BYTES;
-#define NW_LAUNCH(WS_, MODE_, LDS_)                                                                      \
-    hipLaunchKernelGGL((nw_fused_kernel<RS, KIND, WS_, MODE_>), dim3(grid), dim3(TILE_THREADS), LDS_, st, \
-                       q, s, sy, s_norm2, s_scale, q_norm2, q_scale, ls, scores, ws.m, ws.den, ws.nrun, ws.lab, \
-                       ws.num, B, N, d, C,                                                                  \
-                       n_stiles, n_qtiles)
-    // many tiles per CU on split operands: the persistent kernel (fused_f16p.h).  RS = 8 is the tallest
-    // tile whose build stays under 256 VGPRs.
-    const bool persistent = s_scale && !scores && !cand && RS > 5 && (RS == 8 || env_flag("NW_PERSISTENT_ANY_RS")) &&
-                            grid >= 4 * device_cu_count() && d >= 3 * BK && !env_flag("NW_NO_PERSISTENT");
-    if (persistent) {  // runs of equal labels per support tile: once per launch (ws.runid / nrun / lab / bnd)
-        if (!bank_tables_take(sy, N, C, n_stiles, 16 * RS, &ws)) {
-            const int rc = launch_run_tables(ws, sy, N, C, n_stiles, 16 * RS, st);
-            if (rc != NW_OK) return rc;
-        }
+    if (p.status != NW_OK) return p.status;
+    if (p.run_tables && !bank_tables_take(a.sy, a.N, a.C, p.n_stiles, BS, &ws)) {  // once per launch (ws.runid / nrun / lab / bnd)
+        const int rc = launch_run_tables(ws, a.sy, a.N, a.C, p.n_stiles, BS, st);
+        if (rc != NW_OK) return rc;
     }
-    if (s_scale) {  // split-fp16 operands (the caller has checked d % 32 == 0 and supplied the bank's norms)
-        if (!dma || !s_norm2) return NW_ERR_INVALID_ARG;
-        // Raw queries (MODE_F16Q) cost every workgroup a pass over its 64 query rows and the split in its loop
-        // (~5.4 k cycles at T); the split launch costs ~4.4 us + a kernel boundary once.  Measured per forward
-        // (N = 10000, d = 512; raw / split launch): B = 256 20.2 / 21.8 us, 512 40.6 / 40.1, 768 52.7 / 50.4, 1000
-        // 62.4 / 62.3: raw up to 1.5 workgroups per CU.  NW_SPLIT_QUERIES=1 / 0 forces either.
-        const int force_split = knob(KNOB_SPLIT_QUERIES) == KNOB_UNSET ? -1 : knob(KNOB_SPLIT_QUERIES);
-        const bool raw_ok = force_split == 0 || (force_split < 0 && 2 * grid <= 3 * device_cu_count());
-        if (persistent || !raw_ok) {
-            float *qr, *qsc, *qn;
-            int rc;
-            if (cand) rc = launch_split_rows(q, qr = cand->q_rows, qsc = cand->q_scale, qn = cand->q_norm2, B, d, st);
-            else rc = split_queries_into_workspace(q, workspace, workspace_bytes, B, N, d, C, &qr, &qsc, &qn, st);
-            if (rc != NW_OK) return rc;
-            q = qr;
-            q_scale = qsc;
-            q_norm2 = qn;
-        }
+    QueryRows q = {a.q, nullptr, nullptr};
+    if (p.split_queries) {
+        float *qr, *qsc, *qn;
+        int rc = NW_OK;
+        if (cand) qr = cand->q_rows, qsc = cand->q_scale, qn = cand->q_norm2;
+        else rc = query_area_of_workspace(a.workspace, a.workspace_bytes, a.B, a.N, a.d, a.C, &qr, &qsc, &qn);
+        if (rc == NW_OK)
+            rc = p.form == FORM_HALF ? launch_pack_rows_f16(a.q, qr, qsc, qn, a.B, a.d, st) : launch_split_rows(a.q, qr, qsc, qn, a.B, a.d, st);
+        if (rc != NW_OK) return rc;
+        q = {qr, qn, qsc};
     }
-    if (cand) {   // the launch of the score-writing call of this shape (tile height, raw or split queries, grid), OUT_CAND
-        if (!s_scale) return NW_ERR_INVALID_ARG;
+    // OUT_CAND: CandOut's key / row arrays stand where the scores and the run labels go, k where the class count goes
+    // (nw_fused_kernel); ws is all null then.
+    float* scores = cand ? reinterpret_cast<float*>(cand->key) : a.scores;
+    int* lab = cand ? cand->row : ws.lab;
+    const int c_or_k = cand ? cand->k : a.C;
+#define NW_TILE(OUT_, MODE_)                                                                                           \
+    hipLaunchKernelGGL((nw_fused_kernel<RS, KIND, OUT_, MODE_>), dim3(p.grid), dim3(TILE_THREADS), p.lds_bytes, st, q.rows, \
+                       a.s, a.sy, a.s_norm2, a.s_scale, q.norm2, q.scale, a.ls, scores, ws.m, ws.den, ws.nrun, lab, ws.num, \
+                       a.B, a.N, a.d, c_or_k, p.n_stiles, p.n_qtiles)
+#define NW_TILE_CASE(MODE_) \
+    case MODE_: if (p.out == OUT_SCORES) NW_TILE(OUT_SCORES, MODE_); else NW_TILE(OUT_NONE, MODE_); break
+    if (p.out == OUT_CAND) {   // the launch of the score-writing call of this shape (tile height, raw or split queries, grid)
         // (RS = 12 on split operands exists only under the tile_rs knob and spills there: no candidate form of it)
         if constexpr (RS == 12) {
             return NW_ERR_UNSUPPORTED;
         } else {
-#define NW_LAUNCH_CAND(MODE_)                                                                                              \
-    hipLaunchKernelGGL((nw_fused_kernel<RS, KIND, OUT_CAND, MODE_>), dim3(grid), dim3(TILE_THREADS), lds_dma, st, q, s,    \
-                       (const int64_t*)nullptr, s_norm2, s_scale, q_norm2, q_scale, ls, reinterpret_cast<float*>(cand->key), \
-                       (float*)nullptr, (float*)nullptr, (int*)nullptr, cand->row, (float*)nullptr, B, N, d, cand->k,       \
-                       n_stiles, n_qtiles)
-            if (!q_scale) NW_LAUNCH_CAND(MODE_F16Q); else NW_LAUNCH_CAND(MODE_F16);
-#undef NW_LAUNCH_CAND
+            if (p.mode == MODE_F16Q) NW_TILE(OUT_CAND, MODE_F16Q); else NW_TILE(OUT_CAND, MODE_F16);
             NW_CHECK_LAUNCH();
             return NW_OK;
         }
     }
     const int timer_slot = tile_timer_start(st);
-    if (s_scale) {
-        if (!q_scale) {
-            if (scores) NW_LAUNCH(OUT_SCORES, MODE_F16Q, lds_dma); else NW_LAUNCH(OUT_NONE, MODE_F16Q, lds_dma);
-        } else if (scores) {
-            NW_LAUNCH(OUT_SCORES, MODE_F16, lds_dma);
-        } else if (persistent) {
-            const int rc = launch_f16p<RS, KIND>(q, s, sy, s_norm2, s_scale, q_norm2, q_scale, ls, ws, B, N, d, C,
-                                                 n_stiles, n_qtiles, st);
-            if (rc != NW_OK) return rc;
-        } else {
-            NW_LAUNCH(OUT_NONE, MODE_F16, lds_dma);
-        }
-    } else if (dma && s_norm2 && KIND != NW_SCORE_DOT) {
-        if (scores) NW_LAUNCH(OUT_SCORES, MODE_DMA_SN, lds_dma); else NW_LAUNCH(OUT_NONE, MODE_DMA_SN, lds_dma);
-    } else if (dma) {
-        if (scores) NW_LAUNCH(OUT_SCORES, MODE_DMA, lds_dma); else NW_LAUNCH(OUT_NONE, MODE_DMA, lds_dma);
+    if (p.persistent) {
+        const int rc = launch_f16p<RS, KIND>(a, p, q, ws);
+        if (rc != NW_OK) return rc;
     } else {
-        if (scores) NW_LAUNCH(OUT_SCORES, MODE_REG, lds_reg); else NW_LAUNCH(OUT_NONE, MODE_REG, lds_reg);
+        switch (p.mode) {
+            NW_TILE_CASE(MODE_REG);
+            NW_TILE_CASE(MODE_DMA);
+            NW_TILE_CASE(MODE_DMA_SN);
+            NW_TILE_CASE(MODE_F16);
+            NW_TILE_CASE(MODE_F16Q);
+        }
     }
-#undef NW_LAUNCH
+#undef NW_TILE_CASE
+#undef NW_TILE
     tile_timer_stop(timer_slot, st);
     NW_CHECK_LAUNCH();
-    return launch_merge_runs(ws, out, lse, m, den, num, B, C, n_stiles, BS, st);
+    return launch_merge_runs(ws, a.out, a.lse, a.m, a.den, a.num, a.B, a.C, p.n_stiles, BS, st);
 }
 
 }  // namespace
 
+// Every form goes through here: the half-precision one (FORM_HALF) is a plan on tiles of 128 supports like any other.
 template <int KIND>
-int launch_fused_kind(const float* q, const float* s, const int64_t* sy, const float* s_norm2,
-                      const float* s_scale,
-                      const float* ls, float* out, float* scores, float* lse, float* m, float* den,
-                      float* num, void* workspace, size_t wsb, int B, int N, int d, int C, hipStream_t st,
-                      const CandOut* cand) {
-#define NW_RS_CASE(R) \
-    case R: return launch_fused_rs<R, KIND>(q, s, sy, s_norm2, s_scale, ls, out, scores, lse, m, den, num, workspace, wsb, B, N, d, C, st, cand)
-    switch (pick_rs(B, N, d, s_scale != nullptr)) {
-        NW_RS_CASE(2);
-        NW_RS_CASE(4);
-        NW_RS_CASE(5);
-        NW_RS_CASE(6);
-        NW_RS_CASE(8);
-        NW_RS_CASE(10);
-        default: return launch_fused_rs<12, KIND>(q, s, sy, s_norm2, s_scale, ls, out, scores, lse, m, den, num, workspace, wsb, B, N, d, C, st, cand);
+int launch_fused_kind(const FusedArgs& a, const FusedPlan& p) {
+    switch (p.rs) {
+        case 2: return launch_fused_rs<2, KIND>(a, p);
+        case 4: return launch_fused_rs<4, KIND>(a, p);
+        case 5: return launch_fused_rs<5, KIND>(a, p);
+        case 6: return launch_fused_rs<6, KIND>(a, p);
+        case 8: return launch_fused_rs<8, KIND>(a, p);
+        case 10: return launch_fused_rs<10, KIND>(a, p);
+        default: return launch_fused_rs<12, KIND>(a, p);
     }
-#undef NW_RS_CASE
 }
 
 }  // namespace nw
@@ -581,54 +522,36 @@ int launch_fused_kind(const float* q, const float* s, const int64_t* sy, const f
 #include "fused_f16p12.h"
 namespace nw {
 namespace {
+// The one launch of nw_fused_f16p_kernel_w12 (256-query tiles of 128 supports, fused_f16p12.h).  HALF: half-precision rows
+// (a.s / s_scale / s_norm2 from nw_pack_rows_f16, the queries packed likewise); their stride in floats is d / 2 -- the
+// loader and the stage count follow from it.
+template <int KIND, bool HALF>
+int launch_p12(const FusedPlan& p, const FusedArgs& a, const QueryRows& q, const FusedWs& ws) {
+    static const bool attr = hipFuncSetAttribute(reinterpret_cast<const void*>(nw_fused_f16p_kernel_w12<KIND, HALF>),
+                                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)P12::LDS_BYTES) == hipSuccess;
+    (void)attr;
+    hipLaunchKernelGGL((nw_fused_f16p_kernel_w12<KIND, HALF>), dim3(p.workgroups), dim3(P12::THREADS), p.lds_bytes, a.st, q.rows,
+                       a.s, a.s_norm2, a.s_scale, q.norm2, q.scale, a.ls, ws.runid, ws.nrun, ws.bnd, ws.m, ws.den, ws.num, a.B,
+                       a.N, HALF ? a.d / 2 : a.d, p.n_stiles, (a.B + P12::BQP - 1) / P12::BQP, p.qgroup);
+    NW_CHECK_LAUNCH();
+    return NW_OK;
+}
+
+// The persistent kernel of the plan's variant (and, for variant 3, form); the run tables are the caller's job.
 template <int RS, int KIND>
-int launch_f16p(const float* q, const float* s, const int64_t* sy, const float* s_norm2, const float* s_scale,
-                const float* q_norm2, const float* q_scale, const float* ls, const FusedWs& ws, int B, int N,
-                int d, int C, int n_stiles, int n_qtiles, hipStream_t st) {
+int launch_f16p(const FusedArgs& a, const FusedPlan& p, const QueryRows& q, const FusedWs& ws) {
     if constexpr (RS > 5) {
-        (void)sy; (void)C;  // the run tables (launch_run_tables) are the caller's job
-        int cus = device_cu_count() & ~7;  // the same number of workgroups on every XCD
-        // nw_fwd_opts.persistent_wgs: fewer workgroups than CUs (a multiple of 8), to leave CUs to a concurrent RCCL kernel
-        // of the sharded path (ShardedBank leaves one CU per XCD when there is more than one rank)
-        const int wg_cap = fwd_opts().persistent_wgs & ~7;
-        if (wg_cap >= 8 && wg_cap < cus) cus = wg_cap;
-        // 0: 64-query tiles, one workgroup per CU; 1: two per CU; 2: 128-query tiles; 3: 256-query tiles on eight
-        // multiplying waves (fused_f16p12.h, tiles of 128 supports only).  Measured at B = 2048, N = 50000, d = 512
-        // (tools/bench_fused.hip, same device): 387 / 353 / 337 us for 0 / 1 / 2.  The tallest tile whose padding costs no
-        // more than 15 % of the rows (else two 64-query workgroups per CU).
-        int variant = persistent_variant();
-        if (variant < 0) {
-            const double rows64 = 1.15 * ((B + 63) / 64 * 64);
-            variant = (RS == 8 && (B + 255) / 256 * 256 <= rows64) ? 3 : ((B + 127) / 128 * 128 <= rows64) ? 2 : 1;
-        }
-        (void)n_qtiles;
-        if constexpr (RS == 8) {
-            if (variant == 3) {
-                static const bool attr = hipFuncSetAttribute(reinterpret_cast<const void*>(nw_fused_f16p_kernel_w12<KIND>),
-                                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)P12::LDS_BYTES) == hipSuccess;
-                (void)attr;
-                int qgrp = persistent_qgroup() / 2;   // the same bytes of queries resident per XCD as with 128-query tiles
-                if (qgrp < 1) qgrp = 1;
-                hipLaunchKernelGGL((nw_fused_f16p_kernel_w12<KIND>), dim3(cus), dim3(P12::THREADS), P12::LDS_BYTES, st, q, s,
-                                   s_norm2, s_scale, q_norm2, q_scale, ls, ws.runid, ws.nrun, ws.bnd, ws.m, ws.den, ws.num, B, N, d,
-                                   n_stiles, (B + P12::BQP - 1) / P12::BQP, qgrp);
-                NW_CHECK_LAUNCH();
-                return NW_OK;
-            }
-        }
-        if (variant > 2) variant = 2;
-#define NW_LAUNCH_P(TWO_, QB_, GRID_)                                                                             \
-    hipLaunchKernelGGL((nw_fused_f16p_kernel<RS, KIND, TWO_, QB_>), dim3(GRID_), dim3(TILE_THREADS),              \
-                       (PCfg<RS, QB_, TWO_>::LDS_BYTES), st, q, s, s_norm2, s_scale, q_norm2, q_scale, ls, ws.runid, \
-                       ws.nrun, ws.bnd, ws.m, ws.den, ws.num, B, N, d, n_stiles, (B + 64 * (QB_) - 1) / (64 * (QB_)), \
-                       persistent_qgroup())
-        constexpr size_t lds_q2 = PCfg<RS, 2, false>::LDS_BYTES, lds_two = PCfg<RS, 1, true>::LDS_BYTES;
-        if (variant == 2 && lds_q2 <= 160 * 1024) {
-            NW_LAUNCH_P(false, 2, cus);
-        } else if (variant == 1 && lds_two <= 80 * 1024) {
-            NW_LAUNCH_P(true, 1, 2 * cus);
-        } else {
-            NW_LAUNCH_P(false, 1, cus);
+#define NW_LAUNCH_P(TWO_, QB_)                                                                                        \
+    hipLaunchKernelGGL((nw_fused_f16p_kernel<RS, KIND, TWO_, QB_>), dim3(p.workgroups), dim3(TILE_THREADS), p.lds_bytes, \
+                       a.st, q.rows, a.s, a.s_norm2, a.s_scale, q.norm2, q.scale, a.ls, ws.runid, ws.nrun, ws.bnd, ws.m, \
+                       ws.den, ws.num, a.B, a.N, a.d, p.n_stiles, (a.B + 64 * (QB_) - 1) / (64 * (QB_)), p.qgroup)
+        switch (p.variant) {
+            case 3:   // (plan_fused gives variant 3 to tiles of 128 supports only)
+                if constexpr (RS == 8) return p.form == FORM_HALF ? launch_p12<KIND, true>(p, a, q, ws) : launch_p12<KIND, false>(p, a, q, ws);
+                return NW_ERR_UNSUPPORTED;
+            case 2: NW_LAUNCH_P(false, 2); break;
+            case 1: NW_LAUNCH_P(true, 1); break;
+            default: NW_LAUNCH_P(false, 1); break;
         }
 #undef NW_LAUNCH_P
         NW_CHECK_LAUNCH();
@@ -637,54 +560,6 @@ int launch_f16p(const float* q, const float* s, const int64_t* sy, const float* 
 }
 }  // namespace
 
-// The head on half-precision operands (nw_fwd_opts.operand_form = 1): always nw_fused_f16p_kernel_w12<KIND, true> on tiles of
-// 128 supports, whatever the size -- the tile-count rule of launch_fused_rs is a speed heuristic, and this form has no
-// other kernel.  s_rows / s_scale / s_norm2: nw_pack_rows_f16 of the bank; the queries are packed here, into the query
-// area at the tail of the workspace.  Run tables, workspace layout and merge are those of the split path.
-template <int KIND>
-int launch_fused_half_kind(const float* q, const void* s_rows, const int64_t* sy, const float* s_norm2, const float* s_scale,
-                           const float* ls, float* out, float* lse, float* m, float* den, float* num, void* workspace,
-                           size_t workspace_bytes, int B, int N, int d, int C, hipStream_t st) {
-    using P = P12;
-    constexpr int BS = P::BS;
-    const int n_stiles = (N + BS - 1) / BS;
-    FusedWs ws;
-    const size_t need = fused_layout(B, n_stiles, BS, static_cast<char*>(workspace), &ws, C);
-    if (!workspace || workspace_bytes < need) return NW_ERR_WORKSPACE;
-    if (!bank_tables_take(sy, N, C, n_stiles, BS, &ws)) {
-        const int rc = launch_run_tables(ws, sy, N, C, n_stiles, BS, st);
-        if (rc != NW_OK) return rc;
-    }
-    float *qr, *qsc, *qn;
-    int rc = query_area_of_workspace(workspace, workspace_bytes, B, N, d, C, &qr, &qsc, &qn);
-    if (rc != NW_OK) return rc;
-    rc = launch_pack_rows_f16(q, qr, qsc, qn, B, d, st);
-    if (rc != NW_OK) return rc;
-    int cus = device_cu_count() & ~7;
-    const int wg_cap = fwd_opts().persistent_wgs & ~7;
-    if (wg_cap >= 8 && wg_cap < cus) cus = wg_cap;
-    static const bool attr = hipFuncSetAttribute(reinterpret_cast<const void*>(nw_fused_f16p_kernel_w12<KIND, true>),
-                                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)P::LDS_BYTES) == hipSuccess;
-    (void)attr;
-    int qgrp = persistent_qgroup() / 2;
-    if (qgrp < 1) qgrp = 1;
-    const int timer_slot = tile_timer_start(st);
-    // d / 2: the row stride of the fp16 rows in floats -- the loader and the stage count follow from it
-    hipLaunchKernelGGL((nw_fused_f16p_kernel_w12<KIND, true>), dim3(cus), dim3(P::THREADS), P::LDS_BYTES, st, qr,
-                       static_cast<const float*>(s_rows), s_norm2, s_scale, qn, qsc, ls, ws.runid, ws.nrun, ws.bnd, ws.m, ws.den,
-                       ws.num, B, N, d / 2, n_stiles, (B + P::BQP - 1) / P::BQP, qgrp);
-    tile_timer_stop(timer_slot, st);
-    NW_CHECK_LAUNCH();
-    return launch_merge_runs(ws, out, lse, m, den, num, B, C, n_stiles, BS, st);
-}
-
-#define NW_INSTANTIATE_FUSED_KIND(K)                                                                   \
-    template int launch_fused_kind<K>(const float*, const float*, const int64_t*, const float*,        \
-                                      const float*,                                                    \
-                                      const float*, float*, float*, float*, float*, float*, float*,    \
-                                      void*, size_t, int, int, int, int, hipStream_t, const CandOut*); \
-    template int launch_fused_half_kind<K>(const float*, const void*, const int64_t*, const float*, const float*,      \
-                                           const float*, float*, float*, float*, float*, float*, void*, size_t, int,   \
-                                           int, int, int, hipStream_t);
+#define NW_INSTANTIATE_FUSED_KIND(K) template int launch_fused_kind<K>(const FusedArgs&, const FusedPlan&);
 
 }  // namespace nw

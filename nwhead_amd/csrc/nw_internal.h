@@ -107,16 +107,7 @@ int launch_split_rows(const float* x, float* out, float* scale, float* norm2, in
 int launch_pack_rows_f16(const float* x, void* out, float* scale, float* norm2, int64_t rows, int64_t d, hipStream_t st);
 // the head on half-precision operands (nw_fwd_opts.operand_form = 1): s_rows / s_scale / s_norm2 from nw_pack_rows_f16
 bool half_form_shape_ok(int64_t d);
-int launch_fused_half(const float* q, const void* s_rows, const int64_t* sy, const float* s_norm2, const float* s_scale,
-                      const float* logit_scale_dev, float* out, float* lse, float* m, float* den, float* num,
-                      void* workspace, size_t workspace_bytes, int64_t B, int64_t N, int64_t d, int64_t C, int kind,
-                      hipStream_t st);
-int launch_fused(const float* q, const float* s, const int64_t* sy, const float* s_norm2,
-                 const float* s_scale,
-                 const float* logit_scale_dev, float* out, float* scores, float* lse, float* m,
-                 float* den, float* num,
-                 void* workspace, size_t workspace_bytes, int64_t B, int64_t N, int64_t d, int64_t C,
-                 int kind, hipStream_t st);
+// (the fused launch itself: launch_fused(const FusedArgs&, form, kind), fused_plan.h)
 
 // bn_nhwc.hip, for bn_dgrad.hip: the BatchNorm backward finalize over G groups of partial sums
 int bn_bwd_finalize_groups(const float* part, int G, int C, float inv_m, float* dgamma, float* dbeta, float* k, hipStream_t st);

@@ -1,12 +1,13 @@
 """A Python model of the tile order of the persistent split-fp16 kernels (PersistentTiles::decode() in
-nwhead_amd/csrc/persistent_pipe.h, used by fused_f16p.h and fused_f16p12.h) and of the launcher's workgroup count
-(launch_f16p in fused_impl.h), and the shapes of the order edges that test_persistent_schedule_gpu.py derives from them.  A plain helper module: test_persistent_schedule_model.py checks the
-model on the CPU, the GPU tests use it to state what their shapes mean.
+nwhead_amd/csrc/persistent_pipe.h, used by fused_f16p.h and fused_f16p12.h) and of the plan's workgroup count
+(plan_fused in fused.hip), and the shapes of the order edges that test_persistent_schedule_gpu.py derives from them.  A plain
+helper module: test_persistent_schedule_model.py checks the model on the CPU, the GPU tests use it to state what their shapes
+mean -- and assert_persistent() asks the library itself which route a shape takes.
 """
 
 BS = 128                                        # support rows per tile, every persistent variant
 BQP = {0: 64, 1: 64, 2: 128, 3: 256}            # query rows per tile, by NW_PVAR
-QG_DEFAULT = 8                                  # persistent_qgroup() (fused.hip) when NW_QG is unset
+QG_DEFAULT = 8                                  # plan_fused (fused.hip) when NW_QG is unset
 
 
 def n_local(n_stiles, n_qtiles, xcd):
@@ -38,12 +39,25 @@ def kernel_qg(pvar, qg):
 
 
 def workgroups(pvar, cus, wgs):
-    """Grid of launch_f16p: `wgs` rounded down to a multiple of 8, used when it is in [8, CUs); two per CU for pvar 1."""
+    """FusedPlan.workgroups (plan_fused): `wgs` rounded down to a multiple of 8, used when it is in [8, CUs); two per CU for pvar 1."""
     n = cus & ~7
     cap = wgs & ~7
     if 8 <= cap < n:
         n = cap
     return 2 * n if pvar == 1 else n
+
+
+def assert_persistent(B, N, d, cus, variant=None, wgs=0, C=200):
+    """The library's own launch decision (nw_debug_fwd_plan: plan_fused with the knobs as they are set NOW) for a split-operand
+    forward of this shape on `cus` CUs takes the persistent kernel -- of tile variant `variant`, where the test forces one.
+    Returns the plan."""
+    from nwhead_amd import _lib
+    p = _lib.fwd_plan(B, N, d, C, form="split", persistent_wgs=wgs, cus=cus)
+    assert p.status == 0 and p.persistent, \
+        f"B={B} N={N} d={d}: plan_fused does not take the persistent kernel on {cus} CUs (status {p.status}, rs {p.rs}, grid {p.grid})"
+    if variant is not None:
+        assert p.variant == variant, f"B={B} N={N} d={d}: tile variant {p.variant}, not the forced {variant}"
+    return p
 
 
 EDGES = ("fewer_than_8_stiles", "stiles_0_mod_8", "stiles_1_mod_8", "stiles_7_mod_8", "one_tile_per_wg",

@@ -116,6 +116,27 @@ int main() {
     EXPECT(nw_debug_set(nullptr, 1), NW_ERR_INVALID_ARG);
     EXPECT(nw_debug_set("no_such_knob", 1), NW_ERR_INVALID_ARG);
     EXPECT(nw_debug_set("qg", 8), NW_OK);
+    {   // the launch decision as a value: pure host arithmetic, "no device" answers 256 CUs
+        nw_fwd_plan pl;
+        EXPECT(nw_debug_fwd_plan(256, 50000, 512, 200, 1, 0, 0, 1, NW_SCORE_EUCLIDEAN, 0, 0, nullptr), NW_ERR_INVALID_ARG);
+        EXPECT(nw_debug_fwd_plan(-1, 50000, 512, 200, 1, 0, 0, 1, NW_SCORE_EUCLIDEAN, 0, 0, &pl), NW_ERR_INVALID_ARG);
+        EXPECT(nw_debug_fwd_plan(256, -5, 512, 200, 1, 0, 0, 1, NW_SCORE_EUCLIDEAN, 0, 0, &pl), NW_ERR_INVALID_ARG);
+        EXPECT(nw_debug_fwd_plan(256, 50000, 512, 200, 7, 0, 0, 1, NW_SCORE_EUCLIDEAN, 0, 0, &pl), NW_ERR_INVALID_ARG);   // unknown form
+        EXPECT(nw_debug_fwd_plan(256, 50000, 512, 200, 1, 3, 0, 1, NW_SCORE_EUCLIDEAN, 0, 0, &pl), NW_ERR_INVALID_ARG);   // unknown output
+        EXPECT(nw_debug_fwd_plan(256, 50000, 512, 200, 1, 0, 0, 1, 99, 0, 0, &pl), NW_ERR_UNSUPPORTED);
+        EXPECT(nw_debug_fwd_plan(256, 50000, 512, 200, 1, 0, 0, 1, NW_SCORE_EUCLIDEAN, 0, 0, &pl), NW_OK);
+        EXPECT(pl.status == NW_OK && pl.persistent == 1 && pl.workgroups == 256 && pl.n_stiles == 391, 1);
+        EXPECT(nw_debug_fwd_plan(256, 50000, 512, 200, 1, 0, 0, 1, NW_SCORE_EUCLIDEAN, 0, INT32_MAX, &pl), NW_ERR_INVALID_ARG);
+        EXPECT(nw_debug_fwd_plan(0, 0, 0, 0, 0, 0, 0, 0, NW_SCORE_DOT, 0, 0, &pl), NW_OK);                                // empty shape
+        for (int form = 0; form < 3; ++form) {   // huge shapes: refused in the plan, no overflow on the way
+            EXPECT(nw_debug_fwd_plan(INT64_MAX, INT64_MAX, INT64_MAX, INT64_MAX, form, 0, 0, 1, NW_SCORE_EUCLIDEAN, 0, 0, &pl), NW_OK);
+            EXPECT(pl.status, NW_ERR_UNSUPPORTED);
+            EXPECT(nw_debug_fwd_plan((1 << 30) - 1, (1 << 30) - 1, 512, 200, form, 0, 0, 1, NW_SCORE_EUCLIDEAN, 0, 0, &pl), NW_OK);
+            EXPECT(pl.status, NW_ERR_UNSUPPORTED);                                                                         // more tiles than a grid holds
+            EXPECT(nw_debug_fwd_plan(1 << 20, 1 << 20, 512, 200, form, 0, 0, 1, NW_SCORE_EUCLIDEAN, INT32_MAX, 1 << 20, &pl), NW_OK);
+            EXPECT(pl.status, NW_OK);
+        }
+    }
     // split rows, norms, influence, top-k, aggregate
     EXPECT(nw_split_rows_f16x2(F, F, F, F, 4, 48, nullptr), NW_ERR_UNSUPPORTED);      // d % 32 != 0
     EXPECT(nw_split_rows_f16x2(F, F, F, F, -1, 32, nullptr), NW_ERR_INVALID_ARG);

@@ -10,7 +10,8 @@ derived from (fused_f16p.h, pvar 2), bit for bit, on the cases its partial store
     itself is compared, so a value stored into another array's slot cannot hide behind the merge to log-probabilities.
 
 Both variants are forced through NW_PVAR, as in test_persistent_p12_gpu.py.  The shapes are the smallest that take the
-persistent kernel (four 64-query tiles per CU); each test asserts that its shape does.
+persistent kernel (four 64-query tiles per CU); each test asserts that its shape does, and that the forced variant is the one
+the library plans (persistent_schedule.assert_persistent: nw_debug_fwd_plan with the device's CU count).
 """
 import os
 
@@ -19,6 +20,7 @@ import pytest
 import torch
 
 import ws_poison
+from persistent_schedule import assert_persistent
 
 pytestmark = pytest.mark.gpu
 
@@ -107,9 +109,8 @@ def _inputs(dev, B, N, labels):
     return q, s, sy.to(dev)
 
 
-def _assert_persistent(dev, B, N):
-    cus = torch.cuda.get_device_properties(dev).multi_processor_count
-    assert ((B + 63) // 64) * ((N + BS - 1) // BS) >= 4 * cus, "shape too small for the persistent kernel on this device"
+def _assert_persistent(dev, B, N, variant=None):
+    assert_persistent(B, N, D, torch.cuda.get_device_properties(dev).multi_processor_count, variant=variant)
 
 
 def _logit_scale(kind, dev):
@@ -128,9 +129,11 @@ def test_p12_epilogue_log_probs_equal_p2(dev, ops, pvar, kind, B, N, labels):
     # both variants lay the scratch buffer out alike: without the poison a store that one forgets is filled in by the other
     need = ws_poison.fwd_workspace_bytes(B, N, D, C)
     pvar(2)
+    _assert_persistent(dev, B, N, variant=2)
     assert ws_poison.poison_cached_workspaces(need, dev) >= need
     out2 = ops.nw_head(q, s, sy, C, kind, ls, support_cache=cache).clone()
     pvar(3)
+    _assert_persistent(dev, B, N, variant=3)
     assert ws_poison.poison_cached_workspaces(need, dev) >= need
     out3 = ops.nw_head(q, s, sy, C, kind, ls, support_cache=cache).clone()
     torch.cuda.synchronize()
@@ -151,6 +154,7 @@ def test_p12_epilogue_packed_partials_equal_p2(dev, pvar, kind, B, N):
     need = ws_poison.fwd_workspace_bytes(B, N, D, bank.CL)
     for v in (2, 3):
         pvar(v)
+        _assert_persistent(dev, B, N, variant=v)
         # the bank's own scratch buffer (kept from call to call, never cleared) is the one in use; the shared one is poisoned
         # too so that nothing can come from it, and may rightly be empty here: its byte count is not asserted
         bank._ws = ws_poison.poisoned_workspace(need, dev)

@@ -27,8 +27,10 @@ class-sorted copy, which is what the call then passes) and "shuffled_nolabels" (
 tile reach the kernel, tables built by the launch).
 
 Bound against the oracle: that of test_hip_parity.py::test_persistent_many_tiles.  Every GPU test asserts that its shape
-takes the persistent kernel (launch_fused_rs: at least 4 * CUs 64-query tiles, d >= 96, d % 32 == 0; pick_rs, which picks
-the 128-support tile the persistent kernel needs, asks for 1024 of them whatever the device).
+takes the persistent kernel, twice: by the documented rule (plan_fused in fused.hip: at least 4 * CUs 64-query tiles, d >= 96,
+d % 32 == 0; pick_rs, which picks the 128-support tile the persistent kernel needs, asks for 1024 of them whatever the
+device) and by the library's own answer for the shape (persistent_schedule.assert_persistent: nw_debug_fwd_plan with the
+device's CU count; with the forced tile variant once NW_PVAR is set).
 """
 import os
 
@@ -37,7 +39,7 @@ import pytest
 import torch
 
 import ws_poison
-from persistent_schedule import BS, EDGES, edge_shape, n_local, workgroups
+from persistent_schedule import BS, EDGES, assert_persistent, edge_shape, n_local, workgroups
 
 pytestmark = pytest.mark.gpu
 
@@ -107,6 +109,7 @@ def _assert_persistent(dev, B, N, d):
     tiles = ((B + 63) // 64) * ((N + BS - 1) // BS)
     assert tiles >= 4 * cus and tiles >= 1024 and d >= 96 and d % 32 == 0, \
         f"B={B} N={N} d={d}: {tiles} 64-query tiles do not take the persistent kernel on {cus} CUs"
+    assert_persistent(B, N, d, cus)
 
 
 _CASES = {}
@@ -228,6 +231,7 @@ def test_schedule_invariance(dev, ops, knobs, pvar, B, N, kind, labels, wgs, qg)
         knobs(pvar=pvar)
         _DEFAULT_OUT[key] = _forward(dev, ops, c).clone()
     knobs(pvar=pvar, qg=qg)
+    assert assert_persistent(B, N, d, cus, variant=pvar, wgs=w).workgroups == n_wg
     # the sharded bank's setting goes through the sharded bank (class-sorted, as precompute() builds it)
     out = _forward(dev, ops, c, wgs=w, sharded=(wgs == "cus-8" and labels == "sorted"))
     ref = _DEFAULT_OUT[key]
@@ -249,6 +253,7 @@ def test_ring_residues(dev, ops, O, knobs, pvar, d, wgs):
     labels = "shuffled_nolabels" if d in (160, 224) else "sorted"
     c = _case(dev, ops, B, N, d, kind, labels)
     knobs(pvar=pvar)
+    assert_persistent(B, N, d, _cus(dev), variant=pvar)
     out = _forward(dev, ops, c, wgs=_wgs(wgs, _cus(dev)))
     _assert_oracle(O, c, out, f"pvar {pvar} d {d} wgs {wgs} {kind}:")
 
@@ -278,6 +283,7 @@ def test_order_edges(dev, ops, O, knobs, edge):
     outs = {}
     for pvar in PVARS:
         knobs(pvar=pvar)
+        assert_persistent(B, N, d, cus, variant=pvar)
         outs[pvar] = _forward(dev, ops, c).clone()
     for pvar in PVARS:
         _assert_oracle(O, c, outs[pvar], f"{edge} B {B} N {N} pvar {pvar} {kind}:")
@@ -303,6 +309,7 @@ def test_persistent_and_one_workgroup_per_tile(dev, ops, O, knobs, pvar, kind):
         _ONE_WG_PER_TILE[kind] = _forward(dev, ops, c).clone()
         _assert_oracle(O, c, _ONE_WG_PER_TILE[kind], f"{kind} one workgroup per tile:")
     knobs(pvar=pvar)
+    assert_persistent(B, N, d, _cus(dev), variant=pvar)
     out_p = _forward(dev, ops, c).clone()
     _assert_oracle(O, c, out_p, f"{kind} pvar {pvar} persistent:")
     print(f"{kind} pvar {pvar}: {(out_p != _ONE_WG_PER_TILE[kind]).sum().item()} of {out_p.numel()} outputs differ in bits "

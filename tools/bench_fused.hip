@@ -1,6 +1,8 @@
 // Diagnostic harness: phase stamps of nw_fused_kernel (build with -DNW_DIAG_FUSED).
 // Persistent kernels (argv[5] = 2): NW_PVAR=0 / 1 / 2 pick the variants of fused_f16p.h, NW_PVAR=3 the 256-query kernel of
 // fused_f16p12.h (-DNW_BENCH_RS=8); both take -DNW_ABL_NODMA / -DNW_ABL_NORD / -DNW_ABL_NOEPI.
+// Build: hipcc -O3 --offload-arch=gfx950 -I nwhead_amd/csrc -DNW_DIAG_FUSED [-DNW_BENCH_RS=8] tools/bench_fused.hip
+//        nwhead_amd/csrc/split.hip -o tools/bench_fused
 #include <hip/hip_runtime.h>
 #include <cstdio>
 #include <cstdlib>
@@ -12,13 +14,7 @@ namespace nw {
 size_t fused_layout(int64_t, int64_t, int, char*, FusedWs*, int64_t) { return 0; }
 int launch_merge_runs(const FusedWs&, float*, float*, float*, float*, float*, int, int, int, int, hipStream_t) { return 0; }
 int launch_run_tables(const FusedWs&, const int64_t*, int, int, int, int, hipStream_t) { return 0; }  // tables are built on the host below
-int pick_rs(int64_t, int64_t, int64_t, bool) { return 10; }
-int device_cu_count() { return 256; }
-bool env_flag(const char*) { return false; }
-int persistent_variant() { const char* e = getenv("NW_PVAR"); return e ? atoi(e) : 2; }
-int persistent_qgroup() { const char* e = getenv("NW_QG"); return e ? atoi(e) : 8; }
-const FwdOpts& fwd_opts() { static FwdOpts o{}; return o; }
-int knob(int) { return KNOB_UNSET; }
+int knob(int) { return KNOB_UNSET; }   // split.hip, linked in for launch_split_rows, reads its knobs
 int launch_split_rows(const float* x, float* out, float* scale, float* norm2, int64_t rows, int64_t d, hipStream_t st);
 }
 int main(int argc, char** argv) {
@@ -63,13 +59,29 @@ int main(int argc, char** argv) {
     hipMemcpy(runid, h_runid.data(), h_runid.size() * 4, hipMemcpyHostToDevice);
     hipMemcpy(nrun, h_nrun.data(), h_nrun.size() * 4, hipMemcpyHostToDevice);
     hipMemcpy(lab, h_lab.data(), h_lab.size() * 4, hipMemcpyHostToDevice);
+    // the persistent launch: one fixed plan (256 CUs, NW_PVAR / NW_QG as the library's knobs of those names)
+    FusedPlan plan = {};
+    plan.form = FORM_SPLIT, plan.rs = RS, plan.BS = BS, plan.n_stiles = n_stiles, plan.n_qtiles = n_qtiles, plan.mode = MODE_F16;
+    plan.persistent = plan.run_tables = plan.split_queries = true;
+    plan.variant = getenv("NW_PVAR") ? atoi(getenv("NW_PVAR")) : 2;
+    if (plan.variant == 3 && RS != 8) plan.variant = 2;
+    if (plan.variant == 2 && PCfg<RS, 2, false>::LDS_BYTES > 160 * 1024) plan.variant = 0;   // plan_fused's LDS-size fallbacks
+    if (plan.variant == 1 && PCfg<RS, 1, true>::LDS_BYTES > 80 * 1024) plan.variant = 0;
+    plan.workgroups = plan.variant == 1 ? 512 : 256;
+    plan.qgroup = getenv("NW_QG") ? atoi(getenv("NW_QG")) : 8;
+    if (plan.variant == 3) plan.qgroup = std::max(1, plan.qgroup / 2);
+    plan.lds_bytes = plan.variant == 3 ? (size_t)P12::LDS_BYTES : plan.variant == 2 ? (size_t)PCfg<RS, 2, false>::LDS_BYTES
+                     : plan.variant == 1 ? (size_t)PCfg<RS, 1, true>::LDS_BYTES : (size_t)PCfg<RS, 1, false>::LDS_BYTES;
+    FusedArgs args = {};
+    args.s = ssp, args.sy = sy, args.s_norm2 = sn, args.s_scale = ssc, args.B = B, args.N = N, args.d = d, args.C = C;
+    const QueryRows qrows = {qsp, qn, qsc};
     FusedWs wsp; wsp.m = m; wsp.den = den; wsp.nrun = nrun; wsp.lab = lab; wsp.num = num; wsp.runid = runid; wsp.bnd = bndp;
     const int grid = padded_grid(n_stiles, n_qtiles);
     const size_t lds = FUSED_HDR + DmaCfg<RS>::STAGE_BYTES;
     hipEvent_t e0, e1; hipEventCreate(&e0); hipEventCreate(&e1);
     auto launch = [&] {
         if (persistent)
-            launch_f16p<RS, 0>(qsp, ssp, sy, sn, ssc, qn, qsc, nullptr, wsp, B, N, d, C, n_stiles, n_qtiles, 0);
+            launch_f16p<RS, 0>(args, plan, qrows, wsp);
         else if (qraw)
             hipLaunchKernelGGL((nw_fused_kernel<RS, 0, false, MODE_F16Q>), dim3(grid), dim3(TILE_THREADS), lds, 0, q, ssp, sy, sn, ssc,
                                (const float*)nullptr, (const float*)nullptr,
@@ -90,7 +102,7 @@ int main(int argc, char** argv) {
         std::vector<unsigned long long> hp(8 * 1024);
         hipMemcpyFromSymbol(hp.data(), HIP_SYMBOL(nw_diag_p), hp.size() * 8);
         double ph[8] = {0}; int n = 0;
-        const int nwg = persistent_variant() == 1 ? 512 : 256;
+        const int nwg = plan.workgroups;
         for (int b = 0; b < nwg; ++b) { ++n; for (int k = 0; k < 8; ++k) ph[k] += (double)hp[8 * b + k]; }
         {   // the clock the kernel itself saw: shader ticks per 100 MHz real-time tick, per workgroup (LAST launch)
             std::vector<unsigned long long> rt(2 * 1024);
