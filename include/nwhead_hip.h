@@ -306,6 +306,33 @@ int nw_knn_f32(const float *q, const float *s_split, const float *s_scale, const
 int nw_scores_use_split(int64_t B, int64_t N, int64_t d);
 
 /* ---------------------------------------------------------------------------------------------
+ * The k best supports per query over a bank SHARDED into G parts, each of which has been searched on
+ * its own (nw_knn_f32 / nw_topk_f32), and the per-query k-nearest NW head over them: the cross-shard
+ * step of the neighbour modes ('knn' / 'hnsw' with every query's own neighbours; NWNet.get_neighbors).
+ * vals / rows / labels: (G, B, kc) each; shard g starts at base + g*stride_g (in 4-byte words).
+ * Every (g, b) list is sorted best first. Equal scores are in ascending row order.
+ * A slot with row < 0 is "no element" (a shard with fewer than kc rows, or an empty shard); it ends its list.
+ * rows are GLOBAL bank rows (int32; rows are 31-bit), unique over the shards; labels are GLOBAL
+ * class ids (int32).
+ * Writes the k best per query: score descending (nw_topk_f32's order), equal scores by ascending global row.
+ *   idx_out (B,k) int64, val_out (B,k) fp32 optional, label_out (B,k) int64 optional,
+ *   out (B,C) fp32 optional:
+ *     log( sum_{j<k, label_j == c} softmax_j(val[b, 0..k)) + 1e-12 )
+ *     i.e. nw_aggregate_f32 of the merged (B,k) values with labels_batched = 1.
+ *     A label outside [0,C) is treated exactly as that call treats it (its weight counts in the softmax's
+ *     denominator and in no class).  Every element of out is written; a class without a neighbour gets log(1e-12).
+ * 1 <= k <= 32, k <= kc <= 32, 1 <= G <= 64; anything else returns NW_ERR_UNSUPPORTED.
+ * Null vals / rows / labels / idx_out, a negative size, or stride_g < B*kc with G > 1: NW_ERR_INVALID_ARG.
+ * Fewer than k valid candidates for a query: the remaining slots get row -1, value -inf, label -1.
+ * They take no part in the head.
+ * One launch, one wave per query; no atomics: the result is bit-reproducible.  Like every entry: no
+ * workspace, no allocation, no synchronisation, no environment.
+ * ------------------------------------------------------------------------------------------- */
+int nw_knn_merge_f32(const float *vals, const int32_t *rows, const int32_t *labels,
+                     int64_t G, int64_t B, int64_t kc, int64_t stride_g, int64_t k, int64_t C,
+                     int64_t *idx_out, float *val_out, int64_t *label_out, float *out, void *stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Eval-mode BatchNorm (+ ReLU) of the pre-activation backbones as one pass: out = max(x * scale[c] +
  * shift[c], 0).  Replaces the BatchNorm2d -> ReLU pairs in front of the convolutions of
  * model/densenet.py:33-60 (_DenseLayer norm1/relu1), :82-91 (_Transition) and :139 + :160 (norm5 + relu)

@@ -306,6 +306,16 @@ extern "C" int nw_knn_f32(const float* q, const float* s_split, const float* s_s
                           logit_scale_dev, static_cast<hipStream_t>(stream));
 }
 
+extern "C" int nw_knn_merge_f32(const float* vals, const int32_t* rows, const int32_t* labels, int64_t G, int64_t B, int64_t kc,
+                                int64_t stride_g, int64_t k, int64_t C, int64_t* idx_out, float* val_out, int64_t* label_out,
+                                float* out, void* stream) {
+    if (G < 0 || B < 0 || kc < 0 || stride_g < 0 || k < 0 || C < 0) return NW_ERR_INVALID_ARG;
+    if (!vals || !rows || !labels || !idx_out) return NW_ERR_INVALID_ARG;
+    if (G > 1 && stride_g < B * kc) return NW_ERR_INVALID_ARG;   // shards that overlap
+    return nw::launch_knn_merge(vals, rows, labels, G, B, kc, stride_g, k, C, idx_out, val_out, label_out, out,
+                                static_cast<hipStream_t>(stream));
+}
+
 extern "C" int nw_debug_tile_timing(int enable) { return nw::tile_timer_enable(enable != 0); }
 
 extern "C" int nw_debug_tile_timing_read(double* total_us, int64_t* launches) {

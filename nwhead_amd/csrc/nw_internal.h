@@ -96,6 +96,10 @@ size_t knn_workspace_bytes(int64_t B, int64_t N, int64_t d, int64_t k);
 int launch_knn(const float* q, const float* s_split, const float* s_scale, const float* s_norm2, int64_t* idx, float* vals,
                void* workspace, size_t workspace_bytes, int64_t B, int64_t N, int64_t d, int64_t k, int kind,
                const float* logit_scale_dev, hipStream_t st);
+// knn_merge.hip: the k best of G sorted per-shard candidate lists per query, and the per-query k-NN head over them
+// (nw_knn_merge_f32)
+int launch_knn_merge(const float* vals, const int* rows, const int* labels, int64_t G, int64_t B, int64_t kc, int64_t stride_g,
+                     int64_t k, int64_t C, int64_t* idx, float* val_out, int64_t* label_out, float* out, hipStream_t st);
 int tile_timer_enable(bool on);
 int tile_timer_read(double* total_us, int64_t* launches);
 int pick_rs(int64_t B, int64_t N, int64_t d, bool f16 = false);

@@ -170,13 +170,19 @@ class NWNet(nn.Module):
         self.support_eval.knn.bank = self.support_eval.hnsw.bank = self.full_cache   # neighbour search over the same bank
 
     @torch.no_grad()
-    def precompute_sharded(self, group=None, partial_fn=None, merge_fn=None):
+    def precompute_sharded(self, group=None, partial_fn=None, merge_fn=None, search_fn=None, knn_merge_fn=None):
         """'full' inference over a bank sharded across the ranks of `group`: this
         rank featurises ONLY rows [lo, hi) of the balanced, class-sorted bank -- the row order of
         precompute() (environments in order, support.py loader order inside) -- and keeps them resident
         as a ShardedBank; the bank is never gathered.  predict(x, 'full') then exchanges one packed
-        partial per query batch.  The other inference modes still need precompute().
-        partial_fn / merge_fn: compute hooks for the CPU tests (see sharded.ShardedBank)."""
+        partial per query batch.
+        The neighbour search works over the shards as well: get_neighbors(x, k) returns global rows in precompute()'s row
+        order, and predict(x, 'knn' | 'hnsw') with knn_per_query=True evaluates every query over its own n_neighbors
+        nearest supports of the whole bank (ShardedBank.neighbors / predict_knn, k <= 32).  The reference's form of
+        those two modes pools the neighbours of ALL queries of a batch into one shared support; over a sharded bank that
+        would need the neighbours' feature rows gathered across the ranks, which is not done: with knn_per_query=False they
+        raise.  The remaining inference modes still need precompute().
+        partial_fn / merge_fn / search_fn / knn_merge_fn: compute hooks for the CPU tests (see sharded.ShardedBank)."""
         import torch.distributed as dist
         from torch.utils.data import DataLoader, Subset
         from ..sharded import ShardedBank, shard_bounds
@@ -201,13 +207,23 @@ class NWNet(nn.Module):
         y = torch.cat(labels) if labels else torch.empty(0, dtype=torch.int64, device=self.device)
         self.sharded_bank = ShardedBank(feat, y, self.n_classes, self.kernel.kind, self.kernel._logit_scale(),
                                         group=group, partial_fn=partial_fn, merge_fn=merge_fn,
-                                        precision=self.full_precision)
+                                        precision=self.full_precision, row_lo=lo, search_fn=search_fn,
+                                        knn_merge_fn=knn_merge_fn)
         return self.sharded_bank
 
     def predict(self, x, mode='random'):
         qfeat = self._eval_featurizer()(x)
         if mode == 'full' and getattr(self, 'sharded_bank', None) is not None:
             out = self.sharded_bank.predict(qfeat.detach())
+            return (out, torch.full((len(x),), True)) if self.return_mask else out
+        if mode in ('knn', 'hnsw') and getattr(self, 'sharded_bank', None) is not None \
+                and not hasattr(self.support_eval, 'knn'):
+            # a sharded bank and no precompute(): every query over its own neighbours of the whole bank
+            if not self.knn_per_query:
+                raise ops.NWHipError(
+                    f"predict(x, '{mode}') over a sharded bank needs NWNet(knn_per_query=True): the shared-support form, which "
+                    "pools every query's neighbours, would have to gather their feature rows across the ranks")
+            out = self.sharded_bank.predict_knn(qfeat.detach(), self.n_neighbors)
             return (out, torch.full((len(x),), True)) if self.return_mask else out
         sfeat, sy = self.support_eval.get_support(mode, x=qfeat)
         if self.debug_mode:
@@ -232,8 +248,15 @@ class NWNet(nn.Module):
     def get_neighbors(self, x, k=None):
         """Support indices ordered from nearest to farthest under the configured kernel.  k (not in the reference): only the
         k nearest, (B, k), 1 <= k <= N -- for k <= 32 over precompute()'s bank (N % 4 == 0) without the (B, N) score matrix
-        where that pays (ops.nw_knn, ops.knn_fused_pays)."""
+        where that pays (ops.nw_knn, ops.knn_fused_pays).  After precompute_sharded() (and no precompute()): the k <= 32
+        nearest rows of the whole sharded bank, global rows in precompute()'s row order, the same on every rank; k is
+        required there."""
         qfeat = self._eval_featurizer()(x).detach()
+        if getattr(self, 'sharded_bank', None) is not None and not hasattr(self, 'full_feat'):
+            if k is None:
+                raise ops.NWHipError("get_neighbors over a sharded bank needs k (1 <= k <= 32): the full ordering of a "
+                                     "sharded bank is not available")
+            return self.sharded_bank.neighbors(qfeat, k)
         N = self.full_feat.shape[0]
         if k is not None:
             k = int(k)

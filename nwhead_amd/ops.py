@@ -233,6 +233,46 @@ def nw_knn(q, bank, k, kind="euclidean", logit_scale=None, return_values=False, 
     return (idx, vals) if return_values else idx
 
 
+KNN_MERGE_MAX_K, KNN_MERGE_MAX_SHARDS = 32, 64
+
+
+def nw_knn_merge(vals, rows, labels, k, n_classes=None):
+    """The cross-shard step of a neighbour search over a sharded bank (nw_knn_merge_f32): vals fp32 / rows int32 / labels
+    int32, each (G, B, kc) -- per shard and query a list of kc candidates sorted best first, equal scores in ascending row
+    order, rows < 0 marking "no element" -> ``(idx, vals, labels)``, each (B, k): the k best per query over all shards,
+    score descending, equal scores by ascending (global) row; missing ones are (-1, -inf, -1).  With ``n_classes`` also the
+    (B, C) log-probabilities of every query's own k neighbours (``nw_aggregate`` of the merged values and labels).
+
+    The three inputs may be views into one gathered buffer: they need a unit stride inside a list, lists of a shard back to
+    back, and one common stride between shards.  k <= kc <= 32, G <= 64."""
+    _need_hip(vals, rows, labels)
+    lib = _lib.load()
+    if vals.dim() != 3 or rows.shape != vals.shape or labels.shape != vals.shape:
+        raise ValueError("vals, rows and labels must be (G, B, kc) each")
+    if vals.dtype != torch.float32 or rows.dtype != torch.int32 or labels.dtype != torch.int32:
+        raise ValueError("vals must be float32, rows and labels int32")
+    G, B, kc = vals.shape
+    k = int(k)
+    stride_g = vals.stride(0) if G > 1 else B * kc
+    for t in (vals, rows, labels):
+        if B * kc and (t.stride(2) != 1 or (B > 1 and t.stride(1) != kc) or (G > 1 and t.stride(0) != stride_g)):
+            raise ValueError("nw_knn_merge: lists must be dense (B, kc) blocks with one common stride between shards")
+    if k < 1 or k > KNN_MERGE_MAX_K or kc < k or kc > KNN_MERGE_MAX_K or G < 1 or G > KNN_MERGE_MAX_SHARDS:
+        raise NWHipError(f"nw_knn_merge: needs 1 <= k <= kc <= {KNN_MERGE_MAX_K} and 1 <= G <= {KNN_MERGE_MAX_SHARDS} shards, "
+                         f"got k = {k}, kc = {kc}, G = {G}")
+    dev = vals.device
+    C = 0 if n_classes is None else int(n_classes)
+    idx = torch.empty(B, k, dtype=torch.int64, device=dev)
+    val = torch.empty(B, k, dtype=torch.float32, device=dev)
+    lab = torch.empty(B, k, dtype=torch.int64, device=dev)
+    out = None if n_classes is None else torch.empty(B, C, dtype=torch.float32, device=dev)
+    if B:
+        with _OnDevice(dev):
+            _lib.check(lib.nw_knn_merge_f32(_ptr(vals), _ptr(rows), _ptr(labels), G, B, kc, stride_g, k, C, _ptr(idx), _ptr(val),
+                                            _ptr(lab), _ptr(out), _stream(vals)), "nw_knn_merge_f32")
+    return (idx, val, lab) if n_classes is None else (idx, val, lab, out)
+
+
 def row_norm2(x):
     """Squared L2 norm of every row of a (rows,d) fp32 HIP tensor -> (rows,).  Cache this for a support
     bank that does not change between calls and pass it as ``support_norm2``."""

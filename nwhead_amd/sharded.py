@@ -6,6 +6,10 @@ batches -- [m | den | num] per batch -- with a single RCCL all-gather over xGMI 
 hundred KB: latency-bound, so batches are bucketed and the collective of bucket i overlaps the
 kernels of bucket i+1), and every rank merges to the same (B,C) log-probabilities.
 
+The neighbour modes go the same way: every rank searches its slice for each query's k best rows (ops.nw_knn), the ranks
+exchange one packed buffer [vals | rows | labels] of 3 B k words, and every rank merges the G sorted lists to the k best
+overall and, for 'knn' / 'hnsw' prediction, evaluates the head of each query's own k neighbours (ops.nw_knn_merge).
+
     one process per GPU, torch.distributed backend "nccl" (= RCCL on ROCm); "gloo" in CPU tests,
     where the compute hooks are replaced by the oracle (tests/test_sharded_gloo.py).
 """
@@ -15,6 +19,7 @@ import torch
 import torch.distributed as dist
 
 from . import ops
+from ._lib import NWHipError
 
 
 def shard_bounds(n_rows: int, world: int, rank: int):
@@ -40,8 +45,17 @@ def _coalesce(chunk):
 
 class ShardedBank:
     def __init__(self, feat_shard, y_shard, n_classes, kind="euclidean", logit_scale=None, group=None,
-                 partial_fn=None, merge_fn=None, persistent_wgs=None, precision="fp32"):
-        """precision: "fp32" (split-fp16 rows, fp32-grade) or "fp16" (the reduced-precision bank of ops.SplitBank).
+                 partial_fn=None, merge_fn=None, persistent_wgs=None, precision="fp32", row_lo=None, search_fn=None,
+                 knn_merge_fn=None):
+        """row_lo: the global bank row of this shard's first row (what neighbors() adds to the shard's own row numbers).
+        Default: the exclusive prefix sum of the shard sizes over the ranks, from the all-gather below.
+        search_fn / knn_merge_fn: CPU compute hooks of the neighbour search, like partial_fn / merge_fn:
+        search_fn(q, k) -> (rows (B,k) int64 of THIS shard, scores (B,k) fp32), best first, equal scores by ascending row;
+        knn_merge_fn(vals, rows, labels, k, n_classes) -> what ops.nw_knn_merge returns.
+        The neighbour search runs on the fp32 shard through a SplitBank of split-fp16 rows (fp32-grade scores): with
+        precision="fp32" that is the bank 'full' inference uses; with precision="fp16" a second bank is prepared from the
+        fp32 shard on the first search (the fp16-packed rows are not searched), so 'full'-only users pay nothing.
+        precision: "fp32" (split-fp16 rows, fp32-grade) or "fp16" (the reduced-precision bank of ops.SplitBank).
         persistent_wgs: workgroups of the persistent tile kernel (nw_fwd_opts.persistent_wgs, a multiple of 8; 0 = one per
         CU).  Default: with more than one rank, all CUs but one per XCD (count - 8) -- the all-gather of bucket i runs
         under the kernels of bucket i + 1, and a kernel that holds one 160 KB-LDS workgroup on EVERY CU would leave RCCL's
@@ -64,12 +78,20 @@ class ShardedBank:
         # partial forward runs on labels shifted by the slice's lowest class with CL = widest window
         # over the ranks; the exchanged rows are (2 + CL) instead of (2 + C) floats per query.
         self.class_lo, self.CL, self.y_local = None, self.C, self.y
+        self._search = search_fn or self._hip_search
+        self._knn_merge = knn_merge_fn or ops.nw_knn_merge
+        self._search_bank = None
+        self.n_total = int(self.feat.shape[0])       # rows of the whole bank
         if self.world > 1:
             lo = int(self.y.min()) if self.y.numel() else 0
             hi = int(self.y.max()) if self.y.numel() else -1
-            box = torch.tensor([lo, hi], dtype=torch.int64, device=self.feat.device)
-            allb = torch.empty(self.world, 2, dtype=torch.int64, device=self.feat.device)
+            box = torch.tensor([lo, hi, self.feat.shape[0]], dtype=torch.int64, device=self.feat.device)
+            allb = torch.empty(self.world, 3, dtype=torch.int64, device=self.feat.device)
             dist.all_gather_into_tensor(allb.view(-1), box, group=group)
+            sizes = allb[:, 2].tolist()
+            self.n_total = int(sum(sizes))
+            if row_lo is None:
+                row_lo = sum(sizes[:dist.get_rank(group)])
             width = int((allb[:, 1] - allb[:, 0] + 1).clamp_min(1).max())
             if width < self.C:
                 self.CL = width
@@ -80,6 +102,7 @@ class ShardedBank:
         self.norm2 = self.cache.norm2 if self.cache is not None else None
         if self.cache is not None and (self.cache.split is not None or self.cache.packed is not None):
             self.cache.build_tables(self.y_local)   # the labels every call of this shard passes (self.y when there is one rank)
+        self.row_lo = int(row_lo or 0)
 
     # ---- HIP compute hooks (the product path)
     def _hip_partial(self, packed_row, q):
@@ -95,6 +118,68 @@ class ShardedBank:
 
     def _hip_merge(self, gathered_rows, B):
         return ops.nw_merge(gathered_rows, B, self.C, class_lo=self.class_lo, c_local=self.CL)
+
+    def _hip_search(self, q, k):
+        bank = self._search_bank
+        if bank is None:
+            # (the 'full' bank has split rows and no class-sorted copy -- it was prepared without labels -- unless it is fp16)
+            bank = self.cache if (self.cache is not None and self.cache.precision == "fp32") else ops.SplitBank(self.feat)
+            self._search_bank = bank
+        return ops.nw_knn(q, bank, k, self.kind, self.logit_scale, return_values=True, support=self.feat)
+
+    # ---- neighbour search
+    def knn_partial(self, q, k):
+        """This rank's packed candidates for one (B,d) query batch: a flat int32 buffer [vals | rows | labels] of 3 B k
+        words -- per query the min(k, shard rows) best rows of the shard, best first, as (score bits, GLOBAL bank row,
+        GLOBAL class id), padded to k with no-element slots (-inf, -1, -1).  An empty shard emits only those."""
+        k = int(k)
+        q = q.detach().to(torch.float32).contiguous()
+        B, n = q.shape[0], self.feat.shape[0]
+        kk = min(k, n)
+        buf = torch.empty(3, B, k, dtype=torch.int32, device=self.feat.device)
+        vals = buf[0].view(torch.float32)
+        if kk < k:
+            vals.fill_(float("-inf"))
+            buf[1:].fill_(-1)
+        if kk > 0 and B > 0:
+            idx, val = self._search(q, kk)
+            vals[:, :kk] = val
+            buf[1, :, :kk] = idx + self.row_lo
+            buf[2, :, :kk] = self.y[idx]
+        return buf.view(-1)
+
+    def _knn(self, q, k, n_classes):
+        k = int(k)
+        if k > ops.KNN_MERGE_MAX_K:
+            raise NWHipError(f"ShardedBank: k = {k} neighbours; the cross-shard merge takes at most {ops.KNN_MERGE_MAX_K}")
+        if k < 1 or k > self.n_total:
+            raise NWHipError(f"ShardedBank: k = {k} outside [1, N = {self.n_total}] (the rows of the whole bank)")
+        if self.world > ops.KNN_MERGE_MAX_SHARDS or self.n_total >= 2 ** 31:
+            raise NWHipError(f"ShardedBank: the cross-shard merge takes at most {ops.KNN_MERGE_MAX_SHARDS} shards and "
+                             f"2^31 - 1 bank rows, got {self.world} and {self.n_total}")
+        B, G = q.shape[0], self.world
+        packed = self.knn_partial(q, k)
+        if G > 1:
+            gathered = torch.empty(G, packed.numel(), dtype=torch.int32, device=packed.device)
+            dist.all_gather_into_tensor(gathered.view(-1), packed, group=self.group)
+        else:
+            gathered = packed.view(1, -1)
+        n = B * k
+        vals, rows, labels = (gathered[:, i * n:(i + 1) * n].view(G, B, k) for i in range(3))   # views: the kernel strides
+        return self._knn_merge(vals.view(torch.float32), rows, labels, k, n_classes)
+
+    def neighbors(self, q, k, return_values=False, return_labels=False):
+        """The k nearest rows of the WHOLE bank for every query: (B,k) int64 global rows, best score first, equal scores by
+        ascending row; optionally their (B,k) scores and (B,k) int64 class ids.  One all-gather of 3 B k words (none with
+        one rank); identical on every rank.  1 <= k <= min(32, bank rows)."""
+        idx, vals, labels = self._knn(q, k, None)
+        res = (idx,) + ((vals,) if return_values else ()) + ((labels,) if return_labels else ())
+        return res if len(res) > 1 else idx
+
+    def predict_knn(self, q, k):
+        """(B,d) -> (B,C) log-probabilities of every query over its OWN k nearest supports of the whole bank -- the
+        semantics of NWNet(knn_per_query=True) -- identical on every rank."""
+        return self._knn(q, k, self.C)[3]
 
     def row_len(self, B):
         return 2 * B + B * self.CL
