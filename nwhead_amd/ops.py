@@ -4,6 +4,7 @@ autograd bookkeeping); every arithmetic step runs in libnwhead_hip.so.
 """
 from __future__ import annotations
 
+import collections
 import ctypes
 import os
 
@@ -110,7 +111,6 @@ def _default_opts(persistent_wgs=0, operand_form=0):
 
 
 def C_addr(op):
-    import ctypes
     return ctypes.addressof(op)
 
 
@@ -127,10 +127,22 @@ def _workspace(nbytes, device, stream=None):
     return ws
 
 
+def _fwd_workspace(lib, B, N, d, C, device, stream, ws=None, own=False):
+    """(buffer, bytes to name in the call) of a forward call of this shape (d: of the padded queries): the cached buffer of
+    the device and stream, or the caller's ``ws`` (``own``: always theirs, None at first), replaced when too small."""
+    need = _fwd_ws_bytes(lib, B, N, d, C)
+    if ws is None and not own:
+        return _workspace(need, device, stream), need
+    if ws is None or ws.numel() < max(need, 1):
+        ws = torch.empty(max(need, 1), dtype=torch.uint8, device=device)
+    return ws, ws.numel()
+
+
 def nw_scores(q, s, kind="euclidean", logit_scale=None, support_cache=None):
     """q:(B,d), s:(N,d)|(B,N,d) -> (B,N) fp32 scores.  Replaces nwhead/kernel.py:13-44.
-    support_cache: the SplitBank of `s` (a resident bank, e.g. the neighbour search over precompute()'s features): the
-    scores then come from the split-fp16 tile kernel (the forward with its score output; 2-3x the fp32 scores kernel)."""
+    support_cache: the SplitBank of `s` (a resident bank, e.g. the neighbour search over precompute()'s features): a bank
+    that serves `s` with split rows as they stand (SplitBank, "scores") gives the scores from the split-fp16 tile kernel
+    (the forward with its score output; 2-3x the fp32 scores kernel) when N is a multiple of 4."""
     _need_hip(q, s, logit_scale)
     lib = _lib.load()
     q, s = _f32c(q), _f32c(s)
@@ -139,23 +151,19 @@ def nw_scores(q, s, kind="euclidean", logit_scale=None, support_cache=None):
     N = s.shape[-2]
     out = torch.empty(B, N, dtype=torch.float32, device=q.device)
     ls = None if logit_scale is None else _f32c(logit_scale)
-    if (support_cache is not None and not batched and support_cache.split is not None and support_cache.sorted_rows is None
-            and support_cache.matches(s) and B > 0 and N > 0 and N % 4 == 0):
-        q, s = _apply_bank_padding(q, s, support_cache)
-        d = q.shape[1]
+    bank_route = support_cache is not None and not batched and B > 0 and N > 0 and N % 4 == 0 and support_cache.matches(s)
+    call = _resolve_scores(support_cache, q, s) if bank_route else None
+    if call is not None:
         # one class, all labels 0: the aggregation is a formality, the (B, N) score matrix is what is wanted
-        zeros = getattr(support_cache, "_zero_labels", None)
-        if zeros is None or zeros.numel() != N:
-            zeros = support_cache._zero_labels = torch.zeros(N, dtype=torch.int64, device=q.device)
         out1 = torch.empty(B, 1, dtype=torch.float32, device=q.device)
-        ws_bytes = _fwd_ws_bytes(lib, B, N, d, 1)
-        ws = _workspace(ws_bytes, q.device) if ws_bytes else None
+        st, d = _stream(q), call.q.shape[1]
+        ws, ws_bytes = _fwd_workspace(lib, B, N, d, 1, q.device, st)
         with _OnDevice(q.device):
-            _lib.check(lib.nw_fwd_f32(_ptr(q), _ptr(s), _ptr(zeros), _ptr(support_cache.norm2), _ptr(support_cache.split),
-                                      _ptr(support_cache.scale), _ptr(out1), _ptr(out), None, None, _ptr(ws), ws_bytes,
-                                      B, N, d, 1, _kind_id(kind), _ptr(ls), 0, 0, _default_opts(), _stream(q)), "nw_fwd_f32")
+            _lib.check(lib.nw_fwd_f32(_ptr(call.q), _ptr(call.s), _ptr(call.sy), _ptr(call.norm2), _ptr(call.operand),
+                                      _ptr(call.scale), _ptr(out1), _ptr(out), None, None, _ptr(ws), ws_bytes,
+                                      B, N, d, 1, _kind_id(kind), _ptr(ls), 0, 0, call.opts, st), "nw_fwd_f32")
         return out
-    with torch.cuda.device(q.device):
+    with _OnDevice(q.device):
         _lib.check(lib.nw_scores_f32(_ptr(q), _ptr(s), _ptr(out), B, N, d, _kind_id(kind), _ptr(ls),
                                      int(batched), _stream(q)), "nw_scores_f32")
     return out
@@ -172,7 +180,7 @@ def nw_topk(scores, k, return_values=False):
     k = int(k)
     idx = torch.empty(B, k, dtype=torch.int64, device=sc.device)
     vals = torch.empty(B, k, dtype=torch.float32, device=sc.device) if return_values else None
-    with torch.cuda.device(sc.device):
+    with _OnDevice(sc.device):
         _lib.check(lib.nw_topk_f32(_ptr(sc), _ptr(idx), _ptr(vals), B, N, k, _stream(sc)), "nw_topk_f32")
     return (idx, vals) if return_values else idx
 
@@ -203,22 +211,22 @@ def nw_knn(q, bank, k, kind="euclidean", logit_scale=None, return_values=False, 
         raise TypeError("nw_knn searches a prepared bank: pass ops.SplitBank(support)")
     lib = _lib.load()
     q = _f32c(q)
-    B, d0 = q.shape
+    B = q.shape[0]
     k = int(k)
     N = bank.shape[0] if support is None else support.shape[-2]
     if k < 1 or k > N:
         raise NWHipError(f"nw_knn: k = {k} outside [1, N = {N}] (nw_topk refuses it too)")
-    dp = d0 + bank.pad
-    # (nw_scores_use_split: the library's own rule for which tile kernel the bank-route score call of this shape runs)
-    fused = (bank.split is not None and bank.sorted_rows is None and k <= 32 and N > 25 and B > 0 and dp == bank.shape[1]
-             and N == bank.shape[0] and (support is None or (support.dim() == 2 and bank.matches(support)))
-             and (_lib.force_split() or bool(lib.nw_scores_use_split(B, N, dp))))
-    if not fused:
+    # (nw_scores_use_split: the library's own rule for which tile kernel the bank-route score call runs, at the bank's width)
+    fused = (k <= 32 and N > 25 and B > 0 and N == bank.shape[0]
+             and (support is None or (support.dim() == 2 and bank.matches(support)))
+             and (_lib.force_split() or bool(lib.nw_scores_use_split(B, N, bank.shape[1]))))
+    call = _resolve_scores(bank, q) if fused else None
+    if call is None:
         if support is None:
             raise ValueError("nw_knn: this search goes through the score matrix and needs `support`, the tensor the bank was "
                              "prepared from")
         return nw_topk(nw_scores(q, support, kind, logit_scale, support_cache=bank), k, return_values=return_values)
-    q, _ = _apply_bank_padding(q, bank.split, bank)
+    q, dp = call.q, call.q.shape[1]
     ls = None if logit_scale is None else _f32c(logit_scale)
     idx = torch.empty(B, k, dtype=torch.int64, device=q.device)
     vals = torch.empty(B, k, dtype=torch.float32, device=q.device) if return_values else None
@@ -226,10 +234,11 @@ def nw_knn(q, bank, k, kind="euclidean", logit_scale=None, return_values=False, 
     ws_bytes = _WS_BYTES.get(key)
     if ws_bytes is None:
         ws_bytes = _WS_BYTES[key] = lib.nw_knn_workspace_bytes(B, N, dp, k)
-    ws = _workspace(ws_bytes, q.device)
+    st = _stream(q)
+    ws = _workspace(ws_bytes, q.device, st)
     with _OnDevice(q.device):
-        _lib.check(lib.nw_knn_f32(_ptr(q), _ptr(bank.split), _ptr(bank.scale), _ptr(bank.norm2), _ptr(idx), _ptr(vals),
-                                  _ptr(ws), ws_bytes, B, N, dp, k, _kind_id(kind), _ptr(ls), _stream(q)), "nw_knn_f32")
+        _lib.check(lib.nw_knn_f32(_ptr(q), _ptr(call.operand), _ptr(call.scale), _ptr(call.norm2), _ptr(idx), _ptr(vals),
+                                  _ptr(ws), ws_bytes, B, N, dp, k, _kind_id(kind), _ptr(ls), st), "nw_knn_f32")
     return (idx, vals) if return_values else idx
 
 
@@ -280,32 +289,56 @@ def row_norm2(x):
     lib = _lib.load()
     xc = _f32c(x)
     out = torch.empty(xc.shape[0], dtype=torch.float32, device=xc.device)
-    with torch.cuda.device(xc.device):
+    with _OnDevice(xc.device):
         _lib.check(lib.nw_row_norm2_f32(_ptr(xc), _ptr(out), xc.shape[0], xc.shape[1], _stream(xc)), "nw_row_norm2_f32")
     return out
 
 
-class SplitBank:
-    """A support matrix prepared once for repeated 'full' inference: split-fp16 rows, row scales and
-    squared norms (nw_split_rows_f16x2).  Pass it as ``support_cache`` to nw_head / nw_partials.
-    The split format needs d % 32 == 0: a bank of another width (d >= 64) keeps a copy padded with zero columns
-    (``rows``, ``pad``; no dot product or norm changes) and the callers pad the queries to match; narrower ones fall back
-    to norms only (fp32 matrix cores).
+def _check_label_range(lo, hi, n_classes=None, one_hot=False):
+    """The range check of support labels, whose smallest / largest are ``lo`` / ``hi`` (None: not checked); the kernels
+    would skip the others silently.  ``one_hot``: F.one_hot's own RuntimeError and messages (nw_head's validate_labels)."""
+    err = RuntimeError if one_hot else ValueError
+    if lo is not None and lo < 0:
+        raise err("Class values must be non-negative." if one_hot else
+                  "support labels must be non-negative class indices (F.one_hot, nw.py:276, raises too)")
+    if n_classes is not None and hi is not None and hi >= int(n_classes):
+        raise err("Class values must be smaller than num_classes." if one_hot else
+                  f"support label {hi} is outside [0, n_classes={int(n_classes)}) (the reference's F.one_hot, nw.py:276, raises)")
 
-    ``labels``: the (N,) labels that will be used with this bank.  The tile kernels sum softmax weights
-    per RUN of equal consecutive labels, so a class-sorted bank (what precompute() builds) costs 1-2 sums
-    per tile and an unsorted one a sum per row (measured 1862 vs 322 us at B=2048, N=50000).  The output
-    does not depend on the order of the supports, so when unsorted labels are given the bank keeps a
-    class-sorted copy (``sorted_rows`` / ``sorted_labels``, stable order) and nw_head runs on that.
+
+class SplitBank:
+    """A support matrix prepared once for repeated 'full' inference: split-fp16 rows, row scales and squared norms
+    (nw_split_rows_f16x2).  Pass it as ``support_cache`` to the head entry points, or search it with nw_knn.
+    The split format needs d % 32 == 0: a bank of another width (d >= 64) keeps a copy padded with zero columns
+    (``rows``, ``pad``; no dot product or norm changes); narrower ones fall back to norms only (fp32 matrix cores).
+
+    ``labels``: the (N,) labels that will be used with this bank.  The tile kernels sum softmax weights per RUN of equal
+    consecutive labels, so a class-sorted bank (what precompute() builds) costs 1-2 sums per tile and an unsorted one a sum
+    per row (measured 1862 vs 322 us at B=2048, N=50000).  The output does not depend on the order of the supports, so when
+    unsorted labels are given the bank keeps a class-sorted copy (``sorted_rows`` / ``sorted_labels``, stable order).
 
     ``precision="fp16"``: the optional reduced-precision bank.  Instead of split rows it holds the rows ROUNDED to fp16
     with a power-of-two scale per row (nw_pack_rows_f16: ``packed``, ``packed_scale``, ``packed_norm2`` -- the norms of the
-    rounded rows): half the bytes, one fp16 product per term instead of three.  nw_head / nw_partials without gradients
-    and without ``return_weights`` then compute the exact head of the rounded features (queries are rounded the same way
-    inside the call; relative rounding 2^-11 per element).  The width is zero-padded to max(192, next multiple of 64);
-    ``split`` stays None and ``norm2`` holds the norms of the ORIGINAL rows, so every other use of the bank (training
-    steps, weights, scores, influences) runs as with a norms-only bank.  A bank of 25 rows or fewer, which no tile kernel
-    takes, keeps norms only."""
+    rounded rows): half the bytes, one fp16 product per term instead of three; the head computed from them is the exact
+    head of the rounded features (queries are rounded the same way inside the call; relative rounding 2^-11 per element).
+    The width is zero-padded to max(192, next multiple of 64); ``split`` stays None and ``norm2`` holds the norms of the
+    ORIGINAL rows.  A bank of 25 rows or fewer, which no tile kernel takes, keeps norms only.
+
+    What a forward call hands to the library is decided in ONE place, _resolve, which every entry point calls, in this order:
+    * class-sorted copy: it serves the call only when the caller passes the very label tensor the bank was sorted for (the
+      same object, or the same address and shape), no output is indexed by support position (weights, influences, scores)
+      and the support is not part of an autograd graph; otherwise the bank is dropped entirely, norms included (correct,
+      slower).  (A caller that already passes the sorted copy is served as it stands.)
+    * padded bank (``pad`` > 0): the queries are padded alike and the kernels read the bank's padded rows instead of the
+      caller's tensor; of a support in an autograd graph only the norms are kept (the copy is not part of the graph).
+    * nw_head pads queries and supports (torch ops) at d % 4 != 0, and training steps at d % 32 != 0 from d = 256 on (see
+      _resolve), with or without a bank: a bank is then reduced to its norms.
+    * operands: ``norm2`` with ``split`` / ``scale`` (none for a norms-only bank); the fp16 form (``packed*``,
+      nw_fwd_opts.operand_form = 1) only where the call allows it -- no gradients, no weights, a shared support: training
+      steps, weights, scores, influences and searches run on an fp16 bank as on a norms-only one.
+    * scores (nw_scores' bank route, nw_knn's fused search; _resolve_scores): only split rows without a class-sorted copy.
+    * run tables (build_tables): named in the call's options only when its labels are the tensor the tables were built
+      from, unmodified; n_classes must then exceed every label of the tables."""
 
     def __init__(self, s, labels=None, precision="fp32"):
         if precision not in ("fp32", "fp16"):
@@ -319,8 +352,7 @@ class SplitBank:
         self.label_max = None
         if labels is not None and labels.numel():
             lo, hi = (int(v) for v in torch.aminmax(labels.detach()))
-            if lo < 0:
-                raise ValueError("support labels must be non-negative class indices (F.one_hot, nw.py:276, raises too)")
+            _check_label_range(lo, None)
             self.label_max = hi                # nw_head refuses n_classes <= label_max, like F.one_hot
         self.pad, self.rows = 0, None
         half = precision == "fp16" and sc.dim() == 2 and sc.shape[0] > 25
@@ -347,7 +379,7 @@ class SplitBank:
             self.packed = torch.empty(N, d, dtype=torch.float16, device=sc.device)
             self.packed_scale = torch.empty(N, dtype=torch.float32, device=sc.device)
             self.packed_norm2 = torch.empty(N, dtype=torch.float32, device=sc.device)
-            with torch.cuda.device(sc.device):
+            with _OnDevice(sc.device):
                 _lib.check(lib.nw_pack_rows_f16(_ptr(sc), _ptr(self.packed), _ptr(self.packed_scale), _ptr(self.packed_norm2),
                                                 N, d, _stream(sc)), "nw_pack_rows_f16")
             self.norm2 = row_norm2(sc)
@@ -355,16 +387,21 @@ class SplitBank:
             self.split = torch.empty_like(sc)
             self.scale = torch.empty(N, dtype=torch.float32, device=sc.device)
             self.norm2 = torch.empty(N, dtype=torch.float32, device=sc.device)
-            with torch.cuda.device(sc.device):
+            with _OnDevice(sc.device):
                 _lib.check(lib.nw_split_rows_f16x2(_ptr(sc), _ptr(self.split), _ptr(self.scale), _ptr(self.norm2),
                                                    N, d, _stream(sc)), "nw_split_rows_f16x2")
         else:
             self.norm2 = row_norm2(sc)
         self.tables = self._tables_src = None
         self.tables_label_max = -1
-        self._opts = {}
-        if labels is not None and labels.dim() == 1 and (self.split is not None or self.packed is not None):
+        self._opts, self._zero_labels = {}, None
+        if labels is not None and labels.dim() == 1 and self.has_operand_rows:
             self.build_tables(self.sorted_labels if self.sorted_labels is not None else labels)
+
+    @property
+    def has_operand_rows(self):
+        """Whether the bank holds split or fp16-packed rows (the banks that are given run tables when they are built)."""
+        return self.split is not None or self.packed is not None
 
     def build_tables(self, labels):
         """Run tables of this bank under ``labels`` (nw_bank_tables_build): the forward then skips building them on
@@ -376,78 +413,114 @@ class SplitBank:
         if lab64.dim() != 1 or lab64.numel() != N or N == 0 or not lab64.is_cuda:
             return
         lo, hi = (int(v) for v in torch.aminmax(lab64))
-        if lo < 0:
-            raise ValueError("support labels must be non-negative class indices (F.one_hot, nw.py:276, raises too)")
-        self.tables_label_max = hi      # the tables hold every label as a real class: n_classes must exceed it (call_opts)
+        _check_label_range(lo, None)
+        self.tables_label_max = hi      # the tables hold every label as a real class: n_classes must exceed it (_call_opts)
         nbytes = lib.nw_bank_tables_bytes(N)
         tables = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=lab64.device)
-        with torch.cuda.device(lab64.device):
+        with _OnDevice(lab64.device):
             # C: any bound above the labels gives the same tables (nw_head refuses labels >= n_classes)
             _lib.check(lib.nw_bank_tables_build(_ptr(lab64), N, 0x7fffffff, _ptr(tables), nbytes, _stream(lab64)),
                        "nw_bank_tables_build")
         self.tables, self._tables_src, self._opts = tables, _sig(labels), {}
 
-    def call_opts(self, sy, n_classes, persistent_wgs=0, sy_call=None, operand_form=0):
-        """Address of the nw_fwd_opts for a forward call with labels ``sy``: names the cached run tables when ``sy`` is the
-        label tensor they were built from (same storage, unmodified) -- the object stays alive in this bank.  ``sy_call``:
-        the int64 tensor whose address the call passes as its labels (``sy`` itself unless it had to be converted); the
-        library uses the tables only for that address and row count.  ``operand_form``: 1 when the call passes this
-        bank's ``packed`` rows (nw_fwd_opts.operand_form)."""
-        if self.tables is not None and _sig(sy) == self._tables_src:
-            syc = sy if sy_call is None else sy_call
-            if self.tables_label_max >= int(n_classes):
-                raise ValueError(f"support label {self.tables_label_max} is outside [0, n_classes={int(n_classes)}) "
-                                 "(the reference's F.one_hot, nw.py:276, raises)")
-            key = (int(persistent_wgs), _lib.force_split(), syc.data_ptr(), syc.numel(), int(operand_form))
-            op = self._opts.get(key)
-            if op is None:
-                if len(self._opts) > 64:
-                    self._opts.clear()
-                op = self._opts[key] = _lib.fwd_opts(self.tables.data_ptr(), self.tables.numel(), persistent_wgs,
-                                                     syc.data_ptr(), syc.numel(), operand_form)
-            return C_addr(op)
-        return _default_opts(persistent_wgs, operand_form)
-
-    def half_operands(self, d):
-        """(norm2, rows, scale) of the fp16 form for a call whose queries are ``d`` wide, or None when this bank has none."""
-        if self.packed is None:
-            return None
-        if d != self.shape[1]:
-            raise ValueError(f"queries of width {d} against an fp16 bank of (padded) width {self.shape[1]}")
-        return self.packed_norm2, self.packed, self.packed_scale
+    def _call_opts(self, sy, sy_call, n_classes, persistent_wgs, operand_form):
+        """Address of the nw_fwd_opts (kept alive in this bank) for a forward call with labels ``sy``, passed to the library
+        as the int64 tensor ``sy_call``: names the cached run tables when ``sy`` is the label tensor they were built from
+        (same storage, unmodified) -- the library uses them only for the address and row count of ``sy_call``."""
+        if self.tables is None or _sig(sy) != self._tables_src:
+            return _default_opts(persistent_wgs, operand_form)
+        _check_label_range(None, self.tables_label_max, n_classes)
+        key = (int(persistent_wgs), _lib.force_split(), sy_call.data_ptr(), sy_call.numel(), int(operand_form))
+        op = self._opts.get(key)
+        if op is None:
+            if len(self._opts) > 64:
+                self._opts.clear()
+            op = self._opts[key] = _lib.fwd_opts(self.tables.data_ptr(), self.tables.numel(), persistent_wgs,
+                                                 sy_call.data_ptr(), sy_call.numel(), operand_form)
+        return C_addr(op)
 
     def matches(self, s):
         """True when `s` is the very tensor (storage, shape, no in-place update since) this bank was prepared from."""
         return _sig(s) == self._src
 
 
-def _resolve_sorted_bank(s, sy, cache, per_position_outputs=False):
-    """A SplitBank built from UNSORTED labels holds the split form of its class-sorted copy: run on that
-    copy (same output: the order of the supports does not matter) when the caller passes the very label
-    tensor the bank was built with and wants nothing indexed by support position; otherwise drop the cache
-    (correct, slower) rather than pair split rows with labels in another order."""
-    if cache is None or cache.sorted_rows is None:
-        return s, sy, cache
-    same = sy is cache._labels_ref or (sy.data_ptr() == cache._labels_ref.data_ptr() and sy.shape == cache._labels_ref.shape)
-    if per_position_outputs or not same:
-        return s, sy, None
-    return cache.sorted_rows, cache.sorted_labels, cache
+# What one forward call hands to the library (_resolve, _resolve_scores): the queries, padded where the rows are; the rows
+# the kernel reads (None: a search, which reads only the operand); their int64 labels; squared row norms or None; the
+# operand (split-fp16 rows, or fp16-packed rows when the options say operand_form = 1) with its row scales, or None; the
+# address of the call's nw_fwd_opts.
+_Call = collections.namedtuple("_Call", "q s sy norm2 operand scale opts")
+_new_call = tuple.__new__    # (_Call(...) goes through a Python-level __new__: a third of a microsecond per forward)
 
 
-def _apply_bank_padding(q, s, cache):
-    """A bank of a width that is not a multiple of 32 (fp16 banks: of 64, or below 192) holds zero-padded rows
-    (SplitBank.rows / .sorted_rows): pad the queries alike and read the bank's rows instead of the caller's tensor."""
-    if cache is None or not cache.pad:
-        return q, s
-    q = torch.nn.functional.pad(q, (0, cache.pad))
-    if s.shape[-1] != cache.shape[1]:
-        s = cache.rows
-    return q, s
+def _pad_to_bank(bank, q, s):
+    """Queries padded to the width of a padded bank, and the bank's padded rows in place of the caller's tensor."""
+    return torch.nn.functional.pad(q, (0, bank.pad)), (bank.rows if s is not None and s.shape[-1] != bank.shape[1] else s)
+
+
+def _resolve_scores(bank, q, s=None):
+    """The _Call of a score call over the split rows of ``bank`` (rows `s`, one class, all labels zero), or of a search
+    (no `s`, no labels); None when the bank cannot serve it as prepared (SplitBank's docstring, "scores")."""
+    if bank.split is None or bank.sorted_rows is not None or q.shape[1] + bank.pad != bank.shape[1]:
+        return None
+    if bank.pad:
+        q, s = _pad_to_bank(bank, q, s)
+    sy = bank._zero_labels
+    if sy is None and s is not None:
+        sy = bank._zero_labels = torch.zeros(bank.shape[0], dtype=torch.int64, device=q.device)
+    return _new_call(_Call, (q, s, sy, bank.norm2, bank.split, bank.scale, _default_opts()))
+
+
+def _resolve(bank, q, s, sy, n_classes, positional=False, s_in_graph=False, half=False, persistent_wgs=0, norm2=None,
+             torch_pad=None, run_tables=True):
+    """The _Call of one forward (SplitBank's docstring has the rules).  ``bank``: the SplitBank of `s` or None; ``positional``:
+    an output is indexed by support position; ``s_in_graph``: `s` is part of an autograd graph; ``half``: the fp16 operands
+    may be used; ``norm2``: the caller's own norms; ``torch_pad``: nw_head's width rules (False: without, True: with a
+    backward; None: no padding by torch ops); ``run_tables``: False for a call that never names them."""
+    if bank is not None and bank.sorted_rows is not None and s.data_ptr() != bank.sorted_rows.data_ptr():
+        ref = bank._labels_ref
+        if positional or s_in_graph or not (sy is ref or (sy.data_ptr() == ref.data_ptr() and sy.shape == ref.shape)):
+            bank = None
+        else:
+            s, sy = bank.sorted_rows, bank.sorted_labels
+    if bank is not None and bank.pad:
+        if s_in_graph:       # the padded copy is not part of the caller's graph
+            norm2, bank = bank.norm2, None
+        else:
+            q, s = _pad_to_bank(bank, q, s)
+    if torch_pad is not None and q.shape[-1] % 4 and s.dim() == 2 and s.shape[0] > 25:
+        # an embedding size that is not a multiple of 4 would miss every tile kernel (they move 16-byte pieces) and land
+        # on the generic two-kernel path (measured at d = 130: 925 us against 19 at d = 128; 52 ms with 20000 classes):
+        # zero columns change no dot product and no norm, so the operands are padded (torch ops: autograd slices the
+        # gradients back) and the cached norms, the bank's or the caller's, stay valid
+        pad = (-q.shape[-1]) % 4
+        if bank is not None:
+            norm2, bank = bank.norm2, None
+        q, s = torch.nn.functional.pad(q, (0, pad)), torch.nn.functional.pad(s, (0, pad))
+    if torch_pad:
+        _lib.sync_knobs()   # (NW_BWD_SPLIT and the other diagnostic switches may be flipped between steps)
+        d = q.shape[-1]
+        if (bank is None and s.dim() == 2 and d % 32 and d >= 256
+                and _lib.load().nw_bwd_uses_split(q.shape[0], s.shape[0], d + (-d) % 32, int(n_classes), 0)):
+            # a training step at a width that is not a multiple of 32: zero columns take it to the split-row kernels of the
+            # forward and the backward (d = 1000 at T: 326 -> 237 us per eager forward + backward; narrow widths lose more to
+            # the two extra torch ops than the kernels gain: d = 100, 168 -> 232 us); autograd slices the gradients back
+            pad = (-d) % 32
+            q, s = torch.nn.functional.pad(q, (0, pad)), torch.nn.functional.pad(s, (0, pad))
+    syc = sy if (sy.dtype == torch.int64 and sy.is_contiguous()) else sy.detach().to(torch.int64).contiguous()
+    if bank is None:
+        return _new_call(_Call, (q, s, syc, norm2, None, None, _default_opts(persistent_wgs)))
+    norm2, operand, scale, form = bank.norm2, bank.split, bank.scale, 0
+    if half and bank.packed is not None:       # an fp16 bank: the head of the rounded features
+        if q.shape[1] != bank.shape[1]:
+            raise ValueError(f"queries of width {q.shape[1]} against an fp16 bank of (padded) width {bank.shape[1]}")
+        norm2, operand, scale, form = bank.packed_norm2, bank.packed, bank.packed_scale, 1
+    opts = bank._call_opts(sy, syc, n_classes, persistent_wgs, form) if run_tables else _default_opts(persistent_wgs)
+    return _new_call(_Call, (q, s, syc, norm2, operand, scale, opts))
 
 
 class _NoCtx:
     """Stand-in for the autograd context on the inference path."""
-    needs_input_grad = (False, False, False, False)
+    needs_input_grad = (False, False, False)
 
     @staticmethod
     def mark_non_differentiable(*a):
@@ -458,24 +531,19 @@ class _NWHeadFn(torch.autograd.Function):
     """autograd node for NWHead.forward (nwhead/nw.py:266-289)."""
 
     @staticmethod
-    def forward(ctx, q, s, sy, logit_scale, n_classes, kind_id, want_weights, sn2, cache):
-        _need_hip(q, s, sy, logit_scale, sn2)
-        ssplit = sscale = None
-        if cache is not None:
-            sn2, ssplit, sscale = cache.norm2, cache.split, cache.scale
+    def forward(ctx, q, s, logit_scale, call, n_classes, kind_id, want_weights):
+        """``call``: the _Call nw_head resolved; ``q`` / ``s`` are its queries and rows, as arguments of their own for autograd."""
+        _, _, syc, sn2, ssplit, sscale, opts = call
+        _need_hip(q, s, syc, logit_scale, sn2)
         lib = _lib.load()
         qc, sc = _f32c(q), _f32c(s)
-        syc = sy if (sy.dtype == torch.int64 and sy.is_contiguous()) else sy.detach().to(torch.int64).contiguous()
         B, d = qc.shape
         sup_b = sc.dim() == 3
         lab_b = syc.dim() == 2
         N = sc.shape[-2]
         dev = qc.device
-        need_bwd = any(ctx.needs_input_grad[:2]) or (logit_scale is not None and ctx.needs_input_grad[3])
-        if need_bwd:
-            _lib.sync_knobs()          # (NW_BWD_SPLIT and the other diagnostic switches may be flipped between steps)
-        if (need_bwd and ssplit is None and not sup_b and N > 0
-                and lib.nw_bwd_uses_split(B, N, d, n_classes, 0)):
+        need_bwd = any(ctx.needs_input_grad[:2]) or (logit_scale is not None and ctx.needs_input_grad[2])
+        if need_bwd and ssplit is None and not sup_b and N > 0 and lib.nw_bwd_uses_split(B, N, d, n_classes, 0):
             # a training step at a size where the backward's products run on split rows: split the supports once,
             # for this forward (fp16 matrix cores instead of fp32) and for the backward
             ssplit, sscale = torch.empty_like(sc), torch.empty(N, dtype=torch.float32, device=dev)
@@ -484,23 +552,15 @@ class _NWHeadFn(torch.autograd.Function):
                 _lib.check(lib.nw_split_rows_f16x2(_ptr(sc), _ptr(ssplit), _ptr(sscale), _ptr(sn2), N, d, _stream(qc)),
                            "nw_split_rows_f16x2")
         out = torch.empty(B, n_classes, dtype=torch.float32, device=dev)
-        form = 0
-        if cache is not None and not need_bwd and not want_weights and not sup_b:
-            half = cache.half_operands(d)
-            if half is not None:     # an fp16 bank: the head of the rounded features (nw_fwd_opts.operand_form = 1)
-                (sn2, ssplit, sscale), form = half, 1
         scores = torch.empty(B, N, dtype=torch.float32, device=dev) if need_bwd else None
         lse = torch.empty(B, dtype=torch.float32, device=dev) if need_bwd else None
         weights = torch.empty(B, N, dtype=torch.float32, device=dev) if want_weights else None
         ls = None if logit_scale is None else _f32c(logit_scale)
-        ws_bytes = _fwd_ws_bytes(lib, B, N, d, n_classes)
         st = _stream(qc)
-        ws = _workspace(ws_bytes, dev, st) if ws_bytes else None
-        opts = cache.call_opts(sy, n_classes, sy_call=syc, operand_form=form) if cache is not None else _default_opts()
+        ws, ws_bytes = _fwd_workspace(lib, B, N, d, n_classes, dev, st)
         with _OnDevice(dev):
             rc = lib.nw_fwd_f32(_ptr(qc), _ptr(sc), _ptr(syc), _ptr(sn2), _ptr(ssplit), _ptr(sscale), _ptr(out),
-                                _ptr(scores), _ptr(lse),
-                                _ptr(weights), _ptr(ws), ws_bytes, B, N, d, n_classes, kind_id,
+                                _ptr(scores), _ptr(lse), _ptr(weights), _ptr(ws), ws_bytes, B, N, d, n_classes, kind_id,
                                 _ptr(ls), int(sup_b), int(lab_b), opts, st)
         if rc:
             _lib.check(rc, "nw_fwd_f32")
@@ -527,31 +587,26 @@ class _NWHeadFn(torch.autograd.Function):
         ws_bytes = lib.nw_bwd_workspace_bytes(B, N, d, C, kind_id, int(sup_b))
         ws = _workspace(ws_bytes, dev)
         bn2, bsplit, bscale = ctx.bank
-        with torch.cuda.device(dev):
+        with _OnDevice(dev):
             _lib.check(lib.nw_bwd_bank_f32(_ptr(qc), _ptr(sc), _ptr(bn2), _ptr(bsplit), _ptr(bscale), _ptr(syc),
                                            _ptr(scores), _ptr(lse), _ptr(out),
                                            _ptr(g), _ptr(gq), _ptr(gs), _ptr(gls), _ptr(ws), ws_bytes,
                                            B, N, d, C, kind_id, _ptr(ls) if has_ls else None,
                                            int(sup_b), int(lab_b), _stream(qc)), "nw_bwd_bank_f32")
-        return gq, gs, None, gls, None, None, None, None, None
+        return gq, gs, gls, None, None, None, None
 
 
 def nw_head(q, s, sy, n_classes, kind="euclidean", logit_scale=None, return_weights=False,
             support_norm2=None, support_cache=None, validate_labels=False):
     """NWHead.forward(x, sx, sy) -> (B,C) log-probs (and the (B,N) softmax weights on request).
     support_norm2: optional cached ``row_norm2(s)`` for a shared (N,d) support.
-    support_cache: optional ``SplitBank(s)`` (norms + split-fp16 rows: the fast 'full' inference path; built with
-    precision="fp16": the reduced-precision head of the rounded features, see SplitBank).
+    support_cache: optional ``SplitBank(s)`` (the fast 'full' inference path; its docstring says what the call then reads).
     validate_labels: the reference's F.one_hot (nw.py:276) REFUSES labels outside [0, n_classes); the kernels skip such
     supports silently (banks with labels check once, when they are built).  True: check here and raise F.one_hot's
     RuntimeError -- one device round trip per call, which is why it is opt-in (NWHead.validate_labels; NWNet's debug_mode
     turns it on)."""
     if validate_labels and sy.numel():
-        lo, hi = (int(v) for v in torch.aminmax(sy.detach()))
-        if lo < 0:
-            raise RuntimeError("Class values must be non-negative.")                  # F.one_hot's own messages
-        if hi >= int(n_classes):
-            raise RuntimeError("Class values must be smaller than num_classes.")
+        _check_label_range(*(int(v) for v in torch.aminmax(sy.detach())), n_classes, one_hot=True)
     kid = _kind_id(kind)
     if kid == SCORE_KINDS["clip"] and logit_scale is None:
         raise ValueError("clip kernel needs logit_scale")
@@ -561,98 +616,55 @@ def nw_head(q, s, sy, n_classes, kind="euclidean", logit_scale=None, return_weig
         if s.dim() != 2 or support_norm2.shape != (s.shape[0],):
             raise ValueError("support_norm2 must be (N,) for an (N,d) support")
         support_norm2 = _f32c(support_norm2)
-    if support_cache is not None and (s.dim() != 2 or not support_cache.matches(s)):
-        raise ValueError("support_cache was prepared from another support tensor (or the tensor was modified in place "
-                         "since): build a new ops.SplitBank(s) -- the split rows and norms it holds are those of the "
-                         "tensor it was built from")
-    if support_cache is not None and support_cache.label_max is not None and support_cache.label_max >= int(n_classes):
-        raise ValueError(f"support label {support_cache.label_max} is outside [0, n_classes={int(n_classes)}) "
-                         "(the reference's F.one_hot, nw.py:276, raises)")
-    s, sy, support_cache = _resolve_sorted_bank(s, sy, support_cache,
-                                                return_weights or (torch.is_grad_enabled() and s.requires_grad))
-    if support_cache is not None and support_cache.pad:
-        if torch.is_grad_enabled() and s.requires_grad:    # the padded copy is not part of the caller's graph
-            support_norm2, support_cache = support_cache.norm2, None
-        else:
-            q, s = _apply_bank_padding(q, s, support_cache)
-    if q.shape[-1] % 4 and s.dim() == 2 and s.shape[0] > 25:
-        # an embedding size that is not a multiple of 4 would miss every tile kernel (they move 16-byte pieces) and land
-        # on the generic two-kernel path (measured at d = 130: 925 us against 19 at d = 128; 52 ms with 20000 classes):
-        # zero columns change no dot product and no norm, so the operands are padded (torch ops: autograd slices the
-        # gradients back) and the bank's cached norms stay valid
-        pad = (-q.shape[-1]) % 4
-        if support_cache is not None:
-            support_norm2, support_cache = support_cache.norm2, None
-        q, s = torch.nn.functional.pad(q, (0, pad)), torch.nn.functional.pad(s, (0, pad))
-    needs_grad = torch.is_grad_enabled() and (q.requires_grad or s.requires_grad or
-                                              (logit_scale is not None and logit_scale.requires_grad))
-    d_now = q.shape[-1]
-    if needs_grad:
-        _lib.sync_knobs()              # (NW_BWD_SPLIT and the other diagnostic switches may be flipped between steps)
-    if (needs_grad and support_cache is None and s.dim() == 2 and d_now % 32 and d_now >= 256
-            and _lib.load().nw_bwd_uses_split(q.shape[0], s.shape[0], d_now + (-d_now) % 32, int(n_classes), 0)):
-        # a training step at a width that is not a multiple of 32: zero columns take it to the split-row kernels of the
-        # forward and the backward (d = 1000 at T: 326 -> 237 us per eager forward + backward; narrow widths lose more to the
-        # two extra torch ops than the kernels gain: d = 100, 168 -> 232 us); autograd slices the gradients back
-        pad = (-d_now) % 32
-        q, s = torch.nn.functional.pad(q, (0, pad)), torch.nn.functional.pad(s, (0, pad))
+    if support_cache is not None:
+        if s.dim() != 2 or not support_cache.matches(s):
+            raise ValueError("support_cache was prepared from another support tensor (or the tensor was modified in place "
+                             "since): build a new ops.SplitBank(s) -- the split rows and norms it holds are those of the "
+                             "tensor it was built from")
+        _check_label_range(None, support_cache.label_max, n_classes)
+    grad = torch.is_grad_enabled()
+    needs_grad = grad and (q.requires_grad or s.requires_grad or (logit_scale is not None and logit_scale.requires_grad))
+    call = _resolve(support_cache, q, s, sy, n_classes, return_weights, grad and s.requires_grad,
+                    not (needs_grad or return_weights), 0, support_norm2, needs_grad)      # (by position: host-bound)
     if not needs_grad:   # inference: skip the autograd node (its bookkeeping costs more than the kernels at small sizes)
-        return _NWHeadFn.forward(_NoCtx, q, s, sy, logit_scale, int(n_classes), kid, bool(return_weights),
-                                 support_norm2, support_cache)
-    return _NWHeadFn.apply(q, s, sy, logit_scale, int(n_classes), kid, bool(return_weights), support_norm2,
-                           support_cache)
+        return _NWHeadFn.forward(_NoCtx, call.q, call.s, logit_scale, call, int(n_classes), kid, bool(return_weights))
+    return _NWHeadFn.apply(call.q, call.s, logit_scale, call, int(n_classes), kid, bool(return_weights))
 
 
 def nw_partials(q, s, sy, n_classes, kind="euclidean", logit_scale=None, support_cache=None):
     """This rank's (m, den, num) over its shard of the bank; no grad.  ``support_cache``: the
-    shard's SplitBank (split-fp16 fast path; an fp16 bank: the partials of the rounded features)."""
+    shard's SplitBank (see there; an fp16 bank: the partials of the rounded features)."""
     _need_hip(q, s, sy, logit_scale)
-    lib = _lib.load()
-    qc, sc = _f32c(q), _f32c(s)
-    syc = sy.detach().to(torch.int64).contiguous()
-    B, d = qc.shape
-    N = sc.shape[0]
-    dev = qc.device
-    packed = torch.empty(B, n_classes + 2, dtype=torch.float32, device=dev)
-    sc, syc2, support_cache = _resolve_sorted_bank(sc, sy, support_cache)
-    if syc2 is not sy:
-        syc = syc2
-    return nw_partials_into(packed, qc, sc, syc, n_classes, kind, logit_scale, cache=support_cache)
+    qc = _f32c(q)
+    packed = torch.empty(qc.shape[0], n_classes + 2, dtype=torch.float32, device=qc.device)
+    return nw_partials_into(packed, qc, _f32c(s), sy, n_classes, kind, logit_scale, cache=support_cache)
 
 
-def nw_partials_into(packed, qc, sc, syc, n_classes, kind="euclidean", logit_scale=None, ws=None, sn2=None,
+def nw_partials_into(packed, qc, sc, sy, n_classes, kind="euclidean", logit_scale=None, ws=None, sn2=None,
                      cache=None, persistent_wgs=0):
     """Write partials into ``packed`` laid out as [m (B) | den (B) | num (B*C)] (flat, contiguous):
-    one buffer = one collective.  Inputs must already be fp32/int64 contiguous HIP tensors."""
+    one buffer = one collective.  ``qc`` / ``sc`` must already be fp32 contiguous HIP tensors.  ``ws``: a scratch buffer
+    of the caller's (used when large enough, see _fwd_workspace); ``cache``: the SplitBank of ``sc``."""
+    _partials(packed, qc, sc, sy, n_classes, kind, logit_scale, ws, sn2, cache, persistent_wgs)
+    return packed
+
+
+def _partials(packed, qc, sc, sy, n_classes, kind, logit_scale, ws=None, sn2=None, cache=None, persistent_wgs=0, own_ws=False):
+    """nw_partials_into; returns the scratch buffer it used (``own_ws``: ShardedBank keeps its own and lets it grow here)."""
     lib = _lib.load()
-    qc, sc = _apply_bank_padding(qc, sc, cache)
-    B, d = qc.shape
-    N = sc.shape[0]
-    C = int(n_classes)
+    call = _resolve(cache, qc, sc, sy, n_classes, half=True, persistent_wgs=persistent_wgs, norm2=sn2)
+    qc, C = call.q, int(n_classes)
+    (B, d), N = qc.shape, call.s.shape[0]
+    st = _stream(qc)
+    ws, ws_bytes = _fwd_workspace(lib, B, N, d, C, qc.device, st, ws, own_ws)
     flat = packed.view(-1)
     m, den, num = flat[:B], flat[B:2 * B], flat[2 * B:2 * B + B * C]
-    ws_bytes = lib.nw_fwd_workspace_bytes(B, N, d, C)
-    if ws is None or ws.numel() < ws_bytes:
-        ws = _workspace(ws_bytes, qc.device)
     ls = None if logit_scale is None else _f32c(logit_scale)
-    ssplit = sscale = None
-    form = 0
-    if cache is not None:
-        if cache.sorted_rows is not None and sc.data_ptr() != cache.sorted_rows.data_ptr():
-            raise ValueError("this SplitBank holds a class-sorted copy of its support: pass cache.sorted_rows / "
-                             "cache.sorted_labels (or call nw_partials, which does)")
-        sn2, ssplit, sscale = cache.norm2, cache.split, cache.scale
-        half = cache.half_operands(d)
-        if half is not None:
-            (sn2, ssplit, sscale), form = half, 1
-    opts = (cache.call_opts(syc, C, persistent_wgs, sy_call=syc, operand_form=form) if cache is not None
-            else _default_opts(persistent_wgs))
-    with torch.cuda.device(qc.device):
-        _lib.check(lib.nw_fwd_partial_f32(_ptr(qc), _ptr(sc), _ptr(syc), _ptr(sn2), _ptr(ssplit), _ptr(sscale),
-                                          _ptr(m), _ptr(den), _ptr(num),
-                                          _ptr(ws), ws.numel(), B, N, d, C, _kind_id(kind), _ptr(ls), opts,
-                                          _stream(qc)), "nw_fwd_partial_f32")
-    return packed
+    with _OnDevice(qc.device):
+        _lib.check(lib.nw_fwd_partial_f32(_ptr(qc), _ptr(call.s), _ptr(call.sy), _ptr(call.norm2), _ptr(call.operand),
+                                          _ptr(call.scale), _ptr(m), _ptr(den), _ptr(num), _ptr(ws), ws_bytes, B, N, d, C,
+                                          _kind_id(kind), _ptr(ls), call.opts, st), "nw_fwd_partial_f32")
+    return ws
 
 
 def nw_merge(packed_all, B, n_classes, out=None, class_lo=None, c_local=None):
@@ -670,7 +682,7 @@ def nw_merge(packed_all, B, n_classes, out=None, class_lo=None, c_local=None):
     if out is None:
         out = torch.empty(B, C, dtype=torch.float32, device=dev)
     base = packed_all.data_ptr()
-    with torch.cuda.device(dev):
+    with _OnDevice(dev):
         _lib.check(lib.nw_merge_finalize_f32(base, base + 4 * B, base + 8 * B, _ptr(out), G, B, C, L, L, L,
                                              _ptr(class_lo), CL, _stream(packed_all)), "nw_merge_finalize_f32")
     return out
@@ -885,7 +897,7 @@ class _AggregateFn(torch.autograd.Function):
         B, N = sc.shape
         out = torch.empty(B, n_classes, dtype=torch.float32, device=sc.device)
         lse = torch.empty(B, dtype=torch.float32, device=sc.device)
-        with torch.cuda.device(sc.device):
+        with _OnDevice(sc.device):
             _lib.check(lib.nw_aggregate_f32(_ptr(sc), _ptr(syc), _ptr(out), _ptr(lse), None, B, N, n_classes,
                                             int(syc.dim() == 2), _stream(sc)), "nw_aggregate_f32")
         ctx.save_for_backward(sc, syc, lse, out)
@@ -899,7 +911,7 @@ class _AggregateFn(torch.autograd.Function):
         B, N = sc.shape
         g = _f32c(gout)
         gs = torch.empty_like(sc)
-        with torch.cuda.device(sc.device):
+        with _OnDevice(sc.device):
             _lib.check(lib.nw_aggregate_bwd_f32(_ptr(sc), _ptr(syc), _ptr(lse), _ptr(out), _ptr(g), _ptr(gs), B, N, ctx.C,
                                                 int(syc.dim() == 2), _stream(sc)), "nw_aggregate_bwd_f32")
         return gs, None, None
@@ -929,12 +941,10 @@ def nw_head_influence(q, s, sy, n_classes, qy, kind="euclidean", logit_scale=Non
         raise ValueError("nw_head_influence takes a shared (N,d) support with (N,) labels")
     if support_cache is not None and not support_cache.matches(s):
         raise ValueError("support_cache was prepared from another support tensor")
-    # influences are indexed by support position: an unsorted bank's class-sorted copy cannot serve them
-    s, sy, support_cache = _resolve_sorted_bank(s, sy, support_cache, per_position_outputs=True)
-    q, s = _apply_bank_padding(q, s, support_cache)
     lib = _lib.load()
-    qc, sc = _f32c(q), _f32c(s)
-    syc = sy.detach().to(torch.int64).contiguous()
+    # influences are indexed by support position; the call passes the default options (no run tables)
+    call = _resolve(support_cache, _f32c(q), _f32c(s), sy, n_classes, positional=True, run_tables=False)
+    qc, sc = call.q, call.s
     qyc = qy.detach().to(torch.int64).contiguous()
     B, d = qc.shape
     N, C = sc.shape[0], int(n_classes)
@@ -943,16 +953,13 @@ def nw_head_influence(q, s, sy, n_classes, qy, kind="euclidean", logit_scale=Non
     dev = qc.device
     out = torch.empty(B, C, dtype=torch.float32, device=dev)
     infl = torch.empty(B, N, dtype=torch.float32, device=dev)
-    sn2 = ssplit = sscale = None
-    if support_cache is not None:
-        sn2, ssplit, sscale = support_cache.norm2, support_cache.split, support_cache.scale
     ls = None if logit_scale is None else _f32c(logit_scale)
-    ws_bytes = lib.nw_fwd_workspace_bytes(B, N, d, C)
-    ws = _workspace(ws_bytes, dev)
-    with torch.cuda.device(dev):
-        _lib.check(lib.nw_fwd_influence_f32(_ptr(qc), _ptr(sc), _ptr(syc), _ptr(sn2), _ptr(ssplit), _ptr(sscale), _ptr(qyc),
-                                            _ptr(out), None, _ptr(infl), _ptr(ws), ws.numel(), B, N, d, C, kid, _ptr(ls),
-                                            _default_opts(), _stream(qc)), "nw_fwd_influence_f32")
+    st = _stream(qc)
+    ws, ws_bytes = _fwd_workspace(lib, B, N, d, C, dev, st)
+    with _OnDevice(dev):
+        _lib.check(lib.nw_fwd_influence_f32(_ptr(qc), _ptr(sc), _ptr(call.sy), _ptr(call.norm2), _ptr(call.operand),
+                                            _ptr(call.scale), _ptr(qyc), _ptr(out), None, _ptr(infl), _ptr(ws), ws_bytes, B, N,
+                                            d, C, kid, _ptr(ls), call.opts, st), "nw_fwd_influence_f32")
     return out, infl
 
 
@@ -966,7 +973,7 @@ def support_influence_idx(probs, qy, w, sy):
     B, Cc = probs.shape
     N = w.shape[1]
     out = torch.empty(B, N, dtype=torch.float32, device=probs.device)
-    with torch.cuda.device(probs.device):
+    with _OnDevice(probs.device):
         _lib.check(lib.nw_support_influence_f32(_ptr(probs), _ptr(qy), _ptr(w), _ptr(sy), _ptr(out), B, N, Cc,
                                                 _stream(probs)), "nw_support_influence_f32")
     return out

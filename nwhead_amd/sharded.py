@@ -67,7 +67,7 @@ class ShardedBank:
         self.world = dist.get_world_size(group) if dist.is_initialized() else 1
         self._partial = partial_fn or self._hip_partial
         self._merge = merge_fn or self._hip_merge
-        self._ws = None
+        self._ws = None           # this bank's own scratch buffer (ops._partials lets it grow)
         if persistent_wgs is None:
             persistent_wgs = 0
             if self.world > 1 and self.feat.is_cuda:
@@ -100,21 +100,14 @@ class ShardedBank:
         # the shard never changes: prepare it once (squared norms + split-fp16 rows, ops.SplitBank)
         self.cache = ops.SplitBank(self.feat, precision=precision) if (partial_fn is None and self.feat.is_cuda) else None
         self.norm2 = self.cache.norm2 if self.cache is not None else None
-        if self.cache is not None and (self.cache.split is not None or self.cache.packed is not None):
+        if self.cache is not None and self.cache.has_operand_rows:
             self.cache.build_tables(self.y_local)   # the labels every call of this shard passes (self.y when there is one rank)
         self.row_lo = int(row_lo or 0)
 
     # ---- HIP compute hooks (the product path)
     def _hip_partial(self, packed_row, q):
-        N, d = self.feat.shape
-        if self.cache is not None and self.cache.pad:
-            d = self.cache.shape[1]              # a shard whose bank holds zero-padded rows (ops.SplitBank.pad)
-        B = q.shape[0]
-        need = ops._lib.load().nw_fwd_workspace_bytes(B, N, d, self.CL)
-        if self._ws is None or self._ws.numel() < need:
-            self._ws = torch.empty(max(need, 1), dtype=torch.uint8, device=q.device)
-        ops.nw_partials_into(packed_row, q, self.feat, self.y_local, self.CL, self.kind, self.logit_scale,
-                             ws=self._ws, cache=self.cache, persistent_wgs=self.persistent_wgs)
+        self._ws = ops._partials(packed_row, q, self.feat, self.y_local, self.CL, self.kind, self.logit_scale, ws=self._ws,
+                                 cache=self.cache, persistent_wgs=self.persistent_wgs, own_ws=True)
 
     def _hip_merge(self, gathered_rows, B):
         return ops.nw_merge(gathered_rows, B, self.C, class_lo=self.class_lo, c_local=self.CL)
