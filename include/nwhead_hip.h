@@ -306,6 +306,31 @@ int nw_knn_f32(const float *q, const float *s_split, const float *s_scale, const
 int nw_scores_use_split(int64_t B, int64_t N, int64_t d);
 
 /* ---------------------------------------------------------------------------------------------
+ * The same search over a HALF-PRECISION bank (nw_pack_rows_f16): the neighbour modes of the reference
+ * (KNN.__call__ / HNSW.__call__, nwhead/utils.py:185-216; NWNet.get_neighbors, nwhead/nw.py:245-249)
+ * as an exact search over the fp16-rounded features, on the persistent 256-query tile kernel that
+ * serves 'full' inference from such a bank.  Half the bank bytes and a third of the matrix work of
+ * nw_knn_f32, no (B,N) score matrix, no second copy of the bank.
+ *   q         (B,d) fp32 queries, already padded to the bank's width; rounded inside the call
+ *   s_f16 / s_scale / s_norm2   the bank as nw_pack_rows_f16 leaves it ((N,d) fp16, (N,), (N,))
+ *   idx_out   (B,k) int64 bank rows, best score first, equal fp32 scores in ascending row order
+ *   val_out   optional (B,k) fp32: those very scores (the selection keys are made from the floats
+ *             that are returned, so order and values cannot disagree)
+ * The scores are those of the rounded query against the rounded rows, computed in fp32 from the packed
+ * operands and the packed rows' norms.  They are not bit-equal to any other route's (the kernel rotates
+ * its k chunks by the support tile, so equal rows in different tiles may differ in the last bits); they
+ * do not depend on opts->persistent_wgs, and two calls give identical bits.
+ * 1 <= k <= min(N, 32), d % 64 == 0, d >= 192, N > 25; anything else returns NW_ERR_UNSUPPORTED before
+ * anything is launched, and nw_knn_f16_workspace_bytes returns 0 for it.  q, s_f16 and workspace
+ * 16-byte aligned.  opts: NULL, or an nw_fwd_opts of which persistent_wgs is read.  B == 0: NW_OK.
+ * ------------------------------------------------------------------------------------------- */
+size_t nw_knn_f16_workspace_bytes(int64_t B, int64_t N, int64_t d, int64_t k);
+int nw_knn_f16(const float *q, const void *s_f16, const float *s_scale, const float *s_norm2,
+               int64_t *idx_out, float *val_out, void *workspace, size_t workspace_bytes,
+               int64_t B, int64_t N, int64_t d, int64_t k, int kind, const float *logit_scale_dev,
+               const nw_fwd_opts *opts, void *stream);
+
+/* ---------------------------------------------------------------------------------------------
  * The k best supports per query over a bank SHARDED into G parts, each of which has been searched on
  * its own (nw_knn_f32 / nw_topk_f32), and the per-query k-nearest NW head over them: the cross-shard
  * step of the neighbour modes ('knn' / 'hnsw' with every query's own neighbours; NWNet.get_neighbors).

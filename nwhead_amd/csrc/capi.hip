@@ -306,6 +306,24 @@ extern "C" int nw_knn_f32(const float* q, const float* s_split, const float* s_s
                           logit_scale_dev, static_cast<hipStream_t>(stream));
 }
 
+extern "C" size_t nw_knn_f16_workspace_bytes(int64_t B, int64_t N, int64_t d, int64_t k) {
+    return nw::knn_half_workspace_bytes(B, N, d, k);
+}
+
+extern "C" int nw_knn_f16(const float* q, const void* s_f16, const float* s_scale, const float* s_norm2, int64_t* idx_out,
+                          float* val_out, void* workspace, size_t workspace_bytes, int64_t B, int64_t N, int64_t d, int64_t k,
+                          int kind, const float* logit_scale_dev, const nw_fwd_opts* opts, void* stream) {
+    OptsGuard opts_guard(opts);   // (persistent_wgs is read; a struct too short to hold it counts as no options)
+    if (B < 0 || N < 0 || d < 0) return NW_ERR_INVALID_ARG;
+    if (bad_kind(kind)) return NW_ERR_UNSUPPORTED;
+    if (B > 0 && (!q || !s_f16 || !s_scale || !s_norm2 || !idx_out)) return NW_ERR_INVALID_ARG;
+    if (kind == NW_SCORE_CLIP && !logit_scale_dev) return NW_ERR_INVALID_ARG;
+    if ((reinterpret_cast<uintptr_t>(s_f16) | reinterpret_cast<uintptr_t>(q) | reinterpret_cast<uintptr_t>(workspace)) & 15)
+        return NW_ERR_INVALID_ARG;
+    return nw::launch_knn_half(q, s_f16, s_scale, s_norm2, idx_out, val_out, workspace, workspace_bytes, B, N, d, k, kind,
+                               logit_scale_dev, static_cast<hipStream_t>(stream));
+}
+
 extern "C" int nw_knn_merge_f32(const float* vals, const int32_t* rows, const int32_t* labels, int64_t G, int64_t B, int64_t kc,
                                 int64_t stride_g, int64_t k, int64_t C, int64_t* idx_out, float* val_out, int64_t* label_out,
                                 float* out, void* stream) {

@@ -608,7 +608,7 @@ FusedPlan plan_tiles(int64_t B, int64_t N, int64_t d, int form) {
 
 FusedPlan plan_fused(int64_t B, int64_t N, int64_t d, int64_t C, int form, int out, int k, bool norms, bool dot, int cus,
                      const FwdOpts& opts) {
-    (void)C; (void)k;   // (neither moves the decision today: the class count sizes the merge, k the candidate slots)
+    (void)C;   // (the class count sizes the merge; k sizes the candidate slots and bounds the half form's selection)
     if (B < 0 || N < 0 || d < 0 || B >= (1 << 30) || N >= (1 << 30) || d >= (1 << 30)) {   // (fused_eligible's limits)
         FusedPlan none = {};
         return none.status = NW_ERR_UNSUPPORTED, none;
@@ -622,7 +622,10 @@ FusedPlan plan_fused(int64_t B, int64_t N, int64_t d, int64_t C, int form, int o
     p.out = out;
     p.dma = (d % BK) == 0 && (uint64_t)(BQ + p.BS) * 2 * d * 4 < 0xffffffffull;  // per-lane offsets are tile-relative
     if (form == FORM_HALF) {
-        if (out != OUT_NONE || !half_form_shape_ok(d)) return refuse(NW_ERR_UNSUPPORTED);
+        // log-probabilities / partials, or candidates (the epilogue's selection holds 32 keys per query block); no
+        // score-writing half kernel exists
+        if ((out != OUT_NONE && out != OUT_CAND) || !half_form_shape_ok(d)) return refuse(NW_ERR_UNSUPPORTED);
+        if (out == OUT_CAND && (k < 1 || k > 32)) return refuse(NW_ERR_UNSUPPORTED);
         p.persistent = true;
     } else {
         // RS = 5 exists for the LDS-DMA modes only (two workgroups per CU); the register-staged loaders need an even split
@@ -633,13 +636,13 @@ FusedPlan plan_fused(int64_t B, int64_t N, int64_t d, int64_t C, int form, int o
         p.persistent = split && out == OUT_NONE && p.rs > 5 && (p.rs == 8 || env_flag(KNOB_PERSISTENT_ANY_RS)) &&
                        p.grid >= 4 * (int64_t)cus && d >= 3 * BK && !env_flag(KNOB_NO_PERSISTENT);
     }
-    p.run_tables = p.persistent;   // runs of equal labels per support tile: once per launch, or the bank's
+    p.run_tables = p.persistent && out != OUT_CAND;   // runs of equal labels per support tile: once per launch, or the bank's
     if (p.run_tables && p.BS > 192) return refuse(NW_ERR_UNSUPPORTED);   // nw_run_tables_kernel: three rows per lane
     // split-fp16 operands: the caller has checked d % 32 == 0 and supplied the bank's norms
     if (split && (!p.dma || !norms)) return refuse(NW_ERR_INVALID_ARG);
-    if (out == OUT_CAND && !split) return refuse(NW_ERR_INVALID_ARG);
+    if (out == OUT_CAND && form == FORM_F32) return refuse(NW_ERR_INVALID_ARG);
     // (RS = 12 on split operands exists only under the tile_rs knob and spills there: no candidate form of it)
-    if (out == OUT_CAND && p.rs == 12) return refuse(NW_ERR_UNSUPPORTED);
+    if (out == OUT_CAND && split && p.rs == 12) return refuse(NW_ERR_UNSUPPORTED);
     if (p.persistent) {
         p.mode = MODE_F16;
         p.split_queries = true;
@@ -785,6 +788,35 @@ int launch_knn(const float* q, const float* s_split, const float* s_scale, const
     a.q = q, a.s = s_split, a.s_norm2 = s_norm2, a.s_scale = s_scale, a.ls = ls;
     a.B = (int)B, a.N = (int)N, a.d = (int)d, a.C = 1, a.st = st, a.cand = &w.cand;
     const int rc = launch_fused(a, FORM_SPLIT, kind);
+    if (rc != NW_OK) return rc;
+    return launch_topk_candidates(w.cand.key, w.cand.row, idx, vals, B, w.n_stiles * w.kcp, k, st);
+}
+
+// ---- the same search over half-precision rows (nw_knn_f16): the candidate form of the persistent 256-query kernel
+// (fused_f16p12.h, CAND) on tiles of 128 supports at every size, so the layout depends on the shape alone.  The query area
+// holds the packed queries (B * d halves) with their scales and norms.
+bool knn_half_shape_ok(int64_t B, int64_t N, int64_t d, int64_t k) {
+    return B >= 0 && N > 25 && half_form_shape_ok(d) && k >= 1 && k <= 32 && k <= N && B < (1 << 30) && N < (1 << 30);
+}
+
+size_t knn_half_workspace_bytes(int64_t B, int64_t N, int64_t d, int64_t k) {
+    if (!knn_half_shape_ok(B, N, d, k) || B == 0) return 0;
+    return knn_layout(B, N, d / 2, k, BANK_BS, nullptr, nullptr);
+}
+
+int launch_knn_half(const float* q, const void* s_f16, const float* s_scale, const float* s_norm2, int64_t* idx, float* vals,
+                    void* workspace, size_t workspace_bytes, int64_t B, int64_t N, int64_t d, int64_t k, int kind,
+                    const float* ls, hipStream_t st) {
+    if (!knn_half_shape_ok(B, N, d, k)) return NW_ERR_UNSUPPORTED;
+    if (B == 0) return NW_OK;
+    KnnWs w;
+    const size_t need = knn_layout(B, N, d / 2, k, BANK_BS, static_cast<char*>(workspace), &w);
+    if (!workspace || workspace_bytes < need) return NW_ERR_WORKSPACE;
+    if (w.n_stiles * w.kcp >= (1ll << 31)) return NW_ERR_UNSUPPORTED;
+    FusedArgs a = {};   // no labels (sy is null: no run tables), no outputs, no workspace but the CandOut
+    a.q = q, a.s = static_cast<const float*>(s_f16), a.s_norm2 = s_norm2, a.s_scale = s_scale, a.ls = ls;
+    a.B = (int)B, a.N = (int)N, a.d = (int)d, a.C = 1, a.st = st, a.cand = &w.cand;
+    const int rc = launch_fused(a, FORM_HALF, kind);
     if (rc != NW_OK) return rc;
     return launch_topk_candidates(w.cand.key, w.cand.row, idx, vals, B, w.n_stiles * w.kcp, k, st);
 }

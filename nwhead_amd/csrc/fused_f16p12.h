@@ -22,6 +22,12 @@
 // in floats, half the embedding width.  Nothing but the multiply step differs: a 128-byte stage row is then 64
 // consecutive k instead of [32 h | 32 l], the same two 16-byte slots per lane are k 8g .. 8g + 7 and 32 + 8g .. 32 + 8g + 7,
 // and an accumulator takes two products per stage (k ascending) where the split form takes three for half the k.
+//
+// CAND = true (nw_knn_f16; HALF only): the candidate output of fused_impl.h (CandOut) instead of softmax partials.  The
+// main loop, the loader role and the tile order are the same; the epilogue forms the scores as ever and then every wave
+// selects, for each of its two query blocks in turn, the tile's best k scores per query (tile_candidates: 32 key registers
+// per block, in the place of the dead accumulators).  No labels, run tables, statistics or partials are read or written:
+// ws_runid / ws_nrun / ws_bnd / ws_num are null, ws_m / ws_den carry CandOut's key / row arrays and `k` its k.
 #pragma once
 #include "fused_f16p.h"
 
@@ -36,11 +42,11 @@ struct P12 : PipeCfg<128, 256, 8, 4, 3> {
 // epilogue_p<8, KIND, 2, 8> (fused_f16p.h) for a wave that has 168 registers: the same operations on the same values, but
 // the support factors are made per 16-row block and the scores of both query blocks are formed while the accumulators
 // die, so that never more than 64 accumulator / score registers and one block's factors are live together.
-template <int KIND>
+template <int KIND, bool CAND = false>
 __device__ __forceinline__ void epilogue_p12(f32x4 (&acc)[P12::QB][P12::RS], const float* hdr, int nrun, int2 bnd,
                                              float scale, float* __restrict__ ws_m,
                                              float* __restrict__ ws_den, float* __restrict__ ws_num, int B, int N,
-                                             int q0, int s0, int st, int wave, int lane
+                                             int q0, int s0, int st, int wave, int lane, int n_stiles, int k
 #ifdef NW_DIAG_FUSED
                                              , unsigned long long (&diag_)[8], unsigned long long& last_
 #endif
@@ -97,6 +103,26 @@ __device__ __forceinline__ void epilogue_p12(f32x4 (&acc)[P12::QB][P12::RS], con
         __builtin_amdgcn_sched_barrier(0);
     }
     NW_PSTAMP(2);
+    if constexpr (CAND) {
+        // One query block after the other: a block's selection holds its 32 keys next to the other block's 32 scores.  The
+        // distance kinds carry +distance here; tile_candidates takes the score in base-2 units, converts it to the
+        // natural-unit float, keys that very float and gives the rows past the bank the key 0.
+        int ln = lane;  // made per tile: hoisted out of the tile loop, the row offsets and output indices cost the main loop registers
+        asm volatile("" : "+v"(ln));
+        const int ci = ln & 15, cg = ln >> 4;
+#pragma unroll
+        for (int j = 0; j < QB; ++j) {
+            float u[RS][4];
+#pragma unroll
+            for (int r = 0; r < RS; ++r)
+#pragma unroll
+                for (int e = 0; e < 4; ++e) u[r][e] = SF::DIST ? -sc[j][r][e] : sc[j][r][e];
+            tile_candidates<RS>(u, reinterpret_cast<unsigned*>(ws_m), reinterpret_cast<int*>(ws_den), B, N,
+                                q0 + 16 * (QB * wave + j) + ci, s0, cg, st, n_stiles, k);
+            __builtin_amdgcn_sched_barrier(0);
+        }
+        return;
+    }
     // Both query blocks go through every phase together (extrema, lane-group reductions, exp2, run sums, reductions): the
     // swaps of one block lie under the other's hazard padding.  Each value's own operation order is that of epilogue_p.
     constexpr float WORST = SF::DIST ? INFINITY : -INFINITY;
@@ -255,13 +281,14 @@ __device__ __forceinline__ void epilogue_p12(f32x4 (&acc)[P12::QB][P12::RS], con
     NW_PSTAMP(5);
 }
 
-template <int KIND, bool HALF = false>
+template <int KIND, bool HALF = false, bool CAND = false>
 __global__ __launch_bounds__(P12::THREADS, 3) void nw_fused_f16p_kernel_w12(
     const float* __restrict__ q, const float* __restrict__ s, const float* __restrict__ s_norm2,
     const float* __restrict__ s_scale, const float* __restrict__ q_norm2, const float* __restrict__ q_scale,
     const float* __restrict__ logit_scale, const int* __restrict__ ws_runid, const int* __restrict__ ws_nrun,
     const int* __restrict__ ws_bnd, float* __restrict__ ws_m, float* __restrict__ ws_den, float* __restrict__ ws_num, int B,
-    int N, int d, int n_stiles, int n_qtiles, int qg) {
+    int N, int d, int n_stiles, int n_qtiles, int qg, int k) {
+    static_assert(!CAND || HALF, "the candidate form exists for half-precision rows only");
     using P = P12;
     constexpr int RS = P::RS, QB = P::QB, BS = P::BS, BQP = P::BQP, NB = P::NB;
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -275,7 +302,7 @@ __global__ __launch_bounds__(P12::THREADS, 3) void nw_fused_f16p_kernel_w12(
     const int cu = tiles.cu, n_cu = tiles.n_cu, n_local = tiles.n_local;
 
     if (wave >= P::NCW) {
-        persistent_loader<P>(tiles, wave - P::NCW, lane, hdr0, stage, q, s, s_norm2, s_scale, q_norm2, q_scale, ws_runid, B, N,
+        persistent_loader<P, !CAND>(tiles, wave - P::NCW, lane, hdr0, stage, q, s, s_norm2, s_scale, q_norm2, q_scale, ws_runid, B, N,
                              d);
     } else {
         // ================================ CONSUMER ================================
@@ -380,8 +407,12 @@ __global__ __launch_bounds__(P12::THREADS, 3) void nw_fused_f16p_kernel_w12(
             int qt, st;
             tiles.decode(T, qt, st);
             const int q0 = qt * BQP, s0 = st * BS;
-            const int nrun = ws_nrun[st];  // wave-uniform: scalar loads, used after the main loop
-            const int2 bnd = *reinterpret_cast<const int2*>(ws_bnd + 2 * (size_t)st);  // first rows of runs 1 and 2
+            int nrun = 0;
+            int2 bnd = {0, 0};
+            if constexpr (!CAND) {
+                nrun = ws_nrun[st];  // wave-uniform: scalar loads, used after the main loop
+                bnd = *reinterpret_cast<const int2*>(ws_bnd + 2 * (size_t)st);  // first rows of runs 1 and 2
+            }
 #pragma unroll
             for (int j = 0; j < QB; ++j)
 #pragma unroll
@@ -404,12 +435,12 @@ __global__ __launch_bounds__(P12::THREADS, 3) void nw_fused_f16p_kernel_w12(
             }
             NW_PSTAMP(0);
 #ifndef NW_ABL_NOEPI
-            epilogue_p12<KIND>(acc, hdr0 + par * P::HDR_F, nrun, bnd, scale, ws_m, ws_den, ws_num, B, N, q0, s0, st, wave,
-                               lane
+            epilogue_p12<KIND, CAND>(acc, hdr0 + par * P::HDR_F, nrun, bnd, scale, ws_m, ws_den, ws_num, B, N, q0, s0, st, wave,
+                                     lane, n_stiles, k
 #ifdef NW_DIAG_FUSED
-                               , diag_, last_
+                                     , diag_, last_
 #endif
-                               );
+                                     );
 #else
             keep_acc_alive(acc, ws_m, nrun, bnd);
 #endif

@@ -430,6 +430,8 @@ struct QueryRows {
 
 template <int RS, int KIND>
 int launch_f16p(const FusedArgs& a, const FusedPlan& p, const QueryRows& q, const FusedWs& ws);
+template <int KIND, bool HALF, bool CAND>
+int launch_p12(const FusedPlan& p, const FusedArgs& a, const QueryRows& q, const FusedWs& ws);
 
 // Executes a plan of plan_fused (fused.hip) on tiles of RS blocks: workspace layout, the optional run-table launch and
 // query-split / pack launch (into the query area at the tail of the workspace, or into the CandOut), one tile kernel, the
@@ -471,6 +473,12 @@ int launch_fused_rs(const FusedArgs& a, const FusedPlan& p) {
                        a.B, a.N, a.d, c_or_k, p.n_stiles, p.n_qtiles)
 #define NW_TILE_CASE(MODE_) \
     case MODE_: if (p.out == OUT_SCORES) NW_TILE(OUT_SCORES, MODE_); else NW_TILE(OUT_NONE, MODE_); break
+    if (p.out == OUT_CAND && p.persistent) {   // half-precision rows: the 256-query kernel's candidate form (nw_knn_f16)
+        if constexpr (RS == 8) {
+            if (p.form == FORM_HALF && p.variant == 3) return launch_p12<KIND, true, true>(p, a, q, ws);
+        }
+        return NW_ERR_UNSUPPORTED;
+    }
     if (p.out == OUT_CAND) {   // the launch of the score-writing call of this shape (tile height, raw or split queries, grid)
         // (RS = 12 on split operands exists only under the tile_rs knob and spills there: no candidate form of it)
         if constexpr (RS == 12) {
@@ -524,15 +532,18 @@ namespace nw {
 namespace {
 // The one launch of nw_fused_f16p_kernel_w12 (256-query tiles of 128 supports, fused_f16p12.h).  HALF: half-precision rows
 // (a.s / s_scale / s_norm2 from nw_pack_rows_f16, the queries packed likewise); their stride in floats is d / 2 -- the
-// loader and the stage count follow from it.
-template <int KIND, bool HALF>
+// loader and the stage count follow from it.  CAND: the candidate output (a.cand's key / row arrays where the tile
+// maxima / sums go, no run tables, no partials: ws is all null).
+template <int KIND, bool HALF, bool CAND>
 int launch_p12(const FusedPlan& p, const FusedArgs& a, const QueryRows& q, const FusedWs& ws) {
-    static const bool attr = hipFuncSetAttribute(reinterpret_cast<const void*>(nw_fused_f16p_kernel_w12<KIND, HALF>),
+    static const bool attr = hipFuncSetAttribute(reinterpret_cast<const void*>(nw_fused_f16p_kernel_w12<KIND, HALF, CAND>),
                                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)P12::LDS_BYTES) == hipSuccess;
     (void)attr;
-    hipLaunchKernelGGL((nw_fused_f16p_kernel_w12<KIND, HALF>), dim3(p.workgroups), dim3(P12::THREADS), p.lds_bytes, a.st, q.rows,
-                       a.s, a.s_norm2, a.s_scale, q.norm2, q.scale, a.ls, ws.runid, ws.nrun, ws.bnd, ws.m, ws.den, ws.num, a.B,
-                       a.N, HALF ? a.d / 2 : a.d, p.n_stiles, (a.B + P12::BQP - 1) / P12::BQP, p.qgroup);
+    float* m = CAND ? reinterpret_cast<float*>(a.cand->key) : ws.m;
+    float* den = CAND ? reinterpret_cast<float*>(a.cand->row) : ws.den;
+    hipLaunchKernelGGL((nw_fused_f16p_kernel_w12<KIND, HALF, CAND>), dim3(p.workgroups), dim3(P12::THREADS), p.lds_bytes, a.st,
+                       q.rows, a.s, a.s_norm2, a.s_scale, q.norm2, q.scale, a.ls, ws.runid, ws.nrun, ws.bnd, m, den, ws.num, a.B,
+                       a.N, HALF ? a.d / 2 : a.d, p.n_stiles, (a.B + P12::BQP - 1) / P12::BQP, p.qgroup, CAND ? a.cand->k : 0);
     NW_CHECK_LAUNCH();
     return NW_OK;
 }
@@ -547,7 +558,7 @@ int launch_f16p(const FusedArgs& a, const FusedPlan& p, const QueryRows& q, cons
                        ws.den, ws.num, a.B, a.N, a.d, p.n_stiles, (a.B + 64 * (QB_) - 1) / (64 * (QB_)), p.qgroup)
         switch (p.variant) {
             case 3:   // (plan_fused gives variant 3 to tiles of 128 supports only)
-                if constexpr (RS == 8) return p.form == FORM_HALF ? launch_p12<KIND, true>(p, a, q, ws) : launch_p12<KIND, false>(p, a, q, ws);
+                if constexpr (RS == 8) return p.form == FORM_HALF ? launch_p12<KIND, true, false>(p, a, q, ws) : launch_p12<KIND, false, false>(p, a, q, ws);
                 return NW_ERR_UNSUPPORTED;
             case 2: NW_LAUNCH_P(false, 2); break;
             case 1: NW_LAUNCH_P(true, 1); break;

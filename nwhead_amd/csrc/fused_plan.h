@@ -28,7 +28,7 @@ struct CandOut;
 enum { MODE_REG = 0, MODE_DMA = 1, MODE_DMA_SN = 2, MODE_F16 = 3, MODE_F16Q = 4 };
 constexpr bool mode_is_f16(int m) { return m == MODE_F16 || m == MODE_F16Q; }
 // What a tile leaves behind besides (OUT_NONE, OUT_SCORES) or instead of (OUT_CAND) its softmax partials: nothing, its
-// block of the (B,N) score matrix, or its best k scores per query (CandOut; split operands only, no labels, no merge).
+// block of the (B,N) score matrix, or its best k scores per query (CandOut; split or half-precision operands, no labels, no merge).
 enum { OUT_NONE = 0, OUT_SCORES = 1, OUT_CAND = 2 };
 // The support operand: fp32 rows, split rows (nw_split_rows_f16x2) or half-precision rows (nw_pack_rows_f16).
 enum { FORM_F32 = 0, FORM_SPLIT = 1, FORM_HALF = 2 };
@@ -54,7 +54,7 @@ FusedPlan plan_fused(int64_t B, int64_t N, int64_t d, int64_t C, int form, int o
                      const FwdOpts& opts);
 
 // One forward call's operands, as the launchers take them.  out != nullptr: final log-probabilities (+ optional scores /
-// lse); out == nullptr: the partials (m, den, num); cand != nullptr: candidates instead of either (nw_knn_f32).
+// lse); out == nullptr: the partials (m, den, num); cand != nullptr: candidates instead of either (nw_knn_f32, nw_knn_f16).
 struct FusedArgs {
     const float* q;              // the caller's RAW fp32 queries
     const float* s;              // support rows in the plan's form (FORM_HALF: fp16 rows behind a float pointer)

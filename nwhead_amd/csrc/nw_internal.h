@@ -96,6 +96,11 @@ size_t knn_workspace_bytes(int64_t B, int64_t N, int64_t d, int64_t k);
 int launch_knn(const float* q, const float* s_split, const float* s_scale, const float* s_norm2, int64_t* idx, float* vals,
                void* workspace, size_t workspace_bytes, int64_t B, int64_t N, int64_t d, int64_t k, int kind,
                const float* logit_scale_dev, hipStream_t st);
+// ... and over half-precision rows, on the persistent 256-query kernel's candidate form (nw_knn_f16)
+size_t knn_half_workspace_bytes(int64_t B, int64_t N, int64_t d, int64_t k);
+int launch_knn_half(const float* q, const void* s_f16, const float* s_scale, const float* s_norm2, int64_t* idx, float* vals,
+                    void* workspace, size_t workspace_bytes, int64_t B, int64_t N, int64_t d, int64_t k, int kind,
+                    const float* logit_scale_dev, hipStream_t st);
 // knn_merge.hip: the k best of G sorted per-shard candidate lists per query, and the per-query k-NN head over them
 // (nw_knn_merge_f32)
 int launch_knn_merge(const float* vals, const int* rows, const int* labels, int64_t G, int64_t B, int64_t kc, int64_t stride_g,

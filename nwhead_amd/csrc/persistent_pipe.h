@@ -116,7 +116,9 @@ struct PersistentTiles {
 // in flight, and DMAs each tile's header (support norms, row scales, run ids; query norms and scales) into header
 // buffer (tile index mod P::NHB) together with the tile's first stage.  One tile_barrier() per stage plus one in front,
 // matched by the consumers.  -DNW_ABL_NODMA (timing experiment, results wrong): the stages are not filled.
-template <class P>
+// RUNID = false (the candidate-output form, which reads no run tables: ws_runid is null): the run-id pieces repeat the row
+// scales' pieces instead (same bytes to the same place), so that every stage keeps its count of DMAs.
+template <class P, bool RUNID = true>
 __device__ __forceinline__ void persistent_loader(const PersistentTiles& tiles, int lw, int lane, float* hdr0, float4* stage,
                                                   const float* __restrict__ q, const float* __restrict__ s,
                                                   const float* __restrict__ s_norm2, const float* __restrict__ s_scale,
@@ -162,7 +164,8 @@ __device__ __forceinline__ void persistent_loader(const PersistentTiles& tiles, 
                 float* dst = h + arr * P::NH + 64 * c;
                 if (arr == 0) dma4(s_norm2 + min(row, N - 1), dst);
                 else if (arr == 1) dma4(s_scale + min(row, N - 1), dst);
-                else dma4(ws_runid + (size_t)ist * BS + 64 * c + lane, dst);  // padded by 64 entries
+                else if constexpr (RUNID) dma4(ws_runid + (size_t)ist * BS + 64 * c + lane, dst);  // padded by 64 entries
+                else dma4(s_scale + min(row, N - 1), h + P::NH + 64 * c);
             } else {
                 const int qp = pc - 3 * P::N64, arr = qp / (BQP / 64), c = qp - arr * (BQP / 64);  // qn2 pieces, then qsc pieces
                 const int row = min(iq0 + 64 * c + lane, B - 1);

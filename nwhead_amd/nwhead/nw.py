@@ -57,13 +57,22 @@ class NWNet(nn.Module):
                  kernel_type='euclidean', train_type='random', n_way=None, n_shot=1,
                  n_shot_random=1, n_shot_full=100, n_shot_cluster=1, n_neighbors=10,
                  env_array=None, debug_mode=False, device='cuda:0', return_mask=False, cluster_backend='auto',
-                 loader_workers=0, pin_memory=False, knn_per_query=False, full_precision="fp32"):
+                 loader_workers=0, pin_memory=False, knn_per_query=False, full_precision="fp32",
+                 search_precision="fp32"):
         super().__init__()
         # not in the reference: "fp16" serves predict(x, 'full') from a half-precision bank (ops.SplitBank(precision="fp16"):
         # bank and query features rounded to fp16, half the bytes, a third of the matrix-core work); "fp32" is the parity path
         if full_precision not in ("fp32", "fp16"):
             raise ValueError(f"full_precision must be 'fp32' or 'fp16', got {full_precision!r}")
         self.full_precision = full_precision
+        # not in the reference: "fp16" (needs full_precision="fp16") makes get_neighbors(x, k <= 32) and the neighbour selection
+        # of predict(x, 'knn' | 'hnsw') the exact search over the fp16-rounded features (ops.nw_knn(rounded=True)) whenever
+        # the bank can serve it; "fp32" is the fp32-grade search
+        if search_precision not in ("fp32", "fp16"):
+            raise ValueError(f"search_precision must be 'fp32' or 'fp16', got {search_precision!r}")
+        if search_precision == "fp16" and full_precision != "fp16":
+            raise ValueError("search_precision='fp16' searches the half-precision bank: it needs full_precision='fp16'")
+        self.search_precision = search_precision
         self.knn_per_query = bool(knn_per_query)  # not in the reference: 'knn' / 'hnsw' modes give every query ITS OWN neighbours
         self.cluster_backend = cluster_backend   # not in the reference: where 'cluster' mode's k-means runs (utils.compute_clusters)
         # not in the reference either (its bank loaders are single-process, support.py:164-165): DataLoader workers and
@@ -138,7 +147,7 @@ class NWNet(nn.Module):
         self.support_eval = SupportSetEval(support_dataset, self.n_classes, self.n_shot_random,
                                            self.n_shot_full, n_shot_cluster=self.n_shot_cluster,
                                            n_neighbors=self.n_neighbors, env_array=self.env_array,
-                                           knn_per_query=self.knn_per_query,
+                                           knn_per_query=self.knn_per_query, search_precision=self.search_precision,
                                            cluster_backend=self.cluster_backend, loader_workers=self.loader_workers,
                                            pin_memory=self.pin_memory)
 
@@ -208,7 +217,7 @@ class NWNet(nn.Module):
         self.sharded_bank = ShardedBank(feat, y, self.n_classes, self.kernel.kind, self.kernel._logit_scale(),
                                         group=group, partial_fn=partial_fn, merge_fn=merge_fn,
                                         precision=self.full_precision, row_lo=lo, search_fn=search_fn,
-                                        knn_merge_fn=knn_merge_fn)
+                                        knn_merge_fn=knn_merge_fn, search_precision=self.search_precision)
         return self.sharded_bank
 
     def predict(self, x, mode='random'):
@@ -250,7 +259,10 @@ class NWNet(nn.Module):
         k nearest, (B, k), 1 <= k <= N -- for k <= 32 over precompute()'s bank (N % 4 == 0) without the (B, N) score matrix
         where that pays (ops.nw_knn, ops.knn_fused_pays).  After precompute_sharded() (and no precompute()): the k <= 32
         nearest rows of the whole sharded bank, global rows in precompute()'s row order, the same on every rank; k is
-        required there."""
+        required there.
+        NWNet(search_precision="fp16"): for k <= 32 the exact search over the fp16-rounded features of the half-precision
+        bank (ops.nw_knn(rounded=True)) whenever the bank can serve it, at every size; k > 32 or k=None falls back to the
+        routes above."""
         qfeat = self._eval_featurizer()(x).detach()
         if getattr(self, 'sharded_bank', None) is not None and not hasattr(self, 'full_feat'):
             if k is None:
@@ -263,6 +275,10 @@ class NWNet(nn.Module):
             if not 1 <= k <= N:
                 raise ops.NWHipError(f"get_neighbors: k = {k} outside [1, N = {N}]")
             bank = getattr(self, 'full_cache', None)
+            if self.search_precision == "fp16" and isinstance(self.kernel, _ScoreModule) and bank is not None and qfeat.is_cuda \
+                    and self.full_feat.is_cuda and bank.matches(self.full_feat) \
+                    and ops.knn_rounded_refusal(bank, k, qfeat.shape[1]) is None:
+                return ops.nw_knn(qfeat, bank, k, self.kernel.kind, self.kernel._logit_scale(), rounded=True)
             if k <= 32 and N % 4 == 0 and isinstance(self.kernel, _ScoreModule) and bank is not None and qfeat.is_cuda \
                     and self.full_feat.is_cuda and bank.matches(self.full_feat) and ops.knn_fused_pays(qfeat.shape[0], N):
                 return ops.nw_knn(qfeat, bank, k, self.kernel.kind, self.kernel._logit_scale(), support=self.full_feat)

@@ -109,16 +109,26 @@ class KNN:
     """Exact nearest supports by Euclidean distance (utils.py:178-193).  As in the reference, the k
     rows of ALL queries are concatenated into one shared (B*k, d) support -- every query attends to every query's
     neighbours.  per_query=True (not in the reference): each query gets ITS OWN k neighbours, supports
-    (B, k, d) and labels (B, k) for the head's per-query path."""
+    (B, k, d) and labels (B, k) for the head's per-query path.
+    search_precision="fp16" (not in the reference): with an fp16 bank (``bank``, ops.SplitBank(precision="fp16")) the
+    neighbours are those of the exact search over the fp16-rounded features (ops.nw_knn(rounded=True)) whenever the bank
+    can serve it -- k <= 32, packed rows, no class-sorted copy; otherwise, and always for "fp32", the fp32-grade search.
+    The supports handed on are the fp32 rows of the selected neighbours either way."""
 
-    def __init__(self, data, labels, n_neighbors=20, per_query=False):
+    def __init__(self, data, labels, n_neighbors=20, per_query=False, search_precision="fp32"):
+        if search_precision not in ("fp32", "fp16"):
+            raise ValueError(f"search_precision must be 'fp32' or 'fp16', got {search_precision!r}")
         self.data, self.labels, self.n_neighbors, self.per_query = data, labels, n_neighbors, bool(per_query)
+        self.search_precision = search_precision
 
     bank = None   # the data's ops.SplitBank when there is one (NWNet.precompute): scores from the split-fp16 tile kernel
 
     def indices(self, x):
         data = self.data.to(x.device)
         k = min(self.n_neighbors, data.shape[0])
+        if (self.search_precision == "fp16" and self.bank is not None and data.is_cuda and data.dim() == 2
+                and self.bank.matches(data) and ops.knn_rounded_refusal(self.bank, k, x.shape[1]) is None):
+            return ops.nw_knn(x, self.bank, k, "euclidean", rounded=True)   # the caller asked for this route: no size gate
         if (self.bank is not None and data.is_cuda and 1 <= k <= 32 and data.dim() == 2 and data.shape[0] % 4 == 0
                 and ops.knn_fused_pays(x.shape[0], data.shape[0])):
             # no (B, N) score matrix: the tiles of the score kernel select (ops.nw_knn).  N % 4 == 0: the lines below then
@@ -141,7 +151,8 @@ class KNN:
 
 class HNSW(KNN):
     """The reference uses hnswlib's approximate index (utils.py:195-216); hnswlib is not part of
-    this image, so 'hnsw' mode is served by the exact search above (a superset in recall)."""
+    this image, so 'hnsw' mode is served by the exact search above (a superset in recall); with
+    search_precision="fp16" by the exact search over the fp16-rounded features, its fast counterpart."""
 
 
 def _class_argmax(values, inv, n_groups):

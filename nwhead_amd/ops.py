@@ -194,7 +194,8 @@ def knn_fused_pays(B, N):
     return 4 * int(B) * int(N) >= KNN_FUSED_MIN_SCORE_BYTES
 
 
-def nw_knn(q, bank, k, kind="euclidean", logit_scale=None, return_values=False, support=None):
+def nw_knn(q, bank, k, kind="euclidean", logit_scale=None, return_values=False, support=None, rounded=False,
+           persistent_wgs=0):
     """q:(B,d), bank: the SplitBank of an (N,d) support -> (B,k) int64 rows of the tensor the bank was prepared from, best
     score first, equal scores in ascending row order (with return_values: also their (B,k) scores).  The neighbour search
     of nwhead/utils.py:185-193 and nwhead/nw.py:245-249 over a resident bank WITHOUT the (B,N) score matrix: the tiles of
@@ -205,7 +206,18 @@ def nw_knn(q, bank, k, kind="euclidean", logit_scale=None, return_values=False, 
     the bank has no split rows (a norms-only or fp16 bank), holds a class-sorted copy (built from unsorted labels), when
     k > 32, and for shapes whose bank-route scores come from the fp32 tile kernel (below 2e8 multiply-adds, unless
     NW_SPLIT_ALWAYS=1): the rows and values are the same either way.  (A bank whose N is no multiple of 4 has no
-    bank-route scores; its fused search ranks the split kernel's scores, which lie within the same 3e-5 of the exact ones.)"""
+    bank-route scores; its fused search ranks the split kernel's scores, which lie within the same 3e-5 of the exact ones.)
+
+    ``rounded=True`` (not the default, which it leaves as it is bit for bit): the exact search over the fp16-ROUNDED
+    features of a ``precision="fp16"`` bank (nw_knn_f16) -- per query the k <= 32 rows with the largest score between the
+    rounded query and the rounded rows (the rounding of nw_pack_rows_f16), computed in fp32 from ``bank.packed`` on the
+    persistent 256-query kernel that serves 'full' inference from such a bank: half the bank bytes and a third of the
+    matrix work of the split-row search, no score matrix, no second bank.  Order: score descending, equal fp32 scores by
+    ascending row; the values returned are the very floats that were ranked.  Not bit-equal to any other route; the same
+    bits from call to call and for every ``persistent_wgs`` (workgroups of the tile kernel, nw_fwd_opts.persistent_wgs).
+    ``support`` is not needed.  Raises NWHipError when the bank cannot serve it: no packed rows (a bank of another
+    precision, or a norms-only one of N <= 25), a class-sorted copy, k > 32, or queries whose width does not pad to the
+    bank's."""
     _need_hip(q, logit_scale, support)
     if not isinstance(bank, SplitBank):
         raise TypeError("nw_knn searches a prepared bank: pass ops.SplitBank(support)")
@@ -213,6 +225,8 @@ def nw_knn(q, bank, k, kind="euclidean", logit_scale=None, return_values=False, 
     q = _f32c(q)
     B = q.shape[0]
     k = int(k)
+    if rounded:
+        return _nw_knn_rounded(lib, q, bank, k, kind, logit_scale, return_values, persistent_wgs)
     N = bank.shape[0] if support is None else support.shape[-2]
     if k < 1 or k > N:
         raise NWHipError(f"nw_knn: k = {k} outside [1, N = {N}] (nw_topk refuses it too)")
@@ -239,6 +253,48 @@ def nw_knn(q, bank, k, kind="euclidean", logit_scale=None, return_values=False, 
     with _OnDevice(q.device):
         _lib.check(lib.nw_knn_f32(_ptr(q), _ptr(call.operand), _ptr(call.scale), _ptr(call.norm2), _ptr(idx), _ptr(vals),
                                   _ptr(ws), ws_bytes, B, N, dp, k, _kind_id(kind), _ptr(ls), st), "nw_knn_f32")
+    return (idx, vals) if return_values else idx
+
+
+def knn_rounded_refusal(bank, k, width=None):
+    """Why ``nw_knn(..., rounded=True)`` cannot search ``bank`` for k neighbours (queries of ``width`` columns), or None."""
+    N = bank.shape[0]
+    if bank.precision != "fp16":
+        return "the bank holds no fp16-packed rows (prepare it with precision='fp16')"
+    if bank.packed is None:
+        return f"a norms-only bank (N = {N} <= 25 rows: no tile kernel takes it)"
+    if bank.sorted_rows is not None:
+        return "the bank holds a class-sorted copy (it was built from unsorted labels): its rows are not the caller's"
+    if k < 1 or k > N:
+        return f"k = {k} outside [1, N = {N}]"
+    if k > 32:
+        return f"k = {k} > 32 (the tile epilogue's selection holds 32 keys per query)"
+    if width is not None and width + bank.pad != bank.shape[1]:
+        return f"queries of width {width} do not pad to the bank's width {bank.shape[1]} (pad {bank.pad})"
+    return None
+
+
+def _nw_knn_rounded(lib, q, bank, k, kind, logit_scale, return_values, persistent_wgs):
+    why = knn_rounded_refusal(bank, k, q.shape[1])
+    call = None if why else _resolve_scores(bank, q, rounded=True, persistent_wgs=persistent_wgs)
+    if call is None:
+        raise NWHipError(f"nw_knn(rounded=True): {why or 'the bank cannot serve the search'}")
+    q, dp = call.q, call.q.shape[1]
+    B, N = q.shape[0], bank.shape[0]
+    ls = None if logit_scale is None else _f32c(logit_scale)
+    idx = torch.empty(B, k, dtype=torch.int64, device=q.device)
+    vals = torch.empty(B, k, dtype=torch.float32, device=q.device) if return_values else None
+    if B == 0:
+        return (idx, vals) if return_values else idx
+    key = ("knn_f16", B, N, dp, k)
+    ws_bytes = _WS_BYTES.get(key)
+    if ws_bytes is None:
+        ws_bytes = _WS_BYTES[key] = lib.nw_knn_f16_workspace_bytes(B, N, dp, k)
+    st = _stream(q)
+    ws = _workspace(ws_bytes, q.device, st)
+    with _OnDevice(q.device):
+        _lib.check(lib.nw_knn_f16(_ptr(q), _ptr(call.operand), _ptr(call.scale), _ptr(call.norm2), _ptr(idx), _ptr(vals),
+                                  _ptr(ws), ws_bytes, B, N, dp, k, _kind_id(kind), _ptr(ls), call.opts, st), "nw_knn_f16")
     return (idx, vals) if return_values else idx
 
 
@@ -337,6 +393,8 @@ class SplitBank:
       nw_fwd_opts.operand_form = 1) only where the call allows it -- no gradients, no weights, a shared support: training
       steps, weights, scores, influences and searches run on an fp16 bank as on a norms-only one.
     * scores (nw_scores' bank route, nw_knn's fused search; _resolve_scores): only split rows without a class-sorted copy.
+    * searches, rounded (nw_knn(rounded=True); _resolve_scores): only fp16-packed rows without a class-sorted copy; the
+      queries are padded to the bank's width like everywhere else.
     * run tables (build_tables): named in the call's options only when its labels are the tensor the tables were built
       from, unmodified; n_classes must then exceed every label of the tables."""
 
@@ -457,9 +515,17 @@ def _pad_to_bank(bank, q, s):
     return torch.nn.functional.pad(q, (0, bank.pad)), (bank.rows if s is not None and s.shape[-1] != bank.shape[1] else s)
 
 
-def _resolve_scores(bank, q, s=None):
+def _resolve_scores(bank, q, s=None, rounded=False, persistent_wgs=0):
     """The _Call of a score call over the split rows of ``bank`` (rows `s`, one class, all labels zero), or of a search
-    (no `s`, no labels); None when the bank cannot serve it as prepared (SplitBank's docstring, "scores")."""
+    (no `s`, no labels); None when the bank cannot serve it as prepared (SplitBank's docstring, "scores").  ``rounded``: the
+    search over the fp16-packed rows instead ("searches, rounded"), with ``persistent_wgs`` in its options."""
+    if rounded:
+        if bank.packed is None or bank.sorted_rows is not None or q.shape[1] + bank.pad != bank.shape[1]:
+            return None
+        if bank.pad:
+            q, _ = _pad_to_bank(bank, q, None)
+        return _new_call(_Call, (q, None, None, bank.packed_norm2, bank.packed, bank.packed_scale,
+                                 _default_opts(persistent_wgs)))
     if bank.split is None or bank.sorted_rows is not None or q.shape[1] + bank.pad != bank.shape[1]:
         return None
     if bank.pad:

@@ -46,7 +46,7 @@ def _coalesce(chunk):
 class ShardedBank:
     def __init__(self, feat_shard, y_shard, n_classes, kind="euclidean", logit_scale=None, group=None,
                  partial_fn=None, merge_fn=None, persistent_wgs=None, precision="fp32", row_lo=None, search_fn=None,
-                 knn_merge_fn=None):
+                 knn_merge_fn=None, search_precision="fp32"):
         """row_lo: the global bank row of this shard's first row (what neighbors() adds to the shard's own row numbers).
         Default: the exclusive prefix sum of the shard sizes over the ranks, from the all-gather below.
         search_fn / knn_merge_fn: CPU compute hooks of the neighbour search, like partial_fn / merge_fn:
@@ -55,11 +55,20 @@ class ShardedBank:
         The neighbour search runs on the fp32 shard through a SplitBank of split-fp16 rows (fp32-grade scores): with
         precision="fp32" that is the bank 'full' inference uses; with precision="fp16" a second bank is prepared from the
         fp32 shard on the first search (the fp16-packed rows are not searched), so 'full'-only users pay nothing.
+        search_precision="fp16" (needs precision="fp16"): the search runs on the shard's fp16 bank itself
+        (ops.nw_knn(rounded=True): the exact search over the fp16-rounded features), no second bank is ever prepared, and
+        predict_knn is the k-NN head of the rounded scores.  (A shard of 25 rows or fewer, whose bank holds norms only, is
+        searched through its score matrix: fp32 scores of the unrounded rows.)
         precision: "fp32" (split-fp16 rows, fp32-grade) or "fp16" (the reduced-precision bank of ops.SplitBank).
         persistent_wgs: workgroups of the persistent tile kernel (nw_fwd_opts.persistent_wgs, a multiple of 8; 0 = one per
         CU).  Default: with more than one rank, all CUs but one per XCD (count - 8) -- the all-gather of bucket i runs
         under the kernels of bucket i + 1, and a kernel that holds one 160 KB-LDS workgroup on EVERY CU would leave RCCL's
         kernel nowhere to run until it ends; with one rank, one per CU."""
+        if search_precision not in ("fp32", "fp16"):
+            raise ValueError(f"search_precision must be 'fp32' or 'fp16', got {search_precision!r}")
+        if search_precision == "fp16" and precision != "fp16":
+            raise ValueError("search_precision='fp16' searches the half-precision bank: it needs precision='fp16'")
+        self.search_precision = search_precision
         self.feat = feat_shard.detach().to(torch.float32).contiguous()
         self.y = y_shard.detach().to(torch.int64).contiguous()
         self.C = int(n_classes)
@@ -113,6 +122,11 @@ class ShardedBank:
         return ops.nw_merge(gathered_rows, B, self.C, class_lo=self.class_lo, c_local=self.CL)
 
     def _hip_search(self, q, k):
+        if self.search_precision == "fp16" and self.cache is not None:
+            if self.cache.packed is None:    # (25 rows or fewer: norms only; the score matrix of so few rows)
+                return ops.nw_knn(q, self.cache, k, self.kind, self.logit_scale, return_values=True, support=self.feat)
+            return ops.nw_knn(q, self.cache, k, self.kind, self.logit_scale, return_values=True, rounded=True,
+                              persistent_wgs=self.persistent_wgs)
         bank = self._search_bank
         if bank is None:
             # (the 'full' bank has split rows and no class-sorted copy -- it was prepared without labels -- unless it is fp16)
