@@ -300,6 +300,33 @@ int nw_knn_f32(const float *q, const float *s_split, const float *s_scale, const
                int64_t *idx_out, float *val_out, void *workspace, size_t workspace_bytes,
                int64_t B, int64_t N, int64_t d, int64_t k, int kind, const float *logit_scale_dev,
                void *stream);
+/* The same search restricted to a ROW WINDOW per query: row_lo / row_hi (B,) int32 on the device.  A row
+ * is a candidate only when lo[b] <= row < hi[b] (exclude == 0), or only when it is outside that range
+ * (exclude != 0).  lo >= hi is the empty window: no row, or with exclude every row.  The values are
+ * clamped to [0, N] on the device and never used as an address.  In a class-sorted bank "the rows of
+ * class c" is such a window: nearest same-class / other-class supports, leave-one-out neighbours
+ * (window [i, i+1), excluded), one segment of a concatenated bank.
+ * Same contract, limits, alignment rules, launch decision and workspace (nw_knn_workspace_bytes) as
+ * nw_knn_f32, and the same scores bit for bit; the result is the k best rows the window admits, in
+ * nw_topk_f32's order, and where it admits fewer than k the remaining slots hold row -1, value -inf.
+ * row_lo or row_hi NULL: NW_ERR_INVALID_ARG. */
+int nw_knn_window_f32(const float *q, const float *s_split, const float *s_scale, const float *s_norm2,
+                      const int32_t *row_lo, const int32_t *row_hi, int exclude,
+                      int64_t *idx_out, float *val_out, void *workspace, size_t workspace_bytes,
+                      int64_t B, int64_t N, int64_t d, int64_t k, int kind, const float *logit_scale_dev,
+                      void *stream);
+/* support_influence (util/metric.py:23-50) of k SELECTED supports per query, from the head's own outputs:
+ *   vals (B,k) fp32 raw scores and rows (B,k) int64 bank rows (a search's val_out / idx_out),
+ *   sy (N,) int64, qy (B,) int64, out (B,C) log-probabilities and lse (B,) of nw_fwd_f32 over the same bank;
+ *   infl_out (B,k) fp32, label_out optional (B,k) int64: the labels of the selected rows.
+ * w = exp(val - lse[b]), p = exp(out[b, qy_b]), infl = log((p - p*w) / (p - w*[sy_row == qy_b])): the
+ * arithmetic of nw_fwd_influence_f32's finishing pass, every product, difference and quotient rounded on
+ * its own.  A slot whose row is outside [0, N) (the -1 of a padded search) gets influence +0.0, label -1.
+ * One launch, no workspace.  Null pointers (label_out excepted) or a negative size: NW_ERR_INVALID_ARG;
+ * k outside [1, 32]: NW_ERR_UNSUPPORTED; B == 0: NW_OK. */
+int nw_influence_select_f32(const float *vals, const int64_t *rows, const int64_t *sy, const int64_t *qy,
+                            const float *out, const float *lse, float *infl_out, int64_t *label_out,
+                            int64_t B, int64_t k, int64_t N, int64_t C, void *stream);
 /* Whether nw_fwd_f32 / nw_fwd_partial_f32 with split operands (s_split, d % 32 == 0) and no force_split
  * option run the split-fp16 tile kernel at this shape (1) or the fp32 one (0): the size rule alone.  For
  * callers that promise the bits of that call's scores_out, like nw_knn_f32's. */

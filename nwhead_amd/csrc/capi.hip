@@ -306,6 +306,21 @@ extern "C" int nw_knn_f32(const float* q, const float* s_split, const float* s_s
                           logit_scale_dev, static_cast<hipStream_t>(stream));
 }
 
+extern "C" int nw_knn_window_f32(const float* q, const float* s_split, const float* s_scale, const float* s_norm2,
+                                 const int32_t* row_lo, const int32_t* row_hi, int exclude, int64_t* idx_out, float* val_out,
+                                 void* workspace, size_t workspace_bytes, int64_t B, int64_t N, int64_t d, int64_t k, int kind,
+                                 const float* logit_scale_dev, void* stream) {
+    if (!row_lo || !row_hi) return NW_ERR_INVALID_ARG;   // (the search without a window is nw_knn_f32)
+    if (B < 0 || N < 0 || d < 0) return NW_ERR_INVALID_ARG;
+    if (bad_kind(kind)) return NW_ERR_UNSUPPORTED;
+    if (B > 0 && (!q || !s_split || !s_scale || !s_norm2 || !idx_out)) return NW_ERR_INVALID_ARG;
+    if (kind == NW_SCORE_CLIP && !logit_scale_dev) return NW_ERR_INVALID_ARG;
+    if ((reinterpret_cast<uintptr_t>(s_split) | reinterpret_cast<uintptr_t>(q) | reinterpret_cast<uintptr_t>(workspace)) & 15)
+        return NW_ERR_INVALID_ARG;
+    return nw::launch_knn(q, s_split, s_scale, s_norm2, idx_out, val_out, workspace, workspace_bytes, B, N, d, k, kind,
+                          logit_scale_dev, static_cast<hipStream_t>(stream), row_lo, row_hi, exclude);
+}
+
 extern "C" size_t nw_knn_f16_workspace_bytes(int64_t B, int64_t N, int64_t d, int64_t k) {
     return nw::knn_half_workspace_bytes(B, N, d, k);
 }

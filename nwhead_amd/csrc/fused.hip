@@ -732,7 +732,7 @@ bool knn_shape_ok(int64_t B, int64_t N, int64_t d, int64_t k) {
 }
 // BS: the tile height of the score-writing call of this shape (16 * pick_rs on split operands)
 size_t knn_layout(int64_t B, int64_t N, int64_t d, int64_t k, int BS, char* base, KnnWs* out) {
-    KnnWs w;
+    KnnWs w = {};   // (no row window)
     w.n_stiles = (N + BS - 1) / BS;
     w.kcp = cand_slots((int)k, BS);
     size_t off = 0;
@@ -777,19 +777,22 @@ size_t knn_workspace_bytes(int64_t B, int64_t N, int64_t d, int64_t k) {
 
 int launch_knn(const float* q, const float* s_split, const float* s_scale, const float* s_norm2, int64_t* idx, float* vals,
                void* workspace, size_t workspace_bytes, int64_t B, int64_t N, int64_t d, int64_t k, int kind, const float* ls,
-               hipStream_t st) {
+               hipStream_t st, const int32_t* row_lo, const int32_t* row_hi, int exclude) {
     if (!knn_shape_ok(B, N, d, k)) return NW_ERR_UNSUPPORTED;
     if (B == 0) return NW_OK;
+    const bool window = row_lo != nullptr && row_hi != nullptr;
     KnnWs w;
     const size_t need = knn_layout(B, N, d, k, plan_tiles(B, N, d, FORM_SPLIT).BS, static_cast<char*>(workspace), &w);
     if (!workspace || workspace_bytes < need) return NW_ERR_WORKSPACE;
     if (w.n_stiles * w.kcp >= (1ll << 31)) return NW_ERR_UNSUPPORTED;
+    if (window) w.cand.win_lo = row_lo, w.cand.win_hi = row_hi, w.cand.win_exclude = exclude != 0;
     FusedArgs a = {};   // no labels, no outputs, no workspace but the CandOut
     a.q = q, a.s = s_split, a.s_norm2 = s_norm2, a.s_scale = s_scale, a.ls = ls;
     a.B = (int)B, a.N = (int)N, a.d = (int)d, a.C = 1, a.st = st, a.cand = &w.cand;
     const int rc = launch_fused(a, FORM_SPLIT, kind);
     if (rc != NW_OK) return rc;
-    return launch_topk_candidates(w.cand.key, w.cand.row, idx, vals, B, w.n_stiles * w.kcp, k, st);
+    // (a window can leave a query fewer than k rows: the selection pads)
+    return launch_topk_candidates(w.cand.key, w.cand.row, idx, vals, B, w.n_stiles * w.kcp, k, st, window);
 }
 
 // ---- the same search over half-precision rows (nw_knn_f16): the candidate form of the persistent 256-query kernel

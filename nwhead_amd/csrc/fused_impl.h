@@ -33,12 +33,21 @@ int query_area_of_workspace(void* workspace, size_t workspace_bytes, int64_t B, 
 // its kc = min(k, tile rows) best scores, best first, ties in ascending bank-row order, as ordered_bits keys (0: empty slot)
 // and bank rows: key / row [b][st][j], j < kcp = kc rounded up to 4.  q_rows / q_scale / q_norm2: room for the split form
 // of the queries when the launch decision asks for the split launch.
+// win_lo / win_hi (nw_knn_window_f32; null: no window): per query the bank rows [lo, hi) that may be candidates, or,
+// with win_exclude, the rows that may not.  The kernel clamps both to [0, N] and never uses them as addresses.
 struct CandOut {
     unsigned* key;
     int* row;
     int k;
     float *q_rows, *q_scale, *q_norm2;
+    const int *win_lo, *win_hi;
+    int win_exclude;
 };
+constexpr int CAND_EXCLUDE = 1 << 8;   // the flag's place beside k (<= 32) in the kernel's k argument; set only with a window
+// nw_fused_kernel's OUT for the candidate output WITH a row window.  A template argument only (plans say OUT_CAND): the
+// kernels without a window are compiled from the text they always had, so nw_knn_f32's code and bits do not move.
+constexpr int OUT_CAND_WIN = 3;
+constexpr bool out_is_cand(int out) { return out == OUT_CAND || out == OUT_CAND_WIN; }
 __host__ __device__ inline int cand_slots(int k, int BS) { return ((k < BS ? k : BS) + 3) & ~3; }
 int tile_timer_start(hipStream_t st);          // diagnostics (nw_debug_tile_timing): -1 when disabled
 void tile_timer_stop(int slot, hipStream_t st);
@@ -94,10 +103,15 @@ __device__ __forceinline__ void load_tile_labels(const int64_t* __restrict__ sy,
 // candidate: in-lane maximum, maximum over the four lanes, the LOWEST tile row among the keys equal to it (in-lane first,
 // then over the lanes), knock that one element out.  Four rounds fill one slot in each of the column's four lanes, which
 // the whole wave then stores at once (16 bytes per query).
-template <int RS>
+// WIN: win_lo / win_hi hold a row window per query.  Keys of rows that the window does not admit become "no element" as
+// well; k then carries CAND_EXCLUDE.  A (query column, tile) pair that the window leaves whole skips the per-key
+// comparisons, as a tile that does not reach N does above, and a wave none of whose columns keeps a row stores its empty
+// slots without running the selection.
+template <int RS, bool WIN = false>
 __device__ __forceinline__ void tile_candidates(const float (&sc)[RS][4], unsigned* __restrict__ cand_key,
                                                 int* __restrict__ cand_row, int B, int N, int b, int s0, int g, int st,
-                                                int n_stiles, int k) {
+                                                int n_stiles, int k, const int* __restrict__ win_lo = nullptr,
+                                                const int* __restrict__ win_hi = nullptr) {
     constexpr int BS = 16 * RS;
     constexpr float LN2 = 0.693147180559945309417f;
     constexpr unsigned NOPOS = 1u << 20;
@@ -113,8 +127,36 @@ __device__ __forceinline__ void tile_candidates(const float (&sc)[RS][4], unsign
             for (int e = 0; e < 4; ++e)
                 if (s0 + 16 * r + 4 * g + e >= N) key[r][e] = 0u;
     }
+    bool dead = false;   // (window only) this query keeps no row of the tile
+    if constexpr (WIN) {
+        const bool exclude = (k & CAND_EXCLUDE) != 0;
+        k &= CAND_EXCLUDE - 1;
+        const int bb = b < B ? b : B - 1;
+        const int lo = min(max(win_lo[bb], 0), N), hi = min(max(win_hi[bb], 0), N);
+        const unsigned width = hi > lo ? (unsigned)(hi - lo) : 0u;
+        const int tile_end = s0 + BS < N ? s0 + BS : N;
+        const bool disjoint = width == 0u || hi <= s0 || lo >= tile_end;   // no row of the tile is in the window
+        const bool covered = lo <= s0 && hi >= tile_end;                    // every row of the tile is
+        dead = exclude ? covered : disjoint;
+        if (!(exclude ? disjoint : covered)) {
+            const int rel = s0 + 4 * g - lo;   // tile row t = 16r + e of this lane is bank row lo + rel + t
+#pragma unroll
+            for (int r = 0; r < RS; ++r)
+#pragma unroll
+                for (int e = 0; e < 4; ++e)
+                    if (((unsigned)(rel + 16 * r + e) < width) == exclude) key[r][e] = 0u;
+        }
+    }
     const int kc = k < BS ? k : BS, kcp = cand_slots(k, BS);
     const size_t base = ((size_t)b * n_stiles + st) * kcp + g;
+    if (WIN && __all(dead)) {
+        for (int j0 = 0; j0 < kcp; j0 += 4)
+            if (b < B) {
+                cand_key[base + j0] = 0u;
+                cand_row[base + j0] = s0;
+            }
+        return;
+    }
     for (int j0 = 0; j0 < kcp; j0 += 4) {
         unsigned okey = 0u;
         int orow = 0;
@@ -156,6 +198,7 @@ __device__ __forceinline__ void tile_candidates(const float (&sc)[RS][4], unsign
 // The epilogue of one tile: scores -> tile-local softmax statistics -> run sums -> workspace.
 // Called by all threads of the workgroup (loader waves only take part in the run-table copy).
 // OUT_CAND: `scores` / `ws_lab` are CandOut's key / row arrays, n_stiles and k come behind; nothing else is written.
+// OUT_CAND_WIN: `ws_nrun` / `ws_m` are CandOut's window arrays besides, loaded in tile_candidates.
 template <int RS, int KIND, int OUT, int MODE>
 __device__ __forceinline__ void fused_epilogue(
     f32x4 (&acc)[RS], const float* qn2, const float* sn2, const float* ssc, const int* runid,
@@ -200,7 +243,16 @@ __device__ __forceinline__ void fused_epilogue(
             for (int e = 0; e < 4; ++e) {
                 float K, Base;
                 SF::support(nn[e], ss[e], K, Base);
-                sc[r][e] = SF::finish(__builtin_fmaf(acc[r][e], K * Cq, Base + Bq));
+                if constexpr (OUT == OUT_CAND_WIN) {
+                    // The windowed search returns nw_knn_f32's scores bit for bit, and in `Base + Bq` those depend on
+                    // how the compiler contracts the sum in the kernels without a window: a fused multiply-add for every
+                    // element but the lane's last one of the tile, whose product shares a packed multiply with the
+                    // query's and is rounded on its own.  Spelled out here, where another contraction would be another
+                    // result (test_knn_window_gpu.py holds the two to each other at every tile height).
+                    sc[r][e] = SF::finish(__builtin_fmaf(acc[r][e], K * Cq, SF::base_plus(nn[e], Bq, r == RS - 1 && e == 3)));
+                } else {
+                    sc[r][e] = SF::finish(__builtin_fmaf(acc[r][e], K * Cq, Base + Bq));
+                }
             }
         }
         if (partial_tile) {
@@ -212,6 +264,11 @@ __device__ __forceinline__ void fused_epilogue(
         }
         if constexpr (OUT == OUT_CAND) {
             tile_candidates<RS>(sc, reinterpret_cast<unsigned*>(scores), ws_lab, B, N, b, s0, g, st, n_stiles, k);
+            return;
+        }
+        if constexpr (OUT == OUT_CAND_WIN) {
+            tile_candidates<RS, true>(sc, reinterpret_cast<unsigned*>(scores), ws_lab, B, N, b, s0, g, st, n_stiles, k, ws_nrun,
+                                      reinterpret_cast<const int*>(ws_m));
             return;
         }
 #pragma unroll
@@ -236,7 +293,7 @@ __device__ __forceinline__ void fused_epilogue(
         // tile-local max over the wave's 16 query columns: lanes i, i+16, i+32, i+48 hold one query
         mloc = group4_max(mloc);
     }
-    if constexpr (OUT == OUT_CAND) return;   // (the loader waves)
+    if constexpr (out_is_cand(OUT)) return;   // (the loader waves)
     NW_FSTAMP(3);
 
     // ---- 2^(u - mu) and its sums over the runs of equal labels, on the matrix cores:
@@ -341,6 +398,7 @@ __device__ __forceinline__ void fused_epilogue(
 
 
 // OUT_CAND: sy is not read, `scores` / `ws_lab` are CandOut's key / row arrays and `C` carries k.
+// OUT_CAND_WIN: `C` carries CAND_EXCLUDE besides and `ws_nrun` / `ws_m` are the row window's two arrays.
 template <int RS, int KIND, int OUT, int MODE>
 __global__ __launch_bounds__(TILE_THREADS, (RS <= 5 ? 4 : 2)) void nw_fused_kernel(
     const float* __restrict__ q, const float* __restrict__ s, const int64_t* __restrict__ sy,
@@ -386,7 +444,7 @@ __global__ __launch_bounds__(TILE_THREADS, (RS <= 5 ? 4 : 2)) void nw_fused_kern
         for (int t = tid; t < BQ; t += TILE_THREADS) qsc_s[t] = q_scale[min(q0 + t, B - 1)];
     }
     // ---- runs of equal consecutive labels inside this support tile (one wave)
-    if (OUT != OUT_CAND && wave == 0) {
+    if (!out_is_cand(OUT) && wave == 0) {
         int lab[3];
         load_tile_labels<BS>(sy, s0, N, C, lane, lab);
         run_scan_wave<BS>(lab, lane, runid, runlab, nrun_s);
@@ -463,10 +521,16 @@ int launch_fused_rs(const FusedArgs& a, const FusedPlan& p) {
         q = {qr, qn, qsc};
     }
     // OUT_CAND: CandOut's key / row arrays stand where the scores and the run labels go, k where the class count goes
-    // (nw_fused_kernel); ws is all null then.
+    // (nw_fused_kernel); ws is all null then, and the row window's arrays (read only) stand where the tile maxima and
+    // the run counts go.
     float* scores = cand ? reinterpret_cast<float*>(cand->key) : a.scores;
     int* lab = cand ? cand->row : ws.lab;
-    const int c_or_k = cand ? cand->k : a.C;
+    const bool window = cand && cand->win_lo && cand->win_hi;
+    const int c_or_k = cand ? (cand->k | (window && cand->win_exclude ? CAND_EXCLUDE : 0)) : a.C;
+    if (window) {
+        ws.nrun = const_cast<int*>(cand->win_lo);
+        ws.m = reinterpret_cast<float*>(const_cast<int*>(cand->win_hi));
+    }
 #define NW_TILE(OUT_, MODE_)                                                                                           \
     hipLaunchKernelGGL((nw_fused_kernel<RS, KIND, OUT_, MODE_>), dim3(p.grid), dim3(TILE_THREADS), p.lds_bytes, st, q.rows, \
                        a.s, a.sy, a.s_norm2, a.s_scale, q.norm2, q.scale, a.ls, scores, ws.m, ws.den, ws.nrun, lab, ws.num, \
@@ -484,7 +548,11 @@ int launch_fused_rs(const FusedArgs& a, const FusedPlan& p) {
         if constexpr (RS == 12) {
             return NW_ERR_UNSUPPORTED;
         } else {
-            if (p.mode == MODE_F16Q) NW_TILE(OUT_CAND, MODE_F16Q); else NW_TILE(OUT_CAND, MODE_F16);
+            if (window) {
+                if (p.mode == MODE_F16Q) NW_TILE(OUT_CAND_WIN, MODE_F16Q); else NW_TILE(OUT_CAND_WIN, MODE_F16);
+            } else {
+                if (p.mode == MODE_F16Q) NW_TILE(OUT_CAND, MODE_F16Q); else NW_TILE(OUT_CAND, MODE_F16);
+            }
             NW_CHECK_LAUNCH();
             return NW_OK;
         }

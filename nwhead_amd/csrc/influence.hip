@@ -142,6 +142,28 @@ __global__ __launch_bounds__(256) void nw_weights_from_scores_kernel(const float
     }
 }
 
+// The same finishing pass for k SELECTED supports per query (nw_influence_select_f32): vals are their raw scores, rows
+// their bank rows; one thread per (query, slot).  A row outside [0, N) is an empty slot: influence +0.0, label -1.
+__global__ __launch_bounds__(256) void nw_influence_select_kernel(
+    const float* __restrict__ vals, const int64_t* __restrict__ rows, const int64_t* __restrict__ sy,
+    const int64_t* __restrict__ qy, const float* __restrict__ logp, const float* __restrict__ lse, float* __restrict__ infl,
+    int64_t* __restrict__ labels, int64_t B, int64_t k, int64_t N, int64_t C) {
+    const int64_t x = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (x >= B * k) return;
+    const int64_t b = x / k, row = rows[x];
+    float v = 0.f;
+    int64_t y = -1;
+    if ((uint64_t)row < (uint64_t)N) {
+        const int64_t q = qy[b];
+        const bool ok = (uint64_t)q < (uint64_t)C;
+        const float p = expf(ok ? logp[b * C + q] : -INFINITY);
+        y = sy[row];
+        v = infl_one(p, expf(vals[x] - lse[b]), y == q);
+    }
+    infl[x] = v;
+    if (labels) labels[x] = y;
+}
+
 inline unsigned col_blocks(int64_t N) {
     int64_t gx = (N / 4 + 255) / 256;
     return (unsigned)(gx < 1 ? 1 : (gx > 64 ? 64 : gx));
@@ -175,7 +197,28 @@ int launch_influence(const float* probs_or_logp, const int64_t* qy, const float*
     NW_CHECK_LAUNCH();
     return NW_OK;
 }
+int launch_influence_select(const float* vals, const int64_t* rows, const int64_t* sy, const int64_t* qy, const float* logp,
+                            const float* lse, float* infl, int64_t* labels, int64_t B, int64_t k, int64_t N, int64_t C,
+                            hipStream_t st) {
+    const int64_t blocks = (B * k + 255) / 256;
+    if (blocks > 0x7fffffffLL) return NW_ERR_UNSUPPORTED;
+    hipLaunchKernelGGL(nw_influence_select_kernel, dim3((unsigned)blocks), dim3(256), 0, st, vals, rows, sy, qy, logp, lse, infl,
+                       labels, B, k, N, C);
+    NW_CHECK_LAUNCH();
+    return NW_OK;
+}
 }  // namespace nw
+
+extern "C" int nw_influence_select_f32(const float* vals, const int64_t* rows, const int64_t* sy, const int64_t* qy,
+                                       const float* out, const float* lse, float* infl_out, int64_t* label_out, int64_t B,
+                                       int64_t k, int64_t N, int64_t C, void* stream) {
+    if (B < 0 || k < 0 || N < 0 || C < 0) return NW_ERR_INVALID_ARG;
+    if (!vals || !rows || !sy || !qy || !out || !lse || !infl_out) return NW_ERR_INVALID_ARG;
+    if (k < 1 || k > 32 || B >= (1ll << 31)) return NW_ERR_UNSUPPORTED;
+    if (B == 0) return NW_OK;
+    return nw::launch_influence_select(vals, rows, sy, qy, out, lse, infl_out, label_out, B, k, N, C,
+                                       static_cast<hipStream_t>(stream));
+}
 
 extern "C" int nw_support_influence_f32(const float* probs, const int64_t* qy, const float* w,
                                         const int64_t* sy, float* infl, int64_t B, int64_t N,

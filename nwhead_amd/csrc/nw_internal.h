@@ -88,14 +88,22 @@ int knob(int id);
 // fused forward (fused.hip)
 int launch_topk(const float* scores, int64_t* idx, float* vals, int64_t B, int64_t N, int64_t k, hipStream_t st);  // topk.hip
 // the k best of M candidates per query: keys = ordered_bits of the scores (0: empty slot), rows = their bank rows; equal
-// keys must stand in ascending row order (topk.hip)
+// keys must stand in ascending row order (topk.hip).  pad_empty: a query may have fewer than k candidates; a selected empty
+// slot is written as row -1, value -inf, behind the valid ones
 int launch_topk_candidates(const unsigned* keys, const int* rows, int64_t* idx, float* vals, int64_t B, int64_t M, int64_t k,
-                           hipStream_t st);
+                           hipStream_t st, bool pad_empty = false);
 // fused.hip: nearest-neighbour search over a prepared bank without the (B,N) score matrix (nw_knn_f32)
 size_t knn_workspace_bytes(int64_t B, int64_t N, int64_t d, int64_t k);
+// row_lo / row_hi (both or neither): a row window per query, kept or (exclude) left out (nw_knn_window_f32); the result is
+// then padded with (-1, -inf)
 int launch_knn(const float* q, const float* s_split, const float* s_scale, const float* s_norm2, int64_t* idx, float* vals,
                void* workspace, size_t workspace_bytes, int64_t B, int64_t N, int64_t d, int64_t k, int kind,
-               const float* logit_scale_dev, hipStream_t st);
+               const float* logit_scale_dev, hipStream_t st, const int32_t* row_lo = nullptr, const int32_t* row_hi = nullptr,
+               int exclude = 0);
+// influence.hip: the influences of k selected supports per query (nw_influence_select_f32)
+int launch_influence_select(const float* vals, const int64_t* rows, const int64_t* sy, const int64_t* qy, const float* logp,
+                            const float* lse, float* infl, int64_t* labels, int64_t B, int64_t k, int64_t N, int64_t C,
+                            hipStream_t st);
 // ... and over half-precision rows, on the persistent 256-query kernel's candidate form (nw_knn_f16)
 size_t knn_half_workspace_bytes(int64_t B, int64_t N, int64_t d, int64_t k);
 int launch_knn_half(const float* q, const void* s_f16, const float* s_scale, const float* s_norm2, int64_t* idx, float* vals,
@@ -291,6 +299,15 @@ struct ScoreFactors {
         const float in = NORMALISED ? inv_norm(n2) : 1.f;
         Cq = qscale * in * (KIND == NW_SCORE_CLIP ? clip_scale : 1.f);
         Bq = DIST ? (NORMALISED ? n2 * in * in : n2) * (L2E * L2E) : 0.f;
+    }
+    // Base + Bq of support() / query() with its roundings spelled out instead of left to the compiler's contraction: one
+    // fused multiply-add, or (`separate`) the product and the sum rounded on their own.  For a kernel that has to return
+    // another kernel's bits (fused_impl.h, OUT_CAND_WIN).
+    static __device__ __forceinline__ float base_plus(float n2, float Bq, bool separate) {
+        if (!DIST) return 0.f;
+        const float in = NORMALISED ? inv_norm(n2) : 1.f;
+        const float t = NORMALISED ? n2 * in * in : n2;
+        return separate ? __fadd_rn(__fmul_rn(t, L2E * L2E), Bq) : __builtin_fmaf(t, L2E * L2E, Bq);
     }
     static __device__ __forceinline__ float finish(float x) { return DIST ? -fast_sqrt_pos(x) : x; }
     // the same without the sign for the distance kernels (u = -finish_abs(x)): the persistent epilogue

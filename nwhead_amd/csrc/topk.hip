@@ -21,6 +21,9 @@
 // ordered_bits keys (0: an empty slot) with a column -> bank-row map.  Equal keys stand in ascending bank-row order along
 // the row, so the same stable rule gives (score descending, bank row ascending); outputs are the mapped rows and the
 // floats of the keys.
+// PAD (nw_knn_window_f32): a row may hold fewer than k candidates.  Empty slots then count as elements below every score
+// (the threshold can fall to 0, and "equal to the threshold" picks as many of them as are missing), and a selected key
+// of 0 is emitted as row -1 and value -inf: the valid entries come first, in the usual order.
 #include "nw_internal.h"
 
 namespace nw {
@@ -34,7 +37,7 @@ constexpr int TK_U = 8;       // independent loads in flight per thread in the h
 // (seg a multiple of 64, 16 seg >= N) and keeps it in registers, element e of lane l = w seg + 64 e + l (coalesced
 // loads); the histogram passes and the ordered compaction (ranks from ballots inside the wave, wave bases from one
 // LDS round) all work from those registers.  REGS = 0 (N > 65536): the row is re-read in every pass.
-template <int REGS, bool MAPPED = false>
+template <int REGS, bool MAPPED = false, bool PAD = false>
 __global__ __launch_bounds__(TK_THREADS) void nw_topk_kernel(const float* __restrict__ scores,
                                                              int64_t* __restrict__ idx_out,
                                                              float* __restrict__ val_out, int N, int k,
@@ -49,8 +52,11 @@ __global__ __launch_bounds__(TK_THREADS) void nw_topk_kernel(const float* __rest
     const int tid = threadIdx.x, lane = tid & 63;
     const float* row = scores + (size_t)blockIdx.x * N;
     auto key_at = [&](int i) { return MAPPED ? reinterpret_cast<const unsigned*>(row)[i] : ordered_bits(row[i]); };
-    auto emit = [&](int slot, int ix) {
-        if (MAPPED) {
+    auto emit = [&](int slot, int ix, unsigned u) {   // u: the element's key (read by PAD only)
+        if (PAD && u == 0u) {
+            idx_out[(size_t)blockIdx.x * k + slot] = -1;
+            if (val_out) val_out[(size_t)blockIdx.x * k + slot] = -INFINITY;
+        } else if (MAPPED) {
             idx_out[(size_t)blockIdx.x * k + slot] = row_map[(size_t)blockIdx.x * N + ix];
             if (val_out) val_out[(size_t)blockIdx.x * k + slot] = ordered_bits_to_float(key_at(ix));
         } else {
@@ -100,7 +106,8 @@ __global__ __launch_bounds__(TK_THREADS) void nw_topk_kernel(const float* __rest
         if (CACHED) {
 #pragma unroll
             for (int e = 0; e < TK_REGS; ++e) {
-                count(ureg[e], ureg[e] != 0u);   // 0 is the image of no float (the smallest, -inf, is 0x007fffff): "not an element"
+                // (PAD: the row's empty slots count too, so that the k-th largest always exists)
+                count(ureg[e], PAD ? (64 * e < seg && wv * seg + 64 * e + lane < N) : ureg[e] != 0u);   // 0 is the image of no float (the smallest, -inf, is 0x007fffff): "not an element"
                 __builtin_amdgcn_sched_barrier(0);   // (one element at a time: hoisted ballots spill the scalar file)
             }
         } else {
@@ -267,7 +274,7 @@ __global__ __launch_bounds__(TK_THREADS) void nw_topk_kernel(const float* __rest
                         ix = io;
                     }
                 }
-            if (tid < k) emit(tid, ix);
+            if (tid < k) emit(tid, ix, u);
         }
         return;
     }
@@ -286,7 +293,7 @@ __global__ __launch_bounds__(TK_THREADS) void nw_topk_kernel(const float* __rest
             __syncthreads();
         }
     }
-    for (int x = tid; x < k; x += TK_THREADS) emit(x, cand_i[x]);
+    for (int x = tid; x < k; x += TK_THREADS) emit(x, cand_i[x], cand_u[x]);
 }
 
 }  // namespace
@@ -307,16 +314,20 @@ int launch_topk(const float* scores, int64_t* idx, float* vals, int64_t B, int64
 }
 
 int launch_topk_candidates(const unsigned* keys, const int* rows, int64_t* idx, float* vals, int64_t B, int64_t M, int64_t k,
-                           hipStream_t st) {
+                           hipStream_t st, bool pad_empty) {
     if (k < 1 || k > M || k > TK_MAXK || M >= (1ll << 31) || B >= (1ll << 31)) return NW_ERR_UNSUPPORTED;
     if (B == 0) return NW_OK;
     const float* kf = reinterpret_cast<const float*>(keys);
-#define NW_TOPK_MAPPED(R_) \
-    hipLaunchKernelGGL((nw_topk_kernel<R_, true>), dim3((unsigned)B), dim3(TK_THREADS), 0, st, kf, idx, vals, (int)M, (int)k, rows)
-    if (M <= 16 * TK_THREADS) NW_TOPK_MAPPED(16);
-    else if (M <= 32 * TK_THREADS) NW_TOPK_MAPPED(32);
-    else if (M <= 64 * TK_THREADS) NW_TOPK_MAPPED(64);
-    else NW_TOPK_MAPPED(0);
+#define NW_TOPK_MAPPED(R_)                                                                                                  \
+    if (pad_empty)                                                                                                          \
+        hipLaunchKernelGGL((nw_topk_kernel<R_, true, true>), dim3((unsigned)B), dim3(TK_THREADS), 0, st, kf, idx, vals, (int)M, \
+                           (int)k, rows);                                                                                   \
+    else                                                                                                                    \
+        hipLaunchKernelGGL((nw_topk_kernel<R_, true>), dim3((unsigned)B), dim3(TK_THREADS), 0, st, kf, idx, vals, (int)M, (int)k, rows)
+    if (M <= 16 * TK_THREADS) { NW_TOPK_MAPPED(16); }
+    else if (M <= 32 * TK_THREADS) { NW_TOPK_MAPPED(32); }
+    else if (M <= 64 * TK_THREADS) { NW_TOPK_MAPPED(64); }
+    else { NW_TOPK_MAPPED(0); }
 #undef NW_TOPK_MAPPED
     NW_CHECK_LAUNCH();
     return NW_OK;

@@ -286,6 +286,27 @@ class NWNet(nn.Module):
         order = torch.argsort(scores, dim=-1, descending=True)
         return order if k is None else order[:, :k]
 
+    def explain(self, x, y, k=None):
+        """Not in the reference (its util/metric.py:23-50 gives the influence of EVERY support, one query at a time): the k
+        most helpful and the k most harmful supports of every query under the labels `y`, with their influences, over
+        precompute()'s bank -- ops.nw_top_influence of the featurised queries over full_feat / full_y with the configured
+        kernel, no (B, N) matrix.  k defaults to n_neighbors (1 <= k <= 32).  Rows are rows of full_feat.  A sharded bank
+        (precompute_sharded() without precompute()) is not served: NWHipError."""
+        if not hasattr(self, 'full_feat'):
+            if getattr(self, 'sharded_bank', None) is not None:
+                raise ops.NWHipError("explain: a sharded bank is not served (the row windows of ops.nw_top_influence are rows "
+                                     "of one resident bank); call precompute()")
+            raise ops.NWHipError("explain needs the bank of precompute()")
+        if not isinstance(self.kernel, _ScoreModule):
+            raise ops.NWHipError("explain needs one of the built-in score kernels")
+        qfeat = self._eval_featurizer()(x).detach()
+        bank = getattr(self, 'full_cache', None)
+        if bank is not None and not bank.matches(self.full_feat):
+            bank = None
+        return ops.nw_top_influence(qfeat, self.full_feat, self.full_y, self.n_classes, y.to(qfeat.device),
+                                    self.n_neighbors if k is None else int(k), self.kernel.kind, self.kernel._logit_scale(),
+                                    support_cache=bank)
+
     # ------------------------------------------------------------------ training step
     def forward(self, x, y, metadata=None, support_data=None):
         sx, sy, sm = support_data if support_data is not None else self.support_train.get_support(y)

@@ -194,8 +194,38 @@ def knn_fused_pays(B, N):
     return 4 * int(B) * int(N) >= KNN_FUSED_MIN_SCORE_BYTES
 
 
+def _row_window(row_window, B, device):
+    """nw_knn's ``row_window`` as two contiguous (B,) int32 tensors."""
+    if not isinstance(row_window, (tuple, list)) or len(row_window) != 2:
+        raise ValueError("nw_knn: row_window is a pair (lo, hi) of (B,) integer tensors")
+    out = []
+    for t in row_window:
+        if not torch.is_tensor(t) or t.is_floating_point() or t.is_complex() or t.dtype == torch.bool:
+            raise ValueError("nw_knn: row_window holds integer tensors (bank rows)")
+        if t.shape != (B,):
+            raise ValueError(f"nw_knn: row_window tensors must be ({B},), one window per query; got {tuple(t.shape)}")
+        if t.device != device:
+            raise ValueError("nw_knn: row_window tensors must be on the queries' device")
+        out.append(t.detach().to(torch.int32).contiguous())
+    return out
+
+
+def _masked_topk(scores, k, lo, hi, exclude, return_values):
+    """nw_topk over the rows that a window admits, from the (B,N) score matrix; the slots past a query's valid count are
+    (-1, -inf)."""
+    N = scores.shape[1]
+    cols = torch.arange(N, device=scores.device)
+    keep = (cols >= lo[:, None]) & (cols < hi[:, None])
+    if exclude:
+        keep = ~keep
+    idx, vals = nw_topk(scores.masked_fill(~keep, float("-inf")), k, return_values=True)
+    empty = torch.arange(k, device=scores.device)[None, :] >= keep.sum(1)[:, None]
+    idx = idx.masked_fill(empty, -1)
+    return (idx, vals.masked_fill(empty, float("-inf"))) if return_values else idx
+
+
 def nw_knn(q, bank, k, kind="euclidean", logit_scale=None, return_values=False, support=None, rounded=False,
-           persistent_wgs=0):
+           persistent_wgs=0, row_window=None, exclude=False):
     """q:(B,d), bank: the SplitBank of an (N,d) support -> (B,k) int64 rows of the tensor the bank was prepared from, best
     score first, equal scores in ascending row order (with return_values: also their (B,k) scores).  The neighbour search
     of nwhead/utils.py:185-193 and nwhead/nw.py:245-249 over a resident bank WITHOUT the (B,N) score matrix: the tiles of
@@ -217,7 +247,16 @@ def nw_knn(q, bank, k, kind="euclidean", logit_scale=None, return_values=False, 
     bits from call to call and for every ``persistent_wgs`` (workgroups of the tile kernel, nw_fwd_opts.persistent_wgs).
     ``support`` is not needed.  Raises NWHipError when the bank cannot serve it: no packed rows (a bank of another
     precision, or a norms-only one of N <= 25), a class-sorted copy, k > 32, or queries whose width does not pad to the
-    bank's."""
+    bank's.
+
+    ``row_window=(lo, hi)`` (not the default, which it leaves as it is bit for bit): two (B,) integer tensors on the
+    device; query b is searched over the rows lo[b] <= row < hi[b] only, or with ``exclude=True`` over every other row
+    (lo >= hi: the empty window).  In a class-sorted bank that is "the supports of one class" / "of every other class",
+    the leave-one-out search (window [i, i+1), excluded) or one segment of a concatenated bank.  The result is the k best
+    rows the window admits, same scores and order as above; where it admits fewer than k, the remaining slots hold row -1
+    and value -inf.  Where the search without a window is fused, this one is (nw_knn_window_f32: the window is applied in
+    the tile epilogue); otherwise it masks the score matrix with torch ops and needs ``support``.  No window form of
+    ``rounded=True`` exists: NWHipError."""
     _need_hip(q, logit_scale, support)
     if not isinstance(bank, SplitBank):
         raise TypeError("nw_knn searches a prepared bank: pass ops.SplitBank(support)")
@@ -225,6 +264,10 @@ def nw_knn(q, bank, k, kind="euclidean", logit_scale=None, return_values=False, 
     q = _f32c(q)
     B = q.shape[0]
     k = int(k)
+    if row_window is not None:
+        if rounded:
+            raise NWHipError("nw_knn(rounded=True): the rounded search has no window form (row_window needs the fp32 rows)")
+        win_lo, win_hi = _row_window(row_window, B, q.device)
     if rounded:
         return _nw_knn_rounded(lib, q, bank, k, kind, logit_scale, return_values, persistent_wgs)
     N = bank.shape[0] if support is None else support.shape[-2]
@@ -239,7 +282,10 @@ def nw_knn(q, bank, k, kind="euclidean", logit_scale=None, return_values=False, 
         if support is None:
             raise ValueError("nw_knn: this search goes through the score matrix and needs `support`, the tensor the bank was "
                              "prepared from")
-        return nw_topk(nw_scores(q, support, kind, logit_scale, support_cache=bank), k, return_values=return_values)
+        scores = nw_scores(q, support, kind, logit_scale, support_cache=bank)
+        if row_window is not None:
+            return _masked_topk(scores, k, win_lo, win_hi, exclude, return_values)
+        return nw_topk(scores, k, return_values=return_values)
     q, dp = call.q, call.q.shape[1]
     ls = None if logit_scale is None else _f32c(logit_scale)
     idx = torch.empty(B, k, dtype=torch.int64, device=q.device)
@@ -251,8 +297,13 @@ def nw_knn(q, bank, k, kind="euclidean", logit_scale=None, return_values=False, 
     st = _stream(q)
     ws = _workspace(ws_bytes, q.device, st)
     with _OnDevice(q.device):
-        _lib.check(lib.nw_knn_f32(_ptr(q), _ptr(call.operand), _ptr(call.scale), _ptr(call.norm2), _ptr(idx), _ptr(vals),
-                                  _ptr(ws), ws_bytes, B, N, dp, k, _kind_id(kind), _ptr(ls), st), "nw_knn_f32")
+        if row_window is not None:
+            _lib.check(lib.nw_knn_window_f32(_ptr(q), _ptr(call.operand), _ptr(call.scale), _ptr(call.norm2), _ptr(win_lo),
+                                             _ptr(win_hi), int(bool(exclude)), _ptr(idx), _ptr(vals), _ptr(ws), ws_bytes, B, N,
+                                             dp, k, _kind_id(kind), _ptr(ls), st), "nw_knn_window_f32")
+        else:
+            _lib.check(lib.nw_knn_f32(_ptr(q), _ptr(call.operand), _ptr(call.scale), _ptr(call.norm2), _ptr(idx), _ptr(vals),
+                                      _ptr(ws), ws_bytes, B, N, dp, k, _kind_id(kind), _ptr(ls), st), "nw_knn_f32")
     return (idx, vals) if return_values else idx
 
 
@@ -1027,6 +1078,89 @@ def nw_head_influence(q, s, sy, n_classes, qy, kind="euclidean", logit_scale=Non
                                             _ptr(call.scale), _ptr(qyc), _ptr(out), None, _ptr(infl), _ptr(ws), ws_bytes, B, N,
                                             d, C, kid, _ptr(ls), call.opts, st), "nw_fwd_influence_f32")
     return out, infl
+
+
+TopInfluence = collections.namedtuple("TopInfluence", "out helpful_rows helpful_infl harmful_rows harmful_infl")
+INFLUENCE_SELECT_MAX_K = 32
+
+
+def _influence_select(lib, vals, rows, sy, qy, out, lse, want_labels=False):
+    """nw_influence_select_f32: the influences (and labels) of the (B,k) selected rows."""
+    B, k = rows.shape
+    infl = torch.empty(B, k, dtype=torch.float32, device=rows.device)
+    labels = torch.empty(B, k, dtype=torch.int64, device=rows.device) if want_labels else None
+    with _OnDevice(rows.device):
+        _lib.check(lib.nw_influence_select_f32(_ptr(vals), _ptr(rows), _ptr(sy), _ptr(qy), _ptr(out), _ptr(lse), _ptr(infl),
+                                               _ptr(labels), B, k, sy.shape[0], out.shape[1], _stream(rows)),
+                   "nw_influence_select_f32")
+    return (infl, labels) if want_labels else infl
+
+
+def nw_top_influence(q, s, sy, n_classes, qy, k, kind="euclidean", logit_scale=None, support_cache=None,
+                     return_labels=False):
+    """The k most helpful and the k most harmful supports of every query, with their influences (util/metric.py:23-50),
+    without the (B,N) influence matrix of nw_head_influence (no grad).  Returns TopInfluence(out (B,C) log-probabilities,
+    helpful_rows, helpful_infl, harmful_rows, harmful_infl), each of the last four (B,k); rows are rows of `s`.
+
+    infl[b,j] = log((p - p*w_bj) / (p - w_bj*[sy_j == qy_b])) grows with w over the supports of the query's own class
+    (and is >= 0 there) and falls with w over the others (log(1 - w) <= 0): the most helpful supports are the best-scoring
+    rows of class qy_b, the most harmful ones the best-scoring rows of the other classes.  With `sy` non-decreasing -- the
+    bank NWNet.precompute() builds -- a class is one row range, so the two lists are two windowed searches
+    (nw_knn(row_window=...), inside and excluded) and k influences each (nw_influence_select_f32), next to one forward for
+    `out` and the log-sum-exp.  helpful_infl is non-increasing along k and harmful_infl non-decreasing (most harmful
+    first); a list with fewer than k supports (a class of 3 rows) ends in row -1, influence 0.0.
+    1 <= k <= 32.  support_cache: the SplitBank of `s` (one is built for the call otherwise); an fp16 bank is served
+    through the fp32 rows, as every search over it is.  Unsorted `sy`: ValueError (nw_head_influence gives the matrix).
+    return_labels: returns (TopInfluence, (helpful_labels, harmful_labels)), the (B,k) labels of the selected rows (-1 in
+    an empty slot)."""
+    _need_hip(q, s, sy, qy, logit_scale)
+    kid = _kind_id(kind)
+    if kid == SCORE_KINDS["clip"] and logit_scale is None:
+        raise ValueError("clip kernel needs logit_scale")
+    if s.dim() != 2 or sy.dim() != 1 or sy.shape[0] != s.shape[0]:
+        raise ValueError("nw_top_influence takes a shared (N,d) support with (N,) labels")
+    k = int(k)
+    if not 1 <= k <= INFLUENCE_SELECT_MAX_K or k > s.shape[0]:
+        raise NWHipError(f"nw_top_influence: k = {k} outside [1, min(N = {s.shape[0]}, {INFLUENCE_SELECT_MAX_K})]")
+    syc = sy.detach().to(torch.int64).contiguous()
+    if syc.numel() > 1 and bool((syc[1:] < syc[:-1]).any()):
+        raise ValueError("nw_top_influence needs non-decreasing support labels (the class-sorted bank NWNet.precompute() "
+                         "builds): a class must be one row range.  nw_head_influence gives the whole (B,N) influence "
+                         "matrix for any label order")
+    if support_cache is not None and not support_cache.matches(s):
+        raise ValueError("support_cache was prepared from another support tensor")
+    bank = support_cache if support_cache is not None else SplitBank(s, labels=sy)
+    lib = _lib.load()
+    qc, sc = _f32c(q), _f32c(s)
+    B = qc.shape[0]
+    qyc = qy.detach().to(torch.int64).contiguous()
+    if qyc.shape != (B,):
+        raise ValueError("qy must be (B,)")
+    # one forward over the bank: the log-probabilities and the log-sum-exp of the scores (positional: the bank's rows as
+    # they stand)
+    call = _resolve(bank, qc, sc, sy, n_classes, positional=True)
+    fq, fs = call.q, call.s
+    N, C, dev = fs.shape[0], int(n_classes), qc.device
+    out = torch.empty(B, C, dtype=torch.float32, device=dev)
+    lse = torch.empty(B, dtype=torch.float32, device=dev)
+    ls = None if logit_scale is None else _f32c(logit_scale)
+    st = _stream(qc)
+    ws, ws_bytes = _fwd_workspace(lib, B, N, fq.shape[1], C, dev, st)
+    with _OnDevice(dev):
+        _lib.check(lib.nw_fwd_f32(_ptr(fq), _ptr(fs), _ptr(call.sy), _ptr(call.norm2), _ptr(call.operand), _ptr(call.scale),
+                                  _ptr(out), None, _ptr(lse), None, _ptr(ws), ws_bytes, B, N, fq.shape[1], C, kid, _ptr(ls),
+                                  0, 0, call.opts, st), "nw_fwd_f32")
+    # the rows of class qy_b, and the two searches
+    window = (torch.searchsorted(syc, qyc), torch.searchsorted(syc, qyc, right=True))
+    lists = []
+    for exclude in (False, True):
+        rows, vals = nw_knn(qc, bank, k, kind, logit_scale, return_values=True, support=sc, row_window=window,
+                            exclude=exclude)
+        lists.append((rows, _influence_select(lib, vals, rows, syc, qyc, out, lse, want_labels=return_labels)))
+    (hr, hi), (br, bi) = lists
+    if return_labels:
+        return TopInfluence(out, hr, hi[0], br, bi[0]), (hi[1], bi[1])
+    return TopInfluence(out, hr, hi, br, bi)
 
 
 def support_influence_idx(probs, qy, w, sy):
