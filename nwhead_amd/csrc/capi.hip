@@ -290,20 +290,29 @@ extern "C" int nw_scores_use_split(int64_t B, int64_t N, int64_t d) {
 }
 
 extern "C" size_t nw_knn_workspace_bytes(int64_t B, int64_t N, int64_t d, int64_t k) {
-    return nw::knn_workspace_bytes(B, N, d, k);
+    return nw::knn_workspace_bytes(nw::FORM_SPLIT, B, N, d, k);
+}
+
+extern "C" size_t nw_knn_f16_workspace_bytes(int64_t B, int64_t N, int64_t d, int64_t k) {
+    return nw::knn_workspace_bytes(nw::FORM_HALF, B, N, d, k);
+}
+
+// The argument rules of every neighbour-search entry, then the launch (B == 0 answers NW_OK there, after the shape rules)
+static int knn_checked(const nw::KnnCall& c) {
+    if (c.B < 0 || c.N < 0 || c.d < 0) return NW_ERR_INVALID_ARG;
+    if (bad_kind(c.kind)) return NW_ERR_UNSUPPORTED;
+    if (c.B > 0 && (!c.q || !c.s_rows || !c.s_scale || !c.s_norm2 || !c.idx)) return NW_ERR_INVALID_ARG;
+    if (c.kind == NW_SCORE_CLIP && !c.logit_scale_dev) return NW_ERR_INVALID_ARG;
+    if ((reinterpret_cast<uintptr_t>(c.s_rows) | reinterpret_cast<uintptr_t>(c.q) | reinterpret_cast<uintptr_t>(c.workspace)) & 15)
+        return NW_ERR_INVALID_ARG;
+    return nw::launch_knn(c);
 }
 
 extern "C" int nw_knn_f32(const float* q, const float* s_split, const float* s_scale, const float* s_norm2, int64_t* idx_out,
                           float* val_out, void* workspace, size_t workspace_bytes, int64_t B, int64_t N, int64_t d,
                           int64_t k, int kind, const float* logit_scale_dev, void* stream) {
-    if (B < 0 || N < 0 || d < 0) return NW_ERR_INVALID_ARG;
-    if (bad_kind(kind)) return NW_ERR_UNSUPPORTED;
-    if (B > 0 && (!q || !s_split || !s_scale || !s_norm2 || !idx_out)) return NW_ERR_INVALID_ARG;
-    if (kind == NW_SCORE_CLIP && !logit_scale_dev) return NW_ERR_INVALID_ARG;
-    if ((reinterpret_cast<uintptr_t>(s_split) | reinterpret_cast<uintptr_t>(q) | reinterpret_cast<uintptr_t>(workspace)) & 15)
-        return NW_ERR_INVALID_ARG;
-    return nw::launch_knn(q, s_split, s_scale, s_norm2, idx_out, val_out, workspace, workspace_bytes, B, N, d, k, kind,
-                          logit_scale_dev, static_cast<hipStream_t>(stream));
+    return knn_checked({q, s_split, s_scale, s_norm2, idx_out, val_out, workspace, workspace_bytes, B, N, d, k, kind,
+                        logit_scale_dev, static_cast<hipStream_t>(stream), nw::FORM_SPLIT, nullptr, nullptr, 0});
 }
 
 extern "C" int nw_knn_window_f32(const float* q, const float* s_split, const float* s_scale, const float* s_norm2,
@@ -311,32 +320,16 @@ extern "C" int nw_knn_window_f32(const float* q, const float* s_split, const flo
                                  void* workspace, size_t workspace_bytes, int64_t B, int64_t N, int64_t d, int64_t k, int kind,
                                  const float* logit_scale_dev, void* stream) {
     if (!row_lo || !row_hi) return NW_ERR_INVALID_ARG;   // (the search without a window is nw_knn_f32)
-    if (B < 0 || N < 0 || d < 0) return NW_ERR_INVALID_ARG;
-    if (bad_kind(kind)) return NW_ERR_UNSUPPORTED;
-    if (B > 0 && (!q || !s_split || !s_scale || !s_norm2 || !idx_out)) return NW_ERR_INVALID_ARG;
-    if (kind == NW_SCORE_CLIP && !logit_scale_dev) return NW_ERR_INVALID_ARG;
-    if ((reinterpret_cast<uintptr_t>(s_split) | reinterpret_cast<uintptr_t>(q) | reinterpret_cast<uintptr_t>(workspace)) & 15)
-        return NW_ERR_INVALID_ARG;
-    return nw::launch_knn(q, s_split, s_scale, s_norm2, idx_out, val_out, workspace, workspace_bytes, B, N, d, k, kind,
-                          logit_scale_dev, static_cast<hipStream_t>(stream), row_lo, row_hi, exclude);
-}
-
-extern "C" size_t nw_knn_f16_workspace_bytes(int64_t B, int64_t N, int64_t d, int64_t k) {
-    return nw::knn_half_workspace_bytes(B, N, d, k);
+    return knn_checked({q, s_split, s_scale, s_norm2, idx_out, val_out, workspace, workspace_bytes, B, N, d, k, kind,
+                        logit_scale_dev, static_cast<hipStream_t>(stream), nw::FORM_SPLIT, row_lo, row_hi, exclude});
 }
 
 extern "C" int nw_knn_f16(const float* q, const void* s_f16, const float* s_scale, const float* s_norm2, int64_t* idx_out,
                           float* val_out, void* workspace, size_t workspace_bytes, int64_t B, int64_t N, int64_t d, int64_t k,
                           int kind, const float* logit_scale_dev, const nw_fwd_opts* opts, void* stream) {
     OptsGuard opts_guard(opts);   // (persistent_wgs is read; a struct too short to hold it counts as no options)
-    if (B < 0 || N < 0 || d < 0) return NW_ERR_INVALID_ARG;
-    if (bad_kind(kind)) return NW_ERR_UNSUPPORTED;
-    if (B > 0 && (!q || !s_f16 || !s_scale || !s_norm2 || !idx_out)) return NW_ERR_INVALID_ARG;
-    if (kind == NW_SCORE_CLIP && !logit_scale_dev) return NW_ERR_INVALID_ARG;
-    if ((reinterpret_cast<uintptr_t>(s_f16) | reinterpret_cast<uintptr_t>(q) | reinterpret_cast<uintptr_t>(workspace)) & 15)
-        return NW_ERR_INVALID_ARG;
-    return nw::launch_knn_half(q, s_f16, s_scale, s_norm2, idx_out, val_out, workspace, workspace_bytes, B, N, d, k, kind,
-                               logit_scale_dev, static_cast<hipStream_t>(stream));
+    return knn_checked({q, s_f16, s_scale, s_norm2, idx_out, val_out, workspace, workspace_bytes, B, N, d, k, kind,
+                        logit_scale_dev, static_cast<hipStream_t>(stream), nw::FORM_HALF, nullptr, nullptr, 0});
 }
 
 extern "C" int nw_knn_merge_f32(const float* vals, const int32_t* rows, const int32_t* labels, int64_t G, int64_t B, int64_t kc,

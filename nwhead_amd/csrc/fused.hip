@@ -717,20 +717,23 @@ int launch_fused(const FusedArgs& a, int form, int kind) {
 #undef NW_KIND_CASE
 }
 
-// ---- nearest-neighbour search without the (B,N) score matrix (nw_knn_f32): the tile kernel's candidate output
-// (fused_impl.h, OUT_CAND) under the launch decision of the score-writing call, then the k best of every query's
-// candidates (topk.hip).
+// ---- nearest-neighbour search without the (B,N) score matrix (nw_knn_f32, nw_knn_window_f32, nw_knn_f16): the tile
+// kernel's candidate output under the launch decision of the score-writing call of the same operand form, then the k best
+// of every query's candidates (topk.hip).  FORM_SPLIT: nw_fused_kernel / the persistent kernel (fused_impl.h, OUT_CAND) on
+// the tile height of pick_rs.  FORM_HALF: the candidate form of the persistent 256-query kernel (fused_f16p12.h, CAND) on
+// tiles of 128 supports at every size; its query area holds the packed queries (B * d halves), half the width.
 namespace {
 struct KnnWs {
     CandOut cand;
     int64_t n_stiles;
     int kcp;
 };
-bool knn_shape_ok(int64_t B, int64_t N, int64_t d, int64_t k) {
-    return B >= 0 && N > 25 && d >= BK && d % BK == 0 && k >= 1 && k <= 32 && k <= N && B < (1 << 30) && N < (1 << 30) &&
-           d <= (1 << 20);   // (d: the loaders' tile-relative offsets, as in plan_fused)
+bool knn_shape_ok(int form, int64_t B, int64_t N, int64_t d, int64_t k) {
+    // (d: the loaders' tile-relative offsets, as in plan_fused; half-precision rows: whole 64-k stages)
+    const bool d_ok = form == FORM_HALF ? half_form_shape_ok(d) : form == FORM_SPLIT && d >= BK && d % BK == 0 && d <= (1 << 20);
+    return B >= 0 && N > 25 && d_ok && k >= 1 && k <= 32 && k <= N && B < (1 << 30) && N < (1 << 30);
 }
-// BS: the tile height of the score-writing call of this shape (16 * pick_rs on split operands)
+// BS: the tile height of the score-writing call of this shape; d: the width of a query-area row in floats
 size_t knn_layout(int64_t B, int64_t N, int64_t d, int64_t k, int BS, char* base, KnnWs* out) {
     KnnWs w = {};   // (no row window)
     w.n_stiles = (N + BS - 1) / BS;
@@ -751,15 +754,19 @@ size_t knn_layout(int64_t B, int64_t N, int64_t d, int64_t k, int BS, char* base
     if (out) *out = w;
     return off;
 }
+size_t knn_layout(int form, int64_t B, int64_t N, int64_t d, int64_t k, char* base, KnnWs* out) {
+    return knn_layout(B, N, form == FORM_HALF ? d / 2 : d, k, plan_tiles(B, N, d, form).BS, base, out);
+}
 }  // namespace
 
-// What the call needs, made non-decreasing in B, N and k: the tile height follows the shape (pick_rs), and a larger shape
-// on taller tiles can need LESS than a smaller one on short tiles -- so the answer is the largest need over the shapes
-// up to (B, N).  Only shapes below the large-grid rule of pick_rs (fewer than 1024 tiles of 128 rows: there the height
-// is fixed and the need grows with the shape) have to be visited, one N per 16 rows and one B per 64 queries.  (The height
-// rule alone is asked here, ~10^5 times for a large shape: no plans.)
-size_t knn_workspace_bytes(int64_t B, int64_t N, int64_t d, int64_t k) {
-    if (!knn_shape_ok(B, N, d, k) || B == 0) return 0;
+// What the call needs.  Half-precision rows: the layout of the shape.  Split rows: made non-decreasing in B, N and k: the
+// tile height follows the shape (pick_rs), and a larger shape on taller tiles can need LESS than a smaller one on short
+// tiles -- so the answer is the largest need over the shapes up to (B, N).  Only shapes below the large-grid rule of pick_rs
+// (fewer than 1024 tiles of 128 rows: there the height is fixed and the need grows with the shape) have to be visited, one N
+// per 16 rows and one B per 64 queries.  (The height rule alone is asked here, ~10^5 times for a large shape: no plans.)
+size_t knn_workspace_bytes(int form, int64_t B, int64_t N, int64_t d, int64_t k) {
+    if (!knn_shape_ok(form, B, N, d, k) || B == 0) return 0;
+    if (form == FORM_HALF) return knn_layout(form, B, N, d, k, nullptr, nullptr);
     if (pick_rs(B, N, d, true) > 10) return 0;   // (the tile_rs knob at 12: no candidate form, plan_fused refuses)
     size_t need = knn_layout(B, N, d, k, 16 * pick_rs(B, N, d, true), nullptr, nullptr);
     const int64_t nq = (B + BQ - 1) / BQ;
@@ -775,53 +782,24 @@ size_t knn_workspace_bytes(int64_t B, int64_t N, int64_t d, int64_t k) {
     return need;
 }
 
-int launch_knn(const float* q, const float* s_split, const float* s_scale, const float* s_norm2, int64_t* idx, float* vals,
-               void* workspace, size_t workspace_bytes, int64_t B, int64_t N, int64_t d, int64_t k, int kind, const float* ls,
-               hipStream_t st, const int32_t* row_lo, const int32_t* row_hi, int exclude) {
-    if (!knn_shape_ok(B, N, d, k)) return NW_ERR_UNSUPPORTED;
-    if (B == 0) return NW_OK;
-    const bool window = row_lo != nullptr && row_hi != nullptr;
+int launch_knn(const KnnCall& c) {
+    const bool window = c.row_lo != nullptr && c.row_hi != nullptr;
+    if (!knn_shape_ok(c.form, c.B, c.N, c.d, c.k)) return NW_ERR_UNSUPPORTED;
+    if (window && c.form == FORM_HALF) return NW_ERR_UNSUPPORTED;   // (the 256-query kernel has no windowed candidate form)
+    if (c.B == 0) return NW_OK;
     KnnWs w;
-    const size_t need = knn_layout(B, N, d, k, plan_tiles(B, N, d, FORM_SPLIT).BS, static_cast<char*>(workspace), &w);
-    if (!workspace || workspace_bytes < need) return NW_ERR_WORKSPACE;
+    const size_t need = knn_layout(c.form, c.B, c.N, c.d, c.k, static_cast<char*>(c.workspace), &w);
+    if (!c.workspace || c.workspace_bytes < need) return NW_ERR_WORKSPACE;
     if (w.n_stiles * w.kcp >= (1ll << 31)) return NW_ERR_UNSUPPORTED;
-    if (window) w.cand.win_lo = row_lo, w.cand.win_hi = row_hi, w.cand.win_exclude = exclude != 0;
-    FusedArgs a = {};   // no labels, no outputs, no workspace but the CandOut
-    a.q = q, a.s = s_split, a.s_norm2 = s_norm2, a.s_scale = s_scale, a.ls = ls;
-    a.B = (int)B, a.N = (int)N, a.d = (int)d, a.C = 1, a.st = st, a.cand = &w.cand;
-    const int rc = launch_fused(a, FORM_SPLIT, kind);
+    if (window) w.cand.win_lo = c.row_lo, w.cand.win_hi = c.row_hi, w.cand.win_exclude = c.exclude != 0;
+    FusedArgs a = {};   // no labels (sy is null: no run tables), no outputs, no workspace but the CandOut
+    a.q = c.q, a.s = static_cast<const float*>(c.s_rows), a.s_norm2 = c.s_norm2, a.s_scale = c.s_scale;
+    a.ls = c.logit_scale_dev;
+    a.B = (int)c.B, a.N = (int)c.N, a.d = (int)c.d, a.C = 1, a.st = c.st, a.cand = &w.cand;
+    const int rc = launch_fused(a, c.form, c.kind);
     if (rc != NW_OK) return rc;
     // (a window can leave a query fewer than k rows: the selection pads)
-    return launch_topk_candidates(w.cand.key, w.cand.row, idx, vals, B, w.n_stiles * w.kcp, k, st, window);
-}
-
-// ---- the same search over half-precision rows (nw_knn_f16): the candidate form of the persistent 256-query kernel
-// (fused_f16p12.h, CAND) on tiles of 128 supports at every size, so the layout depends on the shape alone.  The query area
-// holds the packed queries (B * d halves) with their scales and norms.
-bool knn_half_shape_ok(int64_t B, int64_t N, int64_t d, int64_t k) {
-    return B >= 0 && N > 25 && half_form_shape_ok(d) && k >= 1 && k <= 32 && k <= N && B < (1 << 30) && N < (1 << 30);
-}
-
-size_t knn_half_workspace_bytes(int64_t B, int64_t N, int64_t d, int64_t k) {
-    if (!knn_half_shape_ok(B, N, d, k) || B == 0) return 0;
-    return knn_layout(B, N, d / 2, k, BANK_BS, nullptr, nullptr);
-}
-
-int launch_knn_half(const float* q, const void* s_f16, const float* s_scale, const float* s_norm2, int64_t* idx, float* vals,
-                    void* workspace, size_t workspace_bytes, int64_t B, int64_t N, int64_t d, int64_t k, int kind,
-                    const float* ls, hipStream_t st) {
-    if (!knn_half_shape_ok(B, N, d, k)) return NW_ERR_UNSUPPORTED;
-    if (B == 0) return NW_OK;
-    KnnWs w;
-    const size_t need = knn_layout(B, N, d / 2, k, BANK_BS, static_cast<char*>(workspace), &w);
-    if (!workspace || workspace_bytes < need) return NW_ERR_WORKSPACE;
-    if (w.n_stiles * w.kcp >= (1ll << 31)) return NW_ERR_UNSUPPORTED;
-    FusedArgs a = {};   // no labels (sy is null: no run tables), no outputs, no workspace but the CandOut
-    a.q = q, a.s = static_cast<const float*>(s_f16), a.s_norm2 = s_norm2, a.s_scale = s_scale, a.ls = ls;
-    a.B = (int)B, a.N = (int)N, a.d = (int)d, a.C = 1, a.st = st, a.cand = &w.cand;
-    const int rc = launch_fused(a, FORM_HALF, kind);
-    if (rc != NW_OK) return rc;
-    return launch_topk_candidates(w.cand.key, w.cand.row, idx, vals, B, w.n_stiles * w.kcp, k, st);
+    return launch_topk_candidates(w.cand.key, w.cand.row, c.idx, c.vals, c.B, w.n_stiles * w.kcp, c.k, c.st, window);
 }
 
 }  // namespace nw

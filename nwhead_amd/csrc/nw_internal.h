@@ -92,23 +92,32 @@ int launch_topk(const float* scores, int64_t* idx, float* vals, int64_t B, int64
 // slot is written as row -1, value -inf, behind the valid ones
 int launch_topk_candidates(const unsigned* keys, const int* rows, int64_t* idx, float* vals, int64_t B, int64_t M, int64_t k,
                            hipStream_t st, bool pad_empty = false);
-// fused.hip: nearest-neighbour search over a prepared bank without the (B,N) score matrix (nw_knn_f32)
-size_t knn_workspace_bytes(int64_t B, int64_t N, int64_t d, int64_t k);
-// row_lo / row_hi (both or neither): a row window per query, kept or (exclude) left out (nw_knn_window_f32); the result is
-// then padded with (-1, -inf)
-int launch_knn(const float* q, const float* s_split, const float* s_scale, const float* s_norm2, int64_t* idx, float* vals,
-               void* workspace, size_t workspace_bytes, int64_t B, int64_t N, int64_t d, int64_t k, int kind,
-               const float* logit_scale_dev, hipStream_t st, const int32_t* row_lo = nullptr, const int32_t* row_hi = nullptr,
-               int exclude = 0);
+// fused.hip: nearest-neighbour search over a prepared bank without the (B,N) score matrix (nw_knn_f32, nw_knn_window_f32,
+// nw_knn_f16): one record for every entry point
+struct KnnCall {
+    const float* q;
+    const void* s_rows;            // the bank's rows in `form`: split rows, or the fp16 rows of nw_pack_rows_f16
+    const float *s_scale, *s_norm2;
+    int64_t* idx;
+    float* vals;
+    void* workspace;
+    size_t workspace_bytes;
+    int64_t B, N, d, k;
+    int kind;
+    const float* logit_scale_dev;
+    hipStream_t st;
+    int form;                      // FORM_SPLIT or FORM_HALF (fused_plan.h)
+    // both or neither: a row window per query, kept or (exclude) left out; the result is then padded with (-1, -inf).
+    // FORM_SPLIT only
+    const int32_t *row_lo, *row_hi;
+    int exclude;
+};
+size_t knn_workspace_bytes(int form, int64_t B, int64_t N, int64_t d, int64_t k);
+int launch_knn(const KnnCall& c);
 // influence.hip: the influences of k selected supports per query (nw_influence_select_f32)
 int launch_influence_select(const float* vals, const int64_t* rows, const int64_t* sy, const int64_t* qy, const float* logp,
                             const float* lse, float* infl, int64_t* labels, int64_t B, int64_t k, int64_t N, int64_t C,
                             hipStream_t st);
-// ... and over half-precision rows, on the persistent 256-query kernel's candidate form (nw_knn_f16)
-size_t knn_half_workspace_bytes(int64_t B, int64_t N, int64_t d, int64_t k);
-int launch_knn_half(const float* q, const void* s_f16, const float* s_scale, const float* s_norm2, int64_t* idx, float* vals,
-                    void* workspace, size_t workspace_bytes, int64_t B, int64_t N, int64_t d, int64_t k, int kind,
-                    const float* logit_scale_dev, hipStream_t st);
 // knn_merge.hip: the k best of G sorted per-shard candidate lists per query, and the per-query k-NN head over them
 // (nw_knn_merge_f32)
 int launch_knn_merge(const float* vals, const int* rows, const int* labels, int64_t G, int64_t B, int64_t kc, int64_t stride_g,

@@ -275,13 +275,16 @@ class NWNet(nn.Module):
             if not 1 <= k <= N:
                 raise ops.NWHipError(f"get_neighbors: k = {k} outside [1, N = {N}]")
             bank = getattr(self, 'full_cache', None)
-            if self.search_precision == "fp16" and isinstance(self.kernel, _ScoreModule) and bank is not None and qfeat.is_cuda \
-                    and self.full_feat.is_cuda and bank.matches(self.full_feat) \
-                    and ops.knn_rounded_refusal(bank, k, qfeat.shape[1]) is None:
-                return ops.nw_knn(qfeat, bank, k, self.kernel.kind, self.kernel._logit_scale(), rounded=True)
-            if k <= 32 and N % 4 == 0 and isinstance(self.kernel, _ScoreModule) and bank is not None and qfeat.is_cuda \
-                    and self.full_feat.is_cuda and bank.matches(self.full_feat) and ops.knn_fused_pays(qfeat.shape[0], N):
-                return ops.nw_knn(qfeat, bank, k, self.kernel.kind, self.kernel._logit_scale(), support=self.full_feat)
+            if isinstance(self.kernel, _ScoreModule) and bank is not None and qfeat.is_cuda and self.full_feat.is_cuda \
+                    and bank.matches(self.full_feat):
+                # size_gate: below it the (B, N) score matrix and the argsort below are the cheaper route
+                # need_n4: for other N the lines below rank the fp32 scores kernel's scores: not nw_knn's to the last bit
+                route = ops.knn_route_for(bank, qfeat.shape[1], qfeat.shape[0], k, True, search_precision=self.search_precision,
+                                          size_gate=True, need_n4=True)
+                if route == "rounded":
+                    return ops.nw_knn(qfeat, bank, k, self.kernel.kind, self.kernel._logit_scale(), rounded=True)
+                if route in ("fused", "matrix"):    # nw_knn's; None: the gates keep the search for the lines below
+                    return ops.nw_knn(qfeat, bank, k, self.kernel.kind, self.kernel._logit_scale(), support=self.full_feat)
         scores = self.kernel(qfeat, self.full_feat.to(qfeat.device))
         order = torch.argsort(scores, dim=-1, descending=True)
         return order if k is None else order[:, :k]

@@ -126,15 +126,16 @@ class KNN:
     def indices(self, x):
         data = self.data.to(x.device)
         k = min(self.n_neighbors, data.shape[0])
-        if (self.search_precision == "fp16" and self.bank is not None and data.is_cuda and data.dim() == 2
-                and self.bank.matches(data) and ops.knn_rounded_refusal(self.bank, k, x.shape[1]) is None):
-            return ops.nw_knn(x, self.bank, k, "euclidean", rounded=True)   # the caller asked for this route: no size gate
-        if (self.bank is not None and data.is_cuda and 1 <= k <= 32 and data.dim() == 2 and data.shape[0] % 4 == 0
-                and ops.knn_fused_pays(x.shape[0], data.shape[0])):
-            # no (B, N) score matrix: the tiles of the score kernel select (ops.nw_knn).  N % 4 == 0: the lines below then
-            # rank the bank route's scores, whose rows nw_knn returns bit for bit; for other N they rank the fp32 scores
-            # kernel's, which the fused search does not reproduce to the last bit.
-            return ops.nw_knn(x, self.bank, k, "euclidean", support=data)
+        if self.bank is not None and data.is_cuda and data.dim() == 2 and self.bank.matches(data):
+            # size_gate: below it the (B, N) score matrix is the cheaper route
+            # need_n4: at N % 4 == 0 the lines below rank the bank route's scores, whose rows nw_knn returns bit for bit; for
+            # other N they rank the fp32 scores kernel's, which the fused search does not reproduce to the last bit
+            route = ops.knn_route_for(self.bank, x.shape[1], x.shape[0], k, True, search_precision=self.search_precision,
+                                      size_gate=True, need_n4=True)
+            if route == "rounded":
+                return ops.nw_knn(x, self.bank, k, "euclidean", rounded=True)
+            if route in ("fused", "matrix"):    # nw_knn's; None: the gates keep the search for the lines below
+                return ops.nw_knn(x, self.bank, k, "euclidean", support=data)
         scores = ops.nw_scores(x, data, "euclidean", support_cache=self.bank if data.is_cuda else None)
         k = min(self.n_neighbors, scores.shape[1])
         # descending score == ascending distance; ties resolve like a stable argsort would

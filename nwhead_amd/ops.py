@@ -260,93 +260,115 @@ def nw_knn(q, bank, k, kind="euclidean", logit_scale=None, return_values=False, 
     _need_hip(q, logit_scale, support)
     if not isinstance(bank, SplitBank):
         raise TypeError("nw_knn searches a prepared bank: pass ops.SplitBank(support)")
-    lib = _lib.load()
     q = _f32c(q)
     B = q.shape[0]
     k = int(k)
+    window = None
     if row_window is not None:
         if rounded:
             raise NWHipError("nw_knn(rounded=True): the rounded search has no window form (row_window needs the fp32 rows)")
-        win_lo, win_hi = _row_window(row_window, B, q.device)
-    if rounded:
-        return _nw_knn_rounded(lib, q, bank, k, kind, logit_scale, return_values, persistent_wgs)
-    N = bank.shape[0] if support is None else support.shape[-2]
-    if k < 1 or k > N:
+        window = (*_row_window(row_window, B, q.device), exclude)
+    N = bank.shape[0] if support is None or rounded else support.shape[-2]
+    if not rounded and (k < 1 or k > N):
         raise NWHipError(f"nw_knn: k = {k} outside [1, N = {N}] (nw_topk refuses it too)")
-    # (nw_scores_use_split: the library's own rule for which tile kernel the bank-route score call runs, at the bank's width)
-    fused = (k <= 32 and N > 25 and B > 0 and N == bank.shape[0]
-             and (support is None or (support.dim() == 2 and bank.matches(support)))
-             and (_lib.force_split() or bool(lib.nw_scores_use_split(B, N, bank.shape[1]))))
-    call = _resolve_scores(bank, q) if fused else None
-    if call is None:
+    matches = None if support is None or rounded else support.dim() == 2 and N == bank.shape[0] and bank.matches(support)
+    route = knn_route_for(bank, q.shape[1], B, k, matches, search_precision="fp16" if rounded else "fp32")
+    if rounded and route != "rounded":
+        raise NWHipError(f"nw_knn(rounded=True): {knn_rounded_refusal(bank, k, q.shape[1])}")
+    if route == "matrix":
         if support is None:
             raise ValueError("nw_knn: this search goes through the score matrix and needs `support`, the tensor the bank was "
                              "prepared from")
         scores = nw_scores(q, support, kind, logit_scale, support_cache=bank)
-        if row_window is not None:
-            return _masked_topk(scores, k, win_lo, win_hi, exclude, return_values)
+        if window is not None:
+            return _masked_topk(scores, k, *window, return_values)
         return nw_topk(scores, k, return_values=return_values)
-    q, dp = call.q, call.q.shape[1]
-    ls = None if logit_scale is None else _f32c(logit_scale)
-    idx = torch.empty(B, k, dtype=torch.int64, device=q.device)
-    vals = torch.empty(B, k, dtype=torch.float32, device=q.device) if return_values else None
-    key = ("knn", B, N, dp, k)
-    ws_bytes = _WS_BYTES.get(key)
-    if ws_bytes is None:
-        ws_bytes = _WS_BYTES[key] = lib.nw_knn_workspace_bytes(B, N, dp, k)
-    st = _stream(q)
-    ws = _workspace(ws_bytes, q.device, st)
-    with _OnDevice(q.device):
-        if row_window is not None:
-            _lib.check(lib.nw_knn_window_f32(_ptr(q), _ptr(call.operand), _ptr(call.scale), _ptr(call.norm2), _ptr(win_lo),
-                                             _ptr(win_hi), int(bool(exclude)), _ptr(idx), _ptr(vals), _ptr(ws), ws_bytes, B, N,
-                                             dp, k, _kind_id(kind), _ptr(ls), st), "nw_knn_window_f32")
-        else:
-            _lib.check(lib.nw_knn_f32(_ptr(q), _ptr(call.operand), _ptr(call.scale), _ptr(call.norm2), _ptr(idx), _ptr(vals),
-                                      _ptr(ws), ws_bytes, B, N, dp, k, _kind_id(kind), _ptr(ls), st), "nw_knn_f32")
-    return (idx, vals) if return_values else idx
+    call = _resolve_scores(bank, q, rounded=rounded, persistent_wgs=persistent_wgs)
+    return _knn_launch(call, N, k, kind, logit_scale, return_values, rounded, window)
 
 
-def knn_rounded_refusal(bank, k, width=None):
-    """Why ``nw_knn(..., rounded=True)`` cannot search ``bank`` for k neighbours (queries of ``width`` columns), or None."""
-    N = bank.shape[0]
-    if bank.precision != "fp16":
-        return "the bank holds no fp16-packed rows (prepare it with precision='fp16')"
-    if bank.packed is None:
-        return f"a norms-only bank (N = {N} <= 25 rows: no tile kernel takes it)"
-    if bank.sorted_rows is not None:
-        return "the bank holds a class-sorted copy (it was built from unsorted labels): its rows are not the caller's"
-    if k < 1 or k > N:
-        return f"k = {k} outside [1, N = {N}]"
-    if k > 32:
-        return f"k = {k} > 32 (the tile epilogue's selection holds 32 keys per query)"
-    if width is not None and width + bank.pad != bank.shape[1]:
-        return f"queries of width {width} do not pad to the bank's width {bank.shape[1]} (pad {bank.pad})"
-    return None
-
-
-def _nw_knn_rounded(lib, q, bank, k, kind, logit_scale, return_values, persistent_wgs):
-    why = knn_rounded_refusal(bank, k, q.shape[1])
-    call = None if why else _resolve_scores(bank, q, rounded=True, persistent_wgs=persistent_wgs)
-    if call is None:
-        raise NWHipError(f"nw_knn(rounded=True): {why or 'the bank cannot serve the search'}")
-    q, dp = call.q, call.q.shape[1]
-    B, N = q.shape[0], bank.shape[0]
+def _knn_launch(call, N, k, kind, logit_scale, return_values, rounded, window):
+    """The launch of a fused search over the operands of ``call`` (_resolve_scores): nw_knn_f16 (``rounded``),
+    nw_knn_window_f32 (``window`` = (lo, hi, exclude)) or nw_knn_f32."""
+    lib, q, (B, dp) = _lib.load(), call.q, call.q.shape
     ls = None if logit_scale is None else _f32c(logit_scale)
     idx = torch.empty(B, k, dtype=torch.int64, device=q.device)
     vals = torch.empty(B, k, dtype=torch.float32, device=q.device) if return_values else None
     if B == 0:
         return (idx, vals) if return_values else idx
-    key = ("knn_f16", B, N, dp, k)
+    sizer = "nw_knn_f16_workspace_bytes" if rounded else "nw_knn_workspace_bytes"
+    key = (sizer, B, N, dp, k)
     ws_bytes = _WS_BYTES.get(key)
     if ws_bytes is None:
-        ws_bytes = _WS_BYTES[key] = lib.nw_knn_f16_workspace_bytes(B, N, dp, k)
+        ws_bytes = _WS_BYTES[key] = getattr(lib, sizer)(B, N, dp, k)
     st = _stream(q)
     ws = _workspace(ws_bytes, q.device, st)
+    operands = (_ptr(q), _ptr(call.operand), _ptr(call.scale), _ptr(call.norm2))
+    rest = (_ptr(idx), _ptr(vals), _ptr(ws), ws_bytes, B, N, dp, k, _kind_id(kind), _ptr(ls))
     with _OnDevice(q.device):
-        _lib.check(lib.nw_knn_f16(_ptr(q), _ptr(call.operand), _ptr(call.scale), _ptr(call.norm2), _ptr(idx), _ptr(vals),
-                                  _ptr(ws), ws_bytes, B, N, dp, k, _kind_id(kind), _ptr(ls), call.opts, st), "nw_knn_f16")
+        if rounded:
+            _lib.check(lib.nw_knn_f16(*operands, *rest, call.opts, st), "nw_knn_f16")
+        elif window is not None:
+            lo, hi, exclude = window
+            _lib.check(lib.nw_knn_window_f32(*operands, _ptr(lo), _ptr(hi), int(bool(exclude)), *rest, st), "nw_knn_window_f32")
+        else:
+            _lib.check(lib.nw_knn_f32(*operands, *rest, st), "nw_knn_f32")
     return (idx, vals) if return_values else idx
+
+
+def _rounded_refusal(precision, packed, sorted_copy, shape, pad, k, width):
+    N = shape[0]
+    if precision != "fp16":
+        return "the bank holds no fp16-packed rows (prepare it with precision='fp16')"
+    if not packed:
+        return f"a norms-only bank (N = {N} <= 25 rows: no tile kernel takes it)"
+    if sorted_copy:
+        return "the bank holds a class-sorted copy (it was built from unsorted labels): its rows are not the caller's"
+    if k < 1 or k > N:
+        return f"k = {k} outside [1, N = {N}]"
+    if k > 32:
+        return f"k = {k} > 32 (the tile epilogue's selection holds 32 keys per query)"
+    if width is not None and width + pad != shape[1]:
+        return f"queries of width {width} do not pad to the bank's width {shape[1]} (pad {pad})"
+    return None
+
+
+def knn_rounded_refusal(bank, k, width=None):
+    """Why ``nw_knn(..., rounded=True)`` cannot search ``bank`` for k neighbours (queries of ``width`` columns), or None."""
+    return _rounded_refusal(bank.precision, bank.packed is not None, bank.sorted_rows is not None, bank.shape, bank.pad, k, width)
+
+
+def knn_route(*, precision, packed, split, sorted_copy, shape, pad, width, B, k, matches=None, search_precision="fp32",
+              size_gate=False, need_n4=False, use_split=True):
+    """Which search serves B queries of ``width`` columns for their k nearest rows of a prepared bank: the one rule of nw_knn
+    and of the callers that choose between it and a search of their own (KNN.indices, NWNet.get_neighbors; a ShardedBank
+    chooses nothing, it always calls nw_knn), over plain facts (no device, no bank object).  The bank: ``precision``,
+    whether it holds ``packed`` (fp16) rows, ``split`` rows, a class-sorted copy, its ``shape`` (N, padded width) and ``pad``.
+    ``matches``: whether the support tensor the caller names is the bank's (None: it names none).  ``use_split``: what
+    nw_scores_use_split / force_split answer for the shape.  The caller's policy: ``search_precision``; ``size_gate``: k > 32
+    and score matrices below KNN_FUSED_MIN_SCORE_BYTES stay the caller's own; ``need_n4``: so do banks with N % 4 != 0.
+    -> "rounded" (nw_knn(rounded=True): nw_knn_f16), "fused" (nw_knn: nw_knn_f32 / nw_knn_window_f32), "matrix" (nw_knn ranks
+    the bank route's score matrix with nw_topk) or None (the caller's gates keep the search: its own score matrix)."""
+    N = shape[0]
+    if search_precision == "fp16" and _rounded_refusal(precision, packed, sorted_copy, shape, pad, k, width) is None:
+        return "rounded"
+    if (size_gate and not (1 <= k <= 32 and knn_fused_pays(B, N))) or (need_n4 and N % 4):
+        return None
+    # the split rows are the caller's, the queries pad to them, and the scores nw_topk would rank are the split-row kernel's
+    fused = (split and not sorted_copy and width + pad == shape[1] and matches is not False and 1 <= k <= 32 and N > 25
+             and B > 0 and use_split)
+    return "fused" if fused else "matrix"
+
+
+def knn_route_for(bank, width, B, k, matches=None, **policy):
+    """knn_route over the facts of ``bank`` (a SplitBank) and the library's size rule at its shape -- which is asked only
+    where it decides: it turns "fused" into "matrix" and changes no other answer (a library call per search otherwise)."""
+    route = knn_route(precision=bank.precision, packed=bank.packed is not None, split=bank.split is not None,
+                      sorted_copy=bank.sorted_rows is not None, shape=bank.shape, pad=bank.pad, width=width, B=B, k=k,
+                      matches=matches, **policy)
+    if route == "fused" and not (_lib.force_split() or _lib.load().nw_scores_use_split(B, *bank.shape)):
+        return "matrix"
+    return route
 
 
 KNN_MERGE_MAX_K, KNN_MERGE_MAX_SHARDS = 32, 64

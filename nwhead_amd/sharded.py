@@ -122,12 +122,16 @@ class ShardedBank:
         return ops.nw_merge(gathered_rows, B, self.C, class_lo=self.class_lo, c_local=self.CL)
 
     def _hip_search(self, q, k):
-        if self.search_precision == "fp16" and self.cache is not None:
-            if self.cache.packed is None:    # (25 rows or fewer: norms only; the score matrix of so few rows)
-                return ops.nw_knn(q, self.cache, k, self.kind, self.logit_scale, return_values=True, support=self.feat)
+        # A shard picks no route: its candidates always come from nw_knn (whose order the cross-shard merge expects), and
+        # nw_knn asks ops.knn_route.  What is decided here is a demand, not a route: search_precision="fp16" over packed rows
+        # passes rounded=True, so that a search the rounded route refuses (queries that do not pad to the shard's width)
+        # raises nw_knn's refusal where KNN.indices and get_neighbors fall back.  A norms-only fp16 shard (25 rows or fewer)
+        # has nothing to round and is searched like any other bank.
+        half = self.search_precision == "fp16" and self.cache is not None
+        if half and self.cache.packed is not None:
             return ops.nw_knn(q, self.cache, k, self.kind, self.logit_scale, return_values=True, rounded=True,
                               persistent_wgs=self.persistent_wgs)
-        bank = self._search_bank
+        bank = self.cache if half else self._search_bank
         if bank is None:
             # (the 'full' bank has split rows and no class-sorted copy -- it was prepared without labels -- unless it is fp16)
             bank = self.cache if (self.cache is not None and self.cache.precision == "fp32") else ops.SplitBank(self.feat)

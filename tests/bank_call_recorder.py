@@ -29,8 +29,8 @@ BANK_ROLES = ("rows", "sorted_rows", "sorted_labels", "split", "scale", "norm2",
 class Recorder:
     """``with Recorder(ops, q=q, s=s, labels=sy, bank=bank) as rec: ...; rec.calls`` -- the records of the calls made inside."""
 
-    def __init__(self, ops, q=None, s=None, labels=None, bank=None):
-        self.ops, self.bank, self.calls = ops, bank, []
+    def __init__(self, ops, q=None, s=None, labels=None, bank=None, entries=ENTRIES):
+        self.ops, self.bank, self.calls, self.entries = ops, bank, [], entries
         self.roles = {}
         for role, t in (("q", q), ("s", s), ("labels", labels)):
             if t is not None:
@@ -43,12 +43,12 @@ class Recorder:
     def __enter__(self):
         from nwhead_amd import _lib
         self._lib_mod, self._load = _lib, self.ops._lib.load
-        real, rec = self._load(), self
+        real, rec, entries = self._load(), self, self.entries
 
         class Proxy:
             def __getattr__(self, name):
                 fn = getattr(real, name)
-                if name not in ENTRIES:
+                if name not in entries:
                     return fn
                 return lambda *a: (rec._note(name, a), fn(*a))[1]
 
@@ -63,7 +63,7 @@ class Recorder:
         return None if not addr else self.roles.get(addr, "other")
 
     def _note(self, entry, args):
-        names = ENTRIES[entry]
+        names = self.entries[entry]
         assert len(args) == len(names), (entry, len(args))
         sig = self._lib_mod.SIGNATURES[entry][1]
         a = dict(zip(names, args))
@@ -81,7 +81,7 @@ class Recorder:
             r["opts"] = {"persistent_wgs": o.persistent_wgs, "force_split": o.force_split, "operand_form": o.operand_form,
                          "tables": None if not o.tables else ("bank.tables" if tables is not None and o.tables == tables.data_ptr()
                                                               else "other"),
-                         "tables_N": o.tables_N, "tables_sy_is_labels": bool(o.tables_sy) and o.tables_sy == a["sy"]}
+                         "tables_N": o.tables_N, "tables_sy_is_labels": bool(o.tables_sy) and o.tables_sy == a.get("sy")}
         self.calls.append(r)
 
 

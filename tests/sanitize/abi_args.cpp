@@ -7,16 +7,7 @@
 #include <cstring>
 #include <vector>
 #include "../../include/nwhead_hip.h"
-
-static int failures = 0;
-#define EXPECT(call, want)                                                                  \
-    do {                                                                                    \
-        const long long got_ = (long long)(call);                                          \
-        if (got_ != (long long)(want)) {                                                    \
-            std::printf("FAIL %s:%d  %s = %lld, expected %s\n", __FILE__, __LINE__, #call, got_, #want); \
-            ++failures;                                                                     \
-        }                                                                                   \
-    } while (0)
+#include "expect.h"
 
 int main() {
     std::vector<float> f(4096, 1.f);
