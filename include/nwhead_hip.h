@@ -511,21 +511,6 @@ int nw_conv2d_nhwc_bnrelu_f16x2(const float *x, const float *pre, const float *a
                                 int64_t pad, int64_t ldx, int64_t ldy, float *moments, void *stream);
 int64_t nw_conv2d_nhwc_moments_groups(int64_t n, int64_t H, int64_t W, int64_t Cin, int64_t Cout, int64_t KH, int64_t KW,
                                       int64_t stride, int64_t pad);
-/* The data gradient of a convolution whose input was relu(batch_norm(x)) (model/densenet.py:33-60: norm - relu - conv):
- * y = dL/d relu(bn(x)) is computed as nw_conv2d_nhwc_f16x2 does (no bias / residual / ReLU), and the epilogue also leaves
- * BatchNorm's backward statistics: per pixel group and channel, partials[(k G + group) Cout + co] = k 0: sum g, 1: sum g xhat,
- * with g = y where the forward's bn(x) = (x - mean) gamma invstd + beta was positive, xhat = (x - mean) invstd; G =
- * nw_conv2d_nhwc_moments_groups(same shape arguments).  x: (pixels, >= Cout) fp32 with row stride ldx, the tensor the
- * BatchNorm read (channel c of x is channel c of y).  nw_bn_relu_nhwc_train_bwd_from_partials_f32 takes it from there. */
-typedef struct nw_conv_bnstat {
-    const float *x; int64_t ldx;
-    const float *mean, *invstd, *gamma, *beta;   /* (Cout,) each */
-    float *partials;                             /* 2 G Cout floats */
-} nw_conv_bnstat;
-int nw_conv2d_nhwc_bnstat_f16x2(const float *x, const float *amax_in, const float *w_split, const float *w_scale, float *y,
-                                float *amax_out, int64_t n, int64_t H, int64_t W, int64_t Cin, int64_t Cout, int64_t KH,
-                                int64_t KW, int64_t stride, int64_t pad, int64_t ldx, int64_t ldy,
-                                const nw_conv_bnstat *bnstat, void *stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Training-mode BatchNorm2d (+ ReLU) in front of / behind the backbones' convolutions, forward and
@@ -664,14 +649,6 @@ int nw_bn_relu_nhwc_apply_f32(const float *x, int64_t ldx, const float *mean, co
                               const float *gamma, const float *beta, float *running_mean, float *running_var,
                               int64_t *num_batches_tracked, float momentum, float *y, float *amax_out, int64_t rows,
                               int64_t c, int relu, void *stream);
-/* The backward from the statistics a data-gradient convolution left (nw_conv2d_nhwc_bnstat_f16x2): the groups are summed
- * (-> dgamma, dbeta), then dx as in nw_bn_relu_nhwc_train_bwd_f32 (relu != 0).  workspace: 2 c floats. */
-int nw_bn_relu_nhwc_train_bwd_from_partials_f32(const float *x, int64_t ldx, const float *dy, const float *gamma,
-                                                const float *beta, const float *save_mean, const float *save_invstd,
-                                                const float *partials, int64_t groups, float *dx, float *dgamma,
-                                                float *dbeta, const float *acc, int64_t ldacc, int64_t lddx,
-                                                float *amax_out, void *workspace, size_t workspace_bytes, int64_t rows,
-                                                int64_t c, void *stream);
 /* The ImageNet stems at inference in one kernel (csrc/stem_pool.hip; model/resnet.py:147, :200-203, model/densenet.py:114-120 with
  * the BatchNorm folded into weight and bias): y = maxpool3x3/2/1(relu(conv7x7/2/3(x) + bias)), 64 output channels; the
  * 112 x 112 map between the two never reaches memory.
@@ -695,22 +672,6 @@ int nw_bn_relu_avgpool2x2_nhwc_f32(const float *x, int64_t ldx, const float *tab
  * and dx's amax record.  amax_out nullable. */
 int nw_add_relu_f32(const float *a, const float *b, float *out, float *amax_out, int64_t count, void *stream);
 int nw_relu_bwd_f32(const float *out, const float *g, float *dx, float *amax_out, int64_t count, void *stream);
-/* Backward of `norm1 -> relu1 -> conv1` of a dense layer (model/densenet.py:36-40; the 1x1 bottleneck convolution) in two
- * streaming passes, without the convolution's data gradient ever reaching memory (csrc/bn_dgrad.hip, round 4):
- *   du (rows, k) fp32, dense: dL/d(conv1 output), k = conv1's output channels (multiple of 32, <= 128); amax_du: its amax record;
- *   w_split / w_scale: conv1's DATA-GRADIENT operand (the (c, k) matrix W^T in nw_split_rows_f16x2 form: what
- *     nw_conv2d_nhwc_f16x2 takes to compute the data gradient of a 1x1 convolution);
- *   x (rows, >= c) with row stride ldx: the tensor norm1 read; tab: norm1's table mean | a | beta (rows tab_stride floats apart,
- *     a = gamma invstd: nw_bn_nhwc_prep_*); invstd (c,);
- *   g (rows, >= c) with row stride ldg: dL/dx is ADDED into g[:, :c] in place; amax_out (nullable): amax record of the result;
- *   dgamma, dbeta (c,): written.  workspace: nw_bn_dgrad1x1_workspace_bytes(rows, c).
- * Equals nw_conv2d_nhwc_f16x2 (data gradient) + nw_bn_relu_nhwc_train_bwd_f32(acc = dx = g) up to fp32 summation order.
- * NW_ERR_UNSUPPORTED for c % 32 != 0 or k outside {32, 64, 96, 128} (callers keep the two-step path for those). */
-size_t nw_bn_dgrad1x1_workspace_bytes(int64_t rows, int64_t c);
-int nw_bn_dgrad1x1_bwd_f16x2(const float *du, const float *amax_du, const float *w_split, const float *w_scale,
-                             const float *x, int64_t ldx, const float *tab, int64_t tab_stride, const float *invstd,
-                             float *g, int64_t ldg, float *amax_out, float *dgamma, float *dbeta, void *workspace,
-                             size_t workspace_bytes, int64_t rows, int64_t c, int64_t k, void *stream);
 int nw_bn_relu_nhwc_train_bwd_f32(const float *x, int64_t ldx, const float *dy, const float *gamma, const float *beta,
                                   const float *save_mean, const float *save_invstd, float *dx, float *dgamma,
                                   float *dbeta, const float *acc, int64_t ldacc, int64_t lddx, float *amax_out,

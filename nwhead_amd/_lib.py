@@ -67,16 +67,11 @@ SIGNATURES = {
     "nw_conv2d_nhwc_supported": (_int, [_i64] * 9),
     "nw_conv2d_nhwc_f16x2": (_int, [_p, _p, _p, _p, _p, _p, _int, _p, _p] + [_i64] * 11 + [_p, _p]),
     "nw_conv2d_nhwc_moments_groups": (_i64, [_i64] * 9),
-    "nw_conv2d_nhwc_bnstat_f16x2": (_int, [_p, _p, _p, _p, _p, _p] + [_i64] * 11 + [_p, _p]),
-    "nw_bn_relu_nhwc_train_bwd_from_partials_f32": (_int, [_p, _i64] + [_p] * 6 + [_i64, _p, _p, _p, _p, _i64, _i64, _p, _p, _sz, _i64,
-                                                           _i64, _p]),
     "nw_stem7x7s2_relu_maxpool_supported": (_int, [_i64] * 4),
     "nw_stem7x7s2_relu_maxpool_f16x2": (_int, [_p] * 7 + [_i64] * 4 + [_p]),
     "nw_bn_relu_avgpool2x2_nhwc_f32": (_int, [_p, _i64, _p, _p, _i64, _p, _i64, _i64, _i64, _i64, _p]),
     "nw_add_relu_f32": (_int, [_p, _p, _p, _p, _i64, _p]),
     "nw_relu_bwd_f32": (_int, [_p, _p, _p, _p, _i64, _p]),
-    "nw_bn_dgrad1x1_workspace_bytes": (_sz, [_i64, _i64]),
-    "nw_bn_dgrad1x1_bwd_f16x2": (_int, [_p, _p, _p, _p, _p, _i64, _p, _i64, _p, _p, _i64, _p, _p, _p, _p, _sz, _i64, _i64, _i64, _p]),
     "nw_bn_nhwc_moments_f32": (_int, [_p, _i64, _i64, _i64, C.c_float, _p, _p, _p, _p, _sz, _p]),
     "nw_bn_nhwc_moments_from_partials_f32": (_int, [_p, _i64, _i64, C.c_float, _p, _p, _p, _p]),
     "nw_bn_nhwc_moments_minmax_f32": (_int, [_p, _i64, _i64, _i64, C.c_float, _p, _p, _p, _p, _p, _p, _sz, _p]),
@@ -151,12 +146,6 @@ class WgradJob(C.Structure):
 class SgdParam(C.Structure):
     """nw_sgd_param (include/nwhead_hip.h)."""
     _fields_ = [("param", C.c_void_p), ("grad", C.c_void_p), ("momentum_buf", C.c_void_p), ("n", C.c_int64)]
-
-
-class ConvBnStat(C.Structure):
-    """nw_conv_bnstat (include/nwhead_hip.h)."""
-    _fields_ = [("x", C.c_void_p), ("ldx", C.c_int64), ("mean", C.c_void_p), ("invstd", C.c_void_p), ("gamma", C.c_void_p),
-                ("beta", C.c_void_p), ("partials", C.c_void_p)]
 
 
 class FwdOpts(C.Structure):

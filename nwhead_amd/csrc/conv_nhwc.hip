@@ -53,11 +53,6 @@ struct ConvP {
                              //   BatchNorm + ReLU applied by the loaders on the way into LDS (round 4: model/densenet.py:36-45's
                              //   norm1-relu1-conv1 / norm2-relu2-conv2 without the tensors between them); amax_in bounds |x'|
     const float4* zeros;     // 32 bytes of zeros (what a loader reads for a pixel that does not exist)
-    // nullable (bnb_part): y is the gradient of relu(batch_norm(bnb_x)) -- the epilogue also leaves, per pixel group and
-    // channel, sum g and sum g xhat with g = y [bn(x) > 0]: BatchNorm's backward statistics without a pass over (x, y)
-    const float* bnb_x; const float* bnb_mean; const float* bnb_invstd; const float* bnb_gamma; const float* bnb_beta;
-    float* bnb_part;
-    int bnb_ldx;
     int N, H, W, Cin, Ho, Wo, Cout, KH, KW, stride, pad, relu;
     int ldx, ldy;            // floats between consecutive pixels of x / y (>= Cin / Cout: a channel window of a wider tensor)
     int IP, IMG;             // virtual raster of PATCH mode: row stride W + pad, image stride (H + pad) IP
@@ -145,8 +140,8 @@ __device__ unsigned long long nw_conv_diag[16 * 1024];
 #define NW_CSTAMP(k)
 #endif
 
-// STATS = false: the instantiation for launches that leave neither moments nor BatchNorm backward sums (inference, data
-// gradients): none of that code and none of its running registers (their mere presence cost every convolution 1-5 %)
+// STATS = false: the instantiation for launches that leave no moments (inference, data gradients): none of that code and
+// none of its running registers (their mere presence cost every convolution 1-5 %)
 // POST = false: likewise without bias, identity and ReLU (the training path's convolutions have none of them)
 // PRE = true: the loaders apply relu((x - mean) a + beta) per input channel (ConvP::pre) in front of the split
 template <int NA, int NB, int WM, int MODE, bool STATS, bool POST, bool PRE = false>
@@ -156,7 +151,6 @@ __global__ __launch_bounds__(512, 1) void nw_conv_nhwc_kernel(const ConvP p) {
     constexpr bool MACC_LDS = NA == 4 && NB == 4;
     const int p_macc = p.macc;
     float* const p_moments = STATS ? p.moments : nullptr;
-    float* const p_bnb_part = STATS ? p.bnb_part : nullptr;
     const float* const p_bias = POST ? p.bias : nullptr;
     const float* const p_res = POST ? p.res : nullptr;
     const int p_relu = POST ? p.relu : 0;
@@ -188,13 +182,12 @@ __global__ __launch_bounds__(512, 1) void nw_conv_nhwc_kernel(const ConvP p) {
     const int ntile = tbeg < tend ? (tend - tbeg + nslot - 1) / nslot : 0;
     if (ntile == 0) {
         if (p.amax_out && tid == 0) amax_write(p.amax_out, 0.f, blockIdx.x, gridDim.x);
-        if ((p_moments || p_bnb_part) && p_macc) {                 // its groups exist and are empty
-            const int G = gridDim.x * WN, nstat = p_moments ? 5 : 2;
-            float* dst = p_moments ? p_moments : p_bnb_part;
-            for (int k = tid; k < nstat * WN * p.Cout; k += 512) {
+        if (p_moments && p_macc) {                                 // its groups exist and are empty
+            const int G = gridDim.x * WN;
+            for (int k = tid; k < 5 * WN * p.Cout; k += 512) {
                 const int w3 = k / p.Cout, c = k - w3 * p.Cout;    // (statistic, wave row)
                 const int stat = w3 / WN;                          // (an empty group: count 0, minimum +inf, maximum -inf)
-                dst[((size_t)stat * G + blockIdx.x * WN + w3 % WN) * p.Cout + c] = stat == 3 ? INFINITY : (stat == 4 ? -INFINITY : 0.f);
+                p_moments[((size_t)stat * G + blockIdx.x * WN + w3 % WN) * p.Cout + c] = stat == 3 ? INFINITY : (stat == 4 ? -INFINITY : 0.f);
             }
         }
         return;
@@ -875,65 +868,6 @@ __global__ __launch_bounds__(512, 1) void nw_conv_nhwc_kernel(const ConvP p) {
             }
             if (p_macc) rcnt = ntot;
         }
-        if (p_bnb_part) {
-            // y = dL/d relu(bn(x)): sum g and sum g xhat over this wave's pixel rows, g = y where the forward's own
-            // bn(x) = (x - mean) (gamma invstd) + beta was positive (the same expression nw_bn_nhwc_bwd_stats_kernel uses)
-            auto rowsum = [](float x) {
-                x += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x), 0x128, 0xf, 0xf, false));
-                x += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x), 0x124, 0xf, 0xf, false));
-                x += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x), 0x4e, 0xf, 0xf, false));
-                x += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x), 0xb1, 0xf, 0xf, false));
-                return x;
-            };
-            const int G = p.mtiles * WN, grp = mt * WN + wave / WM;
-            // every x value first (rows past the end clamped: their g is zeroed below), so that the loads fly together.  (Requested
-            // in front of the store loop instead, their registers stay live across it in EVERY instantiation: all convolutions
-            // 4-5 % slower, K2 1.427 -> 1.494 ms.)
-            float4 x4[NA][NB];
-#pragma unroll
-            for (int a = 0; a < NA; ++a)
-#pragma unroll
-                for (int b = 0; b < NB; ++b) {
-                    const int m = min(m0 + wpx + 16 * b + i, p.M - 1);
-                    x4[a][b] = *reinterpret_cast<const float4*>(p.bnb_x + (size_t)m * p.bnb_ldx + (co0 + wco + 16 * a + 4 * g));
-                }
-#pragma unroll
-            for (int a = 0; a < NA; ++a) {
-                const int co = co0 + wco + 16 * a + 4 * g;
-                const float4 m4 = *reinterpret_cast<const float4*>(p.bnb_mean + co), i4 = *reinterpret_cast<const float4*>(p.bnb_invstd + co),
-                             g4 = *reinterpret_cast<const float4*>(p.bnb_gamma + co), b4 = *reinterpret_cast<const float4*>(p.bnb_beta + co);
-                const float mean[4] = {m4.x, m4.y, m4.z, m4.w}, inv[4] = {i4.x, i4.y, i4.z, i4.w};
-                const float sa[4] = {g4.x * i4.x, g4.y * i4.y, g4.z * i4.z, g4.w * i4.w}, sb[4] = {b4.x, b4.y, b4.z, b4.w};
-                float s1[4] = {0.f, 0.f, 0.f, 0.f}, s2[4] = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-                for (int b = 0; b < NB; ++b) {
-                    const bool ok = m0 + wpx + 16 * b + i < p.M;
-                    const float xv[4] = {x4[a][b].x, x4[a][b].y, x4[a][b].z, x4[a][b].w};
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) {
-                        const float xm = xv[e] - mean[e];
-                        const float pre = __builtin_fmaf(xm, sa[e], sb[e]);
-                        const float gd = (ok && pre > 0.f) ? acc[a][b][e] : 0.f;
-                        s1[e] += gd;
-                        s2[e] = __builtin_fmaf(gd, xm * inv[e], s2[e]);
-                    }
-                }
-#pragma unroll
-                for (int e = 0; e < 4; ++e) { s1[e] = rowsum(s1[e]); s2[e] = rowsum(s2[e]); }
-                if (p_macc) {                                      // one group per workgroup and wave row (the running moments'
-                    if (!MACC_LDS || i == 0) {                     //  storage is free: the two have separate entry points)
-                        float rm[4], rq[4];
-                        run_get(a, rm, rq);
-#pragma unroll
-                        for (int e = 0; e < 4; ++e) { rm[e] += s1[e]; rq[e] += s2[e]; }
-                        run_put(a, rm, rq);
-                    }
-                } else if (i == 0) {
-                    *reinterpret_cast<float4*>(p_bnb_part + ((size_t)0 * G + grp) * p.Cout + co) = make_float4(s1[0], s1[1], s1[2], s1[3]);
-                    *reinterpret_cast<float4*>(p_bnb_part + ((size_t)1 * G + grp) * p.Cout + co) = make_float4(s2[0], s2[1], s2[2], s2[3]);
-                }
-            }
-        }
         NW_CSTAMP(4);                                              // epilogue of the tile
     }
 #ifdef NW_CONV_DIAG
@@ -942,17 +876,6 @@ __global__ __launch_bounds__(512, 1) void nw_conv_nhwc_kernel(const ConvP p) {
         nw_conv_diag[16 * blockIdx.x + 14] = cl_ - cf_;
     }
 #endif
-    if (p_bnb_part && p_macc && i == 0) {
-        const int G = gridDim.x * WN, grp = blockIdx.x * WN + wave / WM;
-#pragma unroll
-        for (int a = 0; a < NA; ++a) {
-            const int co = wco + 16 * a + 4 * g;
-            float rm[4], rq[4];
-            run_get(a, rm, rq);
-            *reinterpret_cast<float4*>(p_bnb_part + ((size_t)0 * G + grp) * p.Cout + co) = make_float4(rm[0], rm[1], rm[2], rm[3]);
-            *reinterpret_cast<float4*>(p_bnb_part + ((size_t)1 * G + grp) * p.Cout + co) = make_float4(rq[0], rq[1], rq[2], rq[3]);
-        }
-    }
     if (p_moments && p_macc && i == 0) {
         const int G = gridDim.x * WN, grp = blockIdx.x * WN + wave / WM;
 #pragma unroll
@@ -1078,7 +1001,7 @@ int launch_conv_cfg(ConvP p, hipStream_t st, int64_t* moments_groups = nullptr, 
         return ok;
     }();
     if (!attr) return NW_ERR_LAUNCH;
-    const bool stats = p.moments || p.bnb_part, post = p.bias || p.res || p.relu;
+    const bool stats = p.moments, post = p.bias || p.res || p.relu;
     if (p.pre) {   // BatchNorm + ReLU in the loaders: training forward (statistics), inference (bias / ReLU behind it) or plain
         if constexpr (MODE == CV_GATHER || MODE == CV_PATCH) {
             using CP = ConvCfg<NA, NB, WM, MODE, true>;
@@ -1159,8 +1082,7 @@ static int conv2d_nhwc_impl(const float* x, const float* amax_in, const float* w
                            const float* bias, const float* residual, int relu, float* y, float* amax_out,
                            int64_t n, int64_t H, int64_t W, int64_t Cin, int64_t Cout, int64_t KH, int64_t KW,
                            int64_t stride, int64_t pad, int64_t ldx, int64_t ldy, float* moments, int64_t* moments_groups,
-                           bool dry, void* stream, const nw_conv_bnstat* bnstat = nullptr, const float* pre = nullptr,
-                           int64_t pre_nrec = 0) {
+                           bool dry, void* stream, const float* pre = nullptr, int64_t pre_nrec = 0) {
     if (n < 0 || H < 0 || W < 0) return NW_ERR_INVALID_ARG;
     if (moments_groups) *moments_groups = 0;
     if (n == 0) return NW_OK;
@@ -1187,18 +1109,6 @@ static int conv2d_nhwc_impl(const float* x, const float* amax_in, const float* w
     p.pre_nrec = (int)pre_nrec;
     if (pre_nrec < 0 || pre_nrec > 4096 || (!pre && pre_nrec)) return NW_ERR_INVALID_ARG;
     if (pre && (Cin % 32 || (reinterpret_cast<uintptr_t>(pre) & 15))) return NW_ERR_INVALID_ARG;
-    p.bnb_x = p.bnb_mean = p.bnb_invstd = p.bnb_gamma = p.bnb_beta = nullptr; p.bnb_part = nullptr; p.bnb_ldx = 0;
-    if (bnstat) {
-        if (Cin % 32) return NW_ERR_UNSUPPORTED;
-        if (!bnstat->x || !bnstat->mean || !bnstat->invstd || !bnstat->gamma || !bnstat->beta || !bnstat->partials ||
-            bnstat->ldx < Cout || bnstat->ldx % 4 || n * ((H + 2 * pad - KH) / stride + 1) * ((W + 2 * pad - KW) / stride + 1) * bnstat->ldx >= (1LL << 31))
-            return NW_ERR_INVALID_ARG;
-        if ((reinterpret_cast<uintptr_t>(bnstat->x) | reinterpret_cast<uintptr_t>(bnstat->mean) | reinterpret_cast<uintptr_t>(bnstat->invstd) |
-             reinterpret_cast<uintptr_t>(bnstat->gamma) | reinterpret_cast<uintptr_t>(bnstat->beta) | reinterpret_cast<uintptr_t>(bnstat->partials)) & 15)
-            return NW_ERR_INVALID_ARG;
-        p.bnb_x = bnstat->x; p.bnb_mean = bnstat->mean; p.bnb_invstd = bnstat->invstd; p.bnb_gamma = bnstat->gamma;
-        p.bnb_beta = bnstat->beta; p.bnb_part = bnstat->partials; p.bnb_ldx = (int)bnstat->ldx;
-    }
     p.zeros = dry ? nullptr : nw::zero_page();
     if (!dry && !p.zeros) return NW_ERR_LAUNCH;
     p.N = (int)n; p.H = (int)H; p.W = (int)W; p.Cin = (int)Cin; p.Cout = (int)Cout; p.KH = (int)KH; p.KW = (int)KW;
@@ -1272,17 +1182,7 @@ extern "C" int nw_conv2d_nhwc_bnrelu_f16x2(const float* x, const float* pre, con
     if (!pre) return NW_ERR_INVALID_ARG;
     int64_t groups = 0;
     return conv2d_nhwc_impl(x, amax_in, w_split, w_scale, bias, nullptr, relu, y, amax_out, n, H, W, Cin, Cout, KH, KW, stride, pad,
-                            ldx, ldy, moments, moments ? &groups : nullptr, false, stream, nullptr, pre, raw_records);
-}
-
-extern "C" int nw_conv2d_nhwc_bnstat_f16x2(const float* x, const float* amax_in, const float* w_split, const float* w_scale, float* y,
-                                           float* amax_out, int64_t n, int64_t H, int64_t W, int64_t Cin, int64_t Cout, int64_t KH,
-                                           int64_t KW, int64_t stride, int64_t pad, int64_t ldx, int64_t ldy,
-                                           const nw_conv_bnstat* bnstat, void* stream) {
-    if (!bnstat) return NW_ERR_INVALID_ARG;
-    int64_t groups = 0;
-    return conv2d_nhwc_impl(x, amax_in, w_split, w_scale, nullptr, nullptr, 0, y, amax_out, n, H, W, Cin, Cout, KH, KW, stride, pad,
-                            ldx, ldy, nullptr, &groups, false, stream, bnstat);
+                            ldx, ldy, moments, moments ? &groups : nullptr, false, stream, pre, raw_records);
 }
 
 extern "C" int64_t nw_conv2d_nhwc_moments_groups(int64_t n, int64_t H, int64_t W, int64_t Cin, int64_t Cout, int64_t KH,

@@ -135,9 +135,6 @@ int launch_pack_rows_f16(const float* x, void* out, float* scale, float* norm2, 
 bool half_form_shape_ok(int64_t d);
 // (the fused launch itself: launch_fused(const FusedArgs&, form, kind), fused_plan.h)
 
-// bn_nhwc.hip, for bn_dgrad.hip: the BatchNorm backward finalize over G groups of partial sums
-int bn_bwd_finalize_groups(const float* part, int G, int C, float inv_m, float* dgamma, float* dbeta, float* k, hipStream_t st);
-
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);

@@ -1692,23 +1692,10 @@ def _amax_of(t):
     return a
 
 
-# Measured and left OFF: with the weight gradient of every convolution on a side stream beside its data gradient a
-# DenseNet-121 step takes 24.9-26.5 ms against 20.8-22.0 (same box, alternated): the two cross-stream dependencies per
-# node (event + barrier packet each way) cost more than the overlap of two kernels that both want every CU returns.
-WGRAD_SIDE_STREAM = os.environ.get("NW_WGRAD_STREAM", "0") == "1"
 # Data and weight gradients of STRIDED many-channel convolutions (the ResNets' 3x3 / 2 and 1x1 / 2) on the own kernels: the data
 # gradient as the stride-1 one over gy with zeros between its pixels, the weight gradient as one 1x1 problem per tap
 # (round 4).  0: torch / MIOpen.
 OWN_STRIDED_GRADS = os.environ.get("NW_OWN_STRIDED_GRADS", "1") != "0"
-_SIDE_STREAMS = {}
-
-
-def _side_stream(dev):
-    idx = dev.index if dev.index is not None else torch.cuda.current_device()
-    s = _SIDE_STREAMS.get(idx)
-    if s is None:
-        s = _SIDE_STREAMS[idx] = torch.cuda.Stream(device=dev)
-    return s
 
 
 class _ConvNhwcFn(torch.autograd.Function):
@@ -1744,17 +1731,6 @@ class _ConvNhwcFn(torch.autograd.Function):
             _CONV_STATS["absmax_fallbacks"] += 1
             gam = absmax(g)
         dx = dw = None
-        # The weight gradient is off the backward's critical path (the data gradient feeds the next node): it goes to a
-        # side stream and runs beside the data gradient; the main stream waits for it before the node returns, so the
-        # tensors autograd sees afterwards are complete on the stream it uses.
-        side = None
-        if ctx.needs_input_grad[1] and ctx.needs_input_grad[0] and WGRAD_SIDE_STREAM:
-            main = torch.cuda.current_stream(g.device)
-            side = _side_stream(g.device)
-            side.wait_stream(main)
-            with torch.cuda.stream(side):
-                dw = conv2d_nhwc_wgrad(xv, g, weight.shape, stride, pad, amax_x if amax_x.numel() else None, gam)
-            dw.record_stream(main)
         if ctx.needs_input_grad[0]:
             if stride == 1 and kh == kw and kh - 1 - pad >= 0 and cout % 32 == 0 and cin % 32 == 0:
                 dg = ctx.dgrad_operand
@@ -1775,9 +1751,7 @@ class _ConvNhwcFn(torch.autograd.Function):
             else:
                 dx = torch.ops.aten.convolution_backward(g, xv, weight, None, [stride, stride], [pad, pad], [1, 1], False,
                                                          [0, 0], 1, [True, False, False])[0]
-        if side is not None:
-            main.wait_stream(side)
-        elif ctx.needs_input_grad[1]:
+        if ctx.needs_input_grad[1]:
             dw = conv2d_nhwc_wgrad(xv, g, weight.shape, stride, pad, amax_x if amax_x.numel() else None, gam)
         return dx, dw, None, None, None, None, None
 
@@ -1863,17 +1837,6 @@ def _bn_tracking(bn):
         bn.num_batches_tracked += 1
         return bn.running_mean, bn.running_var, 1.0 / float(bn.num_batches_tracked), None
     return bn.running_mean, bn.running_var, float(bn.momentum), bn.num_batches_tracked
-
-
-# BatchNorm's backward sums from the data-gradient convolutions' epilogues (nw_conv2d_nhwc_bnstat_f16x2) instead of a statistics
-# pass: one launch and one read of (x, dy) less per BatchNorm, paid for by the x loads of the epilogue.  Measured on K4, three
-# alternations on one box: 18.93-18.97 ms with, 18.79-18.83 without -- left OFF
-DENSE_BWD_STATS_IN_DGRAD = os.environ.get("NW_DENSE_BWD_STATS", "0") == "1"
-# norm1 -> relu1 -> conv1 backward as nw_bn_dgrad1x1_bwd_f16x2 (two streaming passes, no (rows, c) gradient tensor) instead of the
-# data-gradient convolution + the two BatchNorm backward passes.  Half the HBM bytes, but measured SLOWER on K4 (15.3 vs 14.5 ms,
-# alternated on one box): its first pass is instruction-bound (the per-channel sums) and the 14 x 14 / 7 x 7 layers pay three
-# launch-latency floors either way -- left OFF (DESIGN.md 4.7h')
-DENSE_FUSED_NORM1_BWD = os.environ.get("NW_DENSE_FUSED_NORM1_BWD", "0") == "1"
 
 
 class _DenseBlockNhwcFn(torch.autograd.Function):
@@ -2006,83 +1969,35 @@ class _DenseBlockNhwcFn(torch.autograd.Function):
                 wjobs.append(_lib.WgradJob(_ptr(u), _ptr(am2), gv, _ptr(am_g), _ptr(dw2),
                                            n, h, w, mid, growth, kh, kh, 1, kh // 2, 0, ctot, 1, _ptr(tab2)))
                 wkeep.append(am_g)
-                if DENSE_BWD_STATS_IN_DGRAD:
-                    dt2 = torch.empty((rows, mid), **f32)
-                    am_d = torch.empty(3 * AMAX_SLOTS, **f32)              # amax records of dt2 | du | dt1
-                    # the data gradients also leave BatchNorm's backward sums of what they write (sum g, sum g xhat per pixel
-                    # group), so the BatchNorm backward is the sum of the groups + ONE pass (dx), not two
-                    Gd2 = lib.nw_conv2d_nhwc_moments_groups(n, h, w, growth, mid, kh, kh, 1, kh - 1 - kh // 2)
-                    Gd1 = lib.nw_conv2d_nhwc_moments_groups(n, h, w, mid, c, 1, 1, 1, 0)
-                    bpart = torch.empty(2 * max(Gd2 * mid, Gd1 * c), **f32)
-                    bs2 = _lib.ConvBnStat(_ptr(u), mid, _ptr(m2), _ptr(i2), _ptr(g2), _ptr(b2), _ptr(bpart))
-                    _lib.check(lib.nw_conv2d_nhwc_bnstat_f16x2(gv, _ptr(am_g), _ptr(d2.split), _ptr(d2.scale), _ptr(dt2), _ptr(am_d),
-                                                               n, h, w, growth, mid, kh, kh, 1, kh - 1 - kh // 2, ctot, 0,
-                                                               ctypes.byref(bs2), st), "nw_conv2d_nhwc_bnstat_f16x2")
-                    # norm2 + relu
-                    du = torch.empty((rows, mid), **f32)
-                    dg2, db2 = torch.empty(mid, **f32), torch.empty(mid, **f32)
-                    kws = torch.empty(2 * max(c, mid), **f32)
-                    _lib.check(lib.nw_bn_relu_nhwc_train_bwd_from_partials_f32(
-                        _ptr(u), mid, _ptr(dt2), _ptr(g2), _ptr(b2), _ptr(m2), _ptr(i2), _ptr(bpart), Gd2, _ptr(du), _ptr(dg2), _ptr(db2),
-                        None, 0, 0, am_d.data_ptr() + 4 * AMAX_SLOTS, _ptr(kws), 4 * kws.numel(), rows, mid, st),
-                        "nw_bn_relu_nhwc_train_bwd_from_partials_f32")
-                    # conv1 (1x1)
-                    dw1 = torch.empty((mid, c, 1, 1), **f32)     # (a 1x1 kernel: (Cout, 1, 1, Cin) bytes ARE torch's (Cout, Cin, 1, 1): no copy in AccumulateGrad)
-                    wjobs.append(_lib.WgradJob(_ptr(slab), _ptr(am1), _ptr(du), am_d.data_ptr() + 4 * AMAX_SLOTS, _ptr(dw1),
-                                               n, h, w, c, mid, 1, 1, 1, 0, ctot, 0, 0, _ptr(tab1)))
-                    wkeep += [du, am_d]
-                    dt1 = torch.empty((rows, c), **f32)
-                    bs1 = _lib.ConvBnStat(_ptr(slab), ctot, _ptr(m1), _ptr(i1), _ptr(g1), _ptr(b1), _ptr(bpart))
-                    _lib.check(lib.nw_conv2d_nhwc_bnstat_f16x2(_ptr(du), am_d.data_ptr() + 4 * AMAX_SLOTS, _ptr(d1.split), _ptr(d1.scale),
-                                                               _ptr(dt1), am_d.data_ptr() + 8 * AMAX_SLOTS, n, h, w, mid, c, 1, 1, 1, 0, 0, 0,
-                                                               ctypes.byref(bs1), st), "nw_conv2d_nhwc_bnstat_f16x2")
-                    # norm1 + relu over the slab's prefix: dx is ADDED into the gradient slab's prefix, in place
-                    dg1, db1 = torch.empty(c, **f32), torch.empty(c, **f32)
-                    am_g = torch.empty(AMAX_SLOTS, **f32)
-                    _lib.check(lib.nw_bn_relu_nhwc_train_bwd_from_partials_f32(
-                        _ptr(slab), ctot, _ptr(dt1), _ptr(g1), _ptr(b1), _ptr(m1), _ptr(i1), _ptr(bpart), Gd1, _ptr(G), _ptr(dg1), _ptr(db1),
-                        _ptr(G), ctot, ctot, _ptr(am_g), _ptr(kws), 4 * kws.numel(), rows, c, st),
-                        "nw_bn_relu_nhwc_train_bwd_from_partials_f32")
-                else:
-                    dt2 = torch.empty((rows, mid), **f32)
-                    am_d = torch.empty(3 * AMAX_SLOTS, **f32)              # amax records of dt2 | du | dt1
-                    _lib.check(lib.nw_conv2d_nhwc_f16x2(gv, _ptr(am_g), _ptr(d2.split), _ptr(d2.scale), None, None, 0, _ptr(dt2),
-                                                        _ptr(am_d), n, h, w, growth, mid, kh, kh, 1, kh - 1 - kh // 2, ctot, 0, None, st),
-                               "nw_conv2d_nhwc_f16x2")
-                    # norm2 + relu
-                    du = torch.empty((rows, mid), **f32)
-                    dg2, db2 = torch.empty(mid, **f32), torch.empty(mid, **f32)
-                    bnb = max(lib.nw_bn_nhwc_workspace_bytes(rows, c), lib.nw_bn_nhwc_workspace_bytes(rows, mid))
-                    wsn = _workspace(bnb, dev)
-                    _lib.check(lib.nw_bn_relu_nhwc_train_bwd_f32(_ptr(u), mid, _ptr(dt2), _ptr(g2), _ptr(b2), _ptr(m2), _ptr(i2),
-                                                                 _ptr(du), _ptr(dg2), _ptr(db2), None, 0, 0,
-                                                                 am_d.data_ptr() + 4 * AMAX_SLOTS, _ptr(wsn), bnb, rows, mid, 1, st),
-                               "nw_bn_relu_nhwc_train_bwd_f32")
-                    # conv1 (1x1)
-                    dw1 = torch.empty((mid, c, 1, 1), **f32)     # (a 1x1 kernel: (Cout, 1, 1, Cin) bytes ARE torch's (Cout, Cin, 1, 1): no copy in AccumulateGrad)
-                    wjobs.append(_lib.WgradJob(_ptr(slab), _ptr(am1), _ptr(du), am_d.data_ptr() + 4 * AMAX_SLOTS, _ptr(dw1),
-                                               n, h, w, c, mid, 1, 1, 1, 0, ctot, 0, 0, _ptr(tab1)))
-                    wkeep += [du, am_d]
-                    dg1, db1 = torch.empty(c, **f32), torch.empty(c, **f32)
-                    am_g = torch.empty(AMAX_SLOTS, **f32)
-                    if DENSE_FUSED_NORM1_BWD and mid % 32 == 0 and mid <= 128 and c % 32 == 0:
-                        # conv1's data gradient, norm1's statistics and dx in two streaming passes: the (rows, c) gradient never
-                        # reaches memory (csrc/bn_dgrad.hip); dx is ADDED into the gradient slab's prefix, in place
-                        fb = lib.nw_bn_dgrad1x1_workspace_bytes(rows, c)
-                        wsf = _workspace(fb, dev)
-                        _lib.check(lib.nw_bn_dgrad1x1_bwd_f16x2(_ptr(du), am_d.data_ptr() + 4 * AMAX_SLOTS, _ptr(d1.split), _ptr(d1.scale),
-                                                                _ptr(slab), ctot, _ptr(tab1), c, _ptr(i1), _ptr(G), ctot, _ptr(am_g),
-                                                                _ptr(dg1), _ptr(db1), _ptr(wsf), fb, rows, c, mid, st),
-                                   "nw_bn_dgrad1x1_bwd_f16x2")
-                    else:
-                        dt1 = torch.empty((rows, c), **f32)
-                        _lib.check(lib.nw_conv2d_nhwc_f16x2(_ptr(du), am_d.data_ptr() + 4 * AMAX_SLOTS, _ptr(d1.split), _ptr(d1.scale), None,
-                                                            None, 0, _ptr(dt1), am_d.data_ptr() + 8 * AMAX_SLOTS, n, h, w, mid, c, 1, 1, 1, 0,
-                                                            0, 0, None, st), "nw_conv2d_nhwc_f16x2")
-                        # norm1 + relu over the slab's prefix: dx is ADDED into the gradient slab's prefix, in place
-                        _lib.check(lib.nw_bn_relu_nhwc_train_bwd_f32(_ptr(slab), ctot, _ptr(dt1), _ptr(g1), _ptr(b1), _ptr(m1), _ptr(i1),
-                                                                     _ptr(G), _ptr(dg1), _ptr(db1), _ptr(G), ctot, ctot, _ptr(am_g),
-                                                                     _ptr(wsn), bnb, rows, c, 1, st), "nw_bn_relu_nhwc_train_bwd_f32")
+                dt2 = torch.empty((rows, mid), **f32)
+                am_d = torch.empty(3 * AMAX_SLOTS, **f32)              # amax records of dt2 | du | dt1
+                _lib.check(lib.nw_conv2d_nhwc_f16x2(gv, _ptr(am_g), _ptr(d2.split), _ptr(d2.scale), None, None, 0, _ptr(dt2),
+                                                    _ptr(am_d), n, h, w, growth, mid, kh, kh, 1, kh - 1 - kh // 2, ctot, 0, None, st),
+                           "nw_conv2d_nhwc_f16x2")
+                # norm2 + relu
+                du = torch.empty((rows, mid), **f32)
+                dg2, db2 = torch.empty(mid, **f32), torch.empty(mid, **f32)
+                bnb = max(lib.nw_bn_nhwc_workspace_bytes(rows, c), lib.nw_bn_nhwc_workspace_bytes(rows, mid))
+                wsn = _workspace(bnb, dev)
+                _lib.check(lib.nw_bn_relu_nhwc_train_bwd_f32(_ptr(u), mid, _ptr(dt2), _ptr(g2), _ptr(b2), _ptr(m2), _ptr(i2),
+                                                             _ptr(du), _ptr(dg2), _ptr(db2), None, 0, 0,
+                                                             am_d.data_ptr() + 4 * AMAX_SLOTS, _ptr(wsn), bnb, rows, mid, 1, st),
+                           "nw_bn_relu_nhwc_train_bwd_f32")
+                # conv1 (1x1)
+                dw1 = torch.empty((mid, c, 1, 1), **f32)     # (a 1x1 kernel: (Cout, 1, 1, Cin) bytes ARE torch's (Cout, Cin, 1, 1): no copy in AccumulateGrad)
+                wjobs.append(_lib.WgradJob(_ptr(slab), _ptr(am1), _ptr(du), am_d.data_ptr() + 4 * AMAX_SLOTS, _ptr(dw1),
+                                           n, h, w, c, mid, 1, 1, 1, 0, ctot, 0, 0, _ptr(tab1)))
+                wkeep += [du, am_d]
+                dg1, db1 = torch.empty(c, **f32), torch.empty(c, **f32)
+                am_g = torch.empty(AMAX_SLOTS, **f32)
+                dt1 = torch.empty((rows, c), **f32)
+                _lib.check(lib.nw_conv2d_nhwc_f16x2(_ptr(du), am_d.data_ptr() + 4 * AMAX_SLOTS, _ptr(d1.split), _ptr(d1.scale), None,
+                                                    None, 0, _ptr(dt1), am_d.data_ptr() + 8 * AMAX_SLOTS, n, h, w, mid, c, 1, 1, 1, 0,
+                                                    0, 0, None, st), "nw_conv2d_nhwc_f16x2")
+                # norm1 + relu over the slab's prefix: dx is ADDED into the gradient slab's prefix, in place
+                _lib.check(lib.nw_bn_relu_nhwc_train_bwd_f32(_ptr(slab), ctot, _ptr(dt1), _ptr(g1), _ptr(b1), _ptr(m1), _ptr(i1),
+                                                             _ptr(G), _ptr(dg1), _ptr(db1), _ptr(G), ctot, ctot, _ptr(am_g),
+                                                             _ptr(wsn), bnb, rows, c, 1, st), "nw_bn_relu_nhwc_train_bwd_f32")
                 grads[6 * k:6 * k + 6] = [dg1, db1, dw1, dg2, db2, dw2]
             if wjobs:
                 jobs = (_lib.WgradJob * len(wjobs))(*wjobs)

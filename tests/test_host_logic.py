@@ -207,3 +207,31 @@ def test_device_optimizer_has_no_cpu_path_and_the_harness_picks_by_device():
     with pytest.raises(NWHipError):
         opt.step()
     assert torch.equal(p.detach(), torch.zeros(8))                                  # ... and nothing was updated
+
+
+def test_design_switch_table_lists_exactly_the_switches_the_code_reads():
+    """DESIGN.md 6a against the code: the NW_* variables nwhead_amd reads from the environment (environ.get("NW_...") in any of
+    its files, plus NW_<KNOB> for every name in _lib.KNOBS) are the NW_* names of the table, whose bench.py row is bench.py's
+    own; the switches of the removed dense-block backward variants and of the side stream are in neither."""
+    import os
+    import re
+    from nwhead_amd import _lib
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    code = {"NW_" + k.upper() for k in _lib.KNOBS}
+    for d, _, files in os.walk(os.path.join(root, "nwhead_amd")):
+        for f in files:
+            if f.endswith(".py"):
+                with open(os.path.join(d, f)) as fh:
+                    code |= set(re.findall(r"""environ\.get\(\s*["'](NW_[A-Z0-9_]+)""", fh.read()))
+    with open(os.path.join(root, "DESIGN.md")) as fh:
+        section = fh.read().split("\n## 6a. ")[1].split("\n## ")[0]
+    rows = [r for r in section.split("\n") if r.startswith("| ") and not r.startswith("| variable")]
+    assert len(rows) > 10
+    table = set()
+    for r in rows:
+        first, reaches = r.split("|")[1:3]
+        if "bench.py" not in reaches:
+            table |= set(re.findall(r"NW_[A-Z0-9_]+", first))
+    assert code == table, (sorted(code - table), sorted(table - code))
+    for gone in ("NW_DENSE_BWD_STATS", "NW_DENSE_FUSED_NORM1_BWD", "NW_WGRAD_STREAM"):
+        assert gone not in code and gone not in table
