@@ -315,6 +315,30 @@ int nw_knn_window_f32(const float *q, const float *s_split, const float *s_scale
                       int64_t *idx_out, float *val_out, void *workspace, size_t workspace_bytes,
                       int64_t B, int64_t N, int64_t d, int64_t k, int kind, const float *logit_scale_dev,
                       void *stream);
+/* The HEAD over a row window per query (leave-one-out prediction, one segment of a concatenated bank, "without
+ * the query's own class" in a class-sorted bank): nw_fwd_f32's log-probabilities computed from the bank rows
+ * that the query's window admits, and from no other.  row_lo / row_hi (B,) int32 on the device and exclude
+ * mean what they mean for nw_knn_window_f32: row takes part when lo[b] <= row < hi[b] (exclude == 0), or when
+ * it is outside that range (exclude != 0); lo >= hi is the empty window; the values are clamped to [0, N] on
+ * the device and never used as an address.  The window is applied to the scores inside the tile kernel, before
+ * the tile's maximum and exponentials: the result is the softmax over the admitted rows alone, not the full
+ * softmax with terms subtracted (which cancels to nothing when an excluded row dominates).
+ *   q         (B,d) fp32 queries
+ *   s_split / s_scale / s_norm2   the bank as nw_split_rows_f16x2 leaves it ((N,d), (N,), (N,))
+ *   sy        (N,) int64 labels; labels outside [0, C) are skipped as in nw_fwd_f32
+ *   out       (B,C) fp32 log(p + 1e-12);  lse_out  optional (B,) fp32 log-sum-exp of the admitted scores
+ * A query whose window admits no row: out[b, :] = log(1e-12) (every class absent), lse_out[b] = -inf, no NaN.
+ * Always the split-fp16 tile kernel, at the tile height and with the raw-or-split-queries rule of
+ * nw_knn_window_f32 at the same shape; no score matrix.  Regime: d % 32 == 0, 32 <= d <= 2^20, N > 25,
+ * C >= 1, q, s_split and workspace 16-byte aligned; anything else returns NW_ERR_UNSUPPORTED before
+ * anything is launched (callers mask a score matrix and call nw_aggregate_f32).  row_lo, row_hi, sy or out
+ * NULL, or a negative size: NW_ERR_INVALID_ARG.  workspace: nw_fwd_workspace_bytes(B, N, d, C), else
+ * NW_ERR_WORKSPACE.  B == 0: NW_OK.  No allocation, no synchronisation, no environment. */
+int nw_fwd_window_f32(const float *q, const float *s_split, const float *s_scale, const float *s_norm2,
+                      const int64_t *sy, const int32_t *row_lo, const int32_t *row_hi, int exclude,
+                      float *out, float *lse_out, void *workspace, size_t workspace_bytes,
+                      int64_t B, int64_t N, int64_t d, int64_t C, int kind, const float *logit_scale_dev,
+                      void *stream);
 /* support_influence (util/metric.py:23-50) of k SELECTED supports per query, from the head's own outputs:
  *   vals (B,k) fp32 raw scores and rows (B,k) int64 bank rows (a search's val_out / idx_out),
  *   sy (N,) int64, qy (B,) int64, out (B,C) log-probabilities and lse (B,) of nw_fwd_f32 over the same bank;

@@ -230,6 +230,28 @@ extern "C" int nw_fwd_f32(const float* q, const float* s, const int64_t* sy, con
                                 nullptr, nullptr, B, N, C, st, slice_ws, slice_floats);
 }
 
+// The head over a per-query row window of a split bank (fused.hip, OUT_WIN): nw_knn_window_f32's regime, nw_fwd_f32's
+// workspace, no options (nothing of nw_fwd_opts applies: split rows at every size, no run tables, no persistent kernel).
+extern "C" int nw_fwd_window_f32(const float* q, const float* s_split, const float* s_scale, const float* s_norm2,
+                                 const int64_t* sy, const int32_t* row_lo, const int32_t* row_hi, int exclude, float* out,
+                                 float* lse_out, void* workspace, size_t workspace_bytes, int64_t B, int64_t N, int64_t d,
+                                 int64_t C, int kind, const float* logit_scale_dev, void* stream) {
+    if (B < 0 || N < 0 || d < 0 || C < 0) return NW_ERR_INVALID_ARG;
+    if (!row_lo || !row_hi) return NW_ERR_INVALID_ARG;   // (the head without a window is nw_fwd_f32)
+    if (bad_kind(kind)) return NW_ERR_UNSUPPORTED;
+    if (N <= 25 || C < 1 || d < 32 || d % 32 != 0 || d > (1 << 20)) return NW_ERR_UNSUPPORTED;
+    if (B == 0) return NW_OK;
+    if (!q || !s_split || !s_scale || !s_norm2 || !sy || !out) return NW_ERR_INVALID_ARG;
+    if (kind == NW_SCORE_CLIP && !logit_scale_dev) return NW_ERR_INVALID_ARG;
+    if (!nw::fused_eligible(q, s_split, B, N, d, C)) return NW_ERR_UNSUPPORTED;   // alignment, sizes past the tile kernels
+    if (!workspace || workspace_bytes < nw_fwd_workspace_bytes(B, N, d, C)) return NW_ERR_WORKSPACE;
+    if (reinterpret_cast<uintptr_t>(workspace) & 15) return NW_ERR_UNSUPPORTED;
+    nw::FusedArgs a = {q, s_split, sy, s_norm2, s_scale, logit_scale_dev, out, nullptr, lse_out, nullptr, nullptr, nullptr,
+                       workspace, workspace_bytes, (int)B, (int)N, (int)d, (int)C, static_cast<hipStream_t>(stream), nullptr,
+                       row_lo, row_hi, exclude != 0};
+    return nw::launch_fused(a, nw::FORM_SPLIT, kind);
+}
+
 extern "C" int nw_fwd_partial_f32(const float* q, const float* s, const int64_t* sy,
                                   const float* s_norm2, const float* s_split, const float* s_scale,
                                   float* m, float* den, float* num, void* workspace, size_t workspace_bytes,

@@ -227,6 +227,11 @@ __global__ __launch_bounds__(MTHREADS) void nw_merge_runs_kernel(
     M = red[bq];
 #pragma unroll
     for (int k = 1; k < NW; ++k) M = fmaxf(M, red[k * MQ + bq]);
+    // A query whose row window admits no row at all (OUT_WIN) has m = -inf and den = 0 in every tile.  Its rescaling runs
+    // against 0 (2^(-inf - 0) = 0 where -inf - -inf would be NaN) and its 1 / den below is 0: every class comes out as
+    // log(NW_LOG_EPS) and lse as -inf.  Every other call has a finite M and den >= 1, and both selects leave them as they are.
+    const bool no_rows = M == -INFINITY;
+    if (no_rows) M = 0.f;
     // ---- den: every thread adds its tiles in order, the tile lanes of a wave are added in a fixed tree, the
     // waves in order
     float den = 0.f;
@@ -263,7 +268,7 @@ __global__ __launch_bounds__(MTHREADS) void nw_merge_runs_kernel(
     den = red[NW * MQ + bq];
 #pragma unroll
     for (int k = 1; k < NW; ++k) den += red[NW * MQ + k * MQ + bq];
-    if (sl == 0) inv_s[bq] = 1.f / den;
+    if (sl == 0) inv_s[bq] = no_rows ? 0.f : 1.f / den;
     const int nq = min(MQ, B - b0);
     if (sl == 0 && bq < nq) {
         if (PARTIAL) {
@@ -643,6 +648,10 @@ FusedPlan plan_fused(int64_t B, int64_t N, int64_t d, int64_t C, int form, int o
     if (out == OUT_CAND && form == FORM_F32) return refuse(NW_ERR_INVALID_ARG);
     // (RS = 12 on split operands exists only under the tile_rs knob and spills there: no candidate form of it)
     if (out == OUT_CAND && split && p.rs == 12) return refuse(NW_ERR_UNSUPPORTED);
+    // the windowed head: split rows on nw_fused_kernel only (p.persistent above asks for OUT_NONE: never the persistent
+    // kernels, so never run tables either), at the tile heights of the candidate form
+    if (out == OUT_WIN && form == FORM_F32) return refuse(NW_ERR_INVALID_ARG);
+    if (out == OUT_WIN && p.rs == 12) return refuse(NW_ERR_UNSUPPORTED);
     if (p.persistent) {
         p.mode = MODE_F16;
         p.split_queries = true;
@@ -706,7 +715,7 @@ bool fused_eligible(const float* q, const float* s, int64_t B, int64_t N, int64_
 }
 
 int launch_fused(const FusedArgs& a, int form, int kind) {
-    const int out = a.cand ? OUT_CAND : a.scores ? OUT_SCORES : OUT_NONE;
+    const int out = a.cand ? OUT_CAND : (a.win_lo && a.win_hi) ? OUT_WIN : a.scores ? OUT_SCORES : OUT_NONE;
     const FusedPlan p = plan_fused(a.B, a.N, a.d, a.C, form, out, a.cand ? a.cand->k : 0, a.s_norm2 != nullptr,
                                    kind == NW_SCORE_DOT, 0, fwd_opts());
 #define NW_KIND_CASE(K) case K: return launch_fused_kind<K>(a, p);

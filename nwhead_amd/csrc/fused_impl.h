@@ -48,6 +48,17 @@ constexpr int CAND_EXCLUDE = 1 << 8;   // the flag's place beside k (<= 32) in t
 // kernels without a window are compiled from the text they always had, so nw_knn_f32's code and bits do not move.
 constexpr int OUT_CAND_WIN = 3;
 constexpr bool out_is_cand(int out) { return out == OUT_CAND || out == OUT_CAND_WIN; }
+// Softmax partials over a per-query row window (OUT_WIN, nw_fwd_window_f32).  The window is applied to the scores before the
+// tile maximum, so a (query, tile) pair may keep no row: a DEAD pair.  Its tile stores m = -inf, den = 0 and 0 in every run
+// sum below the tile's run count -- all the run merge reads of it (the workspace is never cleared) -- and the merge gives a
+// query whose every pair is dead log(NW_LOG_EPS) in every class and lse = -inf (nw_merge_runs_kernel).
+// The kernel's arguments stay those of every other output: the window's two arrays (read only) stand where the scores and
+// the tile sums go, the flag beside the class count (< 2^30, fused_eligible); the kernel finds the tile sums behind the tile
+// maxima, where fused_layout puts them.
+constexpr int WIN_EXCLUDE = 1 << 30;
+__host__ __device__ inline size_t fused_den_after_m(int64_t n_stiles, int64_t B) {   // floats from FusedWs::m to FusedWs::den
+    return (((size_t)n_stiles * (size_t)B * 4 + 255) & ~(size_t)255) / 4;
+}
 __host__ __device__ inline int cand_slots(int k, int BS) { return ((k < BS ? k : BS) + 3) & ~3; }
 int tile_timer_start(hipStream_t st);          // diagnostics (nw_debug_tile_timing): -1 when disabled
 void tile_timer_stop(int slot, hipStream_t st);
@@ -199,6 +210,8 @@ __device__ __forceinline__ void tile_candidates(const float (&sc)[RS][4], unsign
 // Called by all threads of the workgroup (loader waves only take part in the run-table copy).
 // OUT_CAND: `scores` / `ws_lab` are CandOut's key / row arrays, n_stiles and k come behind; nothing else is written.
 // OUT_CAND_WIN: `ws_nrun` / `ws_m` are CandOut's window arrays besides, loaded in tile_candidates.
+// OUT_WIN: `scores` / `ws_den` are the row window's two arrays (the tile sums go to ws_m + fused_den_after_m), k carries
+// the kernel's C argument (WIN_EXCLUDE); everything else as for OUT_NONE.
 template <int RS, int KIND, int OUT, int MODE>
 __device__ __forceinline__ void fused_epilogue(
     f32x4 (&acc)[RS], const float* qn2, const float* sn2, const float* ssc, const int* runid,
@@ -225,6 +238,12 @@ __device__ __forceinline__ void fused_epilogue(
     const float qn = NEED_NORM ? qn2[qrow] : 0.f;
     const float qsc = mode_is_f16(MODE) ? qsc_s[qrow] : 1.f;  // 2^-e of this lane's query row (LDS header)
     const bool partial_tile = s0 + BS > N;  // only the last support tile has rows past the bank
+    const int *win_lo = nullptr, *win_hi = nullptr;
+    if constexpr (OUT == OUT_WIN) {   // the window's arrays ride in on `scores` / `ws_den`; the tile sums lie behind the maxima
+        win_lo = reinterpret_cast<const int*>(scores);
+        win_hi = reinterpret_cast<const int*>(ws_den);
+        ws_den = ws_m + fused_den_after_m(n_stiles, B);
+    }
 
     float sc[RS][4];
     float mloc = -INFINITY;
@@ -271,6 +290,26 @@ __device__ __forceinline__ void fused_epilogue(
                                       reinterpret_cast<const int*>(ws_m));
             return;
         }
+        if constexpr (OUT == OUT_WIN) {
+            // tile_candidates<RS, true>'s window arithmetic, on the scores: rows that the query's window does not admit leave
+            // the softmax like the rows past the bank.  A (query column, tile) pair that the window leaves whole skips the
+            // per-element comparisons; lo / hi are clamped and never used as addresses.
+            const bool exclude = (k & WIN_EXCLUDE) != 0;
+            const int bb = b < B ? b : B - 1;
+            const int lo = min(max(win_lo[bb], 0), N), hi = min(max(win_hi[bb], 0), N);
+            const unsigned width = hi > lo ? (unsigned)(hi - lo) : 0u;
+            const int tile_end = s0 + BS < N ? s0 + BS : N;
+            const bool disjoint = width == 0u || hi <= s0 || lo >= tile_end;   // no row of the tile is in the window
+            const bool covered = lo <= s0 && hi >= tile_end;                    // every row of the tile is
+            if (!(exclude ? disjoint : covered)) {
+                const int rel = s0 + 4 * g - lo;   // tile row t = 16r + e of this lane is bank row lo + rel + t
+#pragma unroll
+                for (int r = 0; r < RS; ++r)
+#pragma unroll
+                    for (int e = 0; e < 4; ++e)
+                        if (((unsigned)(rel + 16 * r + e) < width) == exclude) sc[r][e] = -INFINITY;
+            }
+        }
 #pragma unroll
         for (int r = 0; r < RS; ++r) mloc = fmaxf(mloc, fmaxf(fmaxf(sc[r][0], sc[r][1]), fmaxf(sc[r][2], sc[r][3])));
         if (WRITE_SCORES && b < B) {  // natural units for the caller (backward, neighbour search)
@@ -304,10 +343,33 @@ __device__ __forceinline__ void fused_epilogue(
     // every lane its four (run, query) sums: no LDS atomics, no divergence, bit-reproducible.
     if (consumer) {
         float dloc = 0.f;
+        float msub = mloc;
+        if constexpr (OUT == OUT_WIN) {
+            // dead pairs (mloc = -inf: the window keeps no row of the tile for this query).  A wave all of whose sixteen
+            // queries are dead stores their zeros and goes; a dead query among live ones takes the sums below with
+            // 2^(-inf - 0) = 0 in every element (-inf - -inf would be NaN), which leaves the same zeros.
+            const bool dead = mloc == -INFINITY;
+            if (__all(dead)) {
+                const int nrun = nrun_s[0];
+                if (b < B) {
+                    for (int run = g; run < nrun; run += 4) ws_num[((size_t)st * BS + run) * B + b] = 0.f;
+                    if (g == 0) {
+                        ws_m[(size_t)st * B + b] = -INFINITY;
+                        ws_den[(size_t)st * B + b] = 0.f;
+                    }
+                }
+                if (qt == 0) {   // this wave's share of the run table (below)
+                    if (tid == 0) ws_nrun[st] = nrun;
+                    for (int x = tid; x < nrun; x += TILE_THREADS) ws_lab[(size_t)st * BS + x] = runlab[x];
+                }
+                return;
+            }
+            msub = dead ? 0.f : mloc;
+        }
 #pragma unroll
         for (int r = 0; r < RS; ++r)
 #pragma unroll
-            for (int e = 0; e < 4; ++e) sc[r][e] = __builtin_amdgcn_exp2f(sc[r][e] - mloc);  // 2^-inf = 0 for padded rows
+            for (int e = 0; e < 4; ++e) sc[r][e] = __builtin_amdgcn_exp2f(sc[r][e] - msub);  // 2^-inf = 0 for padded rows
         // Run sums.  A run is a RANGE of tile rows: with the first rows b1, b2 of runs 1 and 2 the
         // membership of row t is a clamped difference, [t < b] = clamp(b - t, 0, 1) -- for up to three
         // runs (a class-sorted bank has one or two per tile) 2-7 VALU ops per element instead of a
@@ -399,6 +461,7 @@ __device__ __forceinline__ void fused_epilogue(
 
 // OUT_CAND: sy is not read, `scores` / `ws_lab` are CandOut's key / row arrays and `C` carries k.
 // OUT_CAND_WIN: `C` carries CAND_EXCLUDE besides and `ws_nrun` / `ws_m` are the row window's two arrays.
+// OUT_WIN: `scores` / `ws_den` are the row window's two arrays, `C` carries WIN_EXCLUDE besides the class count.
 template <int RS, int KIND, int OUT, int MODE>
 __global__ __launch_bounds__(TILE_THREADS, (RS <= 5 ? 4 : 2)) void nw_fused_kernel(
     const float* __restrict__ q, const float* __restrict__ s, const int64_t* __restrict__ sy,
@@ -446,7 +509,7 @@ __global__ __launch_bounds__(TILE_THREADS, (RS <= 5 ? 4 : 2)) void nw_fused_kern
     // ---- runs of equal consecutive labels inside this support tile (one wave)
     if (!out_is_cand(OUT) && wave == 0) {
         int lab[3];
-        load_tile_labels<BS>(sy, s0, N, C, lane, lab);
+        load_tile_labels<BS>(sy, s0, N, OUT == OUT_WIN ? C & (WIN_EXCLUDE - 1) : C, lane, lab);
         run_scan_wave<BS>(lab, lane, runid, runlab, nrun_s);
     }
 
@@ -523,10 +586,14 @@ int launch_fused_rs(const FusedArgs& a, const FusedPlan& p) {
     // OUT_CAND: CandOut's key / row arrays stand where the scores and the run labels go, k where the class count goes
     // (nw_fused_kernel); ws is all null then, and the row window's arrays (read only) stand where the tile maxima and
     // the run counts go.
-    float* scores = cand ? reinterpret_cast<float*>(cand->key) : a.scores;
+    // OUT_WIN: the head's row window stands where the scores and the tile sums go, its flag beside the class count; the
+    // kernel finds the tile sums behind the tile maxima (fused_den_after_m).
+    const bool head_window = p.out == OUT_WIN;
+    float* scores = cand ? reinterpret_cast<float*>(cand->key) : head_window ? reinterpret_cast<float*>(const_cast<int*>(a.win_lo)) : a.scores;
     int* lab = cand ? cand->row : ws.lab;
     const bool window = cand && cand->win_lo && cand->win_hi;
-    const int c_or_k = cand ? (cand->k | (window && cand->win_exclude ? CAND_EXCLUDE : 0)) : a.C;
+    const int c_or_k = cand ? (cand->k | (window && cand->win_exclude ? CAND_EXCLUDE : 0))
+                            : (a.C | (head_window && a.win_exclude ? WIN_EXCLUDE : 0));
     if (window) {
         ws.nrun = const_cast<int*>(cand->win_lo);
         ws.m = reinterpret_cast<float*>(const_cast<int*>(cand->win_hi));
@@ -555,6 +622,20 @@ int launch_fused_rs(const FusedArgs& a, const FusedPlan& p) {
             }
             NW_CHECK_LAUNCH();
             return NW_OK;
+        }
+    }
+    if (p.out == OUT_WIN) {   // the windowed head: the tile kernel of the windowed search at this shape, then the run merge
+        if constexpr (RS == 12) {
+            return NW_ERR_UNSUPPORTED;
+        } else {
+            if (p.persistent || p.run_tables || !mode_is_f16(p.mode) || !a.win_lo || !a.win_hi) return NW_ERR_UNSUPPORTED;
+            float* const den = ws.den;
+            if (den != ws.m + fused_den_after_m(p.n_stiles, a.B) || a.C >= WIN_EXCLUDE) return NW_ERR_UNSUPPORTED;
+            ws.den = reinterpret_cast<float*>(const_cast<int*>(a.win_hi));
+            if (p.mode == MODE_F16Q) NW_TILE(OUT_WIN, MODE_F16Q); else NW_TILE(OUT_WIN, MODE_F16);
+            ws.den = den;
+            NW_CHECK_LAUNCH();
+            return launch_merge_runs(ws, a.out, a.lse, a.m, a.den, a.num, a.B, a.C, p.n_stiles, BS, st);
         }
     }
     const int timer_slot = tile_timer_start(st);

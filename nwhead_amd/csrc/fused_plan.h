@@ -29,7 +29,9 @@ enum { MODE_REG = 0, MODE_DMA = 1, MODE_DMA_SN = 2, MODE_F16 = 3, MODE_F16Q = 4 
 constexpr bool mode_is_f16(int m) { return m == MODE_F16 || m == MODE_F16Q; }
 // What a tile leaves behind besides (OUT_NONE, OUT_SCORES) or instead of (OUT_CAND) its softmax partials: nothing, its
 // block of the (B,N) score matrix, or its best k scores per query (CandOut; split or half-precision operands, no labels, no merge).
-enum { OUT_NONE = 0, OUT_SCORES = 1, OUT_CAND = 2 };
+// OUT_WIN: the softmax partials of OUT_NONE over the bank rows that a per-query row window admits (FusedArgs::win_lo / win_hi,
+// nw_fwd_window_f32; split operands on nw_fused_kernel only, never the persistent kernels).  (3 is OUT_CAND_WIN, fused_impl.h.)
+enum { OUT_NONE = 0, OUT_SCORES = 1, OUT_CAND = 2, OUT_WIN = 4 };
 // The support operand: fp32 rows, split rows (nw_split_rows_f16x2) or half-precision rows (nw_pack_rows_f16).
 enum { FORM_F32 = 0, FORM_SPLIT = 1, FORM_HALF = 2 };
 
@@ -66,6 +68,8 @@ struct FusedArgs {
     int B, N, d, C;
     hipStream_t st;
     const CandOut* cand;
+    const int *win_lo, *win_hi;
+    int win_exclude;
 };
 int launch_fused(const FusedArgs& a, int form, int kind);   // plan_fused + the launcher of the score kind (fused.hip)
 

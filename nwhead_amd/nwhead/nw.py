@@ -220,7 +220,59 @@ class NWNet(nn.Module):
                                         knn_merge_fn=knn_merge_fn, search_precision=self.search_precision)
         return self.sharded_bank
 
-    def predict(self, x, mode='random'):
+    def _predict_leave_out(self, qfeat, rows, what):
+        """The 'full' head of the featurised queries ``qfeat`` over precompute()'s bank, query b without bank row rows[b]
+        (-1: with every row): ops.nw_head's row window [row, row + 1), excluded; -1 is the empty excluded window [0, 0)."""
+        if getattr(self, 'sharded_bank', None) is not None:
+            raise ops.NWHipError(f"{what}: a sharded bank is not served (a row window is rows of one resident bank); call "
+                                 "precompute()")
+        if not hasattr(self, 'full_feat'):
+            raise ops.NWHipError(f"{what} needs the bank of precompute()")
+        if not isinstance(self.kernel, _ScoreModule):
+            raise ops.NWHipError(f"{what} needs one of the built-in score kernels")
+        rows = torch.as_tensor(rows, device=qfeat.device)
+        if rows.shape != (qfeat.shape[0],) or rows.is_floating_point() or rows.dtype == torch.bool:
+            raise ValueError(f"{what}: leave_out is a ({qfeat.shape[0]},) integer tensor: the bank row of each query, or -1")
+        sfeat, sy = self.full_feat.to(qfeat.device), self.full_y.to(qfeat.device)
+        cache = getattr(self, 'full_cache', None)
+        if cache is None or not cache.matches(sfeat):   # the bank was replaced or updated since precompute()
+            cache = self.full_cache = ops.SplitBank(sfeat, labels=sy, precision=self.full_precision)
+        lo = rows.clamp(min=0)
+        hi = torch.where(rows < 0, lo, lo + 1)
+        with torch.no_grad():
+            return ops.nw_head(qfeat.detach(), sfeat, sy, self.n_classes, self.kernel.kind, self.kernel._logit_scale(),
+                               support_cache=cache, row_window=(lo, hi), exclude=True)
+
+    def predict_loo(self, rows=None, batch_size=256):
+        """Not in the reference: leave-one-out log-probabilities of the bank's own rows, (len(rows), n_classes) -- row i of
+        precompute()'s bank predicted from every row but itself (train-set accuracy without the self-match, label-noise
+        screening, model selection by LOO likelihood).  ``rows``: (R,) int64 bank rows, default all of them.  The queries
+        are full_feat[rows]: no featurizer pass; batches of ``batch_size``.  The exclusion happens inside the tile kernel
+        (ops.nw_head_window), before the softmax -- subtracting the self term afterwards cancels to nothing once the
+        nearest other row is far.  A full_precision="fp16" bank, and a bank whose labels are not class-sorted (several
+        environments), take ops.nw_head_window's score-matrix route: same result, a (batch, N) matrix per batch.
+        Honours return_mask like predict.  A sharded bank is not served: NWHipError."""
+        if getattr(self, 'sharded_bank', None) is None and hasattr(self, 'full_feat'):
+            N = self.full_feat.shape[0]
+            rows = torch.arange(N, device=self.full_feat.device) if rows is None else torch.as_tensor(rows, device=self.full_feat.device)
+            outs = [self._predict_leave_out(self.full_feat[r], r, 'predict_loo') for r in rows.split(max(int(batch_size), 1))]
+            out = torch.cat(outs) if outs else torch.empty(0, self.n_classes, device=self.full_feat.device)
+        else:
+            out = self._predict_leave_out(None, None, 'predict_loo')    # (raises: says why)
+        return (out, torch.full((len(out),), True)) if self.return_mask else out
+
+    def predict(self, x, mode='random', leave_out=None):
+        """leave_out (not in the reference; mode='full' over precompute()'s bank only): (B,) int64, the bank row of each
+        query or -1 for none -- query b is predicted without that row (see predict_loo).  Any other mode or a sharded bank:
+        NWHipError."""
+        if leave_out is not None:
+            if mode != 'full':
+                raise ops.NWHipError(f"predict(x, '{mode}', leave_out=...): only mode='full' over precompute()'s bank leaves "
+                                     "rows out (the other modes build their support per call)")
+            if getattr(self, 'sharded_bank', None) is not None or not hasattr(self, 'full_feat'):
+                self._predict_leave_out(None, None, "predict(x, 'full', leave_out=...)")    # (raises: says why)
+            out = self._predict_leave_out(self._eval_featurizer()(x).detach(), leave_out, "predict(x, 'full', leave_out=...)")
+            return (out, torch.full((len(x),), True)) if self.return_mask else out
         qfeat = self._eval_featurizer()(x)
         if mode == 'full' and getattr(self, 'sharded_bank', None) is not None:
             out = self.sharded_bank.predict(qfeat.detach())

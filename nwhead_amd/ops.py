@@ -371,6 +371,21 @@ def knn_route_for(bank, width, B, k, matches=None, **policy):
     return route
 
 
+HEAD_WINDOW_MAX_CLASSES = 160 * 1024 // 4 - 8     # the run merge's accumulators (fused_eligible)
+
+
+def head_window_route(*, split, sorted_copy, shape, pad, width, B, n_classes):
+    """Which route serves ``nw_head(..., row_window=...)`` for B queries of ``width`` columns over a prepared bank, over plain
+    facts like knn_route: "fused" (nw_fwd_window_f32: the window is applied in the tile epilogue, no score matrix) at EVERY
+    shape the kernel takes -- no size gate, the alternative is never the cheaper one -- that is whenever the bank holds
+    ``split`` rows that are the caller's (no class-sorted copy), the queries pad to them (_resolve_scores' conditions) and
+    N > 25; else "matrix" (nw_scores, a torch mask, nw_aggregate_f32): an fp16 or norms-only bank, a sorted copy, N <= 25."""
+    N, d = shape
+    fused = (split and not sorted_copy and width + pad == d and N > 25 and d % 32 == 0 and 32 <= d <= 1 << 20 and B > 0
+             and 1 <= n_classes <= HEAD_WINDOW_MAX_CLASSES)
+    return "fused" if fused else "matrix"
+
+
 KNN_MERGE_MAX_K, KNN_MERGE_MAX_SHARDS = 32, 64
 
 
@@ -466,6 +481,8 @@ class SplitBank:
       nw_fwd_opts.operand_form = 1) only where the call allows it -- no gradients, no weights, a shared support: training
       steps, weights, scores, influences and searches run on an fp16 bank as on a norms-only one.
     * scores (nw_scores' bank route, nw_knn's fused search; _resolve_scores): only split rows without a class-sorted copy.
+    * the head over a row window (nw_head(row_window=...), nw_head_window; head_window_route): fused on the same terms as the
+      scores -- split rows without a class-sorted copy, whose rows are the caller's -- else through the score matrix.
     * searches, rounded (nw_knn(rounded=True); _resolve_scores): only fp16-packed rows without a class-sorted copy; the
       queries are padded to the bank's width like everywhere else.
     * run tables (build_tables): named in the call's options only when its labels are the tensor the tables were built
@@ -736,8 +753,11 @@ class _NWHeadFn(torch.autograd.Function):
 
 
 def nw_head(q, s, sy, n_classes, kind="euclidean", logit_scale=None, return_weights=False,
-            support_norm2=None, support_cache=None, validate_labels=False):
+            support_norm2=None, support_cache=None, validate_labels=False, row_window=None, exclude=False):
     """NWHead.forward(x, sx, sy) -> (B,C) log-probs (and the (B,N) softmax weights on request).
+    row_window=(lo, hi) (not the default, which it leaves as it is bit for bit; needs ``support_cache``, inference only):
+    the head of query b over the rows lo[b] <= row < hi[b] of `s` alone, or with ``exclude=True`` over every other row --
+    nw_head_window, which says more.
     support_norm2: optional cached ``row_norm2(s)`` for a shared (N,d) support.
     support_cache: optional ``SplitBank(s)`` (the fast 'full' inference path; its docstring says what the call then reads).
     validate_labels: the reference's F.one_hot (nw.py:276) REFUSES labels outside [0, n_classes); the kernels skip such
@@ -763,11 +783,78 @@ def nw_head(q, s, sy, n_classes, kind="euclidean", logit_scale=None, return_weig
         _check_label_range(None, support_cache.label_max, n_classes)
     grad = torch.is_grad_enabled()
     needs_grad = grad and (q.requires_grad or s.requires_grad or (logit_scale is not None and logit_scale.requires_grad))
+    if row_window is not None:
+        if needs_grad or return_weights or support_cache is None:
+            raise ValueError("nw_head(row_window=...) is inference over a prepared bank: it needs support_cache and has no "
+                             "gradients and no return_weights")
+        return nw_head_window(q, s, sy, n_classes, support_cache, row_window, exclude, kind, logit_scale)
     call = _resolve(support_cache, q, s, sy, n_classes, return_weights, grad and s.requires_grad,
                     not (needs_grad or return_weights), 0, support_norm2, needs_grad)      # (by position: host-bound)
     if not needs_grad:   # inference: skip the autograd node (its bookkeeping costs more than the kernels at small sizes)
         return _NWHeadFn.forward(_NoCtx, call.q, call.s, logit_scale, call, int(n_classes), kid, bool(return_weights))
     return _NWHeadFn.apply(call.q, call.s, logit_scale, call, int(n_classes), kid, bool(return_weights))
+
+
+def _window_empty(lo, hi, exclude, N):
+    """(B,) bool: the queries whose window admits no row of an N-row bank (lo / hi clamped to [0, N] like the kernel does)."""
+    lo, hi = lo.clamp(0, N), hi.clamp(0, N)
+    return ((lo <= 0) & (hi >= N)) if exclude else (hi <= lo)
+
+
+def nw_head_window(q, s, sy, n_classes, bank, row_window, exclude=False, kind="euclidean", logit_scale=None, return_lse=False):
+    """``nw_head(q, s, sy, n_classes, support_cache=bank, row_window=(lo, hi), exclude=...)``: the head of every query over
+    its own ROW WINDOW of the bank -> (B,C) log-probs (with ``return_lse`` also the (B,) log-sum-exp of the admitted scores).
+    lo / hi: (B,) integer tensors on the device, rows of `s`, the tensor the bank was prepared from; query b sees the rows
+    lo[b] <= row < hi[b] only, or with ``exclude`` every other row (lo >= hi: the empty window; values are clamped to
+    [0, N]).  Leave-one-out prediction of bank rows is the window [i, i+1), excluded; one environment of a concatenated bank
+    or one class of a class-sorted one is a kept window, "every other" the same window excluded.  The softmax runs over the
+    admitted rows alone -- the window is applied to the scores before the maximum and the exponentials, so an excluded row
+    that would dominate the full softmax (a query's own copy in the bank, at distance 0) leaves no trace.  A query whose
+    window admits no row gets log(1e-12) in every class and lse = -inf.  Inference only.
+
+    Route (head_window_route): nw_fwd_window_f32 -- the split-fp16 tile kernel with the window in its epilogue, no (B,N)
+    matrix -- at every shape the kernel takes, whenever the bank holds split rows without a class-sorted copy and the
+    queries pad to its width; otherwise (a ``precision="fp16"`` or norms-only bank, a bank built from unsorted labels,
+    N <= 25) nw_scores over the bank, a torch mask and nw_aggregate_f32: the same result through the (B,N) score matrix."""
+    _need_hip(q, s, sy, logit_scale)
+    if not isinstance(bank, SplitBank):
+        raise TypeError("nw_head_window runs over a prepared bank: pass ops.SplitBank(support)")
+    if s.dim() != 2 or sy.dim() != 1 or sy.shape[0] != s.shape[0] or not bank.matches(s):
+        raise ValueError("nw_head_window: `s` (N,d) must be the tensor the bank was prepared from and `sy` its (N,) labels")
+    lib = _lib.load()
+    q = _f32c(q)
+    B, N, C = q.shape[0], s.shape[0], int(n_classes)
+    lo, hi = _row_window(row_window, B, q.device)
+    ls = None if logit_scale is None else _f32c(logit_scale)
+    kid = _kind_id(kind)
+    if kid == SCORE_KINDS["clip"] and ls is None:
+        raise ValueError("clip kernel needs logit_scale")
+    syc = sy if (sy.dtype == torch.int64 and sy.is_contiguous()) else sy.detach().to(torch.int64).contiguous()
+    out = torch.empty(B, C, dtype=torch.float32, device=q.device)
+    lse = torch.empty(B, dtype=torch.float32, device=q.device)
+    route = head_window_route(split=bank.split is not None, sorted_copy=bank.sorted_rows is not None, shape=bank.shape,
+                              pad=bank.pad, width=q.shape[1], B=B, n_classes=C)
+    if route == "fused":
+        call = _resolve_scores(bank, q)
+        st, d = _stream(q), call.q.shape[1]
+        ws, ws_bytes = _fwd_workspace(lib, B, N, d, C, q.device, st)
+        with _OnDevice(q.device):
+            _lib.check(lib.nw_fwd_window_f32(_ptr(call.q), _ptr(call.operand), _ptr(call.scale), _ptr(call.norm2), _ptr(syc),
+                                             _ptr(lo), _ptr(hi), int(bool(exclude)), _ptr(out), _ptr(lse), _ptr(ws), ws_bytes,
+                                             B, N, d, C, kid, _ptr(ls), st), "nw_fwd_window_f32")
+    elif B > 0:
+        cols = torch.arange(N, device=q.device)
+        keep = (cols >= lo[:, None]) & (cols < hi[:, None])
+        if exclude:
+            keep = ~keep
+        scores = nw_scores(q, s, kind, logit_scale, support_cache=bank).masked_fill_(~keep, float("-inf"))
+        with _OnDevice(q.device):
+            _lib.check(lib.nw_aggregate_f32(_ptr(scores), _ptr(syc), _ptr(out), _ptr(lse), None, B, N, C, 0, _stream(q)),
+                       "nw_aggregate_f32")
+        empty = _window_empty(lo, hi, exclude, N)     # (a softmax over nothing: the kernel's answer is not defined)
+        out = torch.where(empty[:, None], out.new_tensor(1e-12).log(), out)
+        lse = lse.masked_fill(empty, float("-inf"))
+    return (out, lse) if return_lse else out
 
 
 def nw_partials(q, s, sy, n_classes, kind="euclidean", logit_scale=None, support_cache=None):
