@@ -836,7 +836,7 @@ extern "C" int nw_bn_relu_nhwc_train_bwd_f32(const float* x, int64_t ldx, const 
     int G; int64_t rpc;
     stats_grid(rows, c, &G, &rpc);
     // small maps: at most 8192 chunk sums, merged by the apply workgroups themselves (no finalize launch)
-    const bool inline_fin = rows <= BN_INLINE_ROWS && c <= 1024 && knob(KNOB_BN_INLINE_FIN) != 0;
+    const bool inline_fin = rows <= BN_INLINE_ROWS && c <= 1024;
     if (inline_fin && (int64_t)G * c > BN_INLINE_GC) {
         int64_t g = BN_INLINE_GC / c;
         if (g < 1) g = 1;

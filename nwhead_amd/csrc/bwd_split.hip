@@ -390,11 +390,10 @@ int launch_xgemm(bool x_km, const float* X, int64_t ldx, int64_t x_rows, const f
     if (nwg + pend.blocks > 0x7fffffffLL || gy * gz > 0x7fffffffLL) return NW_ERR_INVALID_ARG;
     const dim3 grid((unsigned)(nwg + pend.blocks));
     // ring depth: deep and one workgroup per CU when there are at most ~one workgroup per CU anyway and K is long
-    const int nbuf_env = knob(KNOB_XGEMM_NBUF) == KNOB_UNSET ? 0 : knob(KNOB_XGEMM_NBUF);
-    const bool deep = nbuf_env ? nbuf_env == 6 : (gx * gy * gz <= 320 && p.k_chunk >= 6 * XK);
+    const bool deep = gx * gy * gz <= 320 && p.k_chunk >= 6 * XK;
     // more than two workgroups per CU's worth of tiles: two stages each, so that three are resident per CU and the whole
     // grid runs in one round (second product at T, 632 workgroups of 8 stages: 17.7 us against 20.3 with three stages)
-    const bool thin = nbuf_env ? nbuf_env == 2 : (!deep && gx * gy * gz > 512);
+    const bool thin = !deep && gx * gy * gz > 512;
     const size_t lds = (size_t)(deep ? 6 : thin ? 2 : 3) * XST_BYTES;
     const char* Xc = reinterpret_cast<const char*>(X);
     const char* Yc = reinterpret_cast<const char*>(Y);

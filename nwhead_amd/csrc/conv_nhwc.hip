@@ -982,7 +982,7 @@ int launch_conv_cfg(ConvP p, hipStream_t st, int64_t* moments_groups = nullptr, 
     grid = (grid + 7) / 8 * 8;
     // one output-channel tile: a workgroup's tiles are all rows of the same channels, and their moments are merged in its
     // registers -- grid x WN groups for the merge kernel instead of mtiles x WN (2058 -> 512 on the 56 x 56 layers)
-    p.macc = p.ntiles == 1 && knob(KNOB_CONV_MOMENTS_PER_TILE) <= 0;
+    p.macc = p.ntiles == 1;
     if (moments_groups) *moments_groups = (p.macc ? grid : (int64_t)p.mtiles) * C::WN;
     if (dry) return NW_OK;
     constexpr size_t lds = C::LDS + (NA == 4 && NB == 4 ? 4096 : 0);   // (+ the 128 x 128 tile's running moments, minima, maxima)
@@ -1127,7 +1127,6 @@ static int conv2d_nhwc_impl(const float* x, const float* amax_in, const float* w
         const int64_t rc = (BM - 1 + W - 1) / W, ic = (BM - 1 + H * W - 1) / (H * W);
         return BM + rc * (p.IP - W) + ic * pad * p.IP + 2 * p.IP + 2 <= BM + 192;
     };
-    const int force_gather = nw::knob(nw::KNOB_CONV_GATHER) == 1;
     if (Cin % 32) {   // ROWRUN: w_split is the split form of the (Cout, KH, 32) matrix [co][ky][kx * Cin + ci], zero-padded
         if (Cin == 4 && (reinterpret_cast<uintptr_t>(x) & 15) == 0) {
             if (Cout % 64 == 0) return nw::launch_conv_cfg<4, 2, 1, nw::CV_ROWRUN4>(p, st);
@@ -1146,7 +1145,7 @@ static int conv2d_nhwc_impl(const float* x, const float* amax_in, const float* w
 #define NW_CONV_TRY(NA_, NB_, WM_, BM_, BN_, COND_)                                                            \
     ++idx;                                                                                                      \
     if (Cout % BN_ == 0 && (force ? idx == force : ((COND_) && seen++ >= skip))) {                              \
-        if (k33 && patch_fits(BM_) && !force_gather)                                                            \
+        if (k33 && patch_fits(BM_))                                                                             \
             return nw::launch_conv_cfg<NA_, NB_, WM_, nw::CV_PATCH>(p, st, moments_groups, dry);                \
         return nw::launch_conv_cfg<NA_, NB_, WM_, nw::CV_GATHER>(p, st, moments_groups, dry);                   \
     }

@@ -497,8 +497,7 @@ bool wgrad_plan(int64_t n, int64_t H, int64_t W, int64_t Cin, int64_t Cout, int6
     int64_t ks = (target_wgs + tiles - 1) / tiles;   // (a batch of problems shares the chip: fewer chunks each)
     // at least 4 (3x3: 8, a chunk starts with four steps of rows around its first stage) stages per chunk: small planes are
     // latency-bound and want many workgroups
-    int64_t minst = pl->taps9 ? 8 : 4;   // (16 / 8 until round 3: K4 19.05 -> 18.83 ms with twice the workgroups on the small planes)
-    if (knob(KNOB_WGRAD_MIN_STAGES) > 0) minst = pl->taps9 ? knob(KNOB_WGRAD_MIN_STAGES) : (knob(KNOB_WGRAD_MIN_STAGES) + 1) / 2;
+    const int64_t minst = pl->taps9 ? 8 : 4;   // (16 / 8 until round 3: K4 19.05 -> 18.83 ms with twice the workgroups on the small planes)
     const int64_t maxks = (pl->nstage + minst - 1) / minst;
     if (ks > maxks) ks = maxks;
     if (ks < 1) ks = 1;
@@ -575,10 +574,9 @@ extern "C" int nw_conv2d_nhwc_wgrad_f16x2(const float* x, const float* amax_x, c
 
 // ---- a batch of weight gradients (nw_wgrad_job, include/nwhead_hip.h)
 static int batch_target_wgs(int64_t njobs) {
-    const int k = nw::knob(nw::KNOB_WGRAD_BATCH_WGS);
-    if (k > 0) return k > 256 ? 256 : k;   // (the jobs' workspace slices are sized for at most 256 workgroups per job: wgrad_job_ws)
     // the jobs share the chip: ~1024 workgroups in all, 64..256 per job (K4: 17.36-17.42 ms at 64 per job, 17.66-17.70 at 256:
-    // fewer chunks = smaller partial tiles and a shorter reduce)
+    // fewer chunks = smaller partial tiles and a shorter reduce; the jobs' workspace slices are sized for at most 256
+    // workgroups per job: wgrad_job_ws)
     const int64_t t = 1024 / (njobs > 0 ? njobs : 1);
     return (int)(t < 64 ? 64 : (t > 256 ? 256 : t));
 }

@@ -75,7 +75,7 @@ int tile_timer_read(double* total_us, int64_t* launches) {
 }
 
 namespace {
-// The device property and the on/off knobs the launch decision reads (plan_fused; the run merge keeps its two switches).
+// The device property and the on/off knob the launch decision reads (plan_fused).
 int device_cu_count() {
     static int n = [] {
         int dev = 0, v = 0;
@@ -131,15 +131,15 @@ namespace {
 constexpr int MTHREADS = 512, MENT = 4, MTPT = 16;
 // TMODE: where the per-class tables (count, first / last tile, up to MENT entries) live: 1 = LDS, built by every
 // workgroup (they fit up to a few thousand classes); 2 = global memory, built once per launch by
-// nw_class_tables_kernel (more classes than LDS holds: MQ = 1, results written directly); 0 = none (every class scans
-// every tile: only when there is no workspace for mode 2).
+// nw_class_tables_kernel (more classes than LDS holds: MQ = 1, results written directly).  (0 was "no tables, every class
+// scans every tile": 4.9 ms per call at T, and fused_layout always carves the workspace that mode 2 needs.)
 template <bool PARTIAL, int MQ, int TMODE>
 __global__ __launch_bounds__(MTHREADS) void nw_merge_runs_kernel(
     const float* __restrict__ ws_m, const float* __restrict__ ws_den, const int* __restrict__ ws_nrun,
     const int* __restrict__ ws_lab, const float* __restrict__ ws_num, float* __restrict__ out,
     float* __restrict__ lse, float* __restrict__ m_out, float* __restrict__ den_out,
     float* __restrict__ num_out, int B, int C, int n_stiles, int BS, const int* __restrict__ ctab) {
-    constexpr bool TABLES = TMODE != 0;
+    static_assert(TMODE == 1 || TMODE == 2, "the per-class tables live in LDS (1) or in the workspace (2)");
     constexpr bool LTAB = TMODE == 1;   // tables built here, in LDS
     constexpr int ML = MTHREADS / MQ;  // tile lanes per query
     constexpr int MNS = MQ + 1;        // row stride of res[class][query] in LDS: odd, the output phase reads columns
@@ -151,7 +151,7 @@ __global__ __launch_bounds__(MTHREADS) void nw_merge_runs_kernel(
     float* Ms = red + 2 * NW * MQ;                // [MQ]
     float* inv_s = Ms + MQ;                       // [MQ]
     int* lds_tab = reinterpret_cast<int*>(inv_s + MQ);
-    int* cnt = TMODE == 2 ? const_cast<int*>(ctab) : lds_tab;  // [C]   entries of class c   (TABLES only, like the next four)
+    int* cnt = TMODE == 2 ? const_cast<int*>(ctab) : lds_tab;  // [C]   entries of class c
     int* tlo = cnt + C;                             // [C]   first tile carrying c
     int* thi = tlo + C;                             // [C]   last tile carrying c
     int* ent = thi + C;                             // [C][MENT]  tile * BS + run, ascending
@@ -290,7 +290,7 @@ __global__ __launch_bounds__(MTHREADS) void nw_merge_runs_kernel(
         const int bb = min(b0 + q, B - 1);
         const float Mq = Ms[q];
         float acc = 0.f;
-        const int n = TABLES ? cnt[c] : MENT + 1;
+        const int n = cnt[c];
         if (n <= MENT) {
             int e[MENT];
             float v[MENT], mt[MENT];
@@ -307,7 +307,7 @@ __global__ __launch_bounds__(MTHREADS) void nw_merge_runs_kernel(
             for (int k = 0; k < MENT; ++k)
                 if (k < n) acc += v[k] * __builtin_amdgcn_exp2f(mt[k] - Mq);
         } else {
-            const int t0 = TABLES ? tlo[c] : 0, t1 = TABLES ? thi[c] : n_stiles - 1;
+            const int t0 = tlo[c], t1 = thi[c];
             for (int t = t0 + sub; t <= t1; t += P) {
                 const int nr = ws_nrun[t];
                 const float f = __builtin_amdgcn_exp2f(ws_m[(size_t)t * B + bb] - Mq);
@@ -501,11 +501,7 @@ int launch_merge_runs(const FusedWs& ws, float* out, float* lse, float* m, float
     // 32 queries x 16 tile lanes per workgroup when a query has few tiles (a shard of the bank), else 16 x 32;
     // below 512 queries one workgroup per query (T: 256 workgroups, one per CU)
     int mq = 1;
-    const int force_mq = knob(KNOB_MERGE_MQ) == KNOB_UNSET ? 0 : knob(KNOB_MERGE_MQ);   // timing experiments
-    if (force_mq == 1 || force_mq == 16 || force_mq == 32) {
-        mq = force_mq;
-        if (lds_bytes(mq, true) > cap) mq = 1;
-    } else if (B >= 512 && !env_flag(KNOB_MERGE_PER_QUERY)) {
+    if (B >= 512) {
         mq = n_stiles >= 128 ? 16 : 32;
         if (lds_bytes(mq, true) > cap) mq = 16;
         if (lds_bytes(mq, true) > cap) mq = 1;
@@ -518,13 +514,10 @@ int launch_merge_runs(const FusedWs& ws, float* out, float* lse, float* m, float
                        ws.lab, ws.num, out, lse, m, den, num, B, C, n_stiles, BS, ws.ctab)
     if (!tables) {
         // more classes than LDS holds tables for (C > ~4200): the tables go to the workspace, built once per launch
+        // in ws.ctab, which fused_layout carves for every class count
         // (measured at C = 5000: 4.9 ms per call at T when every class scanned every tile, 35 ms at B = 4096, N = 50000)
-        if (ws.ctab && !env_flag(KNOB_MERGE_NO_GLOBAL_TABLES)) {
-            hipLaunchKernelGGL(nw_class_tables_kernel, dim3(1), dim3(1024), 0, st, ws.nrun, ws.lab, n_stiles, BS, C, ws.ctab);
-            if (out) NW_MERGE(false, 1, 2); else NW_MERGE(true, 1, 2);
-        } else {
-            if (out) NW_MERGE(false, 1, 0); else NW_MERGE(true, 1, 0);
-        }
+        hipLaunchKernelGGL(nw_class_tables_kernel, dim3(1), dim3(1024), 0, st, ws.nrun, ws.lab, n_stiles, BS, C, ws.ctab);
+        if (out) NW_MERGE(false, 1, 2); else NW_MERGE(true, 1, 2);
     } else if (mq == 1) {
         if (out) NW_MERGE(false, 1, 1); else NW_MERGE(true, 1, 1);
     } else if (mq == 16) {
@@ -577,18 +570,18 @@ bool half_form_shape_ok(int64_t d) {   // whole 64-k stages, at least three of t
 }
 
 namespace {
-struct TileLds {   // dynamic LDS of the tile kernels at one tile height
-    size_t reg, dma;           // nw_fused_kernel: register-staged / LDS-DMA loaders
-    size_t p64, p64x2, p128;   // nw_fused_f16p_kernel: variants 0, 1, 2 (RS > 5)
+struct TileLds {   // dynamic LDS of nw_fused_kernel at one tile height: register-staged / LDS-DMA loaders
+    size_t reg, dma;
 };
 template <int RS>
 constexpr TileLds tile_lds() {
-    if constexpr (RS > 5)
-        return {FUSED_HDR + TileCfg<RS>::STAGE_BYTES, FUSED_HDR + DmaCfg<RS>::STAGE_BYTES, PCfg<RS, 1, false>::LDS_BYTES,
-                PCfg<RS, 1, true>::LDS_BYTES, PCfg<RS, 2, false>::LDS_BYTES};
-    else
-        return {FUSED_HDR + TileCfg<RS>::STAGE_BYTES, FUSED_HDR + DmaCfg<RS>::STAGE_BYTES, 0, 0, 0};
+    return {FUSED_HDR + TileCfg<RS>::STAGE_BYTES, FUSED_HDR + DmaCfg<RS>::STAGE_BYTES};
 }
+// nw_fused_f16p_kernel runs on tiles of 128 supports only (RS = 8): its variants 0, 1, 2.  Two workgroups of variant 1
+// share a CU's LDS; one of variant 2 has it to itself.
+constexpr size_t P64_LDS = PCfg<8, 1, false>::LDS_BYTES, P64X2_LDS = PCfg<8, 1, true>::LDS_BYTES,
+                 P128_LDS = PCfg<8, 2, false>::LDS_BYTES;
+static_assert(P128_LDS <= 160 * 1024 && P64X2_LDS <= 80 * 1024, "the LDS of one CU / of half a CU");
 TileLds tile_lds_of(int rs) {
     return rs == 2 ? tile_lds<2>() : rs == 4 ? tile_lds<4>() : rs == 5 ? tile_lds<5>() : rs == 6 ? tile_lds<6>()
          : rs == 8 ? tile_lds<8>() : rs == 10 ? tile_lds<10>() : tile_lds<12>();
@@ -637,9 +630,9 @@ FusedPlan plan_fused(int64_t B, int64_t N, int64_t d, int64_t C, int form, int o
         // of the tile rows
         if (!p.dma && (p.rs & 1)) return refuse(NW_ERR_UNSUPPORTED);
         // many tiles per CU on split operands: the persistent kernel (fused_f16p.h).  RS = 8 is the tallest tile whose
-        // build stays under 256 VGPRs.
-        p.persistent = split && out == OUT_NONE && p.rs > 5 && (p.rs == 8 || env_flag(KNOB_PERSISTENT_ANY_RS)) &&
-                       p.grid >= 4 * (int64_t)cus && d >= 3 * BK && !env_flag(KNOB_NO_PERSISTENT);
+        // build stays under 256 VGPRs, and the only height it is built for.
+        p.persistent = split && out == OUT_NONE && p.rs == 8 && p.grid >= 4 * (int64_t)cus && d >= 3 * BK &&
+                       !env_flag(KNOB_NO_PERSISTENT);
     }
     p.run_tables = p.persistent && out != OUT_CAND;   // runs of equal labels per support tile: once per launch, or the bank's
     if (p.run_tables && p.BS > 192) return refuse(NW_ERR_UNSUPPORTED);   // nw_run_tables_kernel: three rows per lane
@@ -667,18 +660,15 @@ FusedPlan plan_fused(int64_t B, int64_t N, int64_t d, int64_t C, int form, int o
         int variant = form == FORM_HALF ? 3 : knob(KNOB_PVAR);   // NW_PVAR forces one of 0-3
         if (variant < 0 || variant > 3) {
             const double rows64 = 1.15 * ((B + 63) / 64 * 64);
-            variant = (p.rs == 8 && (B + 255) / 256 * 256 <= rows64) ? 3 : ((B + 127) / 128 * 128 <= rows64) ? 2 : 1;
+            variant = ((B + 255) / 256 * 256 <= rows64) ? 3 : ((B + 127) / 128 * 128 <= rows64) ? 2 : 1;
         }
-        if (variant == 3 && p.rs != 8) variant = 2;
-        if (variant == 2 && lds.p128 > 160 * 1024) variant = 0;   // the LDS of one CU / of half a CU
-        if (variant == 1 && lds.p64x2 > 80 * 1024) variant = 0;
         p.variant = variant;
         p.workgroups = variant == 1 ? 2 * wgs : wgs;
         // query tiles kept L2-resident per XCD (NW_QG = 1..64, else 8); variant 3: the same bytes of queries as with
         // 128-query tiles
         const int qg = (knob(KNOB_QG) >= 1 && knob(KNOB_QG) <= 64) ? knob(KNOB_QG) : 8;
         p.qgroup = variant != 3 ? qg : qg >= 2 ? qg / 2 : 1;
-        p.lds_bytes = variant == 3 ? (size_t)P12::LDS_BYTES : variant == 2 ? lds.p128 : variant == 1 ? lds.p64x2 : lds.p64;
+        p.lds_bytes = variant == 3 ? (size_t)P12::LDS_BYTES : variant == 2 ? P128_LDS : variant == 1 ? P64X2_LDS : P64_LDS;
         return p;
     }
     if (split) {

@@ -228,7 +228,7 @@ __global__ __launch_bounds__(TILE_THREADS, TWO ? 4 : 2) void nw_fused_f16p_kerne
     constexpr bool SINGLE = TWO || QB > 1;  // single-buffered fragments
     static_assert(!(TWO && QB > 1), "two 128-query workgroups do not fit the LDS of a CU");
     static_assert(P::THREADS == TILE_THREADS, "launch bounds");
-    static_assert(RS > 5, "the persistent kernel is built for the tall tiles");
+    static_assert(RS == 8, "the persistent kernel is built for tiles of 128 supports");
     extern __shared__ __attribute__((aligned(16))) char smem[];
     float* hdr0 = reinterpret_cast<float*>(smem);  // NHB header buffers of HDR_F floats, by tile index mod NHB
     float4* stage = reinterpret_cast<float4*>(smem + P::HDR_BYTES);

@@ -697,26 +697,27 @@ int launch_p12(const FusedPlan& p, const FusedArgs& a, const QueryRows& q, const
     return NW_OK;
 }
 
-// The persistent kernel of the plan's variant (and, for variant 3, form); the run tables are the caller's job.
+// The persistent kernel of the plan's variant (and, for variant 3, form); the run tables are the caller's job.  The
+// persistent kernels exist for tiles of 128 supports only: plan_fused gives no other height a persistent plan.
 template <int RS, int KIND>
 int launch_f16p(const FusedArgs& a, const FusedPlan& p, const QueryRows& q, const FusedWs& ws) {
-    if constexpr (RS > 5) {
+    if constexpr (RS == 8) {
 #define NW_LAUNCH_P(TWO_, QB_)                                                                                        \
     hipLaunchKernelGGL((nw_fused_f16p_kernel<RS, KIND, TWO_, QB_>), dim3(p.workgroups), dim3(TILE_THREADS), p.lds_bytes, \
                        a.st, q.rows, a.s, a.s_norm2, a.s_scale, q.norm2, q.scale, a.ls, ws.runid, ws.nrun, ws.bnd, ws.m, \
                        ws.den, ws.num, a.B, a.N, a.d, p.n_stiles, (a.B + 64 * (QB_) - 1) / (64 * (QB_)), p.qgroup)
         switch (p.variant) {
-            case 3:   // (plan_fused gives variant 3 to tiles of 128 supports only)
-                if constexpr (RS == 8) return p.form == FORM_HALF ? launch_p12<KIND, true, false>(p, a, q, ws) : launch_p12<KIND, false, false>(p, a, q, ws);
-                return NW_ERR_UNSUPPORTED;
+            case 3: return p.form == FORM_HALF ? launch_p12<KIND, true, false>(p, a, q, ws) : launch_p12<KIND, false, false>(p, a, q, ws);
             case 2: NW_LAUNCH_P(false, 2); break;
             case 1: NW_LAUNCH_P(true, 1); break;
             default: NW_LAUNCH_P(false, 1); break;
         }
 #undef NW_LAUNCH_P
         NW_CHECK_LAUNCH();
+        return NW_OK;
+    } else {
+        return NW_ERR_UNSUPPORTED;
     }
-    return NW_OK;
 }
 }  // namespace
 

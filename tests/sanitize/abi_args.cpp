@@ -106,6 +106,7 @@ int main() {
     }
     EXPECT(nw_debug_set(nullptr, 1), NW_ERR_INVALID_ARG);
     EXPECT(nw_debug_set("no_such_knob", 1), NW_ERR_INVALID_ARG);
+    EXPECT(nw_debug_set("persistent_any_rs", 1), NW_ERR_INVALID_ARG);   // a removed knob is an unknown name
     EXPECT(nw_debug_set("qg", 8), NW_OK);
     {   // the launch decision as a value: pure host arithmetic, "no device" answers 256 CUs
         nw_fwd_plan pl;

@@ -207,6 +207,55 @@ def test_forward_vs_oracle(dev, ops, O, B, N, d, C, kind, dist):
         close(out, O.nw_head_f32(q, s, sy, C, kind).numpy(), rtol=RTOL, atol=3e-5)
 
 
+def _out_and_lse(ops, q, s, sy, C):
+    """The head's log-probabilities and the per-query log-sum-exp the same launch writes for the backward (the autograd
+    node keeps it)."""
+    out = ops.nw_head(q.clone().requires_grad_(True), s, sy, C)
+    return out.detach(), out.grad_fn.saved_tensors[4]
+
+
+@pytest.mark.parametrize("sorted_labels", [False, True])
+def test_run_merge_with_more_classes_than_lds_holds_tables_for(dev, ops, O, sorted_labels):
+    """The run merge keeps its per-class tables in LDS while C * 9 * 4 + 72 bytes fit in 150 KB (C <= 4265); past that
+    nw_class_tables_kernel builds them once in the workspace and one workgroup per query reads them from there
+    (nw_merge_runs_kernel<., 1, 2>).  4300 classes, 40 of them present: most classes have no entry, some have more than the
+    four a table keeps (unsorted labels: found again by scanning the class's tiles)."""
+    B, N, d, C = 8, 600, 32, 4300
+    g = torch.Generator().manual_seed(4300)
+    q, s = torch.randn(B, d, generator=g), torch.randn(N, d, generator=g)
+    present = torch.cat([torch.randperm(C - 2, generator=g)[:38] + 1, torch.tensor([0, C - 1])])
+    sy = present[torch.randint(0, len(present), (N,), generator=g)]
+    if sorted_labels:
+        sy = sy.sort().values
+    out, lse = _out_and_lse(ops, q.to(dev), s.to(dev), sy.to(dev), C)
+    ref = O.nw_head_f64(q, s, sy, C)
+    close(out, ref.numpy(), rtol=RTOL, atol=3e-5)
+    close(lse, torch.logsumexp(O.scores_f64(q, s), dim=-1).numpy(), rtol=RTOL, atol=3e-5)
+    close(ops.nw_head(q.to(dev), s.to(dev), sy.to(dev), C), ref.numpy(), rtol=RTOL, atol=3e-5)   # inference: no lse asked for
+    if sorted_labels:   # the partials form of the same merge (nw_merge_runs_kernel<true, 1, 2>), once
+        h = N // 2
+        rows = torch.stack([ops.nw_partials(q.to(dev), s[a:b].to(dev), sy[a:b].to(dev), C).view(-1) for a, b in ((0, h), (h, N))])
+        close(ops.nw_merge(rows, B, C), ref.numpy(), rtol=RTOL, atol=3e-5)
+
+
+@pytest.mark.parametrize("N,n_ref", [(200, 512), (24576, 24)])
+def test_run_merge_blocked_over_queries(dev, ops, O, N, n_ref):
+    """From 512 queries up a merge workgroup takes 32 consecutive queries, or 16 once a query has 128 support tiles or more
+    (24576 supports: 128 tiles of 192 rows, the tallest tile, and more of any other).  `n_ref` queries, spread over the
+    workgroups and over the places inside one, against the fp64 oracle (its (B, N, d) cube of differences sets the count);
+    every row sums to 1 + C * eps."""
+    B, d, C = 512, 32, 10
+    g = torch.Generator().manual_seed(N)
+    q, s = torch.randn(B, d, generator=g), torch.randn(N, d, generator=g)
+    sy = torch.randint(0, C, (N,), generator=g)
+    out, lse = _out_and_lse(ops, q.to(dev), s.to(dev), sy.to(dev), C)
+    p = out.exp().sum(-1).cpu()
+    assert torch.allclose(p, torch.full_like(p, 1 + C * 1e-12), atol=2e-5)
+    rows = torch.arange(n_ref) * (B - 1) // (n_ref - 1)       # 0 ... B - 1; a stride of 22 walks through the places of a group
+    close(out[rows.to(dev)], O.nw_head_f64(q[rows], s, sy, C).numpy(), rtol=RTOL, atol=3e-5)
+    close(lse[rows.to(dev)], torch.logsumexp(O.scores_f64(q[rows], s), dim=-1).numpy(), rtol=RTOL, atol=3e-5)
+
+
 def test_empty_and_ragged(dev, ops):
     C = 5
     q = torch.randn(4, 16, device=dev)

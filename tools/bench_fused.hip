@@ -1,8 +1,9 @@
 // Diagnostic harness: phase stamps of nw_fused_kernel (build with -DNW_DIAG_FUSED).
-// Persistent kernels (argv[5] = 2): NW_PVAR=0 / 1 / 2 pick the variants of fused_f16p.h, NW_PVAR=3 the 256-query kernel of
-// fused_f16p12.h (-DNW_BENCH_RS=8); both take -DNW_ABL_NODMA / -DNW_ABL_NORD / -DNW_ABL_NOEPI.
+// Persistent kernels (argv[5] = 2; they exist for tiles of 128 supports only: build with -DNW_BENCH_RS=8, at another height
+// the mode is refused): NW_PVAR=0 / 1 / 2 pick the variants of fused_f16p.h, NW_PVAR=3 the 256-query kernel of
+// fused_f16p12.h; both take -DNW_ABL_NODMA / -DNW_ABL_NORD / -DNW_ABL_NOEPI.
 // Build: hipcc -O3 --offload-arch=gfx950 -I nwhead_amd/csrc -DNW_DIAG_FUSED [-DNW_BENCH_RS=8] tools/bench_fused.hip
-//        nwhead_amd/csrc/split.hip -o tools/bench_fused
+//        nwhead_amd/csrc/split.hip -o tools/bench_fused      (tile height in 16-row blocks; 10 when not given)
 #include <hip/hip_runtime.h>
 #include <cstdio>
 #include <cstdlib>
@@ -23,6 +24,13 @@ int main(int argc, char** argv) {
 #define NW_BENCH_RS 10
 #endif
     constexpr int RS = NW_BENCH_RS, BS = 16 * RS;
+    const bool f16 = argc > 5 && atoi(argv[5]) >= 1;
+    const bool persistent = argc > 5 && atoi(argv[5]) == 2;
+    const bool qraw = argc > 5 && atoi(argv[5]) == 3;   // MODE_F16Q: raw fp32 queries, split in the consumer waves
+    if (persistent && RS != 8) {
+        fprintf(stderr, "bench_fused: the persistent kernels run on tiles of 128 supports only; this build has NW_BENCH_RS=%d (rebuild with -DNW_BENCH_RS=8)\n", RS);
+        return 2;
+    }
     std::vector<float> hq((size_t)B * d), hs((size_t)N * d);
     srand(1);
     for (auto& v : hq) v = (rand() / (float)RAND_MAX) * 2 - 1;
@@ -30,9 +38,6 @@ int main(int argc, char** argv) {
     std::vector<int64_t> hy(N);
     for (int j = 0; j < N; ++j) hy[j] = (int64_t)j * C / N;
     const int n_stiles = (N + BS - 1) / BS, n_qtiles = (B + 63) / 64;
-    const bool f16 = argc > 5 && atoi(argv[5]) >= 1;
-    const bool persistent = argc > 5 && atoi(argv[5]) == 2;
-    const bool qraw = argc > 5 && atoi(argv[5]) == 3;   // MODE_F16Q: raw fp32 queries, split in the consumer waves
     float *q, *s, *sn, *m, *den, *num, *qsp, *ssp, *qsc, *ssc, *qn; int64_t* sy; int *nrun, *lab; unsigned long long* dbg;
     hipMalloc(&qsp, hq.size() * 4); hipMalloc(&ssp, hs.size() * 4); hipMalloc(&qsc, B * 4); hipMalloc(&ssc, N * 4); hipMalloc(&qn, B * 4);
     hipMalloc(&q, hq.size() * 4); hipMalloc(&s, hs.size() * 4); hipMalloc(&sn, N * 4); hipMalloc(&sy, N * 8);
@@ -64,14 +69,11 @@ int main(int argc, char** argv) {
     plan.form = FORM_SPLIT, plan.rs = RS, plan.BS = BS, plan.n_stiles = n_stiles, plan.n_qtiles = n_qtiles, plan.mode = MODE_F16;
     plan.persistent = plan.run_tables = plan.split_queries = true;
     plan.variant = getenv("NW_PVAR") ? atoi(getenv("NW_PVAR")) : 2;
-    if (plan.variant == 3 && RS != 8) plan.variant = 2;
-    if (plan.variant == 2 && PCfg<RS, 2, false>::LDS_BYTES > 160 * 1024) plan.variant = 0;   // plan_fused's LDS-size fallbacks
-    if (plan.variant == 1 && PCfg<RS, 1, true>::LDS_BYTES > 80 * 1024) plan.variant = 0;
     plan.workgroups = plan.variant == 1 ? 512 : 256;
     plan.qgroup = getenv("NW_QG") ? atoi(getenv("NW_QG")) : 8;
     if (plan.variant == 3) plan.qgroup = std::max(1, plan.qgroup / 2);
-    plan.lds_bytes = plan.variant == 3 ? (size_t)P12::LDS_BYTES : plan.variant == 2 ? (size_t)PCfg<RS, 2, false>::LDS_BYTES
-                     : plan.variant == 1 ? (size_t)PCfg<RS, 1, true>::LDS_BYTES : (size_t)PCfg<RS, 1, false>::LDS_BYTES;
+    plan.lds_bytes = plan.variant == 3 ? (size_t)P12::LDS_BYTES : plan.variant == 2 ? (size_t)PCfg<8, 2, false>::LDS_BYTES
+                     : plan.variant == 1 ? (size_t)PCfg<8, 1, true>::LDS_BYTES : (size_t)PCfg<8, 1, false>::LDS_BYTES;
     FusedArgs args = {};
     args.s = ssp, args.sy = sy, args.s_norm2 = sn, args.s_scale = ssc, args.B = B, args.N = N, args.d = d, args.C = C;
     const QueryRows qrows = {qsp, qn, qsc};
