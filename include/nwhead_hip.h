@@ -768,6 +768,18 @@ typedef struct nw_fwd_plan {
 } nw_fwd_plan;
 int nw_debug_fwd_plan(int64_t B, int64_t N, int64_t d, int64_t C, int form, int outputs, int k, int norms, int kind,
                       int persistent_wgs, int cus, nw_fwd_plan *plan);
+/* The map of the forward workspace (nw_fwd_workspace_bytes) for one shape, as every forward entry point carves it: no launch,
+ * no device needed.  Six areas in this order, each starting on a multiple of 256 bytes where the one before ends, the last
+ * ending at `total`: 0 main (the (B,N) scores or the fused partials), 1-3 rows, scales and norms of the split / packed
+ * queries, 4 the log-sum-exp slot, 5 the slice partials of the sliced aggregation (empty when n_slices == 1).
+ * NW_ERR_INVALID_ARG for a null pointer or a negative size; B <= 0 or N <= 0: all zeros. */
+#define NW_FWD_AREAS 6
+typedef struct nw_fwd_layout {
+    uint64_t off[NW_FWD_AREAS], bytes[NW_FWD_AREAS];
+    uint64_t total;                             /* == nw_fwd_workspace_bytes(B, N, d, C) */
+    int32_t n_slices, reserved;
+} nw_fwd_layout;
+int nw_debug_fwd_layout(int64_t B, int64_t N, int64_t d, int64_t C, nw_fwd_layout *layout);
 
 #ifdef __cplusplus
 }

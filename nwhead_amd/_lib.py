@@ -103,6 +103,7 @@ SIGNATURES = {
     "nw_debug_tile_timing": (_int, [_int]),
     "nw_debug_tile_timing_read": (_int, [C.POINTER(C.c_double), C.POINTER(C.c_int64)]),
     "nw_debug_fwd_plan": (_int, [_i64, _i64, _i64, _i64, _int, _int, _int, _int, _int, _int, _int, _p]),
+    "nw_debug_fwd_layout": (_int, [_i64, _i64, _i64, _i64, _p]),
 }
 
 _lib = None
@@ -173,6 +174,22 @@ def fwd_plan(B, N, d, C_, form="split", outputs="log_probs", k=0, norms=True, ki
     check(load().nw_debug_fwd_plan(B, N, d, C_, FORMS[form], OUTPUTS[outputs], k, int(norms), SCORE_KINDS[kind],
                                    persistent_wgs, cus, C.byref(p)), "nw_debug_fwd_plan")
     return p
+
+
+FWD_AREAS = ("main", "q_rows", "q_scale", "q_norm2", "lse", "slices")
+
+
+class FwdLayout(C.Structure):
+    """nw_fwd_layout (include/nwhead_hip.h): offset and size of the forward workspace's areas, in FWD_AREAS order."""
+    _fields_ = [("off", C.c_uint64 * len(FWD_AREAS)), ("bytes", C.c_uint64 * len(FWD_AREAS)), ("total", C.c_uint64),
+                ("n_slices", C.c_int32), ("reserved", C.c_int32)]
+
+
+def fwd_layout(B, N, d, C_):
+    """The library's map of the forward workspace for one shape (nw_debug_fwd_layout): no launch, no device needed."""
+    m = FwdLayout()
+    check(load().nw_debug_fwd_layout(B, N, d, C_, C.byref(m)), "nw_debug_fwd_layout")
+    return m
 
 
 # Environment switches of the Python layer (the C library never reads the environment).  NW_SPLIT_ALWAYS travels in every

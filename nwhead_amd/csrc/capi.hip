@@ -6,7 +6,6 @@
 #include "fused_plan.h"
 
 namespace {
-inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
 inline bool bad_kind(int kind) { return kind < NW_SCORE_EUCLIDEAN || kind > NW_SCORE_CLIP; }
 }  // namespace
 
@@ -136,22 +135,20 @@ extern "C" int nw_scores_f32(const float* q, const float* s, float* scores, int6
 }
 
 // Scratch: the fused path keeps per-tile softmax statistics and label-run sums (fused.hip); the
-// two-kernel path (per-query supports, N <= 25, weights requested) one (B,N) score matrix.
-static size_t agg_slice_bytes(int64_t B, int64_t N, int64_t C) {
-    const int S = nw::aggregate_slices(B, N);
-    return S > 1 ? align256((size_t)S * (size_t)B * (size_t)(2 + (C > 0 ? C : 0)) * sizeof(float)) : 0;
+// two-kernel path (per-query supports, N <= 25, weights requested) one (B,N) score matrix.  nw::FwdLayout is the map.
+extern "C" size_t nw_fwd_workspace_bytes(int64_t B, int64_t N, int64_t d, int64_t C) {
+    return nw::fwd_layout(B, N, d, C, nullptr).total;
 }
 
-extern "C" size_t nw_fwd_workspace_bytes(int64_t B, int64_t N, int64_t d, int64_t C) {
-    (void)d; (void)C;
-    if (B <= 0 || N <= 0) return 0;
-    const size_t plain = align256((size_t)B * (size_t)N * sizeof(float));
-    const size_t fused = align256(nw::fused_workspace_bytes(B, N, d, C));
-    // + room for the split-fp16 form of the queries (rows, scales, norms) behind the fused area
-    const size_t qsplit = align256((size_t)B * (size_t)d * sizeof(float)) + 2 * align256((size_t)B * sizeof(float));
-    // + B floats for the log-sum-exp when weights / influences are derived from the fused kernel's scores
-    // + the slice partials of the two-kernel path's aggregation (few queries, long rows: nw::aggregate_slices)
-    return (plain > fused ? plain : fused) + qsplit + align256((size_t)B * sizeof(float)) + agg_slice_bytes(B, N, C);
+extern "C" int nw_debug_fwd_layout(int64_t B, int64_t N, int64_t d, int64_t C, nw_fwd_layout* layout) {
+    if (!layout || B < 0 || N < 0 || d < 0 || C < 0) return NW_ERR_INVALID_ARG;
+    const nw::FwdLayout L = nw::fwd_layout(B, N, d, C, nullptr);
+    const nw::FwdLayout::Area* const areas[NW_FWD_AREAS] = {&L.main, &L.q_rows, &L.q_scale, &L.q_norm2, &L.lse, &L.slices};
+    *layout = {};
+    for (int i = 0; i < NW_FWD_AREAS; ++i) layout->off[i] = areas[i]->off, layout->bytes[i] = areas[i]->bytes;
+    layout->total = L.total;
+    layout->n_slices = L.n_slices;
+    return NW_OK;
 }
 
 extern "C" int nw_row_norm2_f32(const float* x, float* n2, int64_t rows, int64_t d, void* stream) {
@@ -161,13 +158,12 @@ extern "C" int nw_row_norm2_f32(const float* x, float* n2, int64_t rows, int64_t
     return nw::launch_rownorm2(x, n2, rows, d, static_cast<hipStream_t>(stream));
 }
 
-extern "C" int nw_fwd_f32(const float* q, const float* s, const int64_t* sy, const float* s_norm2,
-                          const float* s_split, const float* s_scale, float* out, float* scores_out, float* lse_out, float* weights_out, void* workspace,
-                          size_t workspace_bytes, int64_t B, int64_t N, int64_t d, int64_t C,
-                          int kind, const float* logit_scale_dev, int sup_batched,
-                          int labels_batched, const nw_fwd_opts* opts, void* stream) {
-    OptsGuard opts_guard(opts);
-    hipStream_t st = static_cast<hipStream_t>(stream);
+// nw_fwd_f32 inside its options guard.  carved: the workspace as an entry point that has checked the shape already carved it
+// (nw_fwd_influence_f32), or null.
+static int fwd_f32(const float* q, const float* s, const int64_t* sy, const float* s_norm2, const float* s_split,
+                   const float* s_scale, float* out, float* scores_out, float* lse_out, float* weights_out, void* workspace,
+                   size_t workspace_bytes, const nw::FwdLayout* carved, int64_t B, int64_t N, int64_t d, int64_t C, int kind,
+                   const float* logit_scale_dev, int sup_batched, int labels_batched, hipStream_t st) {
     if (B < 0 || N < 0 || d < 0 || C < 0) return NW_ERR_INVALID_ARG;
     if (bad_kind(kind)) return NW_ERR_UNSUPPORTED;
     if (B == 0) return NW_OK;
@@ -177,55 +173,55 @@ extern "C" int nw_fwd_f32(const float* q, const float* s, const int64_t* sy, con
     if (labels_batched && !sup_batched) return NW_ERR_INVALID_ARG;
     const int form = nw::fwd_opts().operand_form;
     if (form != 0 && form != 1) return NW_ERR_INVALID_ARG;
+    const nw::FwdLayout L = carved ? *carved : nw::fwd_layout(B, N, d, C, workspace);
     // the fused launch's operands: fp32 supports; the split / half-precision routes below swap the bank's rows in
     nw::FusedArgs a = {q, s, sy, s_norm2, nullptr, logit_scale_dev, out, scores_out, lse_out, nullptr, nullptr, nullptr,
-                       workspace, workspace_bytes, (int)B, (int)N, (int)d, (int)C, st, nullptr};
+                       &L, (int)B, (int)N, (int)d, (int)C, st, nullptr};
     if (form == 1) {
         const int rc = half_form_check(q, s, s_norm2, s_split, s_scale, scores_out ? scores_out : weights_out,
                                        sup_batched || labels_batched, B, N, d, C);
         if (rc != NW_OK) return rc;
         if (N > 0 && C > 0) {
-            if (!workspace || workspace_bytes < nw_fwd_workspace_bytes(B, N, d, C)) return NW_ERR_WORKSPACE;
+            if (!L.fits(workspace_bytes)) return NW_ERR_WORKSPACE;
             a.s = s_split, a.s_scale = s_scale;
             return nw::launch_fused(a, nw::FORM_HALF, kind);
         }
     }
     // Softmax weights on request: the fused kernel writes the scores where the weights go and one in-place pass
-    // normalises them with the merge's log-sum-exp (w = exp(score - lse)); the two-kernel fallback below streams
-    // the (B,N) matrix five times.
+    // normalises them with the merge's log-sum-exp (w = exp(score - lse), the workspace's lse area when the caller asks
+    // for none); the two-kernel fallback below streams the (B,N) matrix five times.
     float* sc_buf = scores_out ? scores_out : weights_out;
     if (N > 0 && C > 0 && !sup_batched && nw::fused_eligible(q, s, B, N, d, C) &&
         (!sc_buf || (reinterpret_cast<uintptr_t>(sc_buf) & 15) == 0)) {
-        if (!workspace || workspace_bytes < nw_fwd_workspace_bytes(B, N, d, C)) return NW_ERR_WORKSPACE;
-        if (weights_out) {
-            float* lse = lse_out;
-            if (!lse) lse = reinterpret_cast<float*>(static_cast<char*>(workspace) + nw_fwd_workspace_bytes(B, N, d, C) -
-                                                     align256((size_t)B * sizeof(float)) - agg_slice_bytes(B, N, C));
-            const int rc = nw_fwd_f32(q, s, sy, s_norm2, s_split, s_scale, out, sc_buf, lse, nullptr, workspace,
-                                      workspace_bytes, B, N, d, C, kind, logit_scale_dev, 0, 0, opts, stream);
-            if (rc != NW_OK) return rc;
-            return nw::launch_weights_from_scores(sc_buf, lse, weights_out, B, N, st);
-        }
-        if (!takes_split(q, s_split, s_scale, s_norm2, B, N, d)) return nw::launch_fused(a, nw::FORM_F32, kind);
-        a.s = s_split, a.s_scale = s_scale;
-        return nw::launch_fused(a, nw::FORM_SPLIT, kind);
+        if (!L.fits(workspace_bytes)) return NW_ERR_WORKSPACE;
+        a.scores = sc_buf;
+        if (weights_out && !a.lse) a.lse = L.at(L.lse);
+        const bool split = takes_split(q, s_split, s_scale, s_norm2, B, N, d);
+        if (split) a.s = s_split, a.s_scale = s_scale;
+        const int rc = nw::launch_fused(a, split ? nw::FORM_SPLIT : nw::FORM_F32, kind);
+        if (rc != NW_OK || !weights_out) return rc;
+        return nw::launch_weights_from_scores(sc_buf, a.lse, weights_out, B, N, st);
     }
     float* scores = scores_out;
     if (!scores && N > 0) {
-        if (!workspace || workspace_bytes < nw_fwd_workspace_bytes(B, N, d, C)) return NW_ERR_WORKSPACE;
-        scores = static_cast<float*>(workspace);
+        if (!L.fits(workspace_bytes)) return NW_ERR_WORKSPACE;
+        scores = L.at(L.main);
     }
     int rc = nw::launch_scores(q, s, scores, B, N, d, kind, logit_scale_dev, sup_batched, st);
     if (rc != NW_OK) return rc;
-    float* slice_ws = nullptr;
-    size_t slice_floats = 0;
-    const size_t sb = agg_slice_bytes(B, N, C);
-    if (sb && workspace && workspace_bytes >= nw_fwd_workspace_bytes(B, N, d, C)) {   // (the last area of the workspace)
-        slice_ws = reinterpret_cast<float*>(static_cast<char*>(workspace) + nw_fwd_workspace_bytes(B, N, d, C) - sb);
-        slice_floats = sb / sizeof(float);
-    }
-    return nw::launch_aggregate(scores, sy, labels_batched, out, lse_out, weights_out, nullptr,
-                                nullptr, nullptr, B, N, C, st, slice_ws, slice_floats);
+    const bool sliced = L.n_slices > 1 && L.fits(workspace_bytes);
+    return nw::launch_aggregate(scores, sy, labels_batched, out, lse_out, weights_out, nullptr, nullptr, nullptr, B, N, C, st,
+                                sliced ? L.at(L.slices) : nullptr, sliced ? L.slices.bytes / sizeof(float) : 0);
+}
+
+extern "C" int nw_fwd_f32(const float* q, const float* s, const int64_t* sy, const float* s_norm2,
+                          const float* s_split, const float* s_scale, float* out, float* scores_out, float* lse_out, float* weights_out, void* workspace,
+                          size_t workspace_bytes, int64_t B, int64_t N, int64_t d, int64_t C,
+                          int kind, const float* logit_scale_dev, int sup_batched,
+                          int labels_batched, const nw_fwd_opts* opts, void* stream) {
+    OptsGuard opts_guard(opts);
+    return fwd_f32(q, s, sy, s_norm2, s_split, s_scale, out, scores_out, lse_out, weights_out, workspace, workspace_bytes, nullptr,
+                   B, N, d, C, kind, logit_scale_dev, sup_batched, labels_batched, static_cast<hipStream_t>(stream));
 }
 
 // The head over a per-query row window of a split bank (fused.hip, OUT_WIN): nw_knn_window_f32's regime, nw_fwd_f32's
@@ -242,10 +238,11 @@ extern "C" int nw_fwd_window_f32(const float* q, const float* s_split, const flo
     if (!q || !s_split || !s_scale || !s_norm2 || !sy || !out) return NW_ERR_INVALID_ARG;
     if (kind == NW_SCORE_CLIP && !logit_scale_dev) return NW_ERR_INVALID_ARG;
     if (!nw::fused_eligible(q, s_split, B, N, d, C)) return NW_ERR_UNSUPPORTED;   // alignment, sizes past the tile kernels
-    if (!workspace || workspace_bytes < nw_fwd_workspace_bytes(B, N, d, C)) return NW_ERR_WORKSPACE;
+    const nw::FwdLayout L = nw::fwd_layout(B, N, d, C, workspace);
+    if (!L.fits(workspace_bytes)) return NW_ERR_WORKSPACE;
     if (reinterpret_cast<uintptr_t>(workspace) & 15) return NW_ERR_UNSUPPORTED;
     nw::FusedArgs a = {q, s_split, sy, s_norm2, s_scale, logit_scale_dev, out, nullptr, lse_out, nullptr, nullptr, nullptr,
-                       workspace, workspace_bytes, (int)B, (int)N, (int)d, (int)C, static_cast<hipStream_t>(stream), nullptr,
+                       &L, (int)B, (int)N, (int)d, (int)C, static_cast<hipStream_t>(stream), nullptr,
                        row_lo, row_hi, exclude != 0};
     return nw::launch_fused(a, nw::FORM_SPLIT, kind);
 }
@@ -269,10 +266,10 @@ extern "C" int nw_fwd_partial_f32(const float* q, const float* s, const int64_t*
         const int rc = half_form_check(q, s, s_norm2, s_split, s_scale, nullptr, 0, B, N, d, C);
         if (rc != NW_OK) return rc;
     }
-    float* scores = static_cast<float*>(workspace);
-    if (N > 0 && (!workspace || workspace_bytes < nw_fwd_workspace_bytes(B, N, d, C))) return NW_ERR_WORKSPACE;
+    const nw::FwdLayout L = nw::fwd_layout(B, N, d, C, workspace);
+    if (N > 0 && !L.fits(workspace_bytes)) return NW_ERR_WORKSPACE;
     nw::FusedArgs a = {q, s, sy, s_norm2, nullptr, logit_scale_dev, nullptr, nullptr, nullptr, m, den, num,
-                       workspace, workspace_bytes, (int)B, (int)N, (int)d, (int)C, st, nullptr};
+                       &L, (int)B, (int)N, (int)d, (int)C, st, nullptr};
     if (form == 1 && N > 0 && C > 0) {
         a.s = s_split, a.s_scale = s_scale;
         return nw::launch_fused(a, nw::FORM_HALF, kind);
@@ -282,6 +279,7 @@ extern "C" int nw_fwd_partial_f32(const float* q, const float* s, const int64_t*
         a.s = s_split, a.s_scale = s_scale;
         return nw::launch_fused(a, nw::FORM_SPLIT, kind);
     }
+    float* scores = L.at(L.main);
     int rc = nw::launch_scores(q, s, scores, B, N, d, kind, logit_scale_dev, 0, st);
     if (rc != NW_OK) return rc;
     return nw::launch_aggregate(scores, sy, 0, nullptr, nullptr, nullptr, m, den, num, B, N, C, st);
@@ -382,13 +380,12 @@ extern "C" int nw_fwd_influence_f32(const float* q, const float* s, const int64_
         return nw_fwd_f32(q, s, sy, s_norm2, s_split, s_scale, out, nullptr, lse_out, nullptr, workspace, workspace_bytes,
                           B, N, d, C, kind, logit_scale_dev, 0, 0, opts, stream);
     if (!qy || !infl_out || !out) return NW_ERR_INVALID_ARG;
-    const size_t need = nw_fwd_workspace_bytes(B, N, d, C);   // its last B floats: the log-sum-exp slot
-    if (!workspace || workspace_bytes < need) return NW_ERR_WORKSPACE;
-    float* lse = lse_out ? lse_out : reinterpret_cast<float*>(static_cast<char*>(workspace) + need - align256((size_t)B * sizeof(float)) -
-                                                              agg_slice_bytes(B, N, C));
+    const nw::FwdLayout L = nw::fwd_layout(B, N, d, C, workspace);
+    if (!L.fits(workspace_bytes)) return NW_ERR_WORKSPACE;
+    float* lse = lse_out ? lse_out : L.at(L.lse);
     // scores into infl_out (fused tile kernel when eligible, else the score kernel of the two-kernel path)
-    const int rc = nw_fwd_f32(q, s, sy, s_norm2, s_split, s_scale, out, infl_out, lse, nullptr, workspace,
-                              workspace_bytes, B, N, d, C, kind, logit_scale_dev, 0, 0, opts, stream);
+    const int rc = fwd_f32(q, s, sy, s_norm2, s_split, s_scale, out, infl_out, lse, nullptr, workspace, workspace_bytes, &L,
+                           B, N, d, C, kind, logit_scale_dev, 0, 0, st);
     if (rc != NW_OK) return rc;
     return nw::launch_influence(out, qy, infl_out, sy, lse, infl_out, B, N, C, st);
 }

@@ -98,7 +98,8 @@ size_t fused_layout(int64_t B, int64_t n_stiles, int BS, char* base, FusedWs* ws
         return p;
     };
     FusedWs w;
-    w.m = reinterpret_cast<float*>(take((size_t)n_stiles * B * 4));
+    // (den follows m at the distance the OUT_WIN tile kernel assumes: both sides read fused_den_after_m)
+    w.m = reinterpret_cast<float*>(take(fused_den_after_m(n_stiles, B) * sizeof(float)));
     w.den = reinterpret_cast<float*>(take((size_t)n_stiles * B * 4));
     w.nrun = reinterpret_cast<int*>(take((size_t)n_stiles * 4));
     w.lab = reinterpret_cast<int*>(take((size_t)n_stiles * BS * 4));
@@ -436,19 +437,6 @@ int env_rs() {
 
 }  // namespace
 
-// The query-split area sits behind the fused area, at the tail of nw_fwd_workspace_bytes (capi.hip sizes it).
-int query_area_of_workspace(void* workspace, size_t workspace_bytes, int64_t B, int64_t N, int64_t d, int64_t C, float** rows,
-                            float** scale, float** norm2) {
-    const size_t total = nw_fwd_workspace_bytes(B, N, d, C);
-    if (!workspace || workspace_bytes < total) return NW_ERR_WORKSPACE;
-    const size_t a = al256((size_t)B * (size_t)d * sizeof(float)), b = al256((size_t)B * sizeof(float));
-    char* base = static_cast<char*>(workspace) + (total - a - 3 * b);  // the last b bytes: the log-sum-exp slot (capi.hip)
-    *rows = reinterpret_cast<float*>(base);
-    *scale = reinterpret_cast<float*>(base + a);
-    *norm2 = reinterpret_cast<float*>(base + a + b);
-    return NW_OK;
-}
-
 int launch_run_tables(const FusedWs& ws, const int64_t* sy, int N, int C, int n_stiles, int BS, hipStream_t st) {
     if (BS > 192) return NW_ERR_UNSUPPORTED;  // three rows per lane
     hipLaunchKernelGGL(nw_run_tables_kernel, dim3(n_stiles), dim3(64), 0, st, sy, N, C, BS, ws.runid, ws.nrun, ws.lab, ws.bnd);
@@ -687,7 +675,7 @@ FusedPlan plan_fused(int64_t B, int64_t N, int64_t d, int64_t C, int form, int o
     return p;
 }
 
-size_t fused_workspace_bytes(int64_t B, int64_t N, int64_t d, int64_t C) {
+static size_t fused_workspace_bytes(int64_t B, int64_t N, int64_t d, int64_t C) {
     size_t need = 0;
     for (int form : {FORM_F32, FORM_SPLIT, FORM_HALF}) {  // any operand form may be chosen at launch
         if (form == FORM_HALF && !half_form_shape_ok(d)) continue;
@@ -696,6 +684,28 @@ size_t fused_workspace_bytes(int64_t B, int64_t N, int64_t d, int64_t C) {
         need = n > need ? n : need;
     }
     return need;
+}
+
+FwdLayout fwd_layout(int64_t B, int64_t N, int64_t d, int64_t C, void* base) {
+    FwdLayout L = {};
+    L.base = static_cast<char*>(base);
+    if (B <= 0 || N <= 0) return L;
+    size_t off = 0;
+    auto take = [&](size_t bytes) {
+        const FwdLayout::Area a = {off, al256(bytes)};
+        off += a.bytes;
+        return a;
+    };
+    const size_t scores = (size_t)B * (size_t)N * sizeof(float), fused = fused_workspace_bytes(B, N, d, C);
+    L.main = take(scores > fused ? scores : fused);
+    L.q_rows = take((size_t)B * (size_t)d * sizeof(float));
+    L.q_scale = take((size_t)B * sizeof(float));
+    L.q_norm2 = take((size_t)B * sizeof(float));
+    L.lse = take((size_t)B * sizeof(float));
+    L.n_slices = aggregate_slices(B, N);
+    L.slices = take(L.n_slices > 1 ? (size_t)L.n_slices * (size_t)B * (size_t)(2 + (C > 0 ? C : 0)) * sizeof(float) : 0);
+    L.total = off;
+    return L;
 }
 
 bool fused_eligible(const float* q, const float* s, int64_t B, int64_t N, int64_t d, int64_t C) {

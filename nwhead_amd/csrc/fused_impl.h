@@ -26,9 +26,6 @@ int launch_run_tables(const FusedWs& ws, const int64_t* sy, int N, int C, int n_
 bool bank_tables_take(const int64_t* sy, int N, int C, int n_stiles, int BS, FusedWs* ws);   // the caller's cached tables, if named for this call
 int launch_merge_runs(const FusedWs& ws, float* out, float* lse, float* m, float* den, float* num,
                       int B, int C, int n_stiles, int BS, hipStream_t st);
-// the query area in the tail of the forward workspace (fused.hip): rows (B * d floats), scales, norms of the split / packed queries
-int query_area_of_workspace(void* workspace, size_t workspace_bytes, int64_t B, int64_t N, int64_t d, int64_t C, float** rows,
-                            float** scale, float** norm2);
 // Candidate output of the tile kernel (nw_knn_f32): instead of softmax partials every (query, support tile) pair leaves
 // its kc = min(k, tile rows) best scores, best first, ties in ascending bank-row order, as ordered_bits keys (0: empty slot)
 // and bank rows: key / row [b][st][j], j < kcp = kc rounded up to 4.  q_rows / q_scale / q_norm2: room for the split form
@@ -555,7 +552,7 @@ template <int KIND, bool HALF, bool CAND>
 int launch_p12(const FusedPlan& p, const FusedArgs& a, const QueryRows& q, const FusedWs& ws);
 
 // Executes a plan of plan_fused (fused.hip) on tiles of RS blocks: workspace layout, the optional run-table launch and
-// query-split / pack launch (into the query area at the tail of the workspace, or into the CandOut), one tile kernel, the
+// query-split / pack launch (into the query areas of the call's FwdLayout, or into the CandOut), one tile kernel, the
 // run merge.  Which of them, and with which grid and LDS, is the plan's business; nothing is decided here.
 template <int RS, int KIND>
 int launch_fused_rs(const FusedArgs& a, const FusedPlan& p) {
@@ -564,8 +561,9 @@ int launch_fused_rs(const FusedArgs& a, const FusedPlan& p) {
     hipStream_t st = a.st;
     FusedWs ws = {};
     if (!cand) {   // (candidate output: the caller's CandOut is all the kernel writes)
-        const size_t need = fused_layout(a.B, p.n_stiles, BS, static_cast<char*>(a.workspace), &ws, a.C);
-        if (!a.workspace || a.workspace_bytes < need) return NW_ERR_WORKSPACE;
+        if (!a.ws || !a.ws->base) return NW_ERR_WORKSPACE;
+        const size_t need = fused_layout(a.B, p.n_stiles, BS, a.ws->base + a.ws->main.off, &ws, a.C);
+        if (need > a.ws->main.bytes) return NW_ERR_WORKSPACE;
     }
     if (p.status != NW_OK) return p.status;
     if (p.run_tables && !bank_tables_take(a.sy, a.N, a.C, p.n_stiles, BS, &ws)) {  // once per launch (ws.runid / nrun / lab / bnd)
@@ -574,12 +572,10 @@ int launch_fused_rs(const FusedArgs& a, const FusedPlan& p) {
     }
     QueryRows q = {a.q, nullptr, nullptr};
     if (p.split_queries) {
-        float *qr, *qsc, *qn;
-        int rc = NW_OK;
-        if (cand) qr = cand->q_rows, qsc = cand->q_scale, qn = cand->q_norm2;
-        else rc = query_area_of_workspace(a.workspace, a.workspace_bytes, a.B, a.N, a.d, a.C, &qr, &qsc, &qn);
-        if (rc == NW_OK)
-            rc = p.form == FORM_HALF ? launch_pack_rows_f16(a.q, qr, qsc, qn, a.B, a.d, st) : launch_split_rows(a.q, qr, qsc, qn, a.B, a.d, st);
+        float* const qr = cand ? cand->q_rows : a.ws->at(a.ws->q_rows);
+        float* const qsc = cand ? cand->q_scale : a.ws->at(a.ws->q_scale);
+        float* const qn = cand ? cand->q_norm2 : a.ws->at(a.ws->q_norm2);
+        const int rc = p.form == FORM_HALF ? launch_pack_rows_f16(a.q, qr, qsc, qn, a.B, a.d, st) : launch_split_rows(a.q, qr, qsc, qn, a.B, a.d, st);
         if (rc != NW_OK) return rc;
         q = {qr, qn, qsc};
     }

@@ -8,6 +8,7 @@
 namespace nw {
 
 struct FwdOpts;
+struct FwdLayout;
 struct CandOut;
 #define NW_FOR_EACH_KIND(X) \
     X(NW_SCORE_EUCLIDEAN) X(NW_SCORE_HYPERSPHERE) X(NW_SCORE_COSINE) X(NW_SCORE_DOT) X(NW_SCORE_CLIP)
@@ -63,8 +64,7 @@ struct FusedArgs {
     const int64_t* sy;
     const float *s_norm2, *s_scale, *ls;
     float *out, *scores, *lse, *m, *den, *num;
-    void* workspace;
-    size_t workspace_bytes;
+    const FwdLayout* ws;         // the call's workspace, carved and checked by the entry point (nw_internal.h); null with cand
     int B, N, d, C;
     hipStream_t st;
     const CandOut* cand;

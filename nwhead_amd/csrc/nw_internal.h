@@ -123,7 +123,25 @@ int tile_timer_enable(bool on);
 int tile_timer_read(double* total_us, int64_t* launches);
 int pick_rs(int64_t B, int64_t N, int64_t d, bool f16 = false);
 bool fused_eligible(const float* q, const float* s, int64_t B, int64_t N, int64_t d, int64_t C);
-size_t fused_workspace_bytes(int64_t B, int64_t N, int64_t d, int64_t C = 0);
+// The forward workspace of one call (nw_fwd_workspace_bytes; every forward entry point and launcher reads this record and
+// nothing else), carved once, in this order: main | q_rows | q_scale | q_norm2 | lse | slices.
+//   main      the (B,N) score matrix of the two-kernel path, or the fused partials (fused_layout): the larger of the two
+//   q_rows, q_scale, q_norm2   the split / packed queries of a launch whose plan asks for them (FusedPlan::split_queries)
+//   lse       B floats, for a call that derives weights or influences from the scores without an lse_out of its own
+//   slices    the partials of the sliced aggregation, n_slices * B * (2 + C) floats; empty when n_slices == 1
+// Every area starts on a multiple of 256 bytes and ends where the next one starts; the last ends at `total`.
+struct FwdLayout {
+    struct Area {
+        size_t off, bytes;
+    };
+    Area main, q_rows, q_scale, q_norm2, lse, slices;
+    int n_slices;   // aggregate_slices(B, N), which sized `slices`
+    size_t total;
+    char* base;     // the caller's buffer; null: offsets and sizes only
+    float* at(const Area& a) const { return base ? reinterpret_cast<float*>(base + a.off) : nullptr; }
+    bool fits(size_t buffer_bytes) const { return base && buffer_bytes >= total; }   // the one workspace check of the entries
+};
+FwdLayout fwd_layout(int64_t B, int64_t N, int64_t d, int64_t C, void* base);   // fused.hip; B <= 0 or N <= 0: all zeros
 int launch_split_rows(const float* x, float* out, float* scale, float* norm2, int64_t rows, int64_t d,
                       hipStream_t st);
 // split.hip: fp32 rows -> dense fp16 rows, row scales and the norms of the ROUNDED rows (nw_pack_rows_f16)

@@ -129,6 +129,20 @@ int main() {
             EXPECT(pl.status, NW_OK);
         }
     }
+    {   // the map of the forward workspace: pure host arithmetic
+        nw_fwd_layout m;
+        EXPECT(nw_debug_fwd_layout(4, 4096, 64, 3, nullptr), NW_ERR_INVALID_ARG);
+        EXPECT(nw_debug_fwd_layout(-1, 4096, 64, 3, &m), NW_ERR_INVALID_ARG);
+        EXPECT(nw_debug_fwd_layout(4, 4096, -64, 3, &m), NW_ERR_INVALID_ARG);
+        EXPECT(nw_debug_fwd_layout(4, 4096, 64, -3, &m), NW_ERR_INVALID_ARG);
+        std::memset(&m, 0xff, sizeof m);
+        EXPECT(nw_debug_fwd_layout(0, 4096, 64, 3, &m), NW_OK);                                                            // empty shape
+        EXPECT(m.total == 0 && m.n_slices == 0 && m.bytes[0] == 0 && m.off[NW_FWD_AREAS - 1] == 0, 1);
+        EXPECT(nw_debug_fwd_layout(4, 4096, 64, 3, &m), NW_OK);                                                            // a sliced shape
+        EXPECT(m.n_slices > 1 && m.bytes[NW_FWD_AREAS - 1] >= (size_t)m.n_slices * 4 * (2 + 3) * 4, 1);
+        EXPECT(m.total, nw_fwd_workspace_bytes(4, 4096, 64, 3));
+        for (int i = 0; i < NW_FWD_AREAS; ++i) EXPECT(m.off[i] + m.bytes[i] <= m.total, 1);
+    }
     // split rows, norms, influence, top-k, aggregate
     EXPECT(nw_split_rows_f16x2(F, F, F, F, 4, 48, nullptr), NW_ERR_UNSUPPORTED);      // d % 32 != 0
     EXPECT(nw_split_rows_f16x2(F, F, F, F, -1, 32, nullptr), NW_ERR_INVALID_ARG);

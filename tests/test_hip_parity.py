@@ -540,9 +540,40 @@ def test_bank_beyond_4gb(dev, ops):
 
 
 # ------------------------------------------------------------------ weights / influences from the fused forward
+# The smallest shape at which the three users of the forward workspace's tail meet: few queries over a long row (B <= 64,
+# N >= 4096: the slice area is sized), split operands with the query-split launch (forced: the shape alone would take raw
+# queries), and no lse_out of the caller's (weights / influences: the workspace's own lse slot).
+TAIL_MEETS = (4, 4096, 64, 3)
+
+
+@pytest.fixture
+def tail_meets(request, dev):
+    """True for the TAIL_MEETS case, which runs under NW_SPLIT_QUERIES=1 (restored afterwards) on a poisoned workspace."""
+    import os
+    from nwhead_amd import _lib
+    B, N, d, C = (request.node.callspec.params[k] for k in "BNdC")
+    if (B, N, d, C) != TAIL_MEETS:
+        yield False
+        return
+    before = os.environ.get("NW_SPLIT_QUERIES")
+    os.environ["NW_SPLIT_QUERIES"] = "1"
+    _lib.sync_knobs()
+    try:
+        assert _lib.force_split(), "conftest pins NW_SPLIT_ALWAYS=1: below the size rule the bank's split rows are used with it only"
+        assert _lib.fwd_plan(B, N, d, C, form="split", outputs="scores").split_queries
+        assert _lib.fwd_layout(B, N, d, C).n_slices > 1
+        yield True
+    finally:
+        if before is None:
+            os.environ.pop("NW_SPLIT_QUERIES", None)
+        else:
+            os.environ["NW_SPLIT_QUERIES"] = before
+        _lib.sync_knobs()
+
+
 @pytest.mark.parametrize("B,N,d,C,cache", [(64, 10000, 512, 200, True), (37, 1001, 96, 7, False), (9, 300, 64, 5, True),
-                                           (5, 20, 32, 4, False)])
-def test_weights_from_the_fused_forward(dev, ops, O, B, N, d, C, cache):
+                                           (5, 20, 32, 4, False), TAIL_MEETS + (True,)])
+def test_weights_from_the_fused_forward(dev, ops, O, tail_meets, B, N, d, C, cache):
     """return_weights=True: the tile kernel writes the scores where the weights go, one in-place pass normalises
     them with the merge's log-sum-exp (N > 25); N <= 25 keeps the two-kernel path.  `sweights` of util/metric.py:23."""
     g = torch.Generator().manual_seed(B + N)
@@ -550,7 +581,11 @@ def test_weights_from_the_fused_forward(dev, ops, O, B, N, d, C, cache):
     sy = torch.randint(0, C, (N,), generator=g).sort().values
     qd, sd, syd = q.to(dev), s.to(dev), sy.to(dev)
     bank = ops.SplitBank(sd, syd) if cache else None
+    if tail_meets:
+        assert ws_poison.poison_cached_workspaces(min_bytes=ws_poison.fwd_workspace_bytes(B, N, d, C), device=dev) > 0
     out, w = ops.nw_head(qd, sd, syd, C, return_weights=True, support_cache=bank)
+    if tail_meets:
+        assert torch.isfinite(out).all() and torch.isfinite(w).all()
     ref, wref = O.nw_head_f64(q, s, sy, C, return_weights=True)
     close(out, ref.numpy(), rtol=RTOL, atol=3e-5)
     np.testing.assert_allclose(w.cpu().numpy(), wref.numpy(), rtol=2e-5, atol=1e-9)
@@ -558,13 +593,16 @@ def test_weights_from_the_fused_forward(dev, ops, O, B, N, d, C, cache):
     # with gradients requested too (scores saved for the backward): weights from the saved scores
     qg = qd.clone().requires_grad_(True)
     out2, w2 = ops.nw_head(qg, sd, syd, C, return_weights=True)
+    if tail_meets:
+        assert torch.isfinite(out2).all() and torch.isfinite(w2).all()
     np.testing.assert_allclose(w2.detach().cpu().numpy(), wref.numpy(), rtol=2e-5, atol=1e-9)
     F.nll_loss(out2, torch.zeros(B, dtype=torch.int64, device=dev)).backward()
     assert torch.isfinite(qg.grad).all()
 
 
-@pytest.mark.parametrize("B,N,d,C,cache", [(256, 10000, 512, 200, True), (33, 999, 64, 10, False), (4, 20, 16, 3, False)])
-def test_forward_plus_influence_in_one_call(dev, ops, O, B, N, d, C, cache):
+@pytest.mark.parametrize("B,N,d,C,cache", [(256, 10000, 512, 200, True), (33, 999, 64, 10, False), (4, 20, 16, 3, False),
+                                           TAIL_MEETS + (True,)])
+def test_forward_plus_influence_in_one_call(dev, ops, O, tail_meets, B, N, d, C, cache):
     """nw_fwd_influence_f32: util/metric.py:23-50 on the head's own outputs without a softmax-weight matrix, against
     the oracle's influence of the oracle's head (fp64 head, the reference's fp32 influence arithmetic)."""
     g = torch.Generator().manual_seed(7 * B + N)
@@ -573,7 +611,11 @@ def test_forward_plus_influence_in_one_call(dev, ops, O, B, N, d, C, cache):
     qy = torch.randint(0, C, (B,), generator=g)
     qd, sd, syd = q.to(dev), s.to(dev), sy.to(dev)
     bank = ops.SplitBank(sd, syd) if cache else None
+    if tail_meets:
+        assert ws_poison.poison_cached_workspaces(min_bytes=ws_poison.fwd_workspace_bytes(B, N, d, C), device=dev) > 0
     out, infl = ops.nw_head_influence(qd, sd, syd, C, qy.to(dev), support_cache=bank)
+    if tail_meets:
+        assert torch.isfinite(out).all() and torch.isfinite(infl).all()
     rows = slice(0, min(B, 32))
     ref, wref = O.nw_head_f64(q[rows], s, sy, C, return_weights=True)
     close(out[rows], ref.numpy(), rtol=RTOL, atol=3e-5)
