@@ -2,9 +2,10 @@
 
 Own definitions of the architectures the reference trains (model/resnet.py, model/densenet.py,
 model/densenet3.py), with the same parameter/buffer names so that reference checkpoints load
-(`featurizer.*` keys) and the same initialisation schemes.  The convolutions run on
-MIOpen (MFMA) through PyTorch-ROCm; what is specific here:
+(`featurizer.*` keys) and the same initialisation schemes.  What is specific here:
 
+  * fp32 RGB batches on the MI355X run on the own channels-last kernels -- training and, for CIFAR_ResNet and DenseNet, eval
+    mode -- and everything else the reference's module sequence (MIOpen convolutions): backbone_route() is the one rule;
   * DenseNet blocks run concat-free under `torch.no_grad()` (precompute()/predict(), the bulk of the
     backbone work in 'full' inference): one channel slab per block is allocated up front and every
     layer writes its `growth_rate` new channels into it instead of re-concatenating all previous
@@ -31,6 +32,36 @@ def _no_pretrained(pretrained):
         raise RuntimeError("pretrained weights need a download; load a state_dict instead")
 
 
+# ----------------------------------------------------------------------------- the eval-mode BatchNorm fold
+# plain tensors, fp32 casts (f32: the inference plans) or the parameters' dtype (fold_batchnorm's modules); callers clone and split
+def _val(t, f32):
+    return t.detach().float() if f32 else t.detach()
+
+
+def _bn_scale(bn, f32=False):
+    """a of an eval-mode BatchNorm."""
+    return _val(bn.weight, f32) * torch.rsqrt(_val(bn.running_var, f32) + bn.eps)
+
+
+def _bn_scale_shift(bn, f32=False):
+    """(a, beta - mean a): bn(x) = a x + shift."""
+    a = _bn_scale(bn, f32)
+    return a, _val(bn.bias, f32) - _val(bn.running_mean, f32) * a
+
+
+def _fold_conv_bn(conv, bn, f32=False):
+    """conv -> bn as one convolution: (w a over the output channel, beta + (b - mean) a), b = 0 without a bias."""
+    a = _bn_scale(bn, f32)
+    b = _val(conv.bias, f32) if conv.bias is not None else torch.zeros_like(a)
+    return _val(conv.weight, f32) * a.view(-1, 1, 1, 1), _val(bn.bias, f32) + (b - _val(bn.running_mean, f32)) * a
+
+
+def _bn_apply_args(bn):
+    """(mean, invstd, gamma, beta) of an eval-mode BatchNorm2d for ops.bn_relu_nhwc_apply."""
+    return (_val(bn.running_mean, True).contiguous(), torch.rsqrt(_val(bn.running_var, True) + bn.eps).contiguous(),
+            _val(bn.weight, True).contiguous(), _val(bn.bias, True).contiguous())
+
+
 # ----------------------------------------------------------------------------- ImageNet-style ResNet
 def _conv_nhwc_train(conv, x, bank):
     """A bias-free nn.Conv2d on the channels-last training kernels (ops.conv2d_nhwc_train; model/resnet.py:15-28)."""
@@ -41,16 +72,29 @@ def _conv_nhwc_train(conv, x, bank):
 def _fold_conv_bn_split(conv, bn):
     """conv -> eval-mode BatchNorm as ONE split-row weight and a bias (what ops.conv2d_nhwc takes)."""
     from .. import ops
-    a = bn.weight.detach().float() * torch.rsqrt(bn.running_var.detach().float() + bn.eps)
-    wf = conv.weight.detach().float() * a.view(-1, 1, 1, 1)
-    b0 = conv.bias.detach().float() if conv.bias is not None else torch.zeros_like(a)
-    return ops.SplitConvWeight(wf), (bn.bias.detach().float() + (b0 - bn.running_mean.detach().float()) * a).contiguous()
+    w, b = _fold_conv_bn(conv, bn, f32=True)
+    return ops.SplitConvWeight(w), b.contiguous()
 
 
-def _bn_apply_args(bn):
-    """(mean, invstd, gamma, beta) of an eval-mode BatchNorm2d for ops.bn_relu_nhwc_apply."""
-    return (bn.running_mean.detach().float().contiguous(), torch.rsqrt(bn.running_var.detach().float() + bn.eps).contiguous(),
-            bn.weight.detach().float().contiguous(), bn.bias.detach().float().contiguous())
+def _weight_bank(model, stem):
+    """The ConvWeightBank of the training forward (every convolution weight's split-row operands; no data gradient for the stem's),
+    rebuilt when its weights are no longer the network's (same Parameters, same order).  The caller refreshes it."""
+    from .. import ops
+    weights = [m.weight for m in model.modules() if isinstance(m, nn.Conv2d)]
+    bank = model.__dict__.get("_nw_bank")
+    if bank is None or len(bank.weights) != len(weights) or any(a is not b for a, b in zip(bank.weights, weights)):
+        bank = model._nw_bank = ops.ConvWeightBank([(w, w is not stem.weight) for w in weights])
+    return bank
+
+
+def _cached_plan(model, dev, build):
+    """build()'s dict, kept on the model and rebuilt when a parameter or buffer (address, in-place version) or the device changes."""
+    ts = list(model.parameters()) + list(model.buffers())
+    sig = (str(dev), len(ts), sum(0 if t.is_inference() else t._version for t in ts), sum(t.data_ptr() & 0xffffff for t in ts))
+    plan = model.__dict__.get("_nw_infer_plan")
+    if plan is None or plan["sig"] != sig:
+        model._nw_infer_plan = plan = dict(build(), sig=sig)
+    return plan
 
 
 def _add_relu_nhwc(z, identity):
@@ -175,24 +219,12 @@ class ResNet(nn.Module):
         blocks += [block(out, planes) for _ in range(1, n)]
         return nn.Sequential(*blocks)
 
-    def _nhwc_train_servable(self):
-        ok = getattr(self, "_nw_nhwc_ok", None)
-        if ok is None:
-            ok = self._nw_nhwc_ok = (_convs_nhwc_servable(self, self.conv1) and _is_pool(self.maxpool, nn.MaxPool2d, 3, 2, 1)
-                                     and all(type(d) is nn.Sequential and len(d) == 2 for d in
-                                             (b.downsample for st in (self.layer1, self.layer2, self.layer3, self.layer4) for b in st)
-                                             if d is not None))
-        return ok
-
     def _forward_nhwc_train(self, x):
         """The training forward in channels-last layout on the MI355X (round 4; same module sequence as
         model/resnet.py:192-207): every convolution -- forward, data and weight gradient, the strided ones included -- in
         csrc/conv_nhwc.hip / conv_wgrad.hip, BatchNorm (+ ReLU) in csrc/bn_nhwc.hip, the max pool in pool_nhwc.hip."""
         from .. import ops
-        bank = getattr(self, "_nw_bank", None)
-        if bank is None or bank.weights[0] is not self.conv1.weight:
-            convs = [(m.weight, m is not self.conv1) for m in self.modules() if isinstance(m, nn.Conv2d)]
-            bank = self._nw_bank = ops.ConvWeightBank(convs)
+        bank = _weight_bank(self, self.conv1)
         bank.refresh(force=True)        # one launch; a fused optimizer's step leaves no trace in the version counters
         y = ops.bn_relu_train_nhwc(_conv_nhwc_train(self.conv1, x, bank), self.bn1)
         y = ops.maxpool3s2_nhwc(y)
@@ -202,15 +234,13 @@ class ResNet(nn.Module):
         return torch.flatten(self.avgpool(y), 1)
 
     def forward(self, x):
-        if (NHWC_TRAINING and RESNET_NHWC_TRAINING and self.training and x.is_cuda and x.dtype == torch.float32
-                and torch.is_grad_enabled() and x.dim() == 4 and x.shape[1] == 3 and not isinstance(self.conv1, ConvBiasAct)
-                and self._nhwc_train_servable()):
+        if backbone_route_for(self, x) == "nhwc_train":
             return self._forward_nhwc_train(x)
         if isinstance(self.conv1, ConvBiasAct):      # folded inference copy
             c1 = self.conv1
-            if (FUSED_CONV_NHWC and x.is_cuda and x.dtype == torch.float32 and x.dim() == 4 and x.shape[1] == 3 and not torch.is_grad_enabled()
-                    and c1.kernel_size == (7, 7) and c1.stride == (2, 2) and c1.padding == (3, 3) and c1.out_channels == 64
-                    and c1.groups == 1 and c1.dilation == (1, 1) and c1.bias is not None and _is_pool(self.maxpool, nn.MaxPool2d, 3, 2, 1)):
+            if (_kernel_input(x.device.type, x.dtype, x.shape) and not torch.is_grad_enabled() and c1.kernel_size == (7, 7)
+                    and c1.stride == (2, 2) and c1.padding == (3, 3) and c1.out_channels == 64 and c1.groups == 1
+                    and c1.dilation == (1, 1) and c1.bias is not None and _is_pool(self.maxpool, nn.MaxPool2d, 3, 2, 1)):
                 from .. import ops       # stem convolution + ReLU + max pool in one kernel: the 112 x 112 map stays on the CU
                 y = ops.stem_conv_relu_maxpool_nhwc(x, c1._split_weight(), c1.bias)
                 y = self.layer4(self.layer3(self.layer2(self.layer1(y))))
@@ -244,9 +274,6 @@ FUSED_CONV3X3 = _os.environ.get("NW_OWN_CONV3X3", "1") != "0"
 # bias, the identity and the ReLU in its store (NCHW; the stem, the strided convolutions and the 1x1 projections stay on
 # MIOpen).  Measured against the channels_last MIOpen path (tools/fold_time.py): see DESIGN.md 4.7e; NW_RESNET_OWN_CONV3X3.
 FUSED_RESNET_CONV3X3 = _os.environ.get("NW_RESNET_OWN_CONV3X3", "0") == "1"
-# Folded channels_last copies (the ResNets): every convolution through ops.conv2d_nhwc (csrc/conv_nhwc.hip: implicit GEMM on
-# the fp16 matrix cores with split-fp16 operands, bias / identity / ReLU in its store).  NW_CONV_NHWC=0: MIOpen + the bias pass.
-FUSED_CONV_NHWC = _os.environ.get("NW_CONV_NHWC", "1") != "0"
 FUSED_CONV1X1 = True            # folded inference copies: 1x1 convolutions with their BatchNorm / ReLU neighbours as one kernel (Conv1x1Fused)
 FUSED_BN_RELU_TRAINING = True   # training-mode BatchNorm2d + ReLU through ops.bn_relu_train on the MI355X
 # Training on the MI355X in channels-last layout: every convolution (forward, data and weight gradient) on the fp16 matrix
@@ -260,8 +287,6 @@ RESNET_NHWC_TRAINING = _os.environ.get("NW_RESNET_NHWC_TRAINING", "1") != "0"
 CIFAR_DENSENET_NHWC_TRAINING = _os.environ.get("NW_CIFAR_DENSENET_NHWC_TRAINING", "0") == "1"
 # a dense block of the channels-last training path as one autograd node over one slab (ops._DenseBlockNhwcFn)
 DENSE_SLAB = _os.environ.get("NW_DENSE_SLAB", "1") != "0"
-# a transition of that path as BatchNorm-ReLU -> 2x2 average pool -> 1x1 convolution (pool and convolution commute)
-TRANSITION_POOL_FIRST = _os.environ.get("NW_TRANSITION_POOL_FIRST", "1") != "0"
 
 
 def _fused_training(bn, x):
@@ -322,31 +347,21 @@ class CIFAR_ResNet(nn.Module):
                 self.in_planes = planes * block.expansion
             setattr(self, f"layer{idx}", nn.Sequential(*blocks))
 
-    def _nhwc_train_servable(self):
-        ok = getattr(self, "_nw_nhwc_ok", None)
-        if ok is None:
-            ok = self._nw_nhwc_ok = (_convs_nhwc_servable(self, self.conv1)
-                                     and all(isinstance(b, PreActBlock) and len(b.shortcut) <= 1
-                                             for st in (self.layer1, self.layer2, self.layer3, self.layer4) for b in st))
-        return ok
-
-    def _nhwc_infer_servable(self):
+    def _nhwc_infer_servable(self, shape=None):
         """Plain modules with running statistics (a copy fold_batchnorm has rewritten runs its own modules)."""
         for m in self.modules():
             if isinstance(m, nn.BatchNorm2d) and (type(m) is not nn.BatchNorm2d or m.running_mean is None or not m.affine):
                 return False
-        return all(type(b.bn1) is nn.BatchNorm2d and type(b.bn2) is nn.BatchNorm2d and isinstance(b.conv1, nn.Conv2d)
-                   and isinstance(b.conv2, nn.Conv2d) for st in (self.layer1, self.layer2, self.layer3, self.layer4) for b in st)
+        return type(self.bn1) is nn.BatchNorm2d and all(
+            type(b.bn1) is nn.BatchNorm2d and type(b.bn2) is nn.BatchNorm2d and isinstance(b.conv1, nn.Conv2d)
+            and isinstance(b.conv2, nn.Conv2d) for st in (self.layer1, self.layer2, self.layer3, self.layer4) for b in st)
 
     def _forward_nhwc_train(self, x):
         """The training forward in channels-last layout on the MI355X (round 4; model/resnet.py:209-239, the reference's default
         CIFAR backbone): every convolution incl. the strided ones and the 1x1 shortcuts in csrc/conv_nhwc.hip / conv_wgrad.hip,
         BatchNorm + ReLU in csrc/bn_nhwc.hip."""
         from .. import ops
-        bank = getattr(self, "_nw_bank", None)
-        if bank is None or bank.weights[0] is not self.conv1.weight:
-            convs = [(m.weight, m is not self.conv1) for m in self.modules() if isinstance(m, nn.Conv2d)]
-            bank = self._nw_bank = ops.ConvWeightBank(convs)
+        bank = _weight_bank(self, self.conv1)
         bank.refresh(force=True)
         y = ops.bn_relu_train_nhwc(_conv_nhwc_train(self.conv1, x, bank), self.bn1)
         for stage in (self.layer1, self.layer2, self.layer3, self.layer4):
@@ -354,22 +369,15 @@ class CIFAR_ResNet(nn.Module):
                 y = blk.forward_nhwc_train(y, bank)
         return torch.flatten(F.avg_pool2d(y, 4), 1)
 
-    def _infer_plan(self, dev):
-        """What the inference kernels read: split-row weights (conv -> BatchNorm pairs folded), biases, BatchNorm factors.
-        Rebuilt when a parameter or buffer has changed (address or in-place version)."""
+    def _build_infer_plan(self):
+        """What the inference kernels read (_cached_plan keeps it): folded split-row weights, biases, BatchNorm factors."""
         from .. import ops
-        ts = list(self.parameters()) + list(self.buffers())
-        sig = (str(dev), len(ts), sum(0 if t.is_inference() else t._version for t in ts), sum(t.data_ptr() & 0xffffff for t in ts))
-        plan = getattr(self, "_nw_infer_plan", None)
-        if plan is not None and plan["sig"] == sig:
-            return plan
-        plan = {"sig": sig, "stem": _fold_conv_bn_split(self.conv1, self.bn1), "blocks": []}
+        plan = {"stem": _fold_conv_bn_split(self.conv1, self.bn1), "blocks": []}
         for stage in (self.layer1, self.layer2, self.layer3, self.layer4):
             for b in stage:
                 sc = ops.SplitConvWeight(b.shortcut[0].weight.detach().float()) if len(b.shortcut) else None
                 plan["blocks"].append((_bn_apply_args(b.bn1), _fold_conv_bn_split(b.conv1, b.bn2), b.conv1.stride[0],
                                        ops.SplitConvWeight(b.conv2.weight.detach().float()), sc))
-        object.__setattr__(self, "_nw_infer_plan", plan)
         return plan
 
     @torch.no_grad()
@@ -378,7 +386,7 @@ class CIFAR_ResNet(nn.Module):
         folded in and ReLU in its store; per block relu(bn1(x)) in one pass (nw_bn_relu_nhwc_apply_f32: the shortcut needs it too),
         conv1 with bn2 folded in + ReLU, conv2 with the shortcut added in its store."""
         from .. import ops
-        plan = self._infer_plan(x.device)
+        plan = _cached_plan(self, x.device, self._build_infer_plan)
         w0, b0 = plan["stem"]
         y = ops.conv2d_nhwc(x, w0, b0, None, True, 1, 1)
         for bn1, (w1, b1), stride, w2, wsc in plan["blocks"]:
@@ -389,14 +397,9 @@ class CIFAR_ResNet(nn.Module):
         return torch.flatten(F.avg_pool2d(y, 4), 1)
 
     def forward(self, x, lin=0, lout=5):
-        if (NHWC_TRAINING and RESNET_NHWC_TRAINING and self.training and x.is_cuda and x.dtype == torch.float32
-                and torch.is_grad_enabled() and x.dim() == 4 and x.shape[1] == 3 and isinstance(self.conv1, nn.Conv2d)
-                and self._nhwc_train_servable()):
-            return self._forward_nhwc_train(x)
-        if (NHWC_INFERENCE and not self.training and x.is_cuda and x.dtype == torch.float32 and not torch.is_grad_enabled()
-                and x.dim() == 4 and x.shape[1] == 3 and isinstance(self.conv1, nn.Conv2d) and type(self.bn1) is nn.BatchNorm2d
-                and self._nhwc_train_servable() and self._nhwc_infer_servable()):
-            return self._forward_nhwc_infer(x)
+        route = backbone_route_for(self, x)
+        if route != "modules":
+            return self._forward_nhwc_train(x) if route == "nhwc_train" else self._forward_nhwc_infer(x)
         x = _bn_relu(self.bn1, self.conv1(x))
         x = self.layer4(self.layer3(self.layer2(self.layer1(x))))
         return torch.flatten(F.avg_pool2d(x, 4), 1)
@@ -540,19 +543,16 @@ class DenseNet(nn.Module):
                 nn.init.zeros_(m.bias)
 
     def forward(self, x):
-        if (NHWC_TRAINING and self.training and x.is_cuda and x.dtype == torch.float32 and torch.is_grad_enabled()
-                and x.dim() == 4 and x.shape[1] == 3 and self._nhwc_servable()):
-            return self._forward_nhwc_train(x)
-        if (NHWC_INFERENCE and not self.training and x.is_cuda and x.dtype == torch.float32 and not torch.is_grad_enabled()
-                and x.dim() == 4 and x.shape[1] == 3 and self._nhwc_servable() and self._nhwc_infer_servable(x)):
-            return self._forward_nhwc_infer(x)
+        route = backbone_route_for(self, x)
+        if route != "modules":
+            return self._forward_nhwc_train(x) if route == "nhwc_train" else self._forward_nhwc_infer(x)
         return torch.flatten(F.adaptive_avg_pool2d(F.relu(self.features(x)), (1, 1)), 1)
 
     # ------------------------------------------------------------------ inference on the channels-last kernels (round 4)
-    def _nhwc_infer_servable(self, x):
+    def _nhwc_infer_servable(self, shape=None):
         """The module sequence the inference plan covers: the reference's (densenet.py:114-145), plain BatchNorm2d / Conv2d
         modules with running statistics (a copy fold_batchnorm has rewritten runs its own modules), the reference's pools,
-        no dropout, maps that halve cleanly."""
+        no dropout, and for a batch of ``shape`` (None: not asked) maps that halve cleanly."""
         f = self.features
         mods = list(f.children())
         if not (isinstance(f.conv0, nn.Conv2d) and type(f.norm0) is nn.BatchNorm2d and type(f.norm5) is nn.BatchNorm2d
@@ -568,7 +568,9 @@ class DenseNet(nn.Module):
             if isinstance(m, _Transition) and (type(m.norm) is not nn.BatchNorm2d or not isinstance(m.conv, nn.Conv2d)
                                                or not _is_pool(m.pool, nn.AvgPool2d, 2, 2, 0)):
                 return False
-        hw = ((x.shape[2] + 6 - 7) // 2 + 1, (x.shape[3] + 6 - 7) // 2 + 1)
+        if shape is None:
+            return True
+        hw = ((shape[2] + 6 - 7) // 2 + 1, (shape[3] + 6 - 7) // 2 + 1)
         hw = ((hw[0] - 1) // 2 + 1, (hw[1] - 1) // 2 + 1)
         for mod in mods:
             if isinstance(mod, _Transition):
@@ -577,37 +579,20 @@ class DenseNet(nn.Module):
                 hw = (hw[0] // 2, hw[1] // 2)
         return min(hw) >= 1
 
-    def _infer_plan(self, dev):
-        """Per module what the inference kernels read: folded split-row weights, biases, BatchNorm tables.  Rebuilt when a
-        parameter or buffer has changed (address or in-place version)."""
+    def _build_infer_plan(self):
+        """Per module what the inference kernels read: folded split-row weights, biases, BatchNorm tables (kept by _cached_plan)."""
         from .. import ops
-        ts = list(self.parameters()) + list(self.buffers())
-        sig = (str(dev), len(ts), sum(0 if t.is_inference() else t._version for t in ts), sum(t.data_ptr() & 0xffffff for t in ts))
-        plan = getattr(self, "_nw_infer_plan", None)
-        if plan is not None and plan["sig"] == sig:
-            return plan
         f = self.features
-
-        def fold(conv, bn):         # conv -> BatchNorm as one weight and bias
-            a = bn.weight.detach().float() * torch.rsqrt(bn.running_var.detach().float() + bn.eps)
-            wf = conv.weight.detach().float() * a.view(-1, 1, 1, 1)
-            b0 = conv.bias.detach().float() if conv.bias is not None else torch.zeros_like(a)
-            return ops.SplitConvWeight(wf), (bn.bias.detach().float() + (b0 - bn.running_mean.detach().float()) * a).contiguous()
-        plan = {"sig": sig, "stem": fold(f.conv0, f.norm0), "mods": []}
+        plan = {"stem": _fold_conv_bn_split(f.conv0, f.norm0), "mods": [], "norm5": _bn_apply_args(f.norm5)}
         for mod in f.children():
             if isinstance(mod, _DenseBlock):
                 layers = []
                 for layer in mod.children():
-                    w1, b1 = fold(layer.conv1, layer.norm2)
+                    w1, b1 = _fold_conv_bn_split(layer.conv1, layer.norm2)
                     layers.append((ops.bn_table(layer.norm1), w1, b1, ops.SplitConvWeight(layer.conv2.weight.detach().float())))
                 plan["mods"].append(("block", layers))
             elif isinstance(mod, _Transition):
                 plan["mods"].append(("transition", (ops.bn_table(mod.norm), ops.SplitConvWeight(mod.conv.weight.detach().float()))))
-        n5 = f.norm5
-        plan["norm5"] = (n5.running_mean.detach().float().contiguous(),
-                         torch.rsqrt(n5.running_var.detach().float() + n5.eps).contiguous(),
-                         n5.weight.detach().float().contiguous(), n5.bias.detach().float().contiguous())
-        object.__setattr__(self, "_nw_infer_plan", plan)
         return plan
 
     @torch.no_grad()
@@ -618,7 +603,7 @@ class DenseNet(nn.Module):
         reference's order norm-relu-conv-pool with norm + relu in the convolution's loaders."""
         from .. import ops
         f = self.features
-        plan = self._infer_plan(x.device)
+        plan = _cached_plan(self, x.device, self._build_infer_plan)
         mods = [m for m in f.children() if isinstance(m, (_DenseBlock, _Transition))]
         rooms = [m.slab_room() if isinstance(m, _DenseBlock) else 0 for m in mods] + [0]
         w0, b0 = plan["stem"]
@@ -628,7 +613,7 @@ class DenseNet(nn.Module):
                 y = ops.dense_block_nhwc_infer(y, pl)
             else:
                 tab, wt = pl
-                if TRANSITION_POOL_FIRST and y.shape[2] >= 2 and y.shape[3] >= 2:
+                if y.shape[2] >= 2 and y.shape[3] >= 2:
                     # BatchNorm + ReLU + the 2 x 2 average in one pass, then the (bias-free: it commutes with the pool) 1 x 1
                     # convolution on a quarter of the pixels, written straight into the next block's slab
                     y = ops.conv2d_nhwc(ops.bn_relu_avgpool2_nhwc(y, tab), wt, None, None, False, 1, 0, room=rooms[i + 1])
@@ -638,24 +623,7 @@ class DenseNet(nn.Module):
         return torch.flatten(F.adaptive_avg_pool2d(y, (1, 1)), 1)
 
     def _nhwc_servable(self):
-        """Do the channels-last kernels serve every layer?  (convolutions: input and output channels in multiples of 32 --
-        DenseNet-161's growth of 48 is not -- apart from the RGB stem; BatchNorms: channels in multiples of 4.)  Otherwise the
-        NCHW path (MIOpen convolutions + the NCHW BatchNorm kernels) runs, as for every other module layout."""
-        ok = getattr(self, "_nw_nhwc_ok", None)
-        if ok is None:
-            f = self.features
-            ok = True
-            for m in self.modules():
-                if isinstance(m, nn.Conv2d):
-                    cout, cin = m.weight.shape[:2]
-                    if m is f.conv0:
-                        ok &= cin == 3 and cout % 32 == 0 and m.bias is None
-                    else:
-                        ok &= cin % 32 == 0 and cout % 32 == 0 and m.bias is None and m.stride == (1, 1) and m.groups == 1
-                elif isinstance(m, nn.BatchNorm2d):
-                    ok &= m.num_features % 4 == 0 and m.affine
-            self._nw_nhwc_ok = ok = bool(ok)
-        return ok
+        return _nhwc_structure(self)
 
     def _forward_nhwc_train(self, x):
         """The training forward in channels-last layout on the MI355X (same values as the reference's module sequence,
@@ -663,12 +631,8 @@ class DenseNet(nn.Module):
         amax record the following convolution scales its operand by), convolutions through ops.conv2d_nhwc_train."""
         from .. import ops
         f = self.features
-        bank = getattr(self, "_nw_bank", None)
-        if bank is None or bank.weights[0] is not f.conv0.weight:
-            # every convolution weight's split-row operands (forward + data gradient), rebuilt by one launch per step
-            convs = [(m.weight, m is not f.conv0) for m in self.modules() if isinstance(m, nn.Conv2d)]
-            bank = self._nw_bank = ops.ConvWeightBank(convs)
-        bank.refresh(force=True)        # one launch (80 us); a fused optimizer's step leaves no trace in the version counters
+        bank = _weight_bank(self, f.conv0)
+        bank.refresh(force=True)       # one launch (80 us); a fused optimizer's step leaves no trace in the version counters
         y = ops.bn_relu_train_nhwc(ops.conv2d_nhwc_train(x, f.conv0.weight, 2, 3, operands=bank.operands(f.conv0.weight)), f.norm0)
         mods = list(f.children())
 
@@ -683,8 +647,7 @@ class DenseNet(nn.Module):
                 y = mod.forward_nhwc_train(y, bank)
             elif isinstance(mod, _Transition):
                 t = ops.bn_relu_train_nhwc(y, mod.norm)
-                if TRANSITION_POOL_FIRST and _is_pool(mod.pool, nn.AvgPool2d, 2, 2, 0) and mod.conv.bias is None \
-                        and t.shape[2] % 2 == 0 and t.shape[3] % 2 == 0:
+                if _is_pool(mod.pool, nn.AvgPool2d, 2, 2, 0) and mod.conv.bias is None and t.shape[2] % 2 == 0 and t.shape[3] % 2 == 0:
                     # the 2 x 2 average and the bias-free 1 x 1 convolution commute (both linear, per pixel / per channel):
                     # pooled first, the convolution and both of its gradients work on a quarter of the pixels
                     # (densenet.py:83-91 runs conv -> pool; the values differ by fp32 rounding only)
@@ -707,9 +670,9 @@ class ScaleShiftReLU(nn.Module):
 
     def __init__(self, bn, relu=True):
         super().__init__()
-        a = bn.weight.detach() * torch.rsqrt(bn.running_var.detach() + bn.eps)
+        a, shift = _bn_scale_shift(bn)
         self.register_buffer("scale", a.clone())
-        self.register_buffer("shift", (bn.bias.detach() - bn.running_mean.detach() * a).clone())
+        self.register_buffer("shift", shift.clone())
         self.relu = relu
 
     def forward(self, x):
@@ -734,21 +697,19 @@ class Conv1x1Fused(nn.Module):
         assert not pool_first or (post_bn is None and not post_relu and conv.bias is None and pre_bn is not None)
         self.pool_first = pool_first
         assert conv.kernel_size == (1, 1) and conv.stride == (1, 1) and conv.padding == (0, 0) and conv.groups == 1
-        w = conv.weight.detach().reshape(conv.out_channels, conv.in_channels)
-        b = conv.bias.detach() if conv.bias is not None else None
+        w, b = conv.weight.detach(), None if conv.bias is None else conv.bias.detach()
         if post_bn is not None:                      # BatchNorm behind the convolution: into weight and bias
-            a = post_bn.weight.detach() * torch.rsqrt(post_bn.running_var.detach() + post_bn.eps)
-            w = w * a[:, None]
-            b = post_bn.bias.detach() + ((b if b is not None else 0) - post_bn.running_mean.detach()) * a
+            w, b = _fold_conv_bn(conv, post_bn)
+        w = w.reshape(conv.out_channels, conv.in_channels)
         self.register_buffer("weight", w.contiguous().clone())            # (cout, cin): the CPU path
         wt = w.t().contiguous()
         pad = (-wt.shape[0]) % 16                    # the kernel's operand: (cin rounded up to 16, cout), zero rows behind
         self.register_buffer("weight_t", torch.cat((wt, wt.new_zeros(pad, wt.shape[1]))).contiguous() if pad else wt.clone())
         self.register_buffer("bias", None if b is None else b.clone())
         if pre_bn is not None:
-            a = pre_bn.weight.detach() * torch.rsqrt(pre_bn.running_var.detach() + pre_bn.eps)
+            a, shift = _bn_scale_shift(pre_bn)
             self.register_buffer("pre_scale", a.clone())
-            self.register_buffer("pre_shift", (pre_bn.bias.detach() - pre_bn.running_mean.detach() * a).clone())
+            self.register_buffer("pre_shift", shift.clone())
         else:
             self.pre_scale = self.pre_shift = None
         self.pre_relu, self.post_relu = pre_bn is not None, post_relu
@@ -779,12 +740,9 @@ class Conv3x3Fused(nn.Module):
         super().__init__()
         assert conv.kernel_size == (3, 3) and conv.stride == (1, 1) and conv.padding == (1, 1) and conv.groups == 1 \
             and conv.dilation == (1, 1)
-        w = conv.weight.detach()
-        b = conv.bias.detach() if conv.bias is not None else None
+        w, b = conv.weight.detach(), None if conv.bias is None else conv.bias.detach()
         if post_bn is not None:
-            a = post_bn.weight.detach() * torch.rsqrt(post_bn.running_var.detach() + post_bn.eps)
-            w = w * a[:, None, None, None]
-            b = post_bn.bias.detach() + ((b if b is not None else 0) - post_bn.running_mean.detach()) * a
+            w, b = _fold_conv_bn(conv, post_bn)
         from ..ops import conv3x3_weight
         self.cin, self.cout = w.shape[1], w.shape[0]
         self.register_buffer("weight", w.contiguous().clone())           # (cout, cin, 3, 3): the torch path
@@ -859,7 +817,7 @@ class CifarTransition(nn.Module):
     def forward_nhwc_train(self, x, bank):
         from .. import ops
         t = ops.bn_relu_train_nhwc(x, self.bn)
-        if TRANSITION_POOL_FIRST and t.shape[2] % 2 == 0 and t.shape[3] % 2 == 0:     # (pool and the bias-free convolution commute)
+        if t.shape[2] % 2 == 0 and t.shape[3] % 2 == 0:     # (pool and the bias-free convolution commute)
             return _conv_nhwc_train(self.conv, ops.avgpool2_nhwc(t), bank)
         return ops.avgpool2_nhwc(_conv_nhwc_train(self.conv, t, bank))
 
@@ -885,24 +843,12 @@ class CIFAR_DenseNet(nn.Module):
         self.bn = nn.BatchNorm2d(c)
         self.num_features = c
 
-    def _nhwc_train_servable(self):
-        ok = getattr(self, "_nw_nhwc_ok", None)
-        if ok is None:
-            ok = self._nw_nhwc_ok = (isinstance(self.conv1, nn.Conv2d) and _convs_nhwc_servable(self, self.conv1)
-                                     and all(isinstance(m, (CifarBottleneck, CifarTransition))
-                                             for k in (1, 2, 3, 4) for m in getattr(self, f"dense{k}"))
-                                     and all(isinstance(getattr(self, f"trans{k}"), CifarTransition) for k in (1, 2, 3)))
-        return ok
-
     def _forward_nhwc_train(self, x):
         """The training forward in channels-last layout on the MI355X (round 4; densenet3.py:37-83): every convolution in
         csrc/conv_nhwc.hip / conv_wgrad.hip, BatchNorm + ReLU in csrc/bn_nhwc.hip, the transitions' pools in pool_nhwc.hip; the
         concatenations are torch copies."""
         from .. import ops
-        bank = getattr(self, "_nw_bank", None)
-        if bank is None or bank.weights[0] is not self.conv1.weight:
-            convs = [(m.weight, m is not self.conv1) for m in self.modules() if isinstance(m, nn.Conv2d)]
-            bank = self._nw_bank = ops.ConvWeightBank(convs)
+        bank = _weight_bank(self, self.conv1)
         bank.refresh(force=True)
         y = _conv_nhwc_train(self.conv1, x, bank)
         for k in (1, 2, 3, 4):
@@ -913,8 +859,7 @@ class CIFAR_DenseNet(nn.Module):
         return torch.flatten(F.avg_pool2d(ops.bn_relu_train_nhwc(y, self.bn), 4), 1)
 
     def forward(self, x):
-        if (NHWC_TRAINING and CIFAR_DENSENET_NHWC_TRAINING and self.training and x.is_cuda and x.dtype == torch.float32
-                and torch.is_grad_enabled() and x.dim() == 4 and x.shape[1] == 3 and self._nhwc_train_servable()):
+        if backbone_route_for(self, x) == "nhwc_train":
             return self._forward_nhwc_train(x)
         x = self.conv1(x)
         x = self.trans1(self.dense1(x))
@@ -922,6 +867,60 @@ class CIFAR_DenseNet(nn.Module):
         x = self.trans3(self.dense3(x))
         x = self.dense4(x)
         return torch.flatten(F.avg_pool2d(_bn_relu(self.bn, x), 4), 1)
+
+
+# ----------------------------------------------------------------------------- which path a forward takes
+def _kernel_input(device_type, dtype, shape, rgb=True):
+    """The input test of every path on the own kernels: fp32 on the device, 4-D, RGB where asked (shape None: any such batch)."""
+    return device_type == "cuda" and dtype == torch.float32 and (shape is None or (len(shape) == 4 and (shape[1] == 3 or not rgb)))
+
+
+def _nhwc_structure(model):
+    """Do the channels-last kernels serve every layer?  (Channels in multiples of 32 -- DenseNet-161's growth of 48 is not -- apart
+    from the RGB stem, BatchNorms of 4; the reference's pools and block types.)  Asked once per network; a folded copy: False."""
+    ok = model.__dict__.get("_nw_nhwc_ok")
+    if ok is not None:
+        return ok
+    if isinstance(model, DenseNet):
+        ok = (all(m.weight.shape[0] % 32 == 0 and m.bias is None and (m.weight.shape[1] == 3 if m is model.features.conv0 else
+                                                                       m.weight.shape[1] % 32 == 0 and m.stride == (1, 1) and m.groups == 1)
+                  for m in model.modules() if isinstance(m, nn.Conv2d))
+              and all(m.num_features % 4 == 0 and m.affine for m in model.modules() if isinstance(m, nn.BatchNorm2d)))
+    elif isinstance(model, CIFAR_DenseNet):
+        ok = (isinstance(model.conv1, nn.Conv2d) and _convs_nhwc_servable(model, model.conv1)
+              and all(isinstance(m, (CifarBottleneck, CifarTransition)) for k in (1, 2, 3, 4) for m in getattr(model, f"dense{k}"))
+              and all(isinstance(getattr(model, f"trans{k}"), CifarTransition) for k in (1, 2, 3)))
+    else:
+        blocks = [b for st in (model.layer1, model.layer2, model.layer3, model.layer4) for b in st]
+        ok = isinstance(model.conv1, nn.Conv2d) and not isinstance(model.conv1, ConvBiasAct) and _convs_nhwc_servable(model, model.conv1)
+        if isinstance(model, ResNet):
+            ok = (ok and _is_pool(model.maxpool, nn.MaxPool2d, 3, 2, 1)
+                  and all(type(b.downsample) is nn.Sequential and len(b.downsample) == 2 for b in blocks if b.downsample is not None))
+        else:
+            ok = ok and all(isinstance(b, PreActBlock) and len(b.shortcut) <= 1 for b in blocks)
+    model._nw_nhwc_ok = ok = bool(ok)
+    return ok
+
+
+def backbone_route(model, *, device_type, dtype, shape, grad, training=None):
+    """Which path a forward of ``model`` (one of the four network classes) takes for a batch of ``shape`` (None: any RGB batch) and
+    ``dtype`` on ``device_type`` with autograd recording or not, over plain facts like ops.knn_route (no tensor, no library
+    call): "nhwc_train" / "nhwc_infer" (_forward_nhwc_train / _forward_nhwc_infer) or "modules" (the reference's module
+    sequence; a copy fold_batchnorm has rewritten always).  The switches are read when asked: tests and bench.py assign them."""
+    training = model.training if training is None else training
+    switches = ((ResNet, RESNET_NHWC_TRAINING), (CIFAR_ResNet, RESNET_NHWC_TRAINING), (DenseNet, True),
+                (CIFAR_DenseNet, CIFAR_DENSENET_NHWC_TRAINING))
+    train_on = next((NHWC_TRAINING and on for cls, on in switches if isinstance(model, cls)), None)
+    if train_on is None or not _kernel_input(device_type, dtype, shape) or training != grad:
+        return "modules"
+    if training:
+        return "nhwc_train" if train_on and _nhwc_structure(model) else "modules"
+    infer = NHWC_INFERENCE and isinstance(model, (CIFAR_ResNet, DenseNet)) and _nhwc_structure(model) and model._nhwc_infer_servable(shape)
+    return "nhwc_infer" if infer else "modules"
+
+
+def backbone_route_for(model, x):
+    return backbone_route(model, device_type=x.device.type, dtype=x.dtype, shape=x.shape, grad=torch.is_grad_enabled())
 
 
 # ----------------------------------------------------------------------------- factories (load_model names)
@@ -1003,9 +1002,9 @@ def CIFAR_DenseNet121(pretrained=False, num_classes=10, bias=True, **kw):
 # ---------------------------------------------------------------------------------------------
 class ConvBiasAct(nn.Conv2d):
     """A convolution with a folded BatchNorm in it (fold_batchnorm): conv(x) + bias [+ residual] [-> ReLU].  On the
-    MI355X with channels_last fp32 tensors (what NWNet.enable_bn_folding gives the ResNets) the bias, the block's identity
-    and the ReLU are ONE in-place pass behind a bias-free convolution (ops.bias_act_nhwc_) instead of MIOpen's bias kernel
-    + add + relu; everywhere else the torch ops of the reference backbone.  Inference only."""
+    MI355X with channels_last fp32 tensors (what NWNet.enable_bn_folding gives the ResNets) all of it is ops.conv2d_nhwc (split-fp16
+    implicit GEMM, bias / identity / ReLU in its store) or, for a shape that kernel does not take, ONE in-place pass behind
+    MIOpen's bias-free convolution (ops.bias_act_nhwc_); everywhere else the torch ops of the reference backbone.  Inference only."""
 
     def _split_weight(self):
         w = self.weight
@@ -1017,16 +1016,15 @@ class ConvBiasAct(nn.Conv2d):
 
     def forward(self, x, residual=None, relu=False):
         c = self.out_channels
-        if (FUSED_CONV_NHWC and x.is_cuda and x.dtype == torch.float32 and x.dim() == 4 and not torch.is_grad_enabled()
-                and self.groups == 1 and self.dilation == (1, 1) and self.padding[0] == self.padding[1]
+        served = _kernel_input(x.device.type, x.dtype, x.shape, rgb=False) and not torch.is_grad_enabled()
+        if (served and self.groups == 1 and self.dilation == (1, 1) and self.padding[0] == self.padding[1]
                 and self.stride[0] == self.stride[1] and isinstance(self.padding[0], int)
                 and (x.is_contiguous(memory_format=torch.channels_last) or x.shape[1] == 3)):
             from .. import ops
             if ops.conv2d_nhwc_supported(x.shape, self.weight.shape, self.stride[0], self.padding[0]):
                 # the whole conv -> bias -> (+ identity) -> ReLU on the fp16 matrix cores at fp32-grade accuracy
                 return ops.conv2d_nhwc(x, self._split_weight(), self.bias, residual, relu, self.stride[0], self.padding[0])
-        if (x.is_cuda and x.dtype == torch.float32 and x.dim() == 4 and c % 4 == 0 and self.bias is not None
-                and not torch.is_grad_enabled() and x.is_contiguous(memory_format=torch.channels_last)
+        if (served and c % 4 == 0 and self.bias is not None and x.is_contiguous(memory_format=torch.channels_last)
                 and not x.is_contiguous()):
             y = F.conv2d(x, self.weight, None, self.stride, self.padding, self.dilation, self.groups)
             if y.is_contiguous(memory_format=torch.channels_last) and (
@@ -1043,12 +1041,11 @@ class ConvBiasAct(nn.Conv2d):
 
 
 def _fold_pair(conv, bn):
-    scale = bn.weight.detach() * torch.rsqrt(bn.running_var.detach() + bn.eps)
     fused = ConvBiasAct(conv.in_channels, conv.out_channels, conv.kernel_size, conv.stride, conv.padding,
                         conv.dilation, conv.groups, bias=True).to(conv.weight.device, conv.weight.dtype)
-    fused.weight.data.copy_(conv.weight.detach() * scale.view(-1, 1, 1, 1))
-    bias = conv.bias.detach() if conv.bias is not None else torch.zeros_like(scale)
-    fused.bias.data.copy_(bn.bias.detach() + (bias - bn.running_mean.detach()) * scale)
+    w, b = _fold_conv_bn(conv, bn)
+    fused.weight.data.copy_(w)
+    fused.bias.data.copy_(b)
     return fused
 
 
@@ -1059,16 +1056,15 @@ def fold_batchnorm(model):
     the weights change."""
     import copy
     m = copy.deepcopy(model).eval()
-    # A DenseNet on the device that the channels-last inference path serves (DenseNet._forward_nhwc_infer: it folds for itself,
-    # from the plain modules) stays as it is; its eval forward on other tensors is the reference's module sequence.
+    # A network on the device that a channels-last inference path serves (DenseNet / CIFAR_ResNet._forward_nhwc_infer: it folds
+    # for itself, from the plain modules) stays as it is; its eval forward on other tensors is the reference's module sequence.
     keep = set()
     for mod in m.modules():
-        if isinstance(mod, DenseNet) and NHWC_INFERENCE and mod._nhwc_servable() and next(mod.parameters()).is_cuda:
+        if isinstance(mod, (ResNet, CIFAR_ResNet, DenseNet, CIFAR_DenseNet)) and backbone_route(
+                mod, device_type=next(mod.parameters()).device.type, dtype=torch.float32, shape=None, grad=False,
+                training=False) == "nhwc_infer":
             keep.update(id(x) for x in mod.modules())
-        if (isinstance(mod, CIFAR_ResNet) and NHWC_INFERENCE and next(mod.parameters()).is_cuda and mod._nhwc_train_servable()
-                and mod._nhwc_infer_servable()):
-            keep.update(id(x) for x in mod.modules())      # (likewise: CIFAR_ResNet._forward_nhwc_infer)
-    for mod in list(m.modules()):                # (the featurizer may sit inside a Sequential: proj_dim > 0)
+    for mod in list(m.modules()):               # (the featurizer may sit inside a Sequential: proj_dim > 0)
         if id(mod) in keep:
             continue
         if isinstance(mod, DenseNet):
@@ -1122,4 +1118,7 @@ def fold_batchnorm(model):
         ds = getattr(mod, "downsample", None)
         if isinstance(ds, nn.Sequential) and len(ds) == 2 and isinstance(ds[0], nn.Conv2d) and isinstance(ds[1], nn.BatchNorm2d):
             mod.downsample = nn.Sequential(_fold_pair(ds[0], ds[1]), nn.Identity())
+    for mod in m.modules():         # the copy answers for itself: nothing the routes kept on the source, or on the copy while
+        for name in ("_nw_nhwc_ok", "_nw_bank", "_nw_infer_plan"):      # it was still unrewritten (the keep rule), lives on in it
+            mod.__dict__.pop(name, None)
     return m

@@ -2136,8 +2136,8 @@ def bn_relu_avgpool2_nhwc(x, tab):
 
 def bn_table(bn):
     """mean | a | beta (3 c floats) of an eval-mode BatchNorm2d for nw_conv2d_nhwc_bnrelu_f16x2: y = (x - mean) a + beta."""
-    a = bn.weight.detach().float() * torch.rsqrt(bn.running_var.detach().float() + bn.eps)
-    return torch.cat((bn.running_mean.detach().float(), a, bn.bias.detach().float())).contiguous()
+    from .model.backbones import _bn_scale
+    return torch.cat((bn.running_mean.detach().float(), _bn_scale(bn, f32=True), bn.bias.detach().float())).contiguous()
 
 
 @torch.no_grad()
