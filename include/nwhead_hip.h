@@ -339,6 +339,28 @@ int nw_fwd_window_f32(const float *q, const float *s_split, const float *s_scale
                       float *out, float *lse_out, void *workspace, size_t workspace_bytes,
                       int64_t B, int64_t N, int64_t d, int64_t C, int kind, const float *logit_scale_dev,
                       void *stream);
+/* Gradient of the head w.r.t. the QUERIES over a resident split bank, the bank a constant: no (B,N) buffer anywhere, no
+ * support gradient.  The scores are recomputed tile by tile on the split-fp16 matrix cores (the forward's tile) and
+ * contracted with the bank rows in the same kernel; the row window of nw_fwd_window_f32 is honoured, so the windowed head
+ * (leave-one-out) is differentiable.
+ *   q (B,d) fp32; s_split / s_scale / s_norm2: the bank of nw_split_rows_f16x2; sy (N,) int64;
+ *   row_lo / row_hi (B,) int32: both NULL (no window) or both set, with `exclude` as in nw_fwd_window_f32;
+ *   lse (B,), out (B,C): what the forward (nw_fwd_f32 with lse_out, or nw_fwd_window_f32) returned for these operands;
+ *   gout (B,C): the upstream gradient;  gq (B,d): the result;  glogit_scale: optional scalar (0 unless clip).
+ *   row_chunks: 0 lets the library choose how many chunks of support tiles share the bank; a positive value is
+ *   clamped to the number of 64-row support tiles (the chunk reduction can then be exercised at small N).
+ * A query whose window admits no row (lse = -inf) gets a zero row.  Two calls give identical bits (no float atomics).
+ * Regime: nw_fwd_window_f32's -- d % 32 == 0, 32 <= d, N > 25, C >= 1, q / s_split / gq / workspace 16-byte aligned;
+ * anything else is NW_ERR_UNSUPPORTED before anything is launched, and its workspace size is 0.  Null required pointers,
+ * one of row_lo / row_hi alone, a negative size, clip without logit_scale_dev: NW_ERR_INVALID_ARG.  A short or NULL
+ * workspace: NW_ERR_WORKSPACE.  B == 0: NW_OK.  No allocation, no synchronisation, no environment. */
+size_t nw_bwd_query_workspace_bytes(int64_t B, int64_t N, int64_t d, int64_t C, int row_chunks);
+int nw_bwd_query_f32(const float *q, const float *s_split, const float *s_scale, const float *s_norm2,
+                     const int64_t *sy, const int32_t *row_lo, const int32_t *row_hi, int exclude,
+                     const float *lse, const float *out, const float *gout,
+                     float *gq, float *glogit_scale, void *workspace, size_t workspace_bytes,
+                     int64_t B, int64_t N, int64_t d, int64_t C, int kind, const float *logit_scale_dev,
+                     int row_chunks, void *stream);
 /* support_influence (util/metric.py:23-50) of k SELECTED supports per query, from the head's own outputs:
  *   vals (B,k) fp32 raw scores and rows (B,k) int64 bank rows (a search's val_out / idx_out),
  *   sy (N,) int64, qy (B,) int64, out (B,C) log-probabilities and lse (B,) of nw_fwd_f32 over the same bank;

@@ -12,6 +12,7 @@
 // cdist backward masks the zero distance the same way).
 #include "nw_internal.h"
 #include "tile_dma.h"
+#include "bwd_coeff.h"
 #include <cstdlib>
 
 namespace nw {
@@ -86,14 +87,9 @@ __global__ __launch_bounds__(1024) void nw_bwd_coeff_kernel(
     }
     t = block_sum(t, red);
 
-    float scale = 1.f, nq = 1.f, inq2 = 0.f;
-    if (KIND == NW_SCORE_CLIP) scale = expf(*logit_scale);
-    if (KIND == NW_SCORE_HYPERSPHERE || KIND == NW_SCORE_COSINE || KIND == NW_SCORE_CLIP) {
-        const float n = sqrtf(qn2[b]);
-        nq = fmaxf(n, NW_NORM_EPS);
-        inq2 = (n > NW_NORM_EPS) ? 1.f / (nq * nq) : 0.f;  // F.normalize clamps: no grad via |q|
-    }
     constexpr bool NORMS = (KIND == NW_SCORE_HYPERSPHERE || KIND == NW_SCORE_COSINE || KIND == NW_SCORE_CLIP);
+    float scale, nq, inq2;   // the per-pair derivatives and the query's factors: bwd_coeff.h
+    bwd_query_factors<KIND>(NORMS ? qn2[b] : 0.f, logit_scale, scale, nq, inq2);
     float rq_acc = 0.f, gls_acc = 0.f, amax = 0.f;
     for (int64_t j0 = tid; j0 < N; j0 += (int64_t)U * nthr) {
         float scv[U], snv[U], ssc[U];
@@ -114,33 +110,7 @@ __global__ __launch_bounds__(1024) void nw_bwd_coeff_kernel(
             const float dw = ((uint64_t)y[u] < (uint64_t)C) ? dP[y[u]] : 0.f;
             const float dS = expf(sc - l) * (dw - t);
             float a, r;
-            if (KIND == NW_SCORE_DOT) {
-                a = dS;
-                r = 0.f;
-            } else if (KIND == NW_SCORE_EUCLIDEAN) {
-                const float D = -sc;
-                a = (D == 0.f) ? 0.f : dS / D;
-                r = -0.5f * a;
-                rq_acc += r;
-            } else {
-                const float sn = sqrtf(snv[u]);
-                const float ns = fmaxf(sn, NW_NORM_EPS);
-                const float ins2 = (sn > NW_NORM_EPS) ? 1.f / (ns * ns) : 0.f;
-                float fc, c;  // df/dcos and cos
-                if (KIND == NW_SCORE_HYPERSPHERE) {
-                    const float D = -sc;
-                    fc = (D == 0.f) ? 0.f : 1.f / D;
-                    c = 1.f - 0.5f * D * D;
-                } else {
-                    fc = scale;
-                    c = sc / scale;
-                    gls_acc += dS * sc;  // d(e^ls cos)/d ls = score
-                }
-                const float gc = dS * fc;
-                a = gc / (nq * ns);
-                rq_acc += gc * (-0.5f * c * inq2);
-                r = gc * (-0.5f * c * ins2);
-            }
+            bwd_pair_coeff<KIND>(sc, dS, snv[u], scale, nq, inq2, a, r, rq_acc, gls_acc);
             if (SPLIT) {
                 const float ah = a * ssc[u];
                 rowbuf[j] = ah;

@@ -1,0 +1,482 @@
+// bwd_query.hip -- gradient of the head w.r.t. the queries over a resident split bank, without a (B,N) matrix
+// (gfx950 / MI355X only; nw_bwd_query_f32).
+//
+// backward.hip's closed form with the bank a constant.  For query b, bank row j, score s_bj = f(dot, |q_b|^2, |s_j|^2):
+//     dP_c = g_bc exp(-out_bc)                 dW_j = dP[y_j]  (0 for a label outside [0, C))
+//     W_j  = exp(s_bj - lse_b) for a row the window admits, 0 otherwise
+//     t_b  = sum_j W_j dW_j                    dS_j = W_j (dW_j - t_b)
+//     A_bj = dS_j df/ddot     rq_b = sum_j dS_j df/d|q|^2     gls = sum_bj dS_j df/dlogit_scale   (bwd_coeff.h)
+//     gq_b = sum_j A_bj s_j + 2 rq_b q_b
+// Nothing of size B x N is read or written: a workgroup owns 64 queries, a contiguous chunk of 64-row support tiles and a
+// slab of 32 * NCH columns of d.  Per support tile it
+//   1. recomputes the tile's dot products like the forward does (tile_dots_f16x2: raw queries split in registers, split
+//      bank rows, LDS-DMA ring) -- query on the lane, support rows 16r + 4g + e in the registers;
+//   2. turns them into A in registers (score, window, W, dW gathered from the (B,C) table of the prologue, dS, the kind's
+//      derivative), scales the row by 2^E_b and the element by the bank row's 2^-e_j, and splits it into fp16 halves;
+//   3. streams the tile's bank rows once more, 32 columns at a time, and adds A' s' to its 64 x (32 NCH) accumulators on
+//      v_mfma_f32_16x16x32_f16 (hl, lh, hh).  The accumulator layout of step 1 IS the A-operand layout of this product
+//      (query = row, eight supports per lane = k), with the k order permuted: element e of block r is tile row
+//      16r + 4g + e.  The bank operand is read with ds_read_b64_tr_b16 in the same order: lane 4q + p of group g supplies
+//      row 32t + 16h + 4g + q, columns 4p .. 4p + 3 of the 16-column block.
+// t_b needs no pass over the bank: it is sum_c dP_c P_c with P_c = exp(out_c) - 1e-12 the class mass.  A class that no
+// admitted row carries has out_c = log(1e-12) exactly (the forward adds 1e-12 to an exact 0) and is left out, so that it
+// contributes exactly 0 (the closed form through the rounded `out` would give ~1e-6 g).
+//
+// Scaling.  s'_j = s_j 2^e_j are the bank's rows; A'_bj = A_bj 2^-e_j 2^E with ONE exponent per query row and chunk, a
+// power of two: gq_b = sum_chunks 2^-E_{b,chunk} sum_j A'_bj s'_j + 2 rq_b q_b, and scaling a row of gout by 2^k scales its
+// row of gq exactly.  E is known before a tile is multiplied, without a pass over the row: it is the split exponent of the
+// largest |A_bj 2^-e_j| the row has shown SO FAR in the chunk (taken in registers, per tile), and when a tile raises it
+// the row's accumulators are rescaled by the power of two between the old and the new exponent (exact; the factor
+// crosses from "query on the lane" to "query in the registers" through 64 floats of LDS that a wave writes and reads
+// itself).  An a-priori bound does not do for the distance kinds: |df/ddot| = 1/D has none, and the bounds that hold
+// (D >= -lse, or the rounding noise of D where lse >= 0) lie 2^12 above the row's real maximum for a large bank
+// (lse ~ ln N - D), which costs the small coefficients their low halves: measured 1.5e-3 of max|gq| at 64 x 65536 x 64
+// against 1e-4 for the route through the matrix.  An element keeps 22 bits down to 2^-28 of the running maximum.
+//
+// Chunks over N fill the chip; each writes its partial gq / rq / gls, nw_bwd_query_finish_kernel adds them in chunk order:
+// no float atomics, two calls give the same bits.
+#include "nw_internal.h"
+#include "tile_dma.h"
+#include "tile_f16.h"
+#include "bwd_coeff.h"
+
+namespace nw {
+namespace {
+
+typedef __fp16 fp16x4 __attribute__((__vector_size__(4 * sizeof(__fp16))));
+typedef _Float16 halfx4 __attribute__((ext_vector_type(4)));
+
+constexpr int QRS = 4;            // support blocks per tile
+constexpr int QBS = 16 * QRS;     // 64 bank rows per tile
+constexpr int Q_HDR = (3 * BQ + 3 * QBS) * 4;   // qn2[BQ] | qsc[BQ] | fac[BQ] | sn2[QBS] | ssc[QBS] | lab[QBS]
+static_assert(Q_HDR % 16 == 0, "stage buffers must stay 16-byte aligned");
+constexpr size_t Q_LDS = Q_HDR + DmaCfg<QRS>::STAGE_BYTES;
+static_assert(Q_LDS <= 160 * 1024, "header + ring exceed LDS");
+// the second product's ring (over the forward's, dead by then): 64 rows x 128 B per stage
+constexpr int Q2_STAGE = QBS * 128, Q2_NBUF = 4, Q2_NI = QBS / 8 / NLOAD;
+static_assert((size_t)Q2_NBUF * Q2_STAGE <= DmaCfg<QRS>::STAGE_BYTES, "second ring inside the first");
+constexpr int Q_CUS = 256;        // workgroups that fill the chip (one per CU: up to 217 registers per lane)
+constexpr float HALF_MAX = 60000.f;
+
+struct BwdQueryWs {
+    float *dptab, *tb, *ascale, *rqp, *glsp, *part;
+};
+struct BwdQueryPlan {
+    int n_stiles, n_qtiles, nch, nslabs, nchunks, tpc;
+};
+struct BwdQueryArgs {
+    const float *q, *s, *s_scale, *s_norm2;
+    const int64_t* sy;
+    const int *win_lo, *win_hi;
+    const float *lse, *logit_scale;
+    BwdQueryWs ws;
+    int exclude, B, N, d, C, n_stiles, n_qtiles, nslabs, nchunks, tpc;
+};
+
+// dP (B,C) and t_b: one workgroup per query.  (The block sum runs in a fixed order: deterministic.)
+__global__ __launch_bounds__(256) void nw_bwd_query_prologue_kernel(const float* __restrict__ out, const float* __restrict__ gout,
+                                                                     float* __restrict__ dptab, float* __restrict__ tb, int64_t C) {
+    __shared__ float red[8];
+    const int64_t b = blockIdx.x;
+    // what the forward's logf gives for an empty class, from the same routine (blockIdx.y is 0: not folded on the host)
+    const float absent = logf((float)blockIdx.y + NW_LOG_EPS);
+    float t = 0.f;
+    for (int64_t c = threadIdx.x; c < C; c += 256) {
+        const float o = out[b * C + c];
+        float dp = 0.f;
+        if (o > absent) {
+            dp = gout[b * C + c] * expf(-o);
+            t += dp * (expf(o) - NW_LOG_EPS);
+        }
+        dptab[b * C + c] = dp;
+    }
+    t = block_sum(t, red);
+    if (threadIdx.x == 0) tb[b] = t;
+}
+
+template <int KIND, int NCH>
+__global__ __launch_bounds__(TILE_THREADS, 2) void nw_bwd_query_kernel(const BwdQueryArgs a) {
+    constexpr bool NEED_NORM = (KIND != NW_SCORE_DOT);
+    constexpr float L2E = 1.44269504088896340736f, LN2 = 0.693147180559945309417f;
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    float* qn2 = reinterpret_cast<float*>(smem);
+    float* qsc_s = qn2 + BQ;
+    float* fac_s = qsc_s + BQ;       // rescaling factors of the rows, wave-private (see the header)
+    float* sn2 = fac_s + BQ;
+    float* ssc = sn2 + QBS;
+    int* lab = reinterpret_cast<int*>(ssc + QBS);
+    float4* stage = reinterpret_cast<float4*>(smem + Q_HDR);
+    const char* ring2 = smem + Q_HDR;
+
+    const int B = a.B, N = a.N, d = a.d;
+    const int tid = threadIdx.x, lane = tid & 63, i = lane & 15, g = lane >> 4;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    // workgroup -> (chunk, slab, query tile): the workgroups that share a chunk's bank rows are neighbours
+    const int qt = blockIdx.x % a.n_qtiles, rest = blockIdx.x / a.n_qtiles;
+    const int slab = rest % a.nslabs, chunk = rest / a.nslabs;
+    const int q0 = qt * BQ;
+    const int nk = d / BK;
+    const int kc0 = slab * NCH;
+    const int nc = min(NCH, nk - kc0);                 // 32-column chunks of this slab
+    const int st_begin = chunk * a.tpc, st_end = min(a.n_stiles, st_begin + a.tpc);
+
+    // ---- what a consumer lane knows of its query (query 16 wave + i on the lane)
+    const int qrow = 16 * (wave & 3) + i;
+    const int b = q0 + qrow, bb = b < B ? b : B - 1;
+    const float lse = a.lse[bb];
+    const float lsev = lse == -INFINITY ? INFINITY : lse * L2E;   // a dead window: W = 2^(u - inf) = 0 in every row
+    const float tq = a.ws.tb[bb];
+    const float* dprow = a.ws.dptab + (size_t)bb * a.C;
+    const bool windowed = a.win_lo != nullptr;
+    int lo = 0, hi = N;
+    if (windowed) lo = min(max(a.win_lo[bb], 0), N), hi = min(max(a.win_hi[bb], 0), N);   // never used as addresses
+    const unsigned width = hi > lo ? (unsigned)(hi - lo) : 0u;
+    const bool exclude = a.exclude != 0;
+
+    f32x4 gacc[NCH][2];
+#pragma unroll
+    for (int c = 0; c < NCH; ++c) gacc[c][0] = gacc[c][1] = f32x4{0.f, 0.f, 0.f, 0.f};
+    float rq_acc = 0.f, gls_acc = 0.f;
+    int Erun = 0;          // the row's exponent in this chunk so far; `have`: some tile has set it
+    bool have = false;
+
+    // transposed reads of the second product: lane 4q + p of group g supplies row 4g + q (+ 16h + 32t), bytes 8(p & 1) of
+    // 16-byte slot (gs + (p >> 1)) ^ sw, sw = 2 ((row >> 1) & 3): the eight rows a 32-lane half touches land on eight
+    // different groups of eight banks
+    const int tq4 = i >> 2, tp = i & 3;
+    const int sw2 = ((2 * g + (tq4 >> 1)) & 3) << 1;
+    const int trow = (4 * g + tq4) * 128 + 8 * (tp & 1);
+    int toff[2][2];   // [half: h, l][16-column block]
+#pragma unroll
+    for (int hl = 0; hl < 2; ++hl)
+#pragma unroll
+        for (int nb = 0; nb < 2; ++nb) toff[hl][nb] = trow + (((4 * hl + 2 * nb + (tp >> 1)) ^ sw2) << 4);
+
+    for (int st = st_begin; st < st_end; ++st) {
+        const int s0 = st * QBS;
+        for (int t = tid; t < QBS; t += TILE_THREADS) {
+            const int j = min(s0 + t, N - 1);
+            if (NEED_NORM) sn2[t] = a.s_norm2[j];
+            ssc[t] = a.s_scale[j];
+            const int64_t y = a.sy[j];
+            lab[t] = ((uint64_t)y < (uint64_t)a.C) ? (int)y : -1;
+        }
+        f32x4 acc[QRS];
+        tile_dots_f16x2<QRS, true>(a.q, a.s, B, N, d, q0, s0, stage, acc, st % nk, qn2, qsc_s);
+        __syncthreads();   // the header is visible, the ring is dead
+
+        if (wave < NCONS) {
+            // ================================ consumers: A' in registers ================================
+            half8 Ah[QRS / 2], Al[QRS / 2];
+            {
+                using SF = ScoreFactors<KIND>;
+                const float qn = NEED_NORM ? qn2[qrow] : 0.f;
+                float scale, nq, inq2, Cq, Bq;
+                bwd_query_factors<KIND>(qn, a.logit_scale, scale, nq, inq2);
+                SF::query(qn, qsc_s[qrow], scale, Cq, Bq);
+                const int tile_end = s0 + QBS < N ? s0 + QBS : N;
+                // the window's rule of the forward (fused_impl.h, OUT_WIN): a pair the window leaves whole skips the comparisons
+                const bool whole = !windowed || (exclude ? (width == 0u || hi <= s0 || lo >= tile_end) : (lo <= s0 && hi >= tile_end));
+                const bool check = !whole || tile_end < s0 + QBS;
+                const int rel = s0 + 4 * g - lo;
+                float dw[QRS][4], xr[QRS][4], amax = 0.f;
+#pragma unroll
+                for (int r = 0; r < QRS; ++r) {
+                    const int4 y4 = *reinterpret_cast<const int4*>(lab + 16 * r + 4 * g);
+                    const int yy[4] = {y4.x, y4.y, y4.z, y4.w};
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) dw[r][e] = dprow[yy[e] < 0 ? 0 : yy[e]];
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) dw[r][e] = yy[e] < 0 ? 0.f : dw[r][e];
+                }
+#pragma unroll
+                for (int r = 0; r < QRS; ++r) {
+                    float4 n4 = make_float4(0.f, 0.f, 0.f, 0.f);
+                    if (NEED_NORM) n4 = *reinterpret_cast<const float4*>(sn2 + 16 * r + 4 * g);
+                    const float4 s4 = *reinterpret_cast<const float4*>(ssc + 16 * r + 4 * g);
+                    const float nn[4] = {n4.x, n4.y, n4.z, n4.w}, ss[4] = {s4.x, s4.y, s4.z, s4.w};
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) {
+                        float K, Base;
+                        SF::support(nn[e], ss[e], K, Base);
+                        const float u = SF::finish(__builtin_fmaf(acc[r][e], K * Cq, Base + Bq));   // base-2 units, as the forward
+                        float W = __builtin_amdgcn_exp2f(u - lsev);
+                        if (check) {
+                            const int t = 16 * r + e;
+                            bool keep = s0 + 4 * g + t < N;
+                            if (windowed) keep = keep && (((unsigned)(rel + t) < width) != exclude);
+                            W = keep ? W : 0.f;
+                        }
+                        const float dS = W * (dw[r][e] - tq);
+                        float av, rs_unused;
+                        bwd_pair_coeff<KIND>(u * LN2, dS, nn[e], scale, nq, inq2, av, rs_unused, rq_acc, gls_acc);
+                        xr[r][e] = av * ss[e];
+                        amax = fmaxf(amax, fabsf(xr[r][e]));
+                    }
+                }
+                // the row's exponent: raised (a smaller E) when this tile holds a larger coefficient than any before it
+                amax = group4_max(amax);
+                float factor = 1.f;
+                if (amax > 0.f && amax < INFINITY) {
+                    const int En = split_exponent(amax);
+                    if (!have || En < Erun) {
+                        if (have) factor = __builtin_ldexpf(1.f, En - Erun);   // (before: the row's accumulators are all zero)
+                        Erun = En;
+                        have = true;
+                    }
+                }
+                const float up = __builtin_ldexpf(1.f, Erun);
+#pragma unroll
+                for (int r = 0; r < QRS; ++r)
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) {
+                        const float x = __builtin_amdgcn_fmed3f(xr[r][e] * up, -HALF_MAX, HALF_MAX);   // (only a non-finite input gets here)
+                        const _Float16 h = (_Float16)x;
+                        Ah[r >> 1][4 * (r & 1) + e] = h;
+                        Al[r >> 1][4 * (r & 1) + e] = (_Float16)(x - (float)h);
+                    }
+                // lane (i, g) holds the accumulators of queries 4g + e: their factors come from the lanes that own them.  A
+                // wave's LDS operations execute in order and the 16 floats are this wave's own: no barrier
+                if (g == 0) fac_s[qrow] = factor;
+                __builtin_amdgcn_wave_barrier();
+                asm volatile("" ::: "memory");
+                if (__any(factor != 1.f)) {
+                    const float4 f4 = *reinterpret_cast<const float4*>(fac_s + 16 * (wave & 3) + 4 * g);
+                    const f32x4 fv = {f4.x, f4.y, f4.z, f4.w};
+#pragma unroll
+                    for (int c = 0; c < NCH; ++c) {
+                        gacc[c][0] *= fv;
+                        gacc[c][1] *= fv;
+                    }
+                }
+            }
+            // ================================ consumers: gq tile += A' s' ================================
+            auto tr8 = [&](const char* base, int off) {
+                const halfx4 v0 = __builtin_bit_cast(halfx4, __builtin_amdgcn_ds_read_tr16_b64_v4f16(
+                    (__attribute__((address_space(3))) fp16x4*)(base + off)));
+                const halfx4 v1 = __builtin_bit_cast(halfx4, __builtin_amdgcn_ds_read_tr16_b64_v4f16(
+                    (__attribute__((address_space(3))) fp16x4*)(base + off + 16 * 128)));
+                return half8{v0[0], v0[1], v0[2], v0[3], v1[0], v1[1], v1[2], v1[3]};
+            };
+            auto mm = [](const half8& x, const half8& y, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x32_f16(x, y, c, 0, 0, 0); };
+#pragma unroll
+            for (int c = 0; c < NCH; ++c) {
+                if (c < nc) {
+                    tile_barrier();   // stage c has landed
+                    const char* buf = ring2 + (c % Q2_NBUF) * Q2_STAGE;
+#pragma unroll
+                    for (int t = 0; t < QRS / 2; ++t) {
+                        const half8 bh0 = tr8(buf, toff[0][0] + 32 * 128 * t), bh1 = tr8(buf, toff[0][1] + 32 * 128 * t);
+                        const half8 bl0 = tr8(buf, toff[1][0] + 32 * 128 * t), bl1 = tr8(buf, toff[1][1] + 32 * 128 * t);
+                        // small terms first, the dominant h*h product last; the two column blocks alternate
+                        gacc[c][0] = mm(Al[t], bh0, gacc[c][0]);
+                        gacc[c][1] = mm(Al[t], bh1, gacc[c][1]);
+                        gacc[c][0] = mm(Ah[t], bl0, gacc[c][0]);
+                        gacc[c][1] = mm(Ah[t], bl1, gacc[c][1]);
+                        gacc[c][0] = mm(Ah[t], bh0, gacc[c][0]);
+                        gacc[c][1] = mm(Ah[t], bh1, gacc[c][1]);
+                    }
+                }
+            }
+            tile_barrier();   // the ring is free for the next tile
+        } else {
+            // ================================ loaders: the tile's rows again, this slab's columns ================================
+            const int lw = wave - NCONS;
+            unsigned voff[Q2_NI];
+#pragma unroll
+            for (int m = 0; m < Q2_NI; ++m) {
+                const int R = 8 * (lw + NLOAD * m) + (lane >> 3);
+                const int lslot = (lane & 7) ^ (((R >> 1) & 3) << 1);   // source-side swizzle (see toff)
+                const int rel = min(s0 + R, N - 1) - s0;
+                voff[m] = ((unsigned)rel * (unsigned)d + lslot * 4) * 4u;
+            }
+            const char* sb = reinterpret_cast<const char*>(a.s + (size_t)s0 * d) + (size_t)kc0 * BK * 4;
+            auto issue = [&](int c) {
+                char* buf = smem + Q_HDR + (c % Q2_NBUF) * Q2_STAGE;
+#pragma unroll
+                for (int m = 0; m < Q2_NI; ++m)
+                    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(sb + (size_t)c * BK * 4 + voff[m]),
+                                                     (__attribute__((address_space(3))) void*)(buf + 1024 * (lw + NLOAD * m)), 16, 0, 0);
+            };
+            constexpr int AHEAD = Q2_NBUF - 1;
+#pragma unroll
+            for (int c = 0; c < AHEAD; ++c)
+                if (c < nc) issue(c);
+            for (int c = 0; c < nc; ++c) {
+                if (c + AHEAD <= nc) wait_vmcnt<(AHEAD - 1) * Q2_NI>(); else wait_vmcnt<0>();
+                tile_barrier();   // stage c is published; the consumers have left stage c - 1
+                if (c + AHEAD < nc) issue(c + AHEAD);
+            }
+            tile_barrier();
+        }
+    }
+
+    if (wave >= NCONS) return;
+    // ---- partial results of this chunk: acc[c][nb][e] of lane (i, g) = gq'[query 16 wave + 4g + e][column 32 (kc0 + c) + 16 nb + i]
+#pragma unroll
+    for (int c = 0; c < NCH; ++c) {
+        if (c < nc) {
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                const int bo = q0 + 16 * wave + 4 * g + e;
+                if (bo < B) {
+                    float* row = a.ws.part + ((size_t)chunk * B + bo) * d + (size_t)(kc0 + c) * BK + i;
+                    row[0] = gacc[c][0][e];
+                    row[16] = gacc[c][1][e];
+                }
+            }
+        }
+    }
+    if (slab == 0) {
+        rq_acc = group4_sum(rq_acc);
+        gls_acc = group4_sum(gls_acc);
+        if (g == 0 && b < B) {
+            a.ws.rqp[(size_t)chunk * B + b] = rq_acc;
+            a.ws.glsp[(size_t)chunk * B + b] = gls_acc;
+            a.ws.ascale[(size_t)chunk * B + b] = __builtin_ldexpf(1.f, -Erun);   // (1 when no tile set it: the partial row is zero)
+        }
+    }
+}
+
+// gq[b,k] = sum_chunks 2^-E[c][b] part[c][b,k] + 2 (sum_chunks rq[c][b]) q[b,k], chunks in order (k in float4s)
+__global__ __launch_bounds__(256) void nw_bwd_query_finish_kernel(const float* __restrict__ part, const float* __restrict__ rqp,
+                                                                   const float* __restrict__ ascale, const float* __restrict__ q,
+                                                                   float* __restrict__ gq, int nchunks, int64_t B, int64_t d) {
+    const int64_t total4 = B * d / 4;
+    const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (idx >= total4) return;
+    const int64_t b = (idx * 4) / d;
+    float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+    float rq = 0.f;
+    for (int c = 0; c < nchunks; ++c) {
+        const float4 w = *reinterpret_cast<const float4*>(part + (int64_t)c * B * d + idx * 4);
+        const float f = ascale[(int64_t)c * B + b];   // a power of two: exact
+        v.x += w.x * f; v.y += w.y * f; v.z += w.z * f; v.w += w.w * f;
+        rq += rqp[(int64_t)c * B + b];
+    }
+    const float r2 = 2.f * rq;
+    const float4 x = *reinterpret_cast<const float4*>(q + idx * 4);
+    v.x = __builtin_fmaf(r2, x.x, v.x); v.y = __builtin_fmaf(r2, x.y, v.y);
+    v.z = __builtin_fmaf(r2, x.z, v.z); v.w = __builtin_fmaf(r2, x.w, v.w);
+    *reinterpret_cast<float4*>(gq + idx * 4) = v;
+}
+
+// glogit_scale = sum_b sum_chunks gls[c][b]: a thread adds its queries' chunks in order, the block in a fixed tree
+__global__ __launch_bounds__(256) void nw_bwd_query_gls_kernel(const float* __restrict__ glsp, float* __restrict__ out, int nchunks,
+                                                                int64_t B) {
+    __shared__ float red[8];
+    float v = 0.f;
+    for (int64_t b = threadIdx.x; b < B; b += 256)
+        for (int c = 0; c < nchunks; ++c) v += glsp[(int64_t)c * B + b];
+    v = block_sum(v, red);
+    if (threadIdx.x == 0) *out = v;
+}
+
+inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
+
+// Slab width and chunk count.  Cost of a workgroup per support tile, in matrix-core time: 3 d/32 for the scores (every
+// slab recomputes them) + 4 per 32 columns of the slab (3 MFMAs per block and the transposed reads, which bound it);
+// the grid runs in ceil(workgroups / CUs) rounds.  The partial tiles are what the workspace holds: the library's own
+// choice keeps nchunks B d 4 bytes below 0.85 B N bytes (a fifth of one score matrix), i.e. a chunk is at least d / 27 tiles.
+BwdQueryPlan bwd_query_plan(int64_t B, int64_t N, int64_t d, int row_chunks) {
+    BwdQueryPlan best = {};
+    const int64_t n_stiles = (N + QBS - 1) / QBS, n_qtiles = (B + BQ - 1) / BQ, nk = d / BK;
+    int64_t best_cost = -1;
+    for (int nch = 8; nch >= 4; nch >>= 1) {
+        if (nch > 4 && nch / 2 >= nk) continue;   // a narrower slab already takes the whole width
+        const int64_t nslabs = (nk + nch - 1) / nch;
+        int64_t want;
+        if (row_chunks > 0) {
+            want = row_chunks < n_stiles ? row_chunks : n_stiles;
+        } else {
+            const int64_t fit = n_stiles * QBS * 27 / (128 * d), cap = fit > 1 ? fit : 1;
+            want = (Q_CUS + n_qtiles * nslabs - 1) / (n_qtiles * nslabs);
+            if (want > cap) want = cap;
+        }
+        const int64_t tpc = (n_stiles + want - 1) / want, nchunks = (n_stiles + tpc - 1) / tpc;
+        const int64_t wgs = n_qtiles * nslabs * nchunks, rounds = (wgs + Q_CUS - 1) / Q_CUS;
+        const int64_t cost = rounds * tpc * (3 * nk + 4 * (nch < nk ? nch : nk));
+        if (best_cost < 0 || cost < best_cost) {
+            best_cost = cost;
+            best = {(int)n_stiles, (int)n_qtiles, nch, (int)nslabs, (int)nchunks, (int)tpc};
+        }
+    }
+    return best;
+}
+
+size_t bwd_query_layout(int64_t B, int64_t d, int64_t C, const BwdQueryPlan& p, char* base, BwdQueryWs* ws) {
+    size_t off = 0;
+    auto take = [&](size_t nfloat) {
+        float* ptr = base ? reinterpret_cast<float*>(base + off) : nullptr;
+        off += align256(nfloat * sizeof(float));
+        return ptr;
+    };
+    BwdQueryWs w;
+    w.dptab = take((size_t)B * C);
+    w.tb = take((size_t)B);
+    w.ascale = take((size_t)p.nchunks * B);
+    w.rqp = take((size_t)p.nchunks * B);
+    w.glsp = take((size_t)p.nchunks * B);
+    w.part = take((size_t)p.nchunks * B * d);
+    if (ws) *ws = w;
+    return off;
+}
+
+template <int KIND, int NCH>
+int launch_bwd_query_kernel(const BwdQueryArgs& a, unsigned grid, hipStream_t st) {
+    static const bool attr = hipFuncSetAttribute(reinterpret_cast<const void*>(nw_bwd_query_kernel<KIND, NCH>),
+                                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)Q_LDS) == hipSuccess;
+    if (!attr) return NW_ERR_LAUNCH;
+    hipLaunchKernelGGL((nw_bwd_query_kernel<KIND, NCH>), dim3(grid), dim3(TILE_THREADS), Q_LDS, st, a);
+    return NW_OK;
+}
+template <int KIND>
+int launch_bwd_query_kind(const BwdQueryArgs& a, int nch, unsigned grid, hipStream_t st) {
+    return nch == 8 ? launch_bwd_query_kernel<KIND, 8>(a, grid, st) : launch_bwd_query_kernel<KIND, 4>(a, grid, st);
+}
+
+}  // namespace
+
+bool bwd_query_shape_ok(int64_t B, int64_t N, int64_t d, int64_t C) {
+    return N > 25 && C >= 1 && d >= 32 && d % 32 == 0 && d <= (1 << 20) && B <= 0x7fffffffLL - BQ && N <= 0x7fffffffLL - QBS
+           && C < (1 << 30);
+}
+
+size_t bwd_query_workspace_bytes(int64_t B, int64_t N, int64_t d, int64_t C, int row_chunks) {
+    if (B <= 0 || !bwd_query_shape_ok(B, N, d, C)) return 0;
+    return bwd_query_layout(B, d, C, bwd_query_plan(B, N, d, row_chunks), nullptr, nullptr);
+}
+
+int launch_bwd_query(const BwdQueryCall& c) {
+    hipStream_t st = c.st;
+    const BwdQueryPlan p = bwd_query_plan(c.B, c.N, c.d, c.row_chunks);
+    BwdQueryWs ws;
+    const size_t need = bwd_query_layout(c.B, c.d, c.C, p, static_cast<char*>(c.workspace), &ws);
+    if (!c.workspace || c.workspace_bytes < need) return NW_ERR_WORKSPACE;
+    const int64_t wgs = (int64_t)p.n_qtiles * p.nslabs * p.nchunks;
+    if (wgs > 0x7fffffffLL || (c.B * c.d / 4 + 255) / 256 > 0x7fffffffLL) return NW_ERR_UNSUPPORTED;
+    hipLaunchKernelGGL(nw_bwd_query_prologue_kernel, dim3((unsigned)c.B), dim3(256), 0, st, c.out, c.gout, ws.dptab, ws.tb, c.C);
+    const BwdQueryArgs a = {c.q, c.s_split, c.s_scale, c.s_norm2, c.sy, c.row_lo, c.row_hi, c.lse, c.logit_scale_dev, ws,
+                            c.exclude, (int)c.B, (int)c.N, (int)c.d, (int)c.C, p.n_stiles, p.n_qtiles, p.nslabs, p.nchunks, p.tpc};
+    int rc;
+    switch (c.kind) {
+        case NW_SCORE_EUCLIDEAN: rc = launch_bwd_query_kind<NW_SCORE_EUCLIDEAN>(a, p.nch, (unsigned)wgs, st); break;
+        case NW_SCORE_HYPERSPHERE: rc = launch_bwd_query_kind<NW_SCORE_HYPERSPHERE>(a, p.nch, (unsigned)wgs, st); break;
+        case NW_SCORE_COSINE: rc = launch_bwd_query_kind<NW_SCORE_COSINE>(a, p.nch, (unsigned)wgs, st); break;
+        case NW_SCORE_DOT: rc = launch_bwd_query_kind<NW_SCORE_DOT>(a, p.nch, (unsigned)wgs, st); break;
+        default: rc = launch_bwd_query_kind<NW_SCORE_CLIP>(a, p.nch, (unsigned)wgs, st); break;
+    }
+    if (rc != NW_OK) return rc;
+    hipLaunchKernelGGL(nw_bwd_query_finish_kernel, dim3((unsigned)((c.B * c.d / 4 + 255) / 256)), dim3(256), 0, st, ws.part, ws.rqp,
+                       ws.ascale, c.q, c.gq, p.nchunks, c.B, c.d);
+    if (c.glogit_scale) {
+        if (c.kind == NW_SCORE_CLIP)
+            hipLaunchKernelGGL(nw_bwd_query_gls_kernel, dim3(1), dim3(256), 0, st, ws.glsp, c.glogit_scale, p.nchunks, c.B);
+        else if (hipMemsetAsync(c.glogit_scale, 0, 4, st) != hipSuccess)
+            return NW_ERR_LAUNCH;
+    }
+    NW_CHECK_LAUNCH();
+    return NW_OK;
+}
+
+}  // namespace nw

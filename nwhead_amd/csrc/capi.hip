@@ -247,6 +247,33 @@ extern "C" int nw_fwd_window_f32(const float* q, const float* s_split, const flo
     return nw::launch_fused(a, nw::FORM_SPLIT, kind);
 }
 
+// The query gradient over a resident split bank (bwd_query.hip): nw_fwd_window_f32's regime, a workspace of its own.
+extern "C" size_t nw_bwd_query_workspace_bytes(int64_t B, int64_t N, int64_t d, int64_t C, int row_chunks) {
+    if (B <= 0 || N < 0 || d < 0 || C < 0) return 0;
+    return nw::bwd_query_workspace_bytes(B, N, d, C, row_chunks);
+}
+
+extern "C" int nw_bwd_query_f32(const float* q, const float* s_split, const float* s_scale, const float* s_norm2,
+                                const int64_t* sy, const int32_t* row_lo, const int32_t* row_hi, int exclude,
+                                const float* lse, const float* out, const float* gout, float* gq, float* glogit_scale,
+                                void* workspace, size_t workspace_bytes, int64_t B, int64_t N, int64_t d, int64_t C,
+                                int kind, const float* logit_scale_dev, int row_chunks, void* stream) {
+    if (B < 0 || N < 0 || d < 0 || C < 0 || row_chunks < 0) return NW_ERR_INVALID_ARG;
+    if ((row_lo != nullptr) != (row_hi != nullptr)) return NW_ERR_INVALID_ARG;
+    if (bad_kind(kind)) return NW_ERR_UNSUPPORTED;
+    if (!nw::bwd_query_shape_ok(B, N, d, C)) return NW_ERR_UNSUPPORTED;
+    if (B == 0) return NW_OK;
+    if (!q || !s_split || !s_scale || !s_norm2 || !sy || !lse || !out || !gout || !gq) return NW_ERR_INVALID_ARG;
+    if (kind == NW_SCORE_CLIP && !logit_scale_dev) return NW_ERR_INVALID_ARG;
+    if ((reinterpret_cast<uintptr_t>(q) | reinterpret_cast<uintptr_t>(s_split) | reinterpret_cast<uintptr_t>(gq)) & 15)
+        return NW_ERR_UNSUPPORTED;
+    if (!workspace || workspace_bytes < nw::bwd_query_workspace_bytes(B, N, d, C, row_chunks)) return NW_ERR_WORKSPACE;
+    if (reinterpret_cast<uintptr_t>(workspace) & 15) return NW_ERR_UNSUPPORTED;
+    return nw::launch_bwd_query({q, s_split, s_scale, s_norm2, sy, row_lo, row_hi, exclude, lse, out, gout, gq, glogit_scale,
+                                 workspace, workspace_bytes, B, N, d, C, kind, logit_scale_dev, row_chunks,
+                                 static_cast<hipStream_t>(stream)});
+}
+
 extern "C" int nw_fwd_partial_f32(const float* q, const float* s, const int64_t* sy,
                                   const float* s_norm2, const float* s_split, const float* s_scale,
                                   float* m, float* den, float* num, void* workspace, size_t workspace_bytes,

@@ -63,6 +63,26 @@ int launch_xgemm(bool x_km, const float* X, int64_t ldx, int64_t x_rows, const f
                  const float* Xo, float* out, int64_t M, int64_t Nn, int64_t K, hipStream_t st,
                  XgemmReduce* defer = nullptr, const XgemmReduce* pending = nullptr);
 
+// bwd_query.hip: the head's gradient w.r.t. the queries over a resident split bank, no (B,N) matrix (nw_bwd_query_f32)
+struct BwdQueryCall {
+    const float *q, *s_split, *s_scale, *s_norm2;
+    const int64_t* sy;
+    const int32_t *row_lo, *row_hi;   // both or neither
+    int exclude;
+    const float *lse, *out, *gout;
+    float *gq, *glogit_scale;
+    void* workspace;
+    size_t workspace_bytes;
+    int64_t B, N, d, C;
+    int kind;
+    const float* logit_scale_dev;
+    int row_chunks;
+    hipStream_t st;
+};
+bool bwd_query_shape_ok(int64_t B, int64_t N, int64_t d, int64_t C);
+size_t bwd_query_workspace_bytes(int64_t B, int64_t N, int64_t d, int64_t C, int row_chunks);
+int launch_bwd_query(const BwdQueryCall& c);
+
 // Options of the forward call in progress on this thread (nw_fwd_opts of the ABI, set for the duration of the call by
 // the entry point): explicit arguments, not process state.
 struct FwdOpts {

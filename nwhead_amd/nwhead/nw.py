@@ -220,9 +220,10 @@ class NWNet(nn.Module):
                                         knn_merge_fn=knn_merge_fn, search_precision=self.search_precision)
         return self.sharded_bank
 
-    def _predict_leave_out(self, qfeat, rows, what):
-        """The 'full' head of the featurised queries ``qfeat`` over precompute()'s bank, query b without bank row rows[b]
-        (-1: with every row): ops.nw_head's row window [row, row + 1), excluded; -1 is the empty excluded window [0, 0)."""
+    def _resident_bank(self, what, device):
+        """precompute()'s bank as ``what`` needs it -- (full_feat, full_y, SplitBank) on ``device`` -- or NWHipError with the
+        reason: a sharded bank, no bank, a custom kernel module.  The SplitBank is rebuilt when full_feat was replaced or
+        updated since precompute(), as predict does."""
         if getattr(self, 'sharded_bank', None) is not None:
             raise ops.NWHipError(f"{what}: a sharded bank is not served (a row window is rows of one resident bank); call "
                                  "precompute()")
@@ -230,18 +231,51 @@ class NWNet(nn.Module):
             raise ops.NWHipError(f"{what} needs the bank of precompute()")
         if not isinstance(self.kernel, _ScoreModule):
             raise ops.NWHipError(f"{what} needs one of the built-in score kernels")
-        rows = torch.as_tensor(rows, device=qfeat.device)
-        if rows.shape != (qfeat.shape[0],) or rows.is_floating_point() or rows.dtype == torch.bool:
-            raise ValueError(f"{what}: leave_out is a ({qfeat.shape[0]},) integer tensor: the bank row of each query, or -1")
-        sfeat, sy = self.full_feat.to(qfeat.device), self.full_y.to(qfeat.device)
+        sfeat, sy = self.full_feat.to(device), self.full_y.to(device)
         cache = getattr(self, 'full_cache', None)
         if cache is None or not cache.matches(sfeat):   # the bank was replaced or updated since precompute()
             cache = self.full_cache = ops.SplitBank(sfeat, labels=sy, precision=self.full_precision)
+        return sfeat, sy, cache
+
+    @staticmethod
+    def _leave_out_window(rows, qfeat, what):
+        """``leave_out`` (bank row per query, -1: none) as ops.nw_head's excluded row window [row, row + 1); -1 is the empty
+        excluded window [0, 0)."""
+        rows = torch.as_tensor(rows, device=qfeat.device)
+        if rows.shape != (qfeat.shape[0],) or rows.is_floating_point() or rows.dtype == torch.bool:
+            raise ValueError(f"{what}: leave_out is a ({qfeat.shape[0]},) integer tensor: the bank row of each query, or -1")
         lo = rows.clamp(min=0)
-        hi = torch.where(rows < 0, lo, lo + 1)
+        return lo, torch.where(rows < 0, lo, lo + 1)
+
+    def _predict_leave_out(self, qfeat, rows, what):
+        """The 'full' head of the featurised queries ``qfeat`` over precompute()'s bank, query b without bank row rows[b]
+        (-1: with every row): ops.nw_head's row window [row, row + 1), excluded."""
+        sfeat, sy, cache = self._resident_bank(what, None if qfeat is None else qfeat.device)
+        window = self._leave_out_window(rows, qfeat, what)
         with torch.no_grad():
             return ops.nw_head(qfeat.detach(), sfeat, sy, self.n_classes, self.kernel.kind, self.kernel._logit_scale(),
-                               support_cache=cache, row_window=(lo, hi), exclude=True)
+                               support_cache=cache, row_window=window, exclude=True)
+
+    def forward_bank(self, x, leave_out=None):
+        """Not in the reference: the 'full' head at TRAINING time -- log-probabilities of ``self.featurizer(x)`` over
+        precompute()'s bank, differentiable in the featurizer, the projection and a clip scale (ops.nw_head_bank: the query
+        gradient is computed without a (B, N) matrix and without a support gradient).  The featurizer is taken as it is,
+        not the folded eval copy.  ``leave_out``: (B,) int64, the bank row of each query or -1 for none -- query b is
+        predicted without that row (a leave-one-out training loss over the bank's own samples).  Honours return_mask.
+
+        The bank is a CONSTANT here: it holds the features of the weights precompute() saw and goes stale as the weights
+        move; the caller decides when to call precompute() again.  A sharded bank, a missing bank and a custom kernel
+        module are refused (NWHipError), like predict_loo.  A full_precision="fp16" bank or a bank whose labels are not
+        class-sorted takes ops.nw_head's route through the score matrix without ``leave_out`` and is refused with it."""
+        what = "forward_bank"
+        if getattr(self, 'sharded_bank', None) is not None or not hasattr(self, 'full_feat'):
+            self._resident_bank(what, None)    # (raises: says why)
+        qfeat = self.featurizer(x)
+        sfeat, sy, cache = self._resident_bank(what, qfeat.device)
+        window = None if leave_out is None else self._leave_out_window(leave_out, qfeat, what)
+        out = ops.nw_head_bank(qfeat, sfeat, sy, self.n_classes, cache, self.kernel.kind, self.kernel._logit_scale(),
+                               row_window=window, exclude=window is not None)
+        return (out, torch.full((len(x),), True)) if self.return_mask else out
 
     def predict_loo(self, rows=None, batch_size=256):
         """Not in the reference: leave-one-out log-probabilities of the bank's own rows, (len(rows), n_classes) -- row i of

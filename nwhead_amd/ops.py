@@ -483,6 +483,8 @@ class SplitBank:
     * scores (nw_scores' bank route, nw_knn's fused search; _resolve_scores): only split rows without a class-sorted copy.
     * the head over a row window (nw_head(row_window=...), nw_head_window; head_window_route): fused on the same terms as the
       scores -- split rows without a class-sorted copy, whose rows are the caller's -- else through the score matrix.
+    * the head's query gradient over the bank as a constant (nw_head_bank; head_bank_route): fused on the same terms again,
+      else nw_head's route without a window and a refusal with one.
     * searches, rounded (nw_knn(rounded=True); _resolve_scores): only fp16-packed rows without a class-sorted copy; the
       queries are padded to the bank's width like everywhere else.
     * run tables (build_tables): named in the call's options only when its labels are the tensor the tables were built
@@ -855,6 +857,139 @@ def nw_head_window(q, s, sy, n_classes, bank, row_window, exclude=False, kind="e
         out = torch.where(empty[:, None], out.new_tensor(1e-12).log(), out)
         lse = lse.masked_fill(empty, float("-inf"))
     return (out, lse) if return_lse else out
+
+
+def head_bank_refusal(*, split, sorted_copy, shape, pad, width, B, n_classes):
+    """Why ``nw_head_bank`` cannot take nw_bwd_query_f32 for B queries of ``width`` columns over a prepared bank, over
+    head_window_route's plain facts -- a sentence for the error text, or None when it can: the bank holds ``split`` rows
+    that are the caller's (no class-sorted copy), the queries pad to its width, and the shape is one the kernel takes."""
+    N, d = shape
+    if not split:
+        return "the bank holds no split rows (a precision='fp16' or norms-only bank)"
+    if sorted_copy:
+        return "the bank was built from unsorted labels and keeps a class-sorted copy, whose rows are not the caller's"
+    if width + pad != d:
+        return f"queries of width {width} do not pad to the bank's width {d}"
+    if N <= 25:
+        return f"a bank of {N} rows is below the tile kernels (N > 25)"
+    if d % 32 or not 32 <= d <= 1 << 20:
+        return f"a bank of width {d} is not a multiple of 32 columns"
+    if not 1 <= n_classes <= HEAD_WINDOW_MAX_CLASSES:
+        return f"{n_classes} classes are outside [1, {HEAD_WINDOW_MAX_CLASSES}]"
+    if B <= 0:
+        return "an empty query batch"
+    return None
+
+
+def head_bank_route(*, split, sorted_copy, shape, pad, width, B, n_classes):
+    """Which route serves the gradients of ``nw_head_bank``, beside head_window_route and over the same facts: "fused"
+    (nw_bwd_query_f32: scores recomputed tile by tile, no (B,N) buffer, no support gradient) whenever head_bank_refusal
+    has nothing to say; else "matrix": nw_head's route through the score matrix without a window, a refusal with one."""
+    return "fused" if head_bank_refusal(split=split, sorted_copy=sorted_copy, shape=shape, pad=pad, width=width, B=B,
+                                        n_classes=n_classes) is None else "matrix"
+
+
+class _NWHeadBankFn(torch.autograd.Function):
+    """autograd node of nw_head_bank: today's inference call forward, nw_bwd_query_f32 backward.  Saves the queries, lse,
+    out and the window: nothing of size B x N."""
+
+    @staticmethod
+    def forward(ctx, q, logit_scale, call, n_classes, kind_id, window, exclude):
+        """``call``: the _Call nw_head_bank resolved (``q`` is its queries, an argument of its own for autograd);
+        ``window``: None or (lo, hi) int32."""
+        _, sc, syc, sn2, ssplit, sscale, opts = call
+        lib = _lib.load()
+        qc = _f32c(q)
+        B, d = qc.shape
+        N, dev = ssplit.shape[0], qc.device
+        out = torch.empty(B, n_classes, dtype=torch.float32, device=dev)
+        lse = torch.empty(B, dtype=torch.float32, device=dev)
+        ls = None if logit_scale is None else _f32c(logit_scale)
+        st = _stream(qc)
+        ws, ws_bytes = _fwd_workspace(lib, B, N, d, n_classes, dev, st)
+        lo, hi = window if window is not None else (None, None)
+        with _OnDevice(dev):
+            if window is None:
+                _lib.check(lib.nw_fwd_f32(_ptr(qc), _ptr(sc), _ptr(syc), _ptr(sn2), _ptr(ssplit), _ptr(sscale), _ptr(out), None,
+                                          _ptr(lse), None, _ptr(ws), ws_bytes, B, N, d, n_classes, kind_id, _ptr(ls), 0, 0, opts,
+                                          st), "nw_fwd_f32")
+            else:
+                _lib.check(lib.nw_fwd_window_f32(_ptr(qc), _ptr(ssplit), _ptr(sscale), _ptr(sn2), _ptr(syc), _ptr(lo), _ptr(hi),
+                                                 int(exclude), _ptr(out), _ptr(lse), _ptr(ws), ws_bytes, B, N, d, n_classes,
+                                                 kind_id, _ptr(ls), st), "nw_fwd_window_f32")
+        ctx.save_for_backward(qc, lse, out, *([ls] if ls is not None else []), *([lo, hi] if window is not None else []))
+        ctx.bank = (ssplit, sscale, sn2, syc)      # a SplitBank's tensors are never written again
+        ctx.meta = (B, N, d, n_classes, kind_id, ls is not None, window is not None, int(exclude))
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gout):
+        lib = _lib.load()
+        B, N, d, C, kind_id, has_ls, windowed, exclude = ctx.meta
+        saved = list(ctx.saved_tensors)
+        qc, lse, out = saved[:3]
+        ls = saved[3] if has_ls else None
+        lo, hi = saved[-2:] if windowed else (None, None)
+        ssplit, sscale, sn2, syc = ctx.bank
+        dev = qc.device
+        g = _f32c(gout)
+        gq = torch.empty_like(qc)
+        gls = torch.empty((), dtype=torch.float32, device=dev) if has_ls else None
+        ws_bytes = lib.nw_bwd_query_workspace_bytes(B, N, d, C, 0)
+        ws = _workspace(ws_bytes, dev)
+        with _OnDevice(dev):
+            _lib.check(lib.nw_bwd_query_f32(_ptr(qc), _ptr(ssplit), _ptr(sscale), _ptr(sn2), _ptr(syc), _ptr(lo), _ptr(hi), exclude,
+                                            _ptr(lse), _ptr(out), _ptr(g), _ptr(gq), _ptr(gls), _ptr(ws), ws_bytes, B, N, d, C,
+                                            kind_id, _ptr(ls), 0, _stream(qc)), "nw_bwd_query_f32")
+        return gq, gls, None, None, None, None, None
+
+
+def nw_head_bank(q, s, sy, n_classes, bank, kind="euclidean", logit_scale=None, row_window=None, exclude=False):
+    """The head over a RESIDENT bank, differentiable in the queries (and a clip ``logit_scale``) with the bank a constant
+    -> (B,C) log-probabilities.  For fine-tuning a featurizer against a frozen or periodically refreshed bank, a
+    leave-one-out training loss (``row_window`` / ``exclude`` as in nw_head_window), input gradients of 'full' inference,
+    test-time adaptation.  `s` must not require grad: ``nw_head`` is the call for support gradients.
+
+    Forward: the inference call as it is -- nw_fwd_f32 over the bank with its log-sum-exp, or nw_fwd_window_f32 -- so the
+    output equals ``nw_head(..., support_cache=bank[, row_window=...])`` under no_grad bit for bit.  Backward:
+    nw_bwd_query_f32, which recomputes the scores tile by tile on the split-fp16 matrix cores and contracts them with the
+    bank rows in the same kernel: no (B,N) buffer is saved or filled (nw_head's route keeps three) and no support gradient
+    is computed.  Route (head_bank_route): that kernel whenever the bank holds split rows without a class-sorted copy and
+    the queries pad to its width; otherwise (an fp16 or norms-only bank, unsorted labels, N <= 25, a width that is no
+    multiple of 32 after padding) nw_head's route without a window, NWHipError with one."""
+    if not isinstance(bank, SplitBank):
+        raise TypeError("nw_head_bank runs over a prepared bank: pass ops.SplitBank(support)")
+    grad = torch.is_grad_enabled()
+    if grad and s.requires_grad:
+        raise ValueError("nw_head_bank: the bank is a constant here and `s` requires grad; nw_head(q, s, sy, ..., "
+                         "support_cache=bank) is the call for support gradients")
+    _need_hip(q, s, sy, logit_scale)
+    if s.dim() != 2 or sy.dim() != 1 or sy.shape[0] != s.shape[0] or not bank.matches(s):
+        raise ValueError("nw_head_bank: `s` (N,d) must be the tensor the bank was prepared from and `sy` its (N,) labels")
+    kid = _kind_id(kind)
+    if kid == SCORE_KINDS["clip"] and logit_scale is None:
+        raise ValueError("clip kernel needs logit_scale")
+    if not (grad and (q.requires_grad or (logit_scale is not None and logit_scale.requires_grad))):
+        return nw_head(q, s, sy, n_classes, kind, logit_scale, support_cache=bank, row_window=row_window, exclude=exclude)
+    C = int(n_classes)
+    _check_label_range(None, bank.label_max, C)
+    why = head_bank_refusal(split=bank.split is not None, sorted_copy=bank.sorted_rows is not None, shape=bank.shape,
+                            pad=bank.pad, width=q.shape[1], B=q.shape[0], n_classes=C)
+    if why is not None:
+        if row_window is None:
+            return nw_head(q, s, sy, C, kind, logit_scale, support_cache=bank)
+        raise NWHipError(f"nw_head_bank(row_window=...) has no gradient route here: {why}")
+    if row_window is None:
+        call = _resolve(bank, q, s, sy, C, False, False, False, 0, None, False)       # nw_head's inference call
+        window = None
+    else:
+        call = _resolve_scores(bank, q)
+        syc = sy if (sy.dtype == torch.int64 and sy.is_contiguous()) else sy.detach().to(torch.int64).contiguous()
+        call = call._replace(sy=syc)
+        window = tuple(_row_window(row_window, q.shape[0], q.device))
+    out = _NWHeadBankFn.apply(call.q, logit_scale, call, C, kid, window, bool(exclude))
+    return out
 
 
 def nw_partials(q, s, sy, n_classes, kind="euclidean", logit_scale=None, support_cache=None):
