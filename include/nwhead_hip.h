@@ -200,6 +200,8 @@ int nw_bank_tables_build(const int64_t *sy, int64_t N, int64_t C, void *tables, 
  *   out, gout     (B,C) forward output and its incoming gradient
  *   gq            (B,d) out;  gs (N,d) or (B,N,d) out;  glogit_scale optional scalar out (CLIP)
  *   workspace     nw_bwd_workspace_bytes(...) bytes
+ * nw_bwd_workspace_bytes and nw_bwd_uses_split are two fields of one plan (route, launch sizes, workspace map):
+ * nw_debug_bwd_plan returns all of it.
  * ------------------------------------------------------------------------------------------- */
 size_t nw_bwd_workspace_bytes(int64_t B, int64_t N, int64_t d, int64_t C, int kind, int sup_batched);
 int nw_bwd_f32(const float *q, const float *s, const int64_t *sy,
@@ -802,6 +804,26 @@ typedef struct nw_fwd_layout {
     int32_t n_slices, reserved;
 } nw_fwd_layout;
 int nw_debug_fwd_layout(int64_t B, int64_t N, int64_t d, int64_t C, nw_fwd_layout *layout);
+/* The plan of the head's backward (nw_bwd_f32 / nw_bwd_bank_f32) for one shape, as the launcher takes it under the current
+ * knobs: no launch, no device needed.  status: what the launcher would answer once its arguments and workspace are in order
+ * (NW_ERR_UNSUPPORTED when the coefficient kernel's LDS exceeds 160 KiB).  route: 0 VALU, 1 fp32 matrix cores, 2 split
+ * fp16 (== nw_bwd_uses_split).  ld: row stride of the coefficient matrices; Bpad: rows of the split queries.  gq_* / gs_*:
+ * K-split of the two products (0 on the VALU route).  Fifteen areas of the workspace in this order, each starting on a
+ * multiple of 256 bytes where the one before ends, the last ending at `total`, an area the route does not use empty:
+ * 0 A, 1 Rs, 2 rq, 3 gls, 4 qn2, 5 sn2, 6 rs, 7 s_split, 8 s_scale, 9 q_split, 10 ascale, 11 qv, 12 gfac, 13 part (partial
+ * tiles of gq), 14 part2 (of gs) -- except that with parts_shared (the fp32 matrix cores) part2 IS part.
+ * NW_ERR_INVALID_ARG for a null pointer or a negative size; B <= 0: all zeros. */
+#define NW_BWD_AREAS 15
+typedef struct nw_bwd_plan {
+    int32_t status, route;
+    int32_t coeff_threads, parts_shared;
+    int32_t gq_chunks, gq_k_chunk, gs_chunks, gs_k_chunk;
+    int64_t ld, Bpad;
+    uint64_t coeff_lds_bytes;                   /* dynamic LDS of the coefficient kernel */
+    uint64_t off[NW_BWD_AREAS], bytes[NW_BWD_AREAS];
+    uint64_t total;                             /* == nw_bwd_workspace_bytes(B, N, d, C, kind, sup_batched) */
+} nw_bwd_plan;
+int nw_debug_bwd_plan(int64_t B, int64_t N, int64_t d, int64_t C, int sup_batched, nw_bwd_plan *plan);
 
 #ifdef __cplusplus
 }

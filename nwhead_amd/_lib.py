@@ -106,6 +106,7 @@ SIGNATURES = {
     "nw_debug_tile_timing_read": (_int, [C.POINTER(C.c_double), C.POINTER(C.c_int64)]),
     "nw_debug_fwd_plan": (_int, [_i64, _i64, _i64, _i64, _int, _int, _int, _int, _int, _int, _int, _p]),
     "nw_debug_fwd_layout": (_int, [_i64, _i64, _i64, _i64, _p]),
+    "nw_debug_bwd_plan": (_int, [_i64, _i64, _i64, _i64, _int, _p]),
 }
 
 _lib = None
@@ -192,6 +193,26 @@ def fwd_layout(B, N, d, C_):
     m = FwdLayout()
     check(load().nw_debug_fwd_layout(B, N, d, C_, C.byref(m)), "nw_debug_fwd_layout")
     return m
+
+
+BWD_ROUTES = ("valu", "mfma", "split")
+BWD_AREAS = ("A", "Rs", "rq", "gls", "qn2", "sn2", "rs", "s_split", "s_scale", "q_split", "ascale", "qv", "gfac", "part", "part2")
+
+
+class BwdPlan(C.Structure):
+    """nw_bwd_plan (include/nwhead_hip.h): route, launch sizes and workspace map of the head's backward; `route` indexes
+    BWD_ROUTES, `off` / `bytes` are in BWD_AREAS order."""
+    _fields_ = [(k, C.c_int32) for k in ("status", "route", "coeff_threads", "parts_shared", "gq_chunks", "gq_k_chunk",
+                                         "gs_chunks", "gs_k_chunk")] + \
+               [("ld", C.c_int64), ("Bpad", C.c_int64), ("coeff_lds_bytes", C.c_uint64),
+                ("off", C.c_uint64 * len(BWD_AREAS)), ("bytes", C.c_uint64 * len(BWD_AREAS)), ("total", C.c_uint64)]
+
+
+def bwd_plan(B, N, d, C_, sup=0):
+    """The library's plan of the backward for one shape under the current knobs (nw_debug_bwd_plan): no launch, no device."""
+    p = BwdPlan()
+    check(load().nw_debug_bwd_plan(B, N, d, C_, int(sup), C.byref(p)), "nw_debug_bwd_plan")
+    return p
 
 
 # Environment switches of the Python layer (the C library never reads the environment).  NW_SPLIT_ALWAYS travels in every

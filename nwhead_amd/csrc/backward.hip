@@ -13,6 +13,8 @@
 #include "nw_internal.h"
 #include "tile_dma.h"
 #include "bwd_coeff.h"
+#include "bwd_plan.h"
+#include "fused_plan.h"   // NW_FOR_EACH_KIND
 #include <cstdlib>
 
 namespace nw {
@@ -465,29 +467,26 @@ __global__ __launch_bounds__(256) void nw_colsum_kernel(const float* __restrict_
     colsum_block(blockIdx.x, red, Rs, ld, rs, B, N);
 }
 
-struct GemmPlan {
-    int nchunks, k_chunk;
-};
 // Split K until the grid has >= 512 workgroups (two per CU: the kernel hides its global-load latency with
 // co-resident workgroups), never below 64 of K per chunk.  Measured at M=10000, N=512, K=256 (316 tiles):
 // 83 us unsplit, 46 + 16 (reduce) split in two, 53 + 26 split in four.
-GemmPlan gemm_plan(int64_t M, int64_t Nn, int64_t K) {
+KSplit gemm_plan(int64_t M, int64_t Nn, int64_t K) {
     const int64_t tiles = ((M + GM - 1) / GM) * ((Nn + GN - 1) / GN);
     int64_t want = tiles >= 512 ? 1 : (512 + tiles - 1) / tiles;
     const int64_t maxc = K / 64 > 1 ? K / 64 : 1;
     if (want > maxc) want = maxc;
     int64_t kc = (K + want - 1) / want;
     kc = (kc + GK - 1) / GK * GK;
-    GemmPlan p;
+    KSplit p;
     p.k_chunk = (int)kc;
     p.nchunks = (int)((K + kc - 1) / kc);
     return p;
 }
 
+// p: this product's K-split as the call's BwdPlan holds it (`part` was sized by the same record)
 template <bool A_KCONTIG>
 int launch_bwd_gemm(const float* A, int64_t lda, const float* Bm, float* part, const float* rowscale, const float* X,
-                    float* Cout, int64_t M, int64_t Nn, int64_t K, hipStream_t st) {
-    const GemmPlan p = gemm_plan(M, Nn, K);
+                    float* Cout, int64_t M, int64_t Nn, int64_t K, const KSplit& p, hipStream_t st) {
     const dim3 grid((unsigned)((Nn + GN - 1) / GN), (unsigned)((M + GM - 1) / GM), (unsigned)p.nchunks);
     if (grid.y > 65535u || grid.z > 65535u) return NW_ERR_INVALID_ARG;
     if (p.nchunks == 1) {
@@ -512,79 +511,46 @@ __global__ __launch_bounds__(256) void nw_sum_kernel(const float* __restrict__ x
     if (threadIdx.x == 0) *out = a;
 }
 
-struct BwdWs {
-    float *A, *Rs, *rq, *gls, *qn2, *sn2, *rs, *part, *part2;   // part2: the second product's partial tiles (split path)
-    float *s_split, *s_scale, *q_split, *ascale, *qv, *gfac;   // split path (bwd_split.hip)
-    int64_t ld;    // row stride of A and Rs: N, N rounded up to 4 floats (fp32 matrix cores) or to 32 (split path)
-    int64_t Bpad;  // rows of q_split: B rounded up to 32, the rest zero
-    bool mfma, split;
-};
-// Shared support, float4-able rows and enough work to fill the chip: the two products run on the matrix cores.
-bool bwd_use_mfma(int64_t B, int64_t N, int64_t d, int sup_batched) {
-    const bool off = knob(KNOB_BWD_NO_MFMA) == 1;
-    return !off && !sup_batched && d % 4 == 0 && B * N * d >= (int64_t)1 << 22;
-}
 inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
-// The products on the fp16 matrix cores (bwd_split.hip): split rows need d % 32 == 0, the coefficient kernel stages a
-// row of A (N rounded up to 32 floats) next to the C class gradients in LDS, and the extra passes (splitting the
-// supports and the queries) have to pay: at B=256, N=10000, d=512 the backward's kernels take 64 us against 157 on the
-// fp32 cores.
-bool bwd_use_split(int64_t B, int64_t N, int64_t d, int64_t C, int sup_batched) {
-    const int mode = knob(KNOB_BWD_SPLIT) == KNOB_UNSET ? -1 : knob(KNOB_BWD_SPLIT);   // 0 off, 1 wherever possible
-    if (mode == 0 || !bwd_use_mfma(B, N, d, sup_batched) || d % 32 != 0) return false;
-    const int64_t ld = (N + 31) / 32 * 32;
-    if ((size_t)(80 + ld + C) * sizeof(float) > 150 * 1024) return false;
-    if (mode == 1) return true;
-    return B >= 16 && N >= 256;   // (with bwd_use_mfma's B N d >= 2^22: ahead at every such shape measured, tools/bwd_crossover.py)
-}
-
-size_t bwd_layout(int64_t B, int64_t N, int64_t d, int64_t C, int sup_batched, char* base, BwdWs* ws) {
-    size_t off = 0;
-    auto take = [&](size_t nfloat) {
-        float* p = base ? reinterpret_cast<float*>(base + off) : nullptr;
-        off += align256(nfloat * sizeof(float));
-        return p;
-    };
-    BwdWs w;
-    w.mfma = bwd_use_mfma(B, N, d, sup_batched);
-    w.split = bwd_use_split(B, N, d, C, sup_batched);
-    w.ld = w.split ? (N + 31) / 32 * 32 : w.mfma ? (N + 3) / 4 * 4 : N;
-    w.Bpad = (B + 31) / 32 * 32;
-    w.A = take((size_t)B * w.ld + (w.split ? XGEMM_TAIL_BYTES / 4 : 0));
-    w.Rs = take((size_t)B * w.ld);
-    w.rq = take((size_t)B);
-    w.gls = take((size_t)B);
-    w.qn2 = take((size_t)B);
-    w.sn2 = take(sup_batched ? (size_t)B * N : (size_t)N);
-    w.rs = w.part = w.part2 = nullptr;
-    w.s_split = w.s_scale = w.q_split = w.ascale = w.qv = w.gfac = nullptr;
-    if (w.mfma) {
-        w.rs = take((size_t)N);
-        int cq, cs;
-        if (w.split) {
-            cq = xgemm_plan(B, d, N).nchunks, cs = xgemm_plan(N, d, B).nchunks;
-            w.s_split = take((size_t)N * d + XGEMM_TAIL_BYTES / 4);
-            w.s_scale = take((size_t)N);
-            w.q_split = take((size_t)w.Bpad * d + XGEMM_TAIL_BYTES / 4);
-            w.ascale = take((size_t)B);
-            w.qv = take((size_t)B);
-            w.gfac = take(1);
-        } else {
-            cq = gemm_plan(B, d, N).nchunks, cs = gemm_plan(N, d, B).nchunks;
-        }
-        const size_t nq = cq > 1 ? (size_t)cq * B * d : 0, ns = cs > 1 ? (size_t)cs * N * d : 0;
-        if (w.split) {   // the first product's partial tiles are still pending while the second product runs
-            w.part = take(nq);
-            w.part2 = take(ns);
-        } else {
-            w.part = w.part2 = take(nq > ns ? nq : ns);
-        }
-    }
-    if (ws) *ws = w;
-    return off;
-}
 
 }  // namespace
+
+// The one statement of the backward's route rule, launch sizes and workspace map (bwd_plan.h).
+BwdPlan plan_bwd(int64_t B, int64_t N, int64_t d, int64_t C, int sup_batched, void* base) {
+    BwdPlan p = {};
+    p.base = static_cast<char*>(base);
+    if (B <= 0 || N < 0) return p;
+    const int split_knob = knob(KNOB_BWD_SPLIT);   // 0: never, 1: wherever possible, anything else: the thresholds
+    const int64_t ld32 = (N + 31) / 32 * 32;
+    const bool mfma = knob(KNOB_BWD_NO_MFMA) != 1 && !sup_batched && d % 4 == 0 && B * N * d >= BWD_MFMA_MIN_WORK;
+    const bool split = mfma && split_knob != 0 && d % 32 == 0 && bwd_coeff_lds_bytes(C, ld32) <= BWD_SPLIT_LDS_CAP &&
+                       (split_knob == 1 || (B >= BWD_SPLIT_MIN_B && N >= BWD_SPLIT_MIN_N));
+    p.route = split ? BWD_SPLIT : mfma ? BWD_MFMA : BWD_VALU;
+    p.ld = split ? ld32 : mfma ? (N + 3) / 4 * 4 : N;
+    p.Bpad = (B + 31) / 32 * 32;
+    p.coeff_threads = bwd_coeff_threads(N);
+    p.coeff_lds = bwd_coeff_lds_bytes(C, split ? p.ld : 0);
+    p.status = p.coeff_lds > BWD_COEFF_LDS_CAP ? NW_ERR_UNSUPPORTED : NW_OK;
+    if (split) p.gq = xgemm_plan(B, d, N), p.gs = xgemm_plan(N, d, B);
+    else if (mfma) p.gq = gemm_plan(B, d, N), p.gs = gemm_plan(N, d, B);
+
+    // the areas' floats in the order of BwdArea; on the split route the first product's partial tiles are still pending
+    // while the second product runs, on the fp32 matrix cores one area serves both (PART2 is PART)
+    const size_t b = B, n = N, bpad = p.Bpad, on = mfma, sp = split, tail = split ? XGEMM_TAIL_BYTES / 4 : 0;
+    const size_t nq = p.gq.nchunks > 1 ? p.gq.nchunks * b * d : 0, ns = p.gs.nchunks > 1 ? p.gs.nchunks * n * d : 0;
+    const size_t nfloat[BWD_AREAS] = {b * p.ld + tail, b * p.ld, b, b, b, sup_batched ? b * n : n, on * n,
+                                      sp * (n * d + tail), sp * n, sp * (bpad * d + tail), sp * b, sp * b, sp,
+                                      split ? nq : (nq > ns ? nq : ns), sp * ns};
+    size_t off = 0;
+    for (int a = 0; a < BWD_AREAS; ++a) {
+        p.area[a] = {off, align256(nfloat[a] * sizeof(float))};
+        off += p.area[a].bytes;
+    }
+    p.parts_shared = mfma && !split;
+    if (p.parts_shared) p.area[BWD_PART2] = p.area[BWD_PART];
+    p.total = off;
+    return p;
+}
 
 int launch_rownorm2(const float* x, float* n2, int64_t rows, int64_t d, hipStream_t st) {
     if (rows <= 0) return NW_OK;
@@ -594,18 +560,135 @@ int launch_rownorm2(const float* x, float* n2, int64_t rows, int64_t d, hipStrea
     return NW_OK;
 }
 
+namespace {
+
+// One call of nw_bwd_bank_f32, in the order of its arguments.
+struct BwdCall {
+    const float *q, *s, *s_norm2, *s_split, *s_scale;
+    const int64_t* sy;
+    const float *scores, *lse, *out, *gout;
+    float *gq, *gs, *glogit_scale;
+    void* workspace;
+    size_t workspace_bytes;
+    int64_t B, N, d, C;
+    int kind;
+    const float* logit_scale_dev;
+    int sup_batched, labels_batched;
+    hipStream_t st;
+    int64_t gs_rows() const { return sup_batched ? B * N : N; }
+    bool empty() const { return B == 0 || N == 0 || d == 0; }
+    bool norms() const { return kind == NW_SCORE_HYPERSPHERE || kind == NW_SCORE_COSINE || kind == NW_SCORE_CLIP; }
+};
+
+// Every refusal of the call, in this precedence; *p is the call's plan once the sizes allow one.  NW_OK for an empty
+// shape too, which reads nothing (bwd_zero_gradients).
+int bwd_check(const BwdCall& c, BwdPlan* p) {
+    if ((c.s_split != nullptr) != (c.s_scale != nullptr) || (c.s_split && !c.s_norm2)) return NW_ERR_INVALID_ARG;
+    if (c.s_split && (c.sup_batched || c.d % 32 != 0 || (reinterpret_cast<uintptr_t>(c.s_split) & 15))) return NW_ERR_INVALID_ARG;
+    if (c.B < 0 || c.N < 0 || c.d < 0 || c.C < 0) return NW_ERR_INVALID_ARG;
+    if (c.kind < NW_SCORE_EUCLIDEAN || c.kind > NW_SCORE_CLIP) return NW_ERR_UNSUPPORTED;
+    if (c.kind == NW_SCORE_CLIP && !c.logit_scale_dev) return NW_ERR_INVALID_ARG;
+    if (c.empty()) return NW_OK;
+    if (!c.q || !c.s || !c.sy || !c.scores || !c.lse || !c.out || !c.gout || !c.gq || !c.gs) return NW_ERR_INVALID_ARG;
+    if (c.B > 0x7fffffffLL || c.gs_rows() > 0x7fffffffLL || (c.d + 255) / 256 > 65535) return NW_ERR_INVALID_ARG;
+    *p = plan_bwd(c.B, c.N, c.d, c.C, c.sup_batched, c.workspace);
+    if (!p->fits(c.workspace_bytes)) return NW_ERR_WORKSPACE;
+    if (p->status != NW_OK) return p->status;
+    const bool aligned = ((reinterpret_cast<uintptr_t>(c.q) | reinterpret_cast<uintptr_t>(c.s) |
+                           reinterpret_cast<uintptr_t>(c.gq) | reinterpret_cast<uintptr_t>(c.gs)) & 15) == 0;
+    if (p->route != BWD_VALU && !aligned) return NW_ERR_INVALID_ARG;  // the layout (row stride of A) is already the matrix-core one
+    return NW_OK;
+}
+
+int bwd_zero_gradients(const BwdCall& c) {
+    if (c.gq && c.B * c.d) if (hipMemsetAsync(c.gq, 0, (size_t)c.B * c.d * 4, c.st) != hipSuccess) return NW_ERR_LAUNCH;
+    if (c.gs && c.gs_rows() * c.d) if (hipMemsetAsync(c.gs, 0, (size_t)c.gs_rows() * c.d * 4, c.st) != hipSuccess) return NW_ERR_LAUNCH;
+    if (c.glogit_scale) if (hipMemsetAsync(c.glogit_scale, 0, 4, c.st) != hipSuccess) return NW_ERR_LAUNCH;
+    return NW_OK;
+}
+
+// What the coefficient kernel and the products read of the supports: split rows, row scales, squared norms.
+struct BwdOperands {
+    const float *s_split, *s_scale, *sn2;
+};
+// The queries' norms, then the supports' side: the caller's bank, a copy split into the workspace, the caller's s_norm2,
+// or norms computed here.
+int bwd_operands(const BwdCall& c, const BwdPlan& p, BwdOperands* o) {
+    *o = {p.at(BWD_S_SPLIT), p.at(BWD_S_SCALE), p.at(BWD_SN2)};
+    if (c.norms()) hipLaunchKernelGGL(nw_rownorm_kernel, dim3((unsigned)((c.B + 3) / 4)), dim3(256), 0, c.st, c.q, p.at(BWD_QN2), c.B, c.d);
+    // The caller's bank is the Y operand of a 64-column tile kernel that reads a clamped last row to the end of its
+    // tile: only a row length that is a multiple of 64 keeps it inside N * d floats (the workspace copy has a tail)
+    if (p.route == BWD_SPLIT && c.s_split && c.d % 64 == 0) {   // the forward's bank: split rows, scales and norms of these very supports
+        *o = {c.s_split, c.s_scale, c.s_norm2};
+    } else if (p.route == BWD_SPLIT) {   // the supports as split rows (the bank format); their squared norms come with it
+        return launch_split_rows(c.s, p.at(BWD_S_SPLIT), p.at(BWD_S_SCALE), p.at(BWD_SN2), c.N, c.d, c.st);
+    } else if (c.norms() && c.s_norm2 && !c.sup_batched) {
+        o->sn2 = c.s_norm2;
+    } else if (c.norms()) {
+        hipLaunchKernelGGL(nw_rownorm_kernel, dim3((unsigned)((c.gs_rows() + 3) / 4)), dim3(256), 0, c.st, c.s, p.at(BWD_SN2), c.gs_rows(), c.d);
+    }
+    return NW_OK;
+}
+
+// The coefficient kernel of the call's kind; on the split route the form that leaves A as a split-row image.
+void launch_coeff(const BwdCall& c, const BwdPlan& p, const BwdOperands& o) {
+    using Kernel = decltype(&nw_bwd_coeff_kernel<NW_SCORE_DOT, false>);
+    const bool split = p.route == BWD_SPLIT;
+    Kernel kernel = nullptr;
+#define NW_KIND_CASE(K) case K: kernel = split ? nw_bwd_coeff_kernel<K, true> : nw_bwd_coeff_kernel<K, false>; break;
+    switch (c.kind) { NW_FOR_EACH_KIND(NW_KIND_CASE) }
+#undef NW_KIND_CASE
+    hipLaunchKernelGGL(kernel, dim3((unsigned)c.B), dim3(p.coeff_threads), p.coeff_lds, c.st, c.scores, c.lse, c.out, c.gout, c.sy,
+                       c.labels_batched, p.at(BWD_QN2), o.sn2, c.sup_batched, c.logit_scale_dev, p.at(BWD_A), p.at(BWD_RS_PAIR),
+                       p.at(BWD_RQ), p.at(BWD_GLS), c.N, c.C, p.ld, split ? c.q : nullptr, split ? c.d : 0, split ? o.s_scale : nullptr,
+                       split ? p.at(BWD_ASCALE) : nullptr, split ? p.at(BWD_QV) : nullptr);
+}
+
+int bwd_products_valu(const BwdCall& c, const BwdPlan& p) {
+    const unsigned kd = (unsigned)((c.d + 255) / 256);
+    const float *A = p.at(BWD_A), *Rs = p.at(BWD_RS_PAIR);
+    hipLaunchKernelGGL(nw_bwd_gq_kernel, dim3((unsigned)c.B, kd), dim3(256), 0, c.st, A, p.at(BWD_RQ), c.q, c.s, c.gq, c.N, c.d, c.sup_batched);
+    if (c.sup_batched)
+        hipLaunchKernelGGL(nw_bwd_gs_batched_kernel, dim3((unsigned)c.gs_rows(), kd), dim3(256), 0, c.st, A, Rs, c.q, c.s, c.gs, c.N, c.d);
+    else
+        hipLaunchKernelGGL(nw_bwd_gs_shared_kernel, dim3((unsigned)c.N, kd), dim3(256), 0, c.st, A, Rs, c.q, c.s, c.gs, c.B, c.N, c.d);
+    return NW_OK;
+}
+
+int bwd_products_mfma(const BwdCall& c, const BwdPlan& p) {
+    const unsigned ncs = (unsigned)((p.ld / 4 + 15) / 16);
+    hipLaunchKernelGGL(nw_colsum_kernel, dim3(ncs), dim3(256), 0, c.st, p.at(BWD_RS_PAIR), p.ld, p.at(BWD_RS), c.B, c.N);
+    const int rc = launch_bwd_gemm<true>(p.at(BWD_A), p.ld, c.s, p.at(BWD_PART), p.at(BWD_RQ), c.q, c.gq, c.B, c.d, c.N, p.gq, c.st);   // gq = A s + 2 rq q
+    if (rc != NW_OK) return rc;
+    return launch_bwd_gemm<false>(p.at(BWD_A), p.ld, c.q, p.at(BWD_PART2), p.at(BWD_RS), c.s, c.gs, c.N, c.d, c.B, p.gs, c.st);         // gs = A^T q + 2 rs s
+}
+
+int bwd_products_split(const BwdCall& c, const BwdPlan& p, const BwdOperands& o) {
+    const unsigned ncs = (unsigned)((p.ld / 4 + 15) / 16), nq = (unsigned)((p.Bpad + 3) / 4);
+    hipLaunchKernelGGL(nw_bwd_prep_kernel, dim3(nq + ncs), dim3(256), 0, c.st, (int)nq, c.q, p.at(BWD_ASCALE), p.at(BWD_QV), p.at(BWD_Q_SPLIT),
+                       p.at(BWD_GFAC), c.B, p.Bpad, c.d, p.at(BWD_RS_PAIR), p.ld, p.at(BWD_RS), c.N);
+    // gq = 2^-E_b (A' s') + 2 rq q: K = N runs along the rows of A' (zero past N), the rows of s' are clamped
+    XgemmReduce gq_reduce;   // the first product's K-split reduction rides along with the second product's launch
+    const int rc = launch_xgemm(false, p.at(BWD_A), p.ld, c.B, o.s_split, c.d, c.N, p.at(BWD_PART), p.at(BWD_ASCALE), 0, nullptr,
+                                p.at(BWD_RQ), c.q, c.gq, c.B, c.d, c.N, p.gq, c.st, &gq_reduce);
+    if (rc != NW_OK) return rc;
+    // gs = 2^(e_j - G) (A'^T q'') + 2 rs s: K = B runs across the rows of A' (clamped), q'' is zero past B
+    return launch_xgemm(true, p.at(BWD_A), p.ld, c.B, p.at(BWD_Q_SPLIT), c.d, p.Bpad, p.at(BWD_PART2), o.s_scale, 1, p.at(BWD_GFAC),
+                        p.at(BWD_RS), c.s, c.gs, c.N, c.d, c.B, p.gs, c.st, nullptr, &gq_reduce);
+}
+
+}  // namespace
 }  // namespace nw
 
 extern "C" size_t nw_bwd_workspace_bytes(int64_t B, int64_t N, int64_t d, int64_t C, int kind,
                                          int sup_batched) {
     (void)kind;
-    if (B <= 0 || N < 0) return 0;
-    return nw::bwd_layout(B, N, d, C, sup_batched, nullptr, nullptr);
+    return nw::plan_bwd(B, N, d, C, sup_batched).total;
 }
 
 extern "C" int nw_bwd_uses_split(int64_t B, int64_t N, int64_t d, int64_t C, int sup_batched) {
     if (B <= 0 || N <= 0 || d <= 0 || C < 0) return 0;
-    return nw::bwd_use_split(B, N, d, C, sup_batched) ? 1 : 0;
+    return nw::plan_bwd(B, N, d, C, sup_batched).route == nw::BWD_SPLIT ? 1 : 0;
 }
 
 extern "C" int nw_bwd_f32(const float* q, const float* s, const int64_t* sy, const float* scores,
@@ -626,111 +709,21 @@ extern "C" int nw_bwd_bank_f32(const float* q, const float* s, const float* s_no
                                const float* logit_scale_dev, int sup_batched, int labels_batched,
                                void* stream) {
     using namespace nw;
-    if ((s_split != nullptr) != (s_scale != nullptr) || (s_split && !s_norm2)) return NW_ERR_INVALID_ARG;
-    if (s_split && (sup_batched || d % 32 != 0 || (reinterpret_cast<uintptr_t>(s_split) & 15))) return NW_ERR_INVALID_ARG;
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    if (B < 0 || N < 0 || d < 0 || C < 0) return NW_ERR_INVALID_ARG;
-    if (kind < NW_SCORE_EUCLIDEAN || kind > NW_SCORE_CLIP) return NW_ERR_UNSUPPORTED;
-    if (kind == NW_SCORE_CLIP && !logit_scale_dev) return NW_ERR_INVALID_ARG;
-    const int64_t gs_rows = sup_batched ? B * N : N;
-    if (B == 0 || N == 0 || d == 0) {
-        if (gq && B * d) if (hipMemsetAsync(gq, 0, (size_t)B * d * 4, st) != hipSuccess) return NW_ERR_LAUNCH;
-        if (gs && gs_rows * d) if (hipMemsetAsync(gs, 0, (size_t)gs_rows * d * 4, st) != hipSuccess) return NW_ERR_LAUNCH;
-        if (glogit_scale) if (hipMemsetAsync(glogit_scale, 0, 4, st) != hipSuccess) return NW_ERR_LAUNCH;
-        return NW_OK;
-    }
-    if (!q || !s || !sy || !scores || !lse || !out || !gout || !gq || !gs) return NW_ERR_INVALID_ARG;
-    if (B > 0x7fffffffLL || gs_rows > 0x7fffffffLL || (d + 255) / 256 > 65535) return NW_ERR_INVALID_ARG;
-    BwdWs ws;
-    const size_t need = bwd_layout(B, N, d, C, sup_batched, static_cast<char*>(workspace), &ws);
-    if (!workspace || workspace_bytes < need) return NW_ERR_WORKSPACE;
-    const size_t lds = (80 + (size_t)C + (ws.split ? (size_t)ws.ld : 0)) * sizeof(float);
-    const unsigned coeff_threads = N >= 2048 ? 1024 : 256;
-    if (lds > 160 * 1024) return NW_ERR_UNSUPPORTED;
-    const bool aligned = ((reinterpret_cast<uintptr_t>(q) | reinterpret_cast<uintptr_t>(s) |
-                           reinterpret_cast<uintptr_t>(gq) | reinterpret_cast<uintptr_t>(gs)) & 15) == 0;
-    if (ws.mfma && !aligned) return NW_ERR_INVALID_ARG;  // the layout (row stride of A) is already the matrix-core one
-
-    const bool norms = (kind == NW_SCORE_HYPERSPHERE || kind == NW_SCORE_COSINE || kind == NW_SCORE_CLIP);
-    if (norms) hipLaunchKernelGGL(nw_rownorm_kernel, dim3((unsigned)((B + 3) / 4)), dim3(256), 0, st, q, ws.qn2, B, d);
-    // The caller's bank is the Y operand of a 64-column tile kernel that reads a clamped last row to the end of its
-    // tile: only a row length that is a multiple of 64 keeps it inside N * d floats (the workspace copy has a tail)
-    if (ws.split && s_split && d % 64 == 0) {   // the forward's bank: split rows, scales and norms of these very supports
-        ws.s_split = const_cast<float*>(s_split);
-        ws.s_scale = const_cast<float*>(s_scale);
-        ws.sn2 = const_cast<float*>(s_norm2);
-    } else if (ws.split) {   // the supports as split rows (the bank format); their squared norms come with it
-        const int rc = launch_split_rows(s, ws.s_split, ws.s_scale, ws.sn2, N, d, st);
-        if (rc != NW_OK) return rc;
-    } else if (norms && s_norm2 && !sup_batched) {
-        ws.sn2 = const_cast<float*>(s_norm2);
-    } else if (norms) {
-        hipLaunchKernelGGL(nw_rownorm_kernel, dim3((unsigned)((gs_rows + 3) / 4)), dim3(256), 0, st, s, ws.sn2, gs_rows, d);
-    }
-#define NW_COEFF(K)                                                                                                      \
-    do {                                                                                                                 \
-        if (ws.split)                                                                                                    \
-            hipLaunchKernelGGL((nw_bwd_coeff_kernel<K, true>), dim3((unsigned)B), dim3(coeff_threads), lds, st, scores, lse, \
-                               out, gout, sy, labels_batched, ws.qn2, ws.sn2, sup_batched, logit_scale_dev, ws.A, ws.Rs,  \
-                               ws.rq, ws.gls, N, C, ws.ld, q, d, ws.s_scale, ws.ascale, ws.qv);                          \
-        else                                                                                                             \
-            hipLaunchKernelGGL((nw_bwd_coeff_kernel<K, false>), dim3((unsigned)B), dim3(coeff_threads), lds, st, scores, lse, \
-                               out, gout, sy, labels_batched, ws.qn2, ws.sn2, sup_batched, logit_scale_dev, ws.A, ws.Rs,  \
-                               ws.rq, ws.gls, N, C, ws.ld);                                                              \
-    } while (0)
-    switch (kind) {
-        case NW_SCORE_EUCLIDEAN: NW_COEFF(NW_SCORE_EUCLIDEAN); break;
-        case NW_SCORE_HYPERSPHERE: NW_COEFF(NW_SCORE_HYPERSPHERE); break;
-        case NW_SCORE_COSINE: NW_COEFF(NW_SCORE_COSINE); break;
-        case NW_SCORE_DOT: NW_COEFF(NW_SCORE_DOT); break;
-        default: NW_COEFF(NW_SCORE_CLIP); break;
-    }
-#undef NW_COEFF
-    if (ws.mfma) {
-        const unsigned ncs = (unsigned)((ws.ld / 4 + 15) / 16);
-        if (ws.split) {
-            const unsigned nq = (unsigned)((ws.Bpad + 3) / 4);
-            hipLaunchKernelGGL(nw_bwd_prep_kernel, dim3(nq + ncs), dim3(256), 0, st, (int)nq, q, ws.ascale, ws.qv, ws.q_split,
-                               ws.gfac, B, ws.Bpad, d, ws.Rs, ws.ld, ws.rs, N);
-        } else {
-            hipLaunchKernelGGL(nw_colsum_kernel, dim3(ncs), dim3(256), 0, st, ws.Rs, ws.ld, ws.rs, B, N);
-        }
-        int rc;
-        if (ws.split) {
-            // gq = 2^-E_b (A' s') + 2 rq q: K = N runs along the rows of A' (zero past N), the rows of s' are clamped
-            XgemmReduce gq_reduce;   // the first product's K-split reduction rides along with the second product's launch
-            rc = launch_xgemm(false, ws.A, ws.ld, B, ws.s_split, d, N, ws.part, ws.ascale, 0, nullptr, ws.rq, q, gq, B, d,
-                              N, st, &gq_reduce);
-            if (rc != NW_OK) return rc;
-            // gs = 2^(e_j - G) (A'^T q'') + 2 rs s: K = B runs across the rows of A' (clamped), q'' is zero past B
-            rc = launch_xgemm(true, ws.A, ws.ld, B, ws.q_split, d, ws.Bpad, ws.part2, ws.s_scale, 1, ws.gfac, ws.rs, s, gs,
-                              N, d, B, st, nullptr, &gq_reduce);
-            if (rc != NW_OK) return rc;
-        } else {
-            rc = launch_bwd_gemm<true>(ws.A, ws.ld, s, ws.part, ws.rq, q, gq, B, d, N, st);   // gq = A s + 2 rq q
-            if (rc != NW_OK) return rc;
-            rc = launch_bwd_gemm<false>(ws.A, ws.ld, q, ws.part, ws.rs, s, gs, N, d, B, st);      // gs = A^T q + 2 rs s
-            if (rc != NW_OK) return rc;
-        }
-        if (glogit_scale) {
-            if (kind == NW_SCORE_CLIP)
-                hipLaunchKernelGGL(nw_sum_kernel, dim3(1), dim3(256), 0, st, ws.gls, glogit_scale, B);
-            else if (hipMemsetAsync(glogit_scale, 0, 4, st) != hipSuccess)
-                return NW_ERR_LAUNCH;
-        }
-        NW_CHECK_LAUNCH();
-        return NW_OK;
-    }
-    const unsigned kd = (unsigned)((d + 255) / 256);
-    hipLaunchKernelGGL(nw_bwd_gq_kernel, dim3((unsigned)B, kd), dim3(256), 0, st, ws.A, ws.rq, q, s, gq, N, d, sup_batched);
-    if (sup_batched)
-        hipLaunchKernelGGL(nw_bwd_gs_batched_kernel, dim3((unsigned)gs_rows, kd), dim3(256), 0, st, ws.A, ws.Rs, q, s, gs, N, d);
-    else
-        hipLaunchKernelGGL(nw_bwd_gs_shared_kernel, dim3((unsigned)N, kd), dim3(256), 0, st, ws.A, ws.Rs, q, s, gs, B, N, d);
+    const BwdCall c = {q, s, s_norm2, s_split, s_scale, sy, scores, lse, out, gout, gq, gs, glogit_scale, workspace, workspace_bytes,
+                       B, N, d, C, kind, logit_scale_dev, sup_batched, labels_batched, static_cast<hipStream_t>(stream)};
+    BwdPlan p;
+    int rc = bwd_check(c, &p);
+    if (rc != NW_OK) return rc;
+    if (c.empty()) return bwd_zero_gradients(c);
+    BwdOperands o;
+    if ((rc = bwd_operands(c, p, &o)) != NW_OK) return rc;
+    launch_coeff(c, p, o);
+    rc = p.route == BWD_SPLIT ? bwd_products_split(c, p, o) : p.route == BWD_MFMA ? bwd_products_mfma(c, p) : bwd_products_valu(c, p);
+    if (rc != NW_OK) return rc;
     if (glogit_scale) {
         if (kind == NW_SCORE_CLIP)
-            hipLaunchKernelGGL(nw_sum_kernel, dim3(1), dim3(256), 0, st, ws.gls, glogit_scale, B);
-        else if (hipMemsetAsync(glogit_scale, 0, 4, st) != hipSuccess)
+            hipLaunchKernelGGL(nw_sum_kernel, dim3(1), dim3(256), 0, c.st, p.at(BWD_GLS), glogit_scale, B);
+        else if (hipMemsetAsync(glogit_scale, 0, 4, c.st) != hipSuccess)
             return NW_ERR_LAUNCH;
     }
     NW_CHECK_LAUNCH();
@@ -748,10 +741,9 @@ extern "C" int nw_aggregate_bwd_f32(const float* scores, const int64_t* sy, cons
     if (B == 0 || N == 0) return NW_OK;
     if (!scores || !sy || !lse || !out || !gout || !gscores) return NW_ERR_INVALID_ARG;
     if (B > 0x7fffffffLL) return NW_ERR_INVALID_ARG;
-    const size_t lds = (80 + (size_t)C) * sizeof(float);
-    if (lds > 160 * 1024) return NW_ERR_UNSUPPORTED;
-    const unsigned threads = N >= 2048 ? 1024 : 256;
-    hipLaunchKernelGGL(nw_bwd_coeff_kernel<NW_SCORE_DOT>, dim3((unsigned)B), dim3(threads), lds, st, scores, lse, out, gout,
+    const size_t lds = bwd_coeff_lds_bytes(C, 0);
+    if (lds > BWD_COEFF_LDS_CAP) return NW_ERR_UNSUPPORTED;
+    hipLaunchKernelGGL(nw_bwd_coeff_kernel<NW_SCORE_DOT>, dim3((unsigned)B), dim3(bwd_coeff_threads(N)), lds, st, scores, lse, out, gout,
                        sy, labels_batched, (const float*)nullptr, (const float*)nullptr, 0, (const float*)nullptr, gscores,
                        (float*)nullptr, (float*)nullptr, (float*)nullptr, N, C, N);
     NW_CHECK_LAUNCH();

@@ -358,7 +358,7 @@ int xgemm_target_wgs() {
 
 }  // namespace
 
-XgemmPlan xgemm_plan(int64_t M, int64_t Nn, int64_t K) {
+KSplit xgemm_plan(int64_t M, int64_t Nn, int64_t K) {
     const int64_t tiles = ((M + XM - 1) / XM) * ((Nn + XN - 1) / XN);
     const int64_t target = xgemm_target_wgs();
     int64_t want = tiles >= target ? 1 : (target + tiles - 1) / tiles;
@@ -366,7 +366,7 @@ XgemmPlan xgemm_plan(int64_t M, int64_t Nn, int64_t K) {
     if (want > maxc) want = maxc;
     int64_t kc = (K + want - 1) / want;
     kc = (kc + XK - 1) / XK * XK;
-    XgemmPlan p;
+    KSplit p;
     p.k_chunk = (int)kc;
     p.nchunks = (int)((K + kc - 1) / kc);
     return p;
@@ -375,12 +375,12 @@ XgemmPlan xgemm_plan(int64_t M, int64_t Nn, int64_t K) {
 // x_km = false: X is (M rows, k along the row) -- true: X is (k rows, m along the row).  Both operands are split-row
 // images (tile_f16.h); K-direction padding must be zero in ONE of them and finite in the other; rows are clamped to
 // x_rows / y_rows, columns past a row's end are read from the bytes that follow (the caller pads the buffers by
-// XGEMM_TAIL_BYTES) and only feed outputs that are never stored.
+// XGEMM_TAIL_BYTES) and only feed outputs that are never stored.  p: the product's K-split as the caller's BwdPlan
+// holds it (`part` was sized by the same record).
 int launch_xgemm(bool x_km, const float* X, int64_t ldx, int64_t x_rows, const float* Y, int64_t ldy, int64_t y_rows,
                  float* part, const float* fac, int fac_inverse, const float* gfac, const float* rowscale,
-                 const float* Xo, float* out, int64_t M, int64_t Nn, int64_t K, hipStream_t st, XgemmReduce* defer,
-                 const XgemmReduce* pending) {
-    const XgemmPlan p = xgemm_plan(M, Nn, K);
+                 const float* Xo, float* out, int64_t M, int64_t Nn, int64_t K, const KSplit& p, hipStream_t st,
+                 XgemmReduce* defer, const XgemmReduce* pending) {
     XgemmReduce pend = {};
     if (pending && pending->blocks > 0) pend = *pending;
     if (defer) *defer = XgemmReduce{};

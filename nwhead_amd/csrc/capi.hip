@@ -4,6 +4,7 @@
 #include <string.h>
 #include "nw_internal.h"
 #include "fused_plan.h"
+#include "bwd_plan.h"
 
 namespace {
 inline bool bad_kind(int kind) { return kind < NW_SCORE_EUCLIDEAN || kind > NW_SCORE_CLIP; }
@@ -148,6 +149,18 @@ extern "C" int nw_debug_fwd_layout(int64_t B, int64_t N, int64_t d, int64_t C, n
     for (int i = 0; i < NW_FWD_AREAS; ++i) layout->off[i] = areas[i]->off, layout->bytes[i] = areas[i]->bytes;
     layout->total = L.total;
     layout->n_slices = L.n_slices;
+    return NW_OK;
+}
+
+extern "C" int nw_debug_bwd_plan(int64_t B, int64_t N, int64_t d, int64_t C, int sup_batched, nw_bwd_plan* plan) {
+    static_assert(NW_BWD_AREAS == nw::BWD_AREAS, "nw_bwd_plan lists the areas of nw::BwdPlan");
+    if (!plan || B < 0 || N < 0 || d < 0 || C < 0) return NW_ERR_INVALID_ARG;
+    const nw::BwdPlan p = nw::plan_bwd(B, N, d, C, sup_batched);
+    *plan = {};
+    plan->status = p.status, plan->route = p.route, plan->coeff_threads = (int32_t)p.coeff_threads, plan->parts_shared = p.parts_shared;
+    plan->gq_chunks = p.gq.nchunks, plan->gq_k_chunk = p.gq.k_chunk, plan->gs_chunks = p.gs.nchunks, plan->gs_k_chunk = p.gs.k_chunk;
+    plan->ld = p.ld, plan->Bpad = p.Bpad, plan->coeff_lds_bytes = p.coeff_lds, plan->total = p.total;
+    for (int i = 0; i < NW_BWD_AREAS; ++i) plan->off[i] = p.area[i].off, plan->bytes[i] = p.area[i].bytes;
     return NW_OK;
 }
 

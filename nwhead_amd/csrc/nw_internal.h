@@ -40,12 +40,20 @@ int launch_influence(const float* probs_or_logp, const int64_t* qy, const float*
 // squared row norms of a (rows,d) matrix (backward.hip)
 int launch_rownorm2(const float* x, float* n2, int64_t rows, int64_t d, hipStream_t st);
 
-// bwd_split.hip: the backward's two products on the fp16 matrix cores (split-row operands)
-struct XgemmPlan {
+// One area of a workspace map (FwdLayout below, BwdPlan in bwd_plan.h): byte offset from the buffer's base and size, both
+// multiples of 256.
+struct Area {
+    size_t off, bytes;
+};
+// The K-split of one product of the backward: nchunks partial tiles of k_chunk each (gemm_plan in backward.hip for the
+// fp32 matrix cores, xgemm_plan for the split route); chosen once per call by plan_bwd and handed to the launcher.
+struct KSplit {
     int nchunks, k_chunk;
 };
+
+// bwd_split.hip: the backward's two products on the fp16 matrix cores (split-row operands)
 constexpr size_t XGEMM_TAIL_BYTES = 512;   // readable bytes every operand buffer needs past its last row
-XgemmPlan xgemm_plan(int64_t M, int64_t Nn, int64_t K);
+KSplit xgemm_plan(int64_t M, int64_t Nn, int64_t K);
 // A K-split product's reduction (out = f(m) sum_chunks part + 2 rowscale Xo), to be run by extra workgroups of a LATER
 // launch_xgemm on the same stream instead of a kernel of its own (blocks == 0: nothing pending).
 struct XgemmReduce {
@@ -60,7 +68,7 @@ struct XgemmReduce {
 };
 int launch_xgemm(bool x_km, const float* X, int64_t ldx, int64_t x_rows, const float* Y, int64_t ldy, int64_t y_rows,
                  float* part, const float* fac, int fac_inverse, const float* gfac, const float* rowscale,
-                 const float* Xo, float* out, int64_t M, int64_t Nn, int64_t K, hipStream_t st,
+                 const float* Xo, float* out, int64_t M, int64_t Nn, int64_t K, const KSplit& p, hipStream_t st,
                  XgemmReduce* defer = nullptr, const XgemmReduce* pending = nullptr);
 
 // bwd_query.hip: the head's gradient w.r.t. the queries over a resident split bank, no (B,N) matrix (nw_bwd_query_f32)
@@ -151,9 +159,7 @@ bool fused_eligible(const float* q, const float* s, int64_t B, int64_t N, int64_
 //   slices    the partials of the sliced aggregation, n_slices * B * (2 + C) floats; empty when n_slices == 1
 // Every area starts on a multiple of 256 bytes and ends where the next one starts; the last ends at `total`.
 struct FwdLayout {
-    struct Area {
-        size_t off, bytes;
-    };
+    using Area = nw::Area;
     Area main, q_rows, q_scale, q_norm2, lse, slices;
     int n_slices;   // aggregate_slices(B, N), which sized `slices`
     size_t total;

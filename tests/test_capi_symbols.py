@@ -19,7 +19,7 @@ def test_header_declares_expected_surface():
     names = _declared()
     for n in ("nw_fwd_f32", "nw_bwd_f32", "nw_scores_f32", "nw_fwd_partial_f32", "nw_merge_finalize_f32",
               "nw_support_influence_f32", "nw_row_norm2_f32", "nw_fwd_workspace_bytes", "nw_bwd_workspace_bytes",
-              "nw_debug_fwd_layout"):
+              "nw_debug_fwd_layout", "nw_debug_bwd_plan"):
         assert n in names
 
 

@@ -5,6 +5,7 @@ Every other backward test feeds the kernels the gradient of F.nll_loss: one non-
 the rows of `gout` are dense, of mixed sign, of very different magnitude (per-sample weights), zero (masked samples), and laid
 out the way autograd really hands them over; the shapes go past 64 KiB of dynamic LDS in the coefficient kernel, to the LDS
 limit of the split route, to the class limit of the launcher, across the 256/1024-thread switch and the default thresholds.
+Last, the backward over a workspace filled with NaN, at the smallest shapes that reach every area of its map.
 
 Bar (the suite's bar for head gradients, test_fuzz_gpu.py): rtol = atol = 1e-4 on values divided by max(|ref|.max(), 1e-3);
 logit_scale.grad: rtol 1e-4, atol 1e-6.  Each case runs on the route it names and ASSERTS that it does:
@@ -89,12 +90,9 @@ def take_route(L):
 
 
 def route_of(L, B, N, d, C, sup=0):
-    """The route the NEXT backward of this shape takes under the current switches."""
+    """The route the NEXT backward of this shape takes under the current switches: the library's own plan."""
     L.sync_knobs()
-    if L.load().nw_bwd_uses_split(B, N, d, C, sup):
-        return "split"
-    mfma = os.environ.get("NW_BWD_NO_MFMA", "") != "1" and not sup and d % 4 == 0 and B * N * d >= 2 ** 22
-    return "mfma" if mfma else "valu"
+    return L.BWD_ROUTES[L.bwd_plan(B, N, d, C, sup).route]
 
 
 WORST = {}   # route -> (largest normalised error seen, where)
@@ -520,3 +518,67 @@ def test_default_thresholds(dev, ops, O, L, take_route, i, B, N, d, route):
     assert (B * N * d >= 2 ** 22) == (route != "valu")
     tag, loss = alternate(i, B, C)
     check(case_of(O, B, N, d, C, ("euclidean", "cosine")[i % 2]), ops, dev, route, tag, loss, f"threshold {(B, N, d)} {tag}")
+
+
+# ------------------------------------------------------------------------------------------ 3  a poisoned workspace
+# the smallest shapes that reach every area of the backward's workspace, with what each is there for
+POISON_SHAPES = [
+    (64, 1024, 64, 5),     # d % 64 == 0: the caller's bank is read; gq K-split, its reduction deferred into the gs launch
+    (64, 1024, 96, 5),     # d % 32 == 0 but d % 64 != 0: the split rows are the workspace copy
+    (256, 512, 64, 5),     # both products K-split: part and part2 live at once (split), one shared area (fp32 matrix cores)
+]
+
+
+@pytest.mark.parametrize("route", ROUTES)                # (the first mark varies fastest: one fp64 graph serves three routes)
+@pytest.mark.parametrize("kind", ("euclidean", "clip"))
+@pytest.mark.parametrize("B,N,d,C", POISON_SHAPES)
+def test_backward_on_a_poisoned_workspace(dev, ops, O, L, take_route, B, N, d, C, kind, route):
+    """The backward never clears its workspace and ops keeps one buffer per stream: whatever a kernel reads there without
+    having written it is the previous call's.  Forward, then the cached buffer filled with 0xFF (NaN as a float), then
+    backward(): every gradient finite, bit-equal to the same step over a zero-filled buffer, and at the bar of the oracle."""
+    from ws_poison import poison_cached_workspaces
+    take_route(route, B)
+    plan = L.bwd_plan(B, N, d, C)
+    assert route_of(L, B, N, d, C) == route and plan.total == L.load().nw_bwd_workspace_bytes(B, N, d, C, 0, 0)
+    cq, cs = plan.gq_chunks, plan.gs_chunks
+    if route == "valu":
+        assert cq == 0 and cs == 0
+    elif (B, N, d) == (64, 1024, 64):
+        assert cq > 1
+    elif (B, N, d) == (256, 512, 64):
+        assert cq > 1 and cs > 1
+        size = dict(zip(L.BWD_AREAS, zip(plan.off, plan.bytes)))
+        assert (size["part"] == size["part2"]) == (route == "mfma") == bool(plan.parts_shared)
+    if route == "split":
+        assert plan.bytes[L.BWD_AREAS.index("s_split")] >= 4 * N * d     # reserved whether or not the bank is read
+    c = case_of(O, B, N, d, C, kind)
+    loss = weighted(dense(B, C))
+
+    def zero_fill():
+        ops._workspace(plan.total, dev)
+        return sum(int(ws.zero_().numel()) for ws in ops._WS_CACHE.values())
+
+    def step(fill):
+        q, s = c.q0.to(dev).requires_grad_(True), c.s0.to(dev).requires_grad_(True)
+        ls = torch.tensor(LS0, device=dev, requires_grad=True) if kind == "clip" else None
+        out = ops.nw_head(q, s, c.sy.to(dev), C, kind, ls)
+        assert fill() >= plan.total > 0
+        try:
+            loss(out).backward()
+            torch.cuda.synchronize()
+        except RuntimeError as e:        # a device fault ends the session, as in Case.gpu
+            if "HIP error" in str(e) or "illegal memory access" in str(e):
+                pytest.exit(f"device fault in {(B, N, d, C)} {kind}: {e}", returncode=3)
+            raise
+        return (q.grad, s.grad) + ((ls.grad,) if ls is not None else ())
+
+    got, clean = step(lambda: poison_cached_workspaces(min_bytes=plan.total, device=dev)), step(zero_fill)
+    what = f"poisoned {kind} {(B, N, d, C)}"
+    for g, z, name in zip(got, clean, ("gq", "gs", "gls")):
+        assert bool(torch.isfinite(g).all()), f"{name} {what} [{route}]"
+        assert torch.equal(g, z), f"{name} {what} [{route}]: differs from the step over a zero-filled workspace"
+    ref = c.ref("dense", loss)
+    close(got[0], ref[0], route, f"gq {what}")
+    close(got[1], ref[1], route, f"gs {what}")
+    if kind == "clip":
+        close(got[2], ref[2], route, f"gls {what}", ls=True)

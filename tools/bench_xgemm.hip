@@ -31,14 +31,14 @@ int main(int argc, char** argv) {
     launch_split_rows(s, ss, sc, n2, N, d, 0);
     hipEvent_t e0, e1; hipEventCreate(&e0); hipEventCreate(&e1);
     for (int which = 0; which < 2; ++which) {
+        const KSplit p = which == 0 ? xgemm_plan(B, d, N) : xgemm_plan(N, d, B);
         auto launch = [&] {
-            if (which == 0) launch_xgemm(false, As, ld, B, ss, d, N, part, sc, 0, nullptr, n2, q, gq, B, d, N, 0);
-            else launch_xgemm(true, As, ld, B, qs, d, Bpad, part, sc, 1, one, n2, s, gs, N, d, B, 0);
+            if (which == 0) launch_xgemm(false, As, ld, B, ss, d, N, part, sc, 0, nullptr, n2, q, gq, B, d, N, p, 0);
+            else launch_xgemm(true, As, ld, B, qs, d, Bpad, part, sc, 1, one, n2, s, gs, N, d, B, p, 0);
         };
         for (int i = 0; i < 20; ++i) launch();
         hipEventRecord(e0); for (int i = 0; i < 100; ++i) launch(); hipEventRecord(e1); hipEventSynchronize(e1);
         float ms; hipEventElapsedTime(&ms, e0, e1);
-        const XgemmPlan p = which == 0 ? xgemm_plan(B, d, N) : xgemm_plan(N, d, B);
 #ifdef XG_DIAG
         {
             std::vector<unsigned long long> h(8 * 4096);
