@@ -8,8 +8,10 @@
 //     fill moves 25 % fewer bytes per flop.  No multiplying wave issues an LDS-DMA;
 //   * three waves per SIMD leave 168 registers per wave: 64 accumulators, 32 for the query fragments (double-buffered:
 //     this stage's and the next one's) and 32 for the support fragments, a rolling window of two pairs of 16-row blocks.
-//     The last pair of a stage is multiplied BEHIND the stage's barrier, under the first LDS reads of the next stage, so
-//     the matrix pipe has work while every wave of the workgroup waits for its first fragments;
+//     The last pair of a stage is multiplied BEHIND the stage's barrier, in FRONT of anything else: both waves of a SIMD
+//     leave the barrier together, and a head of address arithmetic and LDS reads left the matrix pipe idle for ~180 cycles
+//     per stage.  Every LDS read of the loop is issued singly behind an MFMA, at least eleven MFMAs ahead of its first
+//     use, and the lane addresses are kept in bytes and moved from ring slot to ring slot under MFMAs (run_stage);
 //   * 48 KB stages in a ring of three: during stage k the consumers read buffer k only, stage k+1 has landed at barrier
 //     k-1, and the loaders issue stage k+2 right behind barrier k-1 into the buffer that barrier released (every read of
 //     it was waited for in front of the barrier), waiting for all but the youngest stage;
@@ -313,56 +315,85 @@ __global__ __launch_bounds__(P12::THREADS, 3) void nw_fused_f16p_kernel_w12(
         struct QF { float4 bh[QB], bl[QB]; };   // query fragments of one stage
         struct SW { float4 al[2], ah[2]; };     // support fragments of one pair of 16-row blocks
         constexpr int NW_ = RS / 2;             // pairs per stage
-        auto rd_q = [&](QF& f, const float4* S) {
-#pragma unroll
-            for (int j = 0; j < QB; ++j) {
-                f.bh[j] = S[qoff + 16 * j * ROW_F4 + sh];
-                f.bl[j] = S[qoff + 16 * j * ROW_F4 + sl];
-            }
-        };
-        auto rd_w = [&](SW& w, const float4* S, int p) {
-#pragma unroll
-            for (int x = 0; x < 2; ++x) {
-                w.al[x] = S[soff + 16 * (2 * p + x) * ROW_F4 + sl];
-                w.ah[x] = S[soff + 16 * (2 * p + x) * ROW_F4 + sh];
-            }
-        };
+#ifdef NW_DIAG_FUSED
+        unsigned long long diag_[8] = {0, 0, 0, 0, 0, 0, 0, 0}, last_ = 0;
+#endif
+#ifdef NW_DIAG_HEAD  // diagnostic build only: the ticks from a stage's barrier to its first MFMA's issue, summed in diag_[6]
+        unsigned long long h0_ = 0, h1_ = 0;  // read only behind the stage's closing lgkmcnt(0)
+#define NW_HEAD_STAMP(t) asm volatile("s_memtime %0" : "=s"(t))
+#else
+#define NW_HEAD_STAMP(t)
+#endif
         auto mm = [](const float4& a, const float4& b, f32x4 c) {
             return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(half8, a), __builtin_bit_cast(half8, b), c, 0, 0, 0);
         };
         auto pin = []() { __builtin_amdgcn_sched_barrier(0); };
         f32x4 acc[QB][RS];
-        // the twelve MFMAs of pair p: four independent accumulator chains, per accumulator al x bh, ah x bl, ah x bh
-        // (HALF: eight, per accumulator lo x lo, hi x hi)
-        auto mm_w = [&](const SW& w, const QF& f, int p) {
-            if constexpr (HALF) {  // plain fp16 rows: slot `sh` holds k 0 .. 31 of the stage's 64, slot `sl` k 32 .. 63
+        // MFMA m of pair p, in the order every accumulator has always seen: four independent accumulator chains, per
+        // accumulator al x bh, ah x bl, ah x bh (HALF: lo x lo, hi x hi: slot `sh` holds k 0 .. 31 of the stage's 64, slot
+        // `sl` k 32 .. 63); m = 4 * product + 2 * block of the pair + query block
+        constexpr int NM = HALF ? 8 : 12;
+        auto mm_1 = [&](const SW& w, const QF& f, int p, int m) {
+            const int ph = m >> 2, x = (m >> 1) & 1, j = m & 1;
+            const float4& a = HALF ? (ph == 0 ? w.ah[x] : w.al[x]) : (ph == 0 ? w.al[x] : w.ah[x]);
+            const float4& b = HALF ? (ph == 0 ? f.bh[j] : f.bl[j]) : (ph == 1 ? f.bl[j] : f.bh[j]);
+            acc[j][2 * p + x] = mm(a, b, acc[j][2 * p + x]);
+        };
+        // the MFMAs of pair p; behind(m) is issued right behind MFMA m, in this order
+        auto mm_w = [&](const SW& w, const QF& f, int p, auto&& behind) {
 #pragma unroll
-                for (int x = 0; x < 2; ++x)
-#pragma unroll
-                    for (int j = 0; j < QB; ++j) acc[j][2 * p + x] = mm(w.ah[x], f.bh[j], acc[j][2 * p + x]);
-#pragma unroll
-                for (int x = 0; x < 2; ++x)
-#pragma unroll
-                    for (int j = 0; j < QB; ++j) acc[j][2 * p + x] = mm(w.al[x], f.bl[j], acc[j][2 * p + x]);
-            } else {
-#pragma unroll
-                for (int x = 0; x < 2; ++x)
-#pragma unroll
-                    for (int j = 0; j < QB; ++j) acc[j][2 * p + x] = mm(w.al[x], f.bh[j], acc[j][2 * p + x]);
-#pragma unroll
-                for (int x = 0; x < 2; ++x)
-#pragma unroll
-                    for (int j = 0; j < QB; ++j) acc[j][2 * p + x] = mm(w.ah[x], f.bl[j], acc[j][2 * p + x]);
-#pragma unroll
-                for (int x = 0; x < 2; ++x)
-#pragma unroll
-                    for (int j = 0; j < QB; ++j) acc[j][2 * p + x] = mm(w.ah[x], f.bh[j], acc[j][2 * p + x]);
+            for (int m = 0; m < NM; ++m) {
+                mm_1(w, f, p, m);
+                behind(m);
             }
-            __builtin_amdgcn_sched_barrier(0);
+            pin();
+        };
+        auto nothing = [](int) {};
+        // The four lane addresses of the stage being read, in bytes of LDS (high / low slot of the wave's first query row
+        // and of the first support row): shifted once, moved on to the next ring slot under the last MFMAs of each stage.
+        typedef const __attribute__((address_space(3))) f32x4 lds_f4;
+        const unsigned ring0 = (unsigned)(uintptr_t)(__attribute__((address_space(3))) char*)(char*)stage;
+        unsigned a_qh = ring0 + 16u * (qoff + sh), a_ql = ring0 + 16u * (qoff + sl);
+        unsigned a_sh = ring0 + 16u * (soff + sh), a_sl = ring0 + 16u * (soff + sl);
+        asm volatile("" : "+v"(a_qh), "+v"(a_ql), "+v"(a_sh), "+v"(a_sl));
+        auto lds_rd = [](unsigned a, int f4) { return __builtin_bit_cast(float4, *(lds_f4*)(uintptr_t)(a + 16u * f4)); };
+        auto q_h = [&](int j) { return lds_rd(a_qh, 16 * j * ROW_F4); };
+        auto q_l = [&](int j) { return lds_rd(a_ql, 16 * j * ROW_F4); };
+        auto s_h = [&](int blk) { return lds_rd(a_sh, 16 * blk * ROW_F4); };
+        auto s_l = [&](int blk) { return lds_rd(a_sl, 16 * blk * ROW_F4); };
+        auto advance = [&](int slot, int m) {  // one address per call, m = 0 .. 3
+            const unsigned step = (slot + 1 == NB) ? 0u - (unsigned)((NB - 1) * P::TILE_F4 * 16) : (unsigned)(P::TILE_F4 * 16);
+            unsigned& a = (m == 0) ? a_qh : (m == 1) ? a_ql : (m == 2) ? a_sh : a_sl;
+            a += step;
+            asm volatile("" : "+v"(a));
         };
         SW wa, wb;
+        // Read n of a stage's first eight (this stage's query fragments and pair 0), in the order pair 0's MFMAs take them
+        auto rd_first = [&](QF& f, SW& w, int n) {
+            const bool qlo = n >= 4, slo = (n < 4) != HALF;  // the first product's operands, then the second one's
+            const int r = n & 3;                             // support block 0, query blocks 0 and 1, support block 1
+            if (r == 0 || r == 3) {
+                const int x = r == 3;
+                if (slo) w.al[x] = s_l(x);
+                else w.ah[x] = s_h(x);
+            } else {
+                if (qlo) f.bl[r - 1] = q_l(r - 1);
+                else f.bh[r - 1] = q_h(r - 1);
+            }
+        };
+        // Read n of pair p's four, in the order the pair's MFMAs take them
+        auto rd_pair = [&](SW& w, int p, int n) {
+            const int x = n & 1;
+            if ((n < 2) != HALF) w.al[x] = s_l(2 * p + x);
+            else w.ah[x] = s_h(2 * p + x);
+        };
         // One stage.  fp = the previous stage's query fragments, fc = this stage's (read here).  The last pair of the
-        // previous stage (in wb) is multiplied under this stage's first reads; this stage's last pair is left in wb.
+        // previous stage (in wb) is multiplied right behind the barrier: its operands are in registers, so the matrix pipe
+        // starts at once for both waves of a SIMD, and this stage's first eight reads go out one behind each of those MFMAs
+        // (a tile's first stage has no held pair: its reads come first).  The reads of pair p + 1 lie behind the first four
+        // MFMAs of pair p, the four address updates behind MFMAs 4 .. 7 of the last pair but one, after the stage's last
+        // read.  No VALU or LDS instruction stands between the barrier and the first MFMA.  This stage's last pair is
+        // left in wb.
         auto run_stage = [&](const QF& fp, QF& fc, int slot, auto first) {
             constexpr bool FIRST = decltype(first)::value;
 #ifdef NW_ABL_NORD   // timing experiment: no fragment reads in the loop (the fragments of a tile's first stage are reused)
@@ -370,18 +401,43 @@ __global__ __launch_bounds__(P12::THREADS, 3) void nw_fused_f16p_kernel_w12(
 #else
             constexpr bool RD = true;
 #endif
-            const float4* S = stage + slot * P::TILE_F4;
-            if (RD) { rd_q(fc, S); rd_w(wa, S, 0); }
-            pin();
-            if (!FIRST) mm_w(wb, fp, NW_ - 1);
+            if constexpr (FIRST) {
+#pragma unroll
+                for (int n = 0; n < 8; ++n) {
+                    rd_first(fc, wa, n);
+                    pin();
+                }
+            } else {
+                NW_HEAD_STAMP(h0_);
+                mm_w(wb, fp, NW_ - 1, [&](int m) {
+                    if (m == 0) NW_HEAD_STAMP(h1_);
+                    if (m < 8) {
+                        pin();
+                        if (RD) rd_first(fc, wa, m);
+                        pin();
+                    }
+                });
+            }
 #pragma unroll
             for (int p = 0; p + 1 < NW_; ++p) {
-                if (RD) rd_w((p & 1) ? wa : wb, S, p + 1);
-                pin();
-                mm_w((p & 1) ? wb : wa, fc, p);
+                SW& wr = (p & 1) ? wa : wb;
+                mm_w((p & 1) ? wb : wa, fc, p, [&](int m) {
+                    if (m < 4) {
+                        pin();
+                        if (RD) rd_pair(wr, p + 1, m);
+                        pin();
+                    } else if (p + 2 == NW_ && m < 8) {
+                        pin();
+                        advance(slot, m - 4);
+                        pin();
+                    }
+                });
             }
             static_assert(NW_ % 2 == 0, "the last pair of a stage sits in wb");
             tile_barrier();  // every read of this stage's buffer has returned: the loaders may refill it
+#ifdef NW_DIAG_HEAD
+            if (!FIRST) diag_[6] += h1_ - h0_;
+#endif
         };
         using Yes = std::integral_constant<bool, true>;
         using No = std::integral_constant<bool, false>;
@@ -400,7 +456,7 @@ __global__ __launch_bounds__(P12::THREADS, 3) void nw_fused_f16p_kernel_w12(
             return b;
         };
 #ifdef NW_DIAG_FUSED
-        unsigned long long diag_[8] = {0, 0, 0, 0, 0, 0, 0, 0}, last_ = __builtin_amdgcn_s_memtime();
+        last_ = __builtin_amdgcn_s_memtime();
         const unsigned long long first_ = last_, first_rt_ = __builtin_amdgcn_s_memrealtime();
 #endif
         for (int T = cu; T < n_local; T += n_cu) {
@@ -419,7 +475,8 @@ __global__ __launch_bounds__(P12::THREADS, 3) void nw_fused_f16p_kernel_w12(
                 for (int r = 0; r < RS; ++r) acc[j][r] = f32x4{0.f, 0.f, 0.f, 0.f};
             QF f0, f1;
 #ifdef NW_ABL_NORD
-            rd_q(f1, stage + gi * P::TILE_F4);
+#pragma unroll
+            for (int n = 0; n < 8; ++n) rd_first(f1, wa, n);
 #endif
             run_stage(f1, f0, next_slot(), Yes{});
             int kt = 1;
@@ -429,9 +486,9 @@ __global__ __launch_bounds__(P12::THREADS, 3) void nw_fused_f16p_kernel_w12(
             }
             if (kt < nk) {
                 run_stage(f0, f1, next_slot(), No{});
-                mm_w(wb, f1, NW_ - 1);
+                mm_w(wb, f1, NW_ - 1, nothing);
             } else {
-                mm_w(wb, f0, NW_ - 1);
+                mm_w(wb, f0, NW_ - 1, nothing);
             }
             NW_PSTAMP(0);
 #ifndef NW_ABL_NOEPI
@@ -445,7 +502,9 @@ __global__ __launch_bounds__(P12::THREADS, 3) void nw_fused_f16p_kernel_w12(
             keep_acc_alive(acc, ws_m, nrun, bnd);
 #endif
             par = (par + 1 == P::NHB) ? 0 : par + 1;
+#ifndef NW_DIAG_HEAD
             NW_PSTAMP(6);
+#endif
         }
 #ifdef NW_DIAG_FUSED
         diag_write_out(diag_, last_, first_, first_rt_);

@@ -1,7 +1,8 @@
 // Diagnostic harness: phase stamps of nw_fused_kernel (build with -DNW_DIAG_FUSED).
 // Persistent kernels (argv[5] = 2; they exist for tiles of 128 supports only: build with -DNW_BENCH_RS=8, at another height
 // the mode is refused): NW_PVAR=0 / 1 / 2 pick the variants of fused_f16p.h, NW_PVAR=3 the 256-query kernel of
-// fused_f16p12.h; both take -DNW_ABL_NODMA / -DNW_ABL_NORD / -DNW_ABL_NOEPI.
+// fused_f16p12.h; both take -DNW_ABL_NODMA / -DNW_ABL_NORD / -DNW_ABL_NOEPI.  -DNW_DIAG_HEAD (NW_PVAR=3 only): the last
+// slot sums the ticks from each stage barrier to the issue of the stage's first MFMA instead of the tile loop's rest.
 // Build: hipcc -O3 --offload-arch=gfx950 -I nwhead_amd/csrc -DNW_DIAG_FUSED [-DNW_BENCH_RS=8] tools/bench_fused.hip
 //        nwhead_amd/csrc/split.hip -o tools/bench_fused      (tile height in 16-row blocks; 10 when not given)
 #include <hip/hip_runtime.h>
@@ -117,8 +118,13 @@ int main(int argc, char** argv) {
                 printf("in-kernel clock (ticks / s_memrealtime, per workgroup): median %.3f GHz, min %.3f, max %.3f; wave lifetime %.1f us\n",
                        ghz[ghz.size() / 2], ghz.front(), ghz.back(), ph[7] / n / (ghz[ghz.size() / 2] * 1e3));
         }
-        printf("persistent kernel %.2f us | per WG (s_memtime ticks): main loops %.0f | epilogue: header reads %.0f, scores %.0f, mask+max+exp+den %.0f, run sums+stores %.0f, m/den stores %.0f, rest %.0f | total %.0f\n",
-               ms * 10, ph[0] / n, ph[1] / n, ph[2] / n, ph[3] / n, ph[4] / n, ph[5] / n, ph[6] / n, ph[7] / n);
+#ifdef NW_DIAG_HEAD  // the 256-query kernel only: the last slot sums barrier release -> first MFMA issued over the stages
+        const char* last_slot = "stage heads (barrier -> first MFMA issued; inside main loops)";
+#else
+        const char* last_slot = "rest";
+#endif
+        printf("persistent kernel %.2f us | per WG (s_memtime ticks): main loops %.0f | epilogue: header reads %.0f, scores %.0f, mask+max+exp+den %.0f, run sums+stores %.0f, m/den stores %.0f, %s %.0f | total %.0f\n",
+               ms * 10, ph[0] / n, ph[1] / n, ph[2] / n, ph[3] / n, ph[4] / n, ph[5] / n, last_slot, ph[6] / n, ph[7] / n);
         return 0;
     }
     std::vector<unsigned long long> h(8 * grid);
