@@ -95,6 +95,39 @@ int nw_split_rows_f16x2(const float *x, float *out_split, float *row_scale, floa
 int nw_pack_rows_f16(const float *x, uint16_t *out_rows, float *row_scale, float *row_norm2,
                      int64_t rows, int64_t d, void *stream);
 
+/* Rows of a PREPARED bank replaced in place: R given rows of the fp32 matrix get new values and every prepared form
+ * of those rows is left, bit for bit, as the three calls above would have made it from the new fp32 row.  For a
+ * memory bank that follows the weights during training (each batch's features written back, optionally blended with
+ * what was there) and for swapping samples of a live bank; the labels do not change.
+ *   x        (R, dx) fp32, 1 <= dx <= d; columns dx .. d-1 of a new row are zero (the bank's zero padding).  Any
+ *            alignment and width (16-byte loads only when dx % 4 == 0 and x is 16-byte aligned)
+ *   rows     (R,) int64 on the device
+ *   momentum 0: the new row is x[i], its bits as they are (-0 and NaN pass unchanged); otherwise
+ *            momentum * old + (1.0f - momentum) * x[i] with the two products and the sum each rounded on their own,
+ *            old read from s_rows, 1.0f - momentum formed in fp32
+ *   s_rows   (N, d) fp32: the matrix the prepared forms are derived from (read for the blend, written)
+ *   s_user   optional (N, dx): the caller's own tensor when s_rows is a zero-padded copy of it; receives the first
+ *            dx columns of the new row
+ *   s_norm2  (N,)
+ *   s_split + s_scale               optional as a group: the forms of nw_split_rows_f16x2 (s_norm2 is then its
+ *            row_norm2; the "split_lbits" diagnostic knob applies as it does there)
+ *   s_f16 + f16_scale + f16_norm2   optional as a group: the forms of nw_pack_rows_f16.  With this group alone
+ *            s_norm2 is nw_row_norm2_f32's
+ * Item i with r = rows[i] is skipped when r < 0, when r >= N (compared, never used as an address) or when a later
+ * item j > i names the same row: the LAST occurrence wins, the others take no part, not even in the blend.  Whatever
+ * a skipped item would touch, and every row no item names, keeps its bits.
+ * One launch, one wave per item: no workspace, no allocation, no synchronisation, no environment, no atomics.
+ * Status, decided in this order before anything is launched: a negative size, dx outside [1, d], a momentum that is
+ * not finite or outside [0, 1): NW_ERR_INVALID_ARG;  R == 0 or N == 0: NW_OK;  x, rows, s_rows or s_norm2 NULL, a
+ * form group given in part, s_rows / s_split / s_f16 not 16-byte aligned: NW_ERR_INVALID_ARG;  neither form group
+ * (a norms-only bank), the split group with d % 32 != 0, the fp16 group with d % 64 != 0 or d < 192, R > 16384 (every
+ * wave scans the rest of `rows` for its row): NW_ERR_UNSUPPORTED. */
+int nw_bank_update_rows_f32(const float *x, const int64_t *rows, int64_t R, int64_t dx, float momentum,
+                            float *s_rows, float *s_user, float *s_norm2,
+                            float *s_split, float *s_scale,
+                            void *s_f16, float *f16_scale, float *f16_norm2,
+                            int64_t N, int64_t d, void *stream);
+
 /* ---------------------------------------------------------------------------------------------
  * Forward.  Replaces NWHead.forward nwhead/nw.py:266-289:
  *     one_hot(sy) -> kernel scores -> softmax over supports -> bmm with one-hot -> log(. + 1e-12)

@@ -30,6 +30,7 @@ SIGNATURES = {
     "nw_row_norm2_f32": (_int, [_p, _p, _i64, _i64, _p]),
     "nw_split_rows_f16x2": (_int, [_p, _p, _p, _p, _i64, _i64, _p]),
     "nw_pack_rows_f16": (_int, [_p, _p, _p, _p, _i64, _i64, _p]),
+    "nw_bank_update_rows_f32": (_int, [_p, _p, _i64, _i64, C.c_float, _p, _p, _p, _p, _p, _p, _p, _p, _i64, _i64, _p]),
     "nw_fwd_f32": (_int, [_p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _sz, _i64, _i64, _i64, _i64, _int, _p, _int, _int, _p, _p]),
     "nw_fwd_partial_f32": (_int, [_p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _sz, _i64, _i64, _i64, _i64, _int, _p, _p, _p]),
     "nw_merge_finalize_f32": (_int, [_p, _p, _p, _p, _i64, _i64, _i64, _i64, _i64, _i64, _p, _i64, _p]),

@@ -11,6 +11,7 @@
 // Euclidean: df/ddot = 1/D, df/d|q|^2 = df/d|s|^2 = -1/(2D), all taken as 0 where D == 0 (torch's
 // cdist backward masks the zero distance the same way).
 #include "nw_internal.h"
+#include "row_forms.h"
 #include "tile_dma.h"
 #include "bwd_coeff.h"
 #include "bwd_plan.h"
@@ -27,8 +28,7 @@ __global__ __launch_bounds__(256) void nw_rownorm_kernel(const float* __restrict
     const int lane = threadIdx.x & 63;
     if (r >= rows) return;
     const float* p = x + r * d;
-    float a = 0.f;
-    for (int64_t k = lane; k < d; k += 64) a += p[k] * p[k];
+    float a = row_norm2_lane([&](int64_t k) { return p[k]; }, d, lane);
     a = wave_sum(a);
     if (lane == 0) n2[r] = a;
 }

@@ -7,6 +7,7 @@
 // ORIGINAL values (the pow(2).sum(-1) half of torch.cdist's matmul form).
 // One wave per row; HBM-bound streaming (8*d bytes per row).
 #include "nw_internal.h"
+#include "row_forms.h"
 #include <type_traits>
 #include <cstdlib>
 
@@ -36,52 +37,20 @@ __global__ __launch_bounds__(256) void nw_split_rows_kernel(const float* __restr
             keep[u] = (c < n4) ? src[c] : make_float4(0.f, 0.f, 0.f, 0.f);
         }
 #pragma unroll
-        for (int u = 0; u < KEEP; ++u) {
-            const float4 v = keep[u];
-            mx = fmaxf(fmaxf(mx, fmaxf(fabsf(v.x), fabsf(v.y))), fmaxf(fabsf(v.z), fabsf(v.w)));
-            n2 += v.x * v.x + v.y * v.y + v.z * v.z + v.w * v.w;
-        }
+        for (int u = 0; u < KEEP; ++u) row_split_accum(mx, n2, keep[u]);
     } else {
-        for (int64_t c = lane; c < n4; c += 64) {
-            const float4 v = src[c];
-            mx = fmaxf(fmaxf(mx, fmaxf(fabsf(v.x), fabsf(v.y))), fmaxf(fabsf(v.z), fabsf(v.w)));
-            n2 += v.x * v.x + v.y * v.y + v.z * v.z + v.w * v.w;
-        }
+        for (int64_t c = lane; c < n4; c += 64) row_split_accum(mx, n2, src[c]);
     }
     mx = wave_max(mx);
     n2 = wave_sum(n2);
-    int e = 0;
-    if (mx > 0.f && mx < INFINITY) {
-        frexpf(mx, &e);   // mx = f * 2^e, f in [0.5, 1)
-        e = 14 - e;       // mx * 2^e in [2^13, 2^14)
-        if (e > 126) e = 126;  // a row of subnormal magnitudes (max < 2^-112): 2^e must stay finite and 2^-e normal
-    }
+    const int e = row_scale_exponent(mx);
     const float up = ldexpf(1.f, e);
     if (lane == 0) {
         scale[r] = ldexpf(1.f, -e);
         norm2[r] = n2;
     }
-    // chunk c (4 floats) of the row -> halves 4*(c % 8) .. +3 of the 32-k chunk c / 8
     _Float16* dst = reinterpret_cast<_Float16*>(out + r * d);
-    typedef _Float16 half4 __attribute__((ext_vector_type(4)));
-    auto emit = [&](int64_t c, const float4 v) {
-        const float sv[4] = {v.x * up, v.y * up, v.z * up, v.w * up};
-        half4 h, l;
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            h[k] = (_Float16)sv[k];
-            l[k] = (_Float16)(sv[k] - (float)h[k]);
-        }
-        if (lmask != 0xffffu) {  // diagnostic (NW_SPLIT_LBITS): fewer significant bits in the low halves
-            typedef unsigned short us4 __attribute__((ext_vector_type(4)));
-            us4 b = __builtin_bit_cast(us4, l);
-            b &= (unsigned short)lmask;
-            l = __builtin_bit_cast(half4, b);
-        }
-        const int64_t chunk = c >> 3, within = (c & 7) * 4;
-        *reinterpret_cast<half4*>(dst + chunk * 64 + within) = h;
-        *reinterpret_cast<half4*>(dst + chunk * 64 + 32 + within) = l;
-    };
+    auto emit = [&](int64_t c, const float4 v) { row_split_emit(dst, c, v, up, lmask); };
     if (in_regs) {
 #pragma unroll
         for (int u = 0; u < KEEP; ++u) {
@@ -95,19 +64,23 @@ __global__ __launch_bounds__(256) void nw_split_rows_kernel(const float* __restr
 
 }  // namespace
 
-int launch_split_rows(const float* x, float* out, float* scale, float* norm2, int64_t rows, int64_t d,
-                      hipStream_t st) {
-    if (rows <= 0) return NW_OK;
-    if ((rows + 3) / 4 > 0x7fffffffLL) return NW_ERR_INVALID_ARG;
+// The mask of the low halves under the "split_lbits" knob (0xffff: all bits, the default).
+static unsigned split_lmask() {
     // Mantissa bits kept in the low halves (default 10 = all: the split is exact to 22 bits).  The tile kernel's pace
     // follows the operands' bit activity: K3 launch 583 us at 10 bits, 572 at 6, 563 at 3, 556 at 0 (max error vs fp64
     // 0.9 / 1.1 / 3.7 / 24 e-6).  Not taken: the large-norm, small-distance cases (golden G8) need the bits.  (Diagnostic
     // knob "split_lbits".)
     const int kb = knob(KNOB_SPLIT_LBITS);
     const int keep = kb == KNOB_UNSET ? 10 : kb;
-    const unsigned lmask = keep >= 10 ? 0xffffu : (0xffffu << (10 - (keep < 0 ? 0 : keep))) & 0xffffu;
+    return keep >= 10 ? 0xffffu : (0xffffu << (10 - (keep < 0 ? 0 : keep))) & 0xffffu;
+}
+
+int launch_split_rows(const float* x, float* out, float* scale, float* norm2, int64_t rows, int64_t d,
+                      hipStream_t st) {
+    if (rows <= 0) return NW_OK;
+    if ((rows + 3) / 4 > 0x7fffffffLL) return NW_ERR_INVALID_ARG;
     hipLaunchKernelGGL(nw_split_rows_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, st, x, out, scale,
-                       norm2, rows, d, lmask);
+                       norm2, rows, d, split_lmask());
     NW_CHECK_LAUNCH();
     return NW_OK;
 }
@@ -144,9 +117,6 @@ __global__ __launch_bounds__(256) void nw_pack_rows_f16_kernel(const float* __re
     const bool in_regs = n4 <= 64 * KEEP;
     float4 keep[KEEP];
     float mx = 0.f;
-    auto amax4 = [](float m, const float4 v) {
-        return fmaxf(fmaxf(m, fmaxf(fabsf(v.x), fabsf(v.y))), fmaxf(fabsf(v.z), fabsf(v.w)));
-    };
     if (in_regs) {
 #pragma unroll
         for (int u = 0; u < KEEP; ++u) {
@@ -154,32 +124,16 @@ __global__ __launch_bounds__(256) void nw_pack_rows_f16_kernel(const float* __re
             keep[u] = (c < n4) ? src[c] : make_float4(0.f, 0.f, 0.f, 0.f);
         }
 #pragma unroll
-        for (int u = 0; u < KEEP; ++u) mx = amax4(mx, keep[u]);
+        for (int u = 0; u < KEEP; ++u) mx = row_amax4(mx, keep[u]);
     } else {
-        for (int64_t c = lane; c < n4; c += 64) mx = amax4(mx, src[c]);
+        for (int64_t c = lane; c < n4; c += 64) mx = row_amax4(mx, src[c]);
     }
     mx = wave_max(mx);
-    int e = 0;
-    if (mx > 0.f && mx < INFINITY) {
-        frexpf(mx, &e);
-        e = 14 - e;
-        if (e > 126) e = 126;
-    }
+    const int e = row_scale_exponent(mx);
     const float up = ldexpf(1.f, e), down = ldexpf(1.f, -e);
-    typedef _Float16 half4 __attribute__((ext_vector_type(4)));
     half4* dst = reinterpret_cast<half4*>(out + r * d);
     float n2 = 0.f;
-    auto emit = [&](int64_t c, const float4 v) {
-        const float sv[4] = {v.x * up, v.y * up, v.z * up, v.w * up};
-        half4 h;
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            h[k] = (_Float16)sv[k];
-            const float back = (float)h[k] * down;
-            n2 = __builtin_fmaf(back, back, n2);
-        }
-        dst[c] = h;
-    };
+    auto emit = [&](int64_t c, const float4 v) { row_pack_emit(dst, c, v, up, down, n2); };
     if (in_regs) {
 #pragma unroll
         for (int u = 0; u < KEEP; ++u) {
@@ -217,6 +171,200 @@ extern "C" int nw_pack_rows_f16(const float* x, uint16_t* out_rows, float* row_s
     if (!x || !out_rows || !row_scale || !row_norm2) return NW_ERR_INVALID_ARG;
     if ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(out_rows)) & 15) return NW_ERR_INVALID_ARG;
     return nw::launch_pack_rows_f16(x, out_rows, row_scale, row_norm2, rows, d, static_cast<hipStream_t>(stream));
+}
+
+// ------------------------------------------------------------------------------------------------------------------
+// Rows of a PREPARED bank replaced in place (nw_bank_update_rows_f32): item i writes x[i] -- or, with a momentum, its blend
+// with the row that was there -- to row rows[i] of the fp32 matrix and leaves every prepared form of that row as the
+// kernels above (and nw_row_norm2_f32) would have made it from the new fp32 row: the same per-row functions (row_forms.h),
+// the same lanes, the same order.  One wave per item, one launch, no workspace and no atomics.
+// An item is skipped when its row is negative or past the bank, or when a LATER item names the same row (the wave scans
+// the rest of `rows` 64 at a time): the last occurrence wins and is blended once with the old row; rows are written by one
+// wave only, so there is no race.  Rows of up to 2048 floats stay in registers from the blend to the emit; longer ones are
+// written to s_rows and read back by the same lane at the same index.
+namespace nw {
+namespace {
+
+struct BankUpdate {
+    const float* x;          // (R, dx); columns dx .. d-1 of a new row are zero
+    const int64_t* rows;     // (R,)
+    int64_t R, dx;
+    float momentum;
+    float* s_rows;           // (N, d) fp32: read (the old row of a blend) and written
+    float* s_user;           // (N, dx) or null: the caller's own tensor when s_rows is the padded copy
+    float* s_norm2;
+    float *s_split, *s_scale;                 // both or neither
+    _Float16* s_f16;                          // all three or none
+    float *f16_scale, *f16_norm2;
+    int64_t N, d;
+    unsigned lmask;
+    int vec_x;               // x may be read in 16-byte pieces (aligned, dx % 4 == 0)
+};
+
+// momentum * old + (1 - momentum) * new with the two products and the sum each rounded on their own, whatever the
+// translation unit's contraction mode: what three elementwise fp32 tensor operations give
+__device__ __forceinline__ float blend_rounded(float m, float om, float old, float nw_) {
+#pragma clang fp contract(off)
+    const float a = m * old;
+    const float b = om * nw_;
+    return a + b;
+}
+
+__global__ __launch_bounds__(256) void nw_bank_update_rows_kernel(const BankUpdate a) {
+    const int64_t i = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    const int lane = threadIdx.x & 63;
+    if (i >= a.R) return;
+    const int64_t r = a.rows[i];
+    if (r < 0 || r >= a.N) return;            // compared, never used as an address
+    bool later = false;
+    for (int64_t j = i + 1 + lane; j < a.R; j += 64) later |= a.rows[j] == r;
+    if (__any(later)) return;                 // (wave-uniform: the whole wave leaves)
+
+    const int64_t d = a.d, dx = a.dx, n4 = d / 4;
+    const float* xi = a.x + i * dx;
+    float* row = a.s_rows + r * d;
+    const float m = a.momentum, om = 1.0f - a.momentum;
+    const bool blend = m != 0.f;
+    // the new row's element k / chunk c; with no momentum x's bits as they are
+    auto mix = [&](float old, float nw_) { return blend_rounded(m, om, old, nw_); };
+    auto elem = [&](int64_t k) -> float {
+        const float v = k < dx ? xi[k] : 0.f;
+        return blend ? mix(row[k], v) : v;
+    };
+    auto chunk = [&](int64_t c) -> float4 {
+        float4 v;
+        if (a.vec_x) {
+            v = 4 * c < dx ? reinterpret_cast<const float4*>(xi)[c] : make_float4(0.f, 0.f, 0.f, 0.f);
+        } else {
+            const int64_t k = 4 * c;
+            v.x = k < dx ? xi[k] : 0.f;
+            v.y = k + 1 < dx ? xi[k + 1] : 0.f;
+            v.z = k + 2 < dx ? xi[k + 2] : 0.f;
+            v.w = k + 3 < dx ? xi[k + 3] : 0.f;
+        }
+        if (blend) {
+            const float4 o = reinterpret_cast<const float4*>(row)[c];
+            v.x = mix(o.x, v.x), v.y = mix(o.y, v.y), v.z = mix(o.z, v.z), v.w = mix(o.w, v.w);
+        }
+        return v;
+    };
+    auto store = [&](int64_t c, const float4 v) {
+        reinterpret_cast<float4*>(row)[c] = v;
+        if (a.s_user) {
+            float* u = a.s_user + r * dx;
+            const int64_t k = 4 * c;
+            if (k < dx) u[k] = v.x;
+            if (k + 1 < dx) u[k + 1] = v.y;
+            if (k + 2 < dx) u[k + 2] = v.z;
+            if (k + 3 < dx) u[k + 3] = v.w;
+        }
+    };
+    const bool split = a.s_split != nullptr, f16 = a.s_f16 != nullptr;
+    // a bank of fp16 rows keeps the PLAIN norms of its fp32 rows (nw_row_norm2_f32), which sums element k on lane k % 64:
+    // gathered here from the operands, before anything of the row is written
+    float plain = 0.f;
+    if (!split) plain = wave_sum(row_norm2_lane(elem, d, lane));
+
+    constexpr int KEEP = 8;
+    const bool in_regs = n4 <= 64 * KEEP;
+    float4 keep[KEEP];
+    float mx = 0.f, n2 = 0.f;
+    if (in_regs) {
+#pragma unroll
+        for (int u = 0; u < KEEP; ++u) {
+            const int64_t c = lane + 64 * u;
+            keep[u] = (c < n4) ? chunk(c) : make_float4(0.f, 0.f, 0.f, 0.f);
+        }
+#pragma unroll
+        for (int u = 0; u < KEEP; ++u) {
+            const int64_t c = lane + 64 * u;
+            if (c < n4) store(c, keep[u]);
+        }
+        if (split) {
+#pragma unroll
+            for (int u = 0; u < KEEP; ++u) row_split_accum(mx, n2, keep[u]);
+        } else {
+#pragma unroll
+            for (int u = 0; u < KEEP; ++u) mx = row_amax4(mx, keep[u]);
+        }
+    } else {
+        for (int64_t c = lane; c < n4; c += 64) {
+            const float4 v = chunk(c);
+            store(c, v);
+            if (split) row_split_accum(mx, n2, v);
+            else mx = row_amax4(mx, v);
+        }
+    }
+    mx = wave_max(mx);
+    const int e = row_scale_exponent(mx);
+    const float up = ldexpf(1.f, e), down = ldexpf(1.f, -e);
+    const float4* back = reinterpret_cast<const float4*>(row);     // (the streamed row: this lane's own stores)
+    if (split) {
+        n2 = wave_sum(n2);
+        if (lane == 0) {
+            a.s_scale[r] = down;
+            a.s_norm2[r] = n2;
+        }
+        _Float16* dst = reinterpret_cast<_Float16*>(a.s_split + r * d);
+        if (in_regs) {
+#pragma unroll
+            for (int u = 0; u < KEEP; ++u) {
+                const int64_t c = lane + 64 * u;
+                if (c < n4) row_split_emit(dst, c, keep[u], up, a.lmask);
+            }
+        } else {
+            for (int64_t c = lane; c < n4; c += 64) row_split_emit(dst, c, back[c], up, a.lmask);
+        }
+    } else if (lane == 0) {
+        a.s_norm2[r] = plain;
+    }
+    if (f16) {
+        half4* dst = reinterpret_cast<half4*>(a.s_f16 + r * d);
+        float hn2 = 0.f;
+        if (in_regs) {
+#pragma unroll
+            for (int u = 0; u < KEEP; ++u) {
+                const int64_t c = lane + 64 * u;
+                if (c < n4) row_pack_emit(dst, c, keep[u], up, down, hn2);
+            }
+        } else {
+            for (int64_t c = lane; c < n4; c += 64) row_pack_emit(dst, c, back[c], up, down, hn2);
+        }
+        hn2 = wave_sum(hn2);
+        if (lane == 0) {
+            a.f16_scale[r] = down;
+            a.f16_norm2[r] = hn2;
+        }
+    }
+}
+
+}  // namespace
+}  // namespace nw
+
+extern "C" int nw_bank_update_rows_f32(const float* x, const int64_t* rows, int64_t R, int64_t dx, float momentum,
+                                       float* s_rows, float* s_user, float* s_norm2, float* s_split, float* s_scale,
+                                       void* s_f16, float* f16_scale, float* f16_norm2, int64_t N, int64_t d, void* stream) {
+    if (R < 0 || N < 0 || d < 0) return NW_ERR_INVALID_ARG;
+    if (dx < 1 || dx > d) return NW_ERR_INVALID_ARG;
+    if (!(momentum >= 0.f && momentum < 1.f)) return NW_ERR_INVALID_ARG;      // (a NaN fails both)
+    if (R == 0 || N == 0) return NW_OK;
+    if (!x || !rows || !s_rows || !s_norm2) return NW_ERR_INVALID_ARG;
+    const bool split = s_split || s_scale, f16 = s_f16 || f16_scale || f16_norm2;
+    if (split && !(s_split && s_scale)) return NW_ERR_INVALID_ARG;
+    if (f16 && !(s_f16 && f16_scale && f16_norm2)) return NW_ERR_INVALID_ARG;
+    if ((reinterpret_cast<uintptr_t>(s_rows) | reinterpret_cast<uintptr_t>(s_split) | reinterpret_cast<uintptr_t>(s_f16)) & 15)
+        return NW_ERR_INVALID_ARG;
+    if (!split && !f16) return NW_ERR_UNSUPPORTED;
+    if (split && d % 32 != 0) return NW_ERR_UNSUPPORTED;
+    if (f16 && (d % 64 != 0 || d < 192)) return NW_ERR_UNSUPPORTED;
+    if (R > 16384) return NW_ERR_UNSUPPORTED;
+    const int vec_x = dx % 4 == 0 && (reinterpret_cast<uintptr_t>(x) & 15) == 0;
+    const nw::BankUpdate a = {x, rows, R, dx, momentum, s_rows, s_user, s_norm2, s_split, s_scale, static_cast<_Float16*>(s_f16),
+                              f16_scale, f16_norm2, N, d, nw::split_lmask(), vec_x};
+    hipLaunchKernelGGL(nw::nw_bank_update_rows_kernel, dim3((unsigned)((R + 3) / 4)), dim3(256), 0,
+                       static_cast<hipStream_t>(stream), a);
+    NW_CHECK_LAUNCH();
+    return NW_OK;
 }
 
 // ------------------------------------------------------------------------------------------------------------------

@@ -264,18 +264,41 @@ class NWNet(nn.Module):
         predicted without that row (a leave-one-out training loss over the bank's own samples).  Honours return_mask.
 
         The bank is a CONSTANT here: it holds the features of the weights precompute() saw and goes stale as the weights
-        move; the caller decides when to call precompute() again.  A sharded bank, a missing bank and a custom kernel
+        move; the caller decides when to call precompute() again, or writes each batch's features back with
+        refresh_bank(rows) -- they are kept, detached, in ``bank_features`` (a view, not a copy).  A sharded bank, a missing bank and a custom kernel
         module are refused (NWHipError), like predict_loo.  A full_precision="fp16" bank or a bank whose labels are not
         class-sorted takes ops.nw_head's route through the score matrix without ``leave_out`` and is refused with it."""
         what = "forward_bank"
         if getattr(self, 'sharded_bank', None) is not None or not hasattr(self, 'full_feat'):
             self._resident_bank(what, None)    # (raises: says why)
         qfeat = self.featurizer(x)
+        self.bank_features = qfeat.detach()
         sfeat, sy, cache = self._resident_bank(what, qfeat.device)
         window = None if leave_out is None else self._leave_out_window(leave_out, qfeat, what)
         out = ops.nw_head_bank(qfeat, sfeat, sy, self.n_classes, cache, self.kernel.kind, self.kernel._logit_scale(),
                                row_window=window, exclude=window is not None)
         return (out, torch.full((len(x),), True)) if self.return_mask else out
+
+    def refresh_bank(self, rows, feats=None, momentum=0.0):
+        """Not in the reference: write fresh features into rows of precompute()'s bank IN PLACE (ops.SplitBank.update_rows:
+        one launch, R rows read and written, no backbone pass, no rebuild of the bank, no host synchronisation) -- the step
+        of memory-bank training after forward_bank(x, leave_out=rows), backward and the optimizer step.  ``rows``: (R,)
+        integer tensor, the bank row of each feature row (-1 or a row past the bank: skipped; of repeated rows the last
+        wins); ``feats``: (R, feat_dim), default the features of the last forward_bank, ``bank_features``, which is then
+        cleared; ``momentum`` in [0, 1): the row becomes momentum * old + (1 - momentum) * new, 0 replaces it.  The labels
+        of the rows do not change.  A sharded bank, a missing bank and a custom kernel module raise as for forward_bank; a
+        bank with several environments' unsorted labels or too few rows for prepared forms is refused (NWHipError).
+
+        What follows the refresh: predict('full') (with leave_out too), forward_bank and predict_loo; get_neighbors and
+        explain over the bank; the 'knn' / 'hnsw' / 'random' modes, which read the same tensor.  What does not: the cluster
+        centroids and the per-environment copies of 'ensemble' keep precompute()'s features until it runs again."""
+        what = "refresh_bank"
+        if feats is None:
+            feats, self.bank_features = getattr(self, 'bank_features', None), None
+            if feats is None:
+                raise ops.NWHipError(f"{what}: no features to write: call forward_bank first, or pass feats")
+        sfeat, _sy, cache = self._resident_bank(what, feats.device)
+        cache.update_rows(sfeat, torch.as_tensor(rows, device=sfeat.device), feats.detach(), momentum)
 
     def predict_loo(self, rows=None, batch_size=256):
         """Not in the reference: leave-one-out log-probabilities of the bank's own rows, (len(rows), n_classes) -- row i of

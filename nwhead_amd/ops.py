@@ -488,7 +488,10 @@ class SplitBank:
     * searches, rounded (nw_knn(rounded=True); _resolve_scores): only fp16-packed rows without a class-sorted copy; the
       queries are padded to the bank's width like everywhere else.
     * run tables (build_tables): named in the call's options only when its labels are the tensor the tables were built
-      from, unmodified; n_classes must then exceed every label of the tables."""
+      from, unmodified; n_classes must then exceed every label of the tables.
+
+    The bank's tensors are written again only by ``update_rows``, which replaces rows of the support and of every prepared
+    form in place and keeps the bank matching its tensor."""
 
     def __init__(self, s, labels=None, precision="fp32"):
         if precision not in ("fp32", "fp16"):
@@ -545,8 +548,57 @@ class SplitBank:
         self.tables = self._tables_src = None
         self.tables_label_max = -1
         self._opts, self._zero_labels = {}, None
+        self.writes = 0        # update_rows calls so far (an autograd node that reads the bank in its backward checks it)
         if labels is not None and labels.dim() == 1 and self.has_operand_rows:
             self.build_tables(self.sorted_labels if self.sorted_labels is not None else labels)
+
+    def update_rows(self, support, rows, x, momentum=0.0):
+        """Replace rows of the bank IN PLACE (nw_bank_update_rows_f32, one launch): ``support`` -- the tensor this bank was
+        prepared from -- gets ``x[i]`` in row ``rows[i]``, or with ``momentum`` in (0, 1) the blend
+        ``momentum * old + (1 - momentum) * x[i]`` (every operation rounded in fp32), and every prepared form of those rows
+        (fp32 rows of a padded bank, split rows and scales, norms, fp16-packed rows with their scales and norms) is left
+        bit for bit as ``SplitBank(support, labels, precision)`` would build it from the updated tensor.  No other row is
+        read or written, nothing is sorted, no host synchronisation; the labels, the run tables and the cached call options
+        stay as they are (the labels of the rows do not change).
+
+        rows: (R,) integer tensor on the device, R <= 16384; x: (R, support.shape[1]).  A row that is negative (the -1 of
+        ``leave_out``) or past the bank is skipped; of several items naming one row the LAST wins and the others take no
+        part.  The bank still ``matches(support)`` afterwards; ``support``'s in-place version is bumped, so autograd refuses
+        a backward through a graph that saved it, and ``writes`` counts the call, which nw_head_bank's backward checks (it
+        recomputes the scores from the bank).  Refused with NWHipError (bank_update_refusal): a bank built from unsorted
+        labels, a norms-only bank, another feature width, R > 16384."""
+        if not 0.0 <= float(momentum) < 1.0:
+            raise ValueError(f"SplitBank.update_rows: momentum must be in [0, 1), got {momentum}")
+        if not self.matches(support):
+            raise ValueError("SplitBank.update_rows: `support` must be the tensor this bank was prepared from, unmodified since")
+        _need_hip(support, rows, x)
+        if x.dim() != 2 or rows.dim() != 1 or rows.shape[0] != x.shape[0] or rows.is_floating_point() or rows.dtype == torch.bool:
+            raise ValueError("SplitBank.update_rows: rows is an (R,) integer tensor and x the (R, width) new rows")
+        if support.dtype != torch.float32 or not support.is_contiguous():
+            raise ValueError("SplitBank.update_rows writes into `support`: it must be a contiguous fp32 tensor")
+        why = bank_update_refusal(split=self.split is not None, packed=self.packed is not None,
+                                  sorted_copy=self.sorted_rows is not None, shape=self.shape, pad=self.pad, width=x.shape[1],
+                                  R=x.shape[0])
+        if why is not None:
+            raise NWHipError(f"SplitBank.update_rows: {why}")
+        xc = _f32c(x)
+        if xc.untyped_storage().data_ptr() == support.untyped_storage().data_ptr():
+            xc = xc.clone()            # (rows of the bank itself, e.g. support[perm]: read while they are written)
+        rc = rows.detach()
+        rc = rc if (rc.dtype == torch.int64 and rc.is_contiguous()) else rc.to(torch.int64).contiguous()
+        N, d = self.shape
+        padded = self.rows is not None
+        s_rows = self.rows if padded else support.detach()
+        with _OnDevice(support.device):
+            _lib.check(_lib.load().nw_bank_update_rows_f32(
+                _ptr(xc), _ptr(rc), xc.shape[0], xc.shape[1], float(momentum), _ptr(s_rows),
+                _ptr(support.detach()) if padded else None, _ptr(self.norm2), _ptr(self.split), _ptr(self.scale),
+                _ptr(self.packed), _ptr(self.packed_scale), _ptr(self.packed_norm2), N, d, _stream(support)),
+                "nw_bank_update_rows_f32")
+        if not support.is_inference():
+            torch.autograd.graph.increment_version(support)
+        self._src = _sig(support)
+        self.writes += 1
 
     @property
     def has_operand_rows(self):
@@ -725,7 +777,8 @@ class _NWHeadFn(torch.autograd.Function):
         if need_bwd:
             ctx.save_for_backward(qc, sc, syc, scores, lse, out, ls if ls is not None else torch.empty(0, device=dev))
             ctx.meta = (B, N, d, n_classes, kind_id, sup_b, lab_b, ls is not None)
-            # the bank of these supports, if there is one (a SplitBank's tensors are never written again)
+            # the bank of these supports, if there is one (SplitBank.update_rows writes it in place, but bumps the version
+            # of the support saved above: autograd then refuses this backward)
             ctx.bank = (sn2, ssplit, sscale) if (ssplit is not None and not sup_b) else (None, None, None)
         if want_weights:
             ctx.mark_non_differentiable(weights)
@@ -889,14 +942,33 @@ def head_bank_route(*, split, sorted_copy, shape, pad, width, B, n_classes):
                                         n_classes=n_classes) is None else "matrix"
 
 
+BANK_UPDATE_MAX_ROWS = 16384     # nw_bank_update_rows_f32: every wave scans the rest of `rows` for its own row
+
+
+def bank_update_refusal(*, split, packed, sorted_copy, shape, pad, width, R):
+    """Why ``SplitBank.update_rows`` cannot write R new rows of ``width`` columns into a prepared bank, over the plain
+    facts of the bank -- a sentence for the error text, or None when it can: the bank's rows are the caller's (no
+    class-sorted copy), it holds ``split`` or fp16-``packed`` rows, the new rows pad to its width and R is within the kernel's."""
+    N, d = shape
+    if sorted_copy:
+        return "the bank was built from unsorted labels and keeps a class-sorted copy, whose rows are not the caller's"
+    if not (split or packed):
+        return "a norms-only bank holds no prepared rows to refresh (build a new ops.SplitBank)"
+    if width + pad != d:
+        return f"new rows of width {width} do not pad to the bank's width {d}"
+    if R > BANK_UPDATE_MAX_ROWS:
+        return f"{R} rows in one call are above {BANK_UPDATE_MAX_ROWS}"
+    return None
+
+
 class _NWHeadBankFn(torch.autograd.Function):
     """autograd node of nw_head_bank: today's inference call forward, nw_bwd_query_f32 backward.  Saves the queries, lse,
     out and the window: nothing of size B x N."""
 
     @staticmethod
-    def forward(ctx, q, logit_scale, call, n_classes, kind_id, window, exclude):
+    def forward(ctx, q, logit_scale, call, n_classes, kind_id, window, exclude, bank=None):
         """``call``: the _Call nw_head_bank resolved (``q`` is its queries, an argument of its own for autograd);
-        ``window``: None or (lo, hi) int32."""
+        ``window``: None or (lo, hi) int32; ``bank``: the SplitBank the call reads, whose ``writes`` the backward checks."""
         _, sc, syc, sn2, ssplit, sscale, opts = call
         lib = _lib.load()
         qc = _f32c(q)
@@ -918,7 +990,9 @@ class _NWHeadBankFn(torch.autograd.Function):
                                                  int(exclude), _ptr(out), _ptr(lse), _ptr(ws), ws_bytes, B, N, d, n_classes,
                                                  kind_id, _ptr(ls), st), "nw_fwd_window_f32")
         ctx.save_for_backward(qc, lse, out, *([ls] if ls is not None else []), *([lo, hi] if window is not None else []))
-        ctx.bank = (ssplit, sscale, sn2, syc)      # a SplitBank's tensors are never written again
+        # the backward recomputes the scores from these: SplitBank.update_rows writes them in place and counts in `writes`
+        ctx.bank = (ssplit, sscale, sn2, syc)
+        ctx.bank_writes = (bank, bank.writes) if bank is not None else None
         ctx.meta = (B, N, d, n_classes, kind_id, ls is not None, window is not None, int(exclude))
         return out
 
@@ -932,6 +1006,9 @@ class _NWHeadBankFn(torch.autograd.Function):
         ls = saved[3] if has_ls else None
         lo, hi = saved[-2:] if windowed else (None, None)
         ssplit, sscale, sn2, syc = ctx.bank
+        if ctx.bank_writes is not None and ctx.bank_writes[0].writes != ctx.bank_writes[1]:
+            raise RuntimeError("nw_head_bank: the bank was written (SplitBank.update_rows) between this forward and its "
+                               "backward, which recomputes the scores from the bank: call backward() first, then update")
         dev = qc.device
         g = _f32c(gout)
         gq = torch.empty_like(qc)
@@ -942,7 +1019,7 @@ class _NWHeadBankFn(torch.autograd.Function):
             _lib.check(lib.nw_bwd_query_f32(_ptr(qc), _ptr(ssplit), _ptr(sscale), _ptr(sn2), _ptr(syc), _ptr(lo), _ptr(hi), exclude,
                                             _ptr(lse), _ptr(out), _ptr(g), _ptr(gq), _ptr(gls), _ptr(ws), ws_bytes, B, N, d, C,
                                             kind_id, _ptr(ls), 0, _stream(qc)), "nw_bwd_query_f32")
-        return gq, gls, None, None, None, None, None
+        return gq, gls, None, None, None, None, None, None
 
 
 def nw_head_bank(q, s, sy, n_classes, bank, kind="euclidean", logit_scale=None, row_window=None, exclude=False):
@@ -988,7 +1065,7 @@ def nw_head_bank(q, s, sy, n_classes, bank, kind="euclidean", logit_scale=None, 
         syc = sy if (sy.dtype == torch.int64 and sy.is_contiguous()) else sy.detach().to(torch.int64).contiguous()
         call = call._replace(sy=syc)
         window = tuple(_row_window(row_window, q.shape[0], q.device))
-    out = _NWHeadBankFn.apply(call.q, logit_scale, call, C, kid, window, bool(exclude))
+    out = _NWHeadBankFn.apply(call.q, logit_scale, call, C, kid, window, bool(exclude), bank)
     return out
 
 

@@ -5,6 +5,7 @@ surface and reproducing its epoch order (train.py:287-303):
 
     eval():  precompute() -> predict(mode) over the validation set for random, full, cluster
     train(): network(img, label) -> NLLLoss -> backward -> SGD(momentum 0.9, nesterov, weight decay)
+             (--train_type bank: forward_bank(img, leave_out=row) over the resident bank instead, then refresh_bank(row))
     MultiStepLR.step(), checkpoint every `log_interval` epochs (+ model.best.h5 by 'full' accuracy)
 
 and its per-step result dictionary (train.py:400-422: loss, acc in percent, batch_size, prob, gt).
@@ -77,6 +78,11 @@ def make_parser():
     p.add_argument("--n_shot", type=int, default=1)
     p.add_argument("--n_way", type=int, default=None)
     p.add_argument("--freeze_featurizer", action="store_true")
+    p.add_argument("--train_type", default="random", choices=("random", "bank"),
+                   help="random: a sampled support per step (the reference's loop); bank: memory-bank training -- every step is "
+                        "a leave-one-out prediction of bank samples over the resident bank, whose rows are then refreshed")
+    p.add_argument("--bank_momentum", type=float, default=0.5,
+                   help="--train_type bank: a refreshed row is bank_momentum * old + (1 - bank_momentum) * new features")
     p.add_argument("--resume", action="store_true", help="continue from the newest checkpoint of this run")
     p.add_argument("--no_fold_bn", action="store_true",
                    help="evaluate with the training featurizer instead of its folded inference copy (model.fold_batchnorm)")
@@ -86,6 +92,20 @@ def make_parser():
     p.add_argument("--synthetic_size", type=int, default=32)
     p.add_argument("--synthetic_noise", type=float, default=0.35)
     return p
+
+
+class BankRows(torch.utils.data.Dataset):
+    """The samples of a resident bank with their bank row: (img, label, row) in the row order of precompute()."""
+
+    def __init__(self, full_dataset):
+        self.ds = full_dataset
+
+    def __len__(self):
+        return len(self.ds)
+
+    def __getitem__(self, i):
+        img, label = self.ds[i][:2]
+        return img, label, i
 
 
 class Trainer:
@@ -122,6 +142,14 @@ class Trainer:
                              proj_dim=args.proj_dim, kernel_type=args.kernel_type, n_shot=args.n_shot,
                              n_way=args.n_way, device=str(self.device)).to(self.device)
         self.network.enable_bn_folding(not args.no_fold_bn)   # precompute()/predict() in the eval epochs
+        if args.train_type == "bank":
+            # the loader walks the bank's own samples, shuffled; fit() builds the bank (precompute()) before every epoch
+            from .ops import bank_update_refusal
+            envs = self.network.support_eval.full_datasets
+            if len(envs) != 1:
+                raise ValueError("--train_type bank: " + bank_update_refusal(
+                    split=True, packed=False, sorted_copy=True, shape=(0, feat_dim), pad=0, width=feat_dim, R=0))
+            self.train_loader = loader(BankRows(envs[0]), batch_size=args.batch_size, shuffle=True, num_workers=args.workers)
         self.criterion = nn.NLLLoss()
         # the reference's optimizer (train.py:243-247); on the GPU the same update in nw_sgd_step_f32 (optim.SGD: all parameter
         # tensors in a few launches, 0.05 ms for DenseNet-121 where torch's foreach kernels take 0.91 and its fused ones 0.34)
@@ -146,15 +174,21 @@ class Trainer:
 
     # ------------------------------------------------------------------ one step
     def nw_step(self, batch, is_train=True, mode="random"):
-        img, label = batch
+        img, label = batch[:2]
         img, label = img.float().to(self.device), label.to(self.device)
+        row = batch[2].to(self.device) if is_train and self.args.train_type == "bank" else None
         self.optimizer.zero_grad()
         with torch.set_grad_enabled(is_train):
-            output = self.network(img, label) if is_train else self.network.predict(img, mode)
+            if row is not None:
+                output = self.network.forward_bank(img, leave_out=row)
+            else:
+                output = self.network(img, label) if is_train else self.network.predict(img, mode)
             loss = self.criterion(output, label)
             if is_train:
                 loss.backward()
                 self.optimizer.step()
+                if row is not None:       # the batch's features, as this step's forward computed them, back into their rows
+                    self.network.refresh_bank(row, momentum=self.args.bank_momentum)
             acc = metric.acc(output.argmax(-1), label)
         return {"loss": loss.detach().cpu().numpy(), "acc": acc * 100, "batch_size": len(img),
                 "prob": output.detach().exp(), "gt": label}
