@@ -396,6 +396,41 @@ int nw_bwd_query_f32(const float *q, const float *s_split, const float *s_scale,
                      float *gq, float *glogit_scale, void *workspace, size_t workspace_bytes,
                      int64_t B, int64_t N, int64_t d, int64_t C, int kind, const float *logit_scale_dev,
                      int row_chunks, void *stream);
+/* SUPPORT WEIGHTS: the head with a prior weight w_j per bank row,
+ *   out[b,c] = log( sum_{j admitted, sy_j = c} w_j exp(score_bj) / sum_{j admitted} w_j exp(score_bj) + 1e-12 ),
+ * i.e. nw_fwd_window_f32 over the scores score_bj + a_j, a_j = log w_j: soft deletion and non-contiguous subsets of a live
+ * bank (a_j = -inf removes row j from numerator and denominator alike), a flat class prior over an unbalanced bank
+ * (a_j = -log n_class(j)), importance weights.  The weight is added in the tile epilogue, before the masks and the tile
+ * maximum: no (B,N) matrix, and the maximum is that of the weighted scores.
+ *   row_logw  (N,) fp32 on the device, required, 16-byte aligned: natural-log weights in the units of the scores.  Every
+ *             value is finite or -inf.  NaN, +inf and magnitudes whose base-2 form (a * log2 e) overflows fp32 are outside
+ *             the contract: the result for the queries that admit such a row is undefined, but nothing faults -- the value
+ *             is never used as an address, and the library makes no device-side check and no synchronisation.
+ *   row_lo / row_hi  both NULL (no window) or both set, with `exclude`, as in nw_fwd_window_f32 (exclude is ignored
+ *             without a window).
+ *   lse_out   optional (B,): log sum_{admitted} exp(score + a).
+ * A DEAD query -- every admitted row has a = -inf, or the window is empty -- gets out = log(1e-12) in every class and
+ * lse = -inf; no NaN anywhere.  With a = 0 everywhere the result is nw_fwd_window_f32's bit for bit.
+ * Everything else -- operands, regime, alignment, tile height and raw-or-split-queries rule, workspace
+ * (nw_fwd_workspace_bytes), status codes, refusals before anything is launched -- is nw_fwd_window_f32's; row_logw NULL
+ * or one of row_lo / row_hi alone: NW_ERR_INVALID_ARG. */
+int nw_fwd_weighted_f32(const float *q, const float *s_split, const float *s_scale, const float *s_norm2,
+                        const int64_t *sy, const float *row_logw,
+                        const int32_t *row_lo, const int32_t *row_hi, int exclude,
+                        float *out, float *lse_out, void *workspace, size_t workspace_bytes,
+                        int64_t B, int64_t N, int64_t d, int64_t C, int kind, const float *logit_scale_dev, void *stream);
+/* nw_bwd_query_f32 for the weighted head: lse and out are nw_fwd_weighted_f32's for the same operands, weights and window.
+ * The weights are a CONSTANT: there is no gradient with respect to row_logw.  They enter the softmax weight
+ * W = exp(score + a - lse) only; the derivative of the score with respect to the query is taken at the raw score.  A dead
+ * query (lse = -inf) gets a zero row of gq.  With a = 0 everywhere the result is nw_bwd_query_f32's bit for bit.
+ * Regime, workspace (nw_bwd_query_workspace_bytes), row_chunks and status codes are nw_bwd_query_f32's; row_logw as above. */
+int nw_bwd_query_weighted_f32(const float *q, const float *s_split, const float *s_scale, const float *s_norm2,
+                              const int64_t *sy, const float *row_logw,
+                              const int32_t *row_lo, const int32_t *row_hi, int exclude,
+                              const float *lse, const float *out, const float *gout,
+                              float *gq, float *glogit_scale, void *workspace, size_t workspace_bytes,
+                              int64_t B, int64_t N, int64_t d, int64_t C, int kind, const float *logit_scale_dev,
+                              int row_chunks, void *stream);
 /* support_influence (util/metric.py:23-50) of k SELECTED supports per query, from the head's own outputs:
  *   vals (B,k) fp32 raw scores and rows (B,k) int64 bank rows (a search's val_out / idx_out),
  *   sy (N,) int64, qy (B,) int64, out (B,C) log-probabilities and lse (B,) of nw_fwd_f32 over the same bank;

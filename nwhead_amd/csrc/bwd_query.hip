@@ -1,9 +1,11 @@
 // bwd_query.hip -- gradient of the head w.r.t. the queries over a resident split bank, without a (B,N) matrix
-// (gfx950 / MI355X only; nw_bwd_query_f32).
+// (gfx950 / MI355X only; nw_bwd_query_f32, nw_bwd_query_weighted_f32).
 //
 // backward.hip's closed form with the bank a constant.  For query b, bank row j, score s_bj = f(dot, |q_b|^2, |s_j|^2):
 //     dP_c = g_bc exp(-out_bc)                 dW_j = dP[y_j]  (0 for a label outside [0, C))
 //     W_j  = exp(s_bj - lse_b) for a row the window admits, 0 otherwise
+//            (row weights, WGT: exp(s_bj + a_j - lse_b), lse and out those of the weighted forward.  The weights are a
+//            constant: only W carries a_j, the derivatives df/d. below are taken at the raw score s_bj)
 //     t_b  = sum_j W_j dW_j                    dS_j = W_j (dW_j - t_b)
 //     A_bj = dS_j df/ddot     rq_b = sum_j dS_j df/d|q|^2     gls = sum_bj dS_j df/dlogit_scale   (bwd_coeff.h)
 //     gq_b = sum_j A_bj s_j + 2 rq_b q_b
@@ -49,9 +51,10 @@ typedef _Float16 halfx4 __attribute__((ext_vector_type(4)));
 constexpr int QRS = 4;            // support blocks per tile
 constexpr int QBS = 16 * QRS;     // 64 bank rows per tile
 constexpr int Q_HDR = (3 * BQ + 3 * QBS) * 4;   // qn2[BQ] | qsc[BQ] | fac[BQ] | sn2[QBS] | ssc[QBS] | lab[QBS]
-static_assert(Q_HDR % 16 == 0, "stage buffers must stay 16-byte aligned");
-constexpr size_t Q_LDS = Q_HDR + DmaCfg<QRS>::STAGE_BYTES;
-static_assert(Q_LDS <= 160 * 1024, "header + ring exceed LDS");
+constexpr int Q_HDR_W = Q_HDR + QBS * 4;        // ... | law[QBS]: the tile's row log-weights (the weighted kernels only)
+static_assert(Q_HDR % 16 == 0 && Q_HDR_W % 16 == 0, "stage buffers must stay 16-byte aligned");
+constexpr size_t Q_LDS = Q_HDR + DmaCfg<QRS>::STAGE_BYTES, Q_LDS_W = Q_HDR_W + DmaCfg<QRS>::STAGE_BYTES;
+static_assert(Q_LDS_W <= 160 * 1024, "header + ring exceed LDS");
 // the second product's ring (over the forward's, dead by then): 64 rows x 128 B per stage
 constexpr int Q2_STAGE = QBS * 128, Q2_NBUF = 4, Q2_NI = QBS / 8 / NLOAD;
 static_assert((size_t)Q2_NBUF * Q2_STAGE <= DmaCfg<QRS>::STAGE_BYTES, "second ring inside the first");
@@ -68,7 +71,7 @@ struct BwdQueryArgs {
     const float *q, *s, *s_scale, *s_norm2;
     const int64_t* sy;
     const int *win_lo, *win_hi;
-    const float *lse, *logit_scale;
+    const float *lse, *logit_scale, *row_logw;
     BwdQueryWs ws;
     int exclude, B, N, d, C, n_stiles, n_qtiles, nslabs, nchunks, tpc;
 };
@@ -94,9 +97,11 @@ __global__ __launch_bounds__(256) void nw_bwd_query_prologue_kernel(const float*
     if (threadIdx.x == 0) tb[b] = t;
 }
 
-template <int KIND, int NCH>
+// WGT: a.row_logw holds a natural-log weight per bank row, staged per tile beside the labels (a fourth header array).
+template <int KIND, int NCH, bool WGT>
 __global__ __launch_bounds__(TILE_THREADS, 2) void nw_bwd_query_kernel(const BwdQueryArgs a) {
     constexpr bool NEED_NORM = (KIND != NW_SCORE_DOT);
+    constexpr int HDR = WGT ? Q_HDR_W : Q_HDR;
     constexpr float L2E = 1.44269504088896340736f, LN2 = 0.693147180559945309417f;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     float* qn2 = reinterpret_cast<float*>(smem);
@@ -105,8 +110,9 @@ __global__ __launch_bounds__(TILE_THREADS, 2) void nw_bwd_query_kernel(const Bwd
     float* sn2 = fac_s + BQ;
     float* ssc = sn2 + QBS;
     int* lab = reinterpret_cast<int*>(ssc + QBS);
-    float4* stage = reinterpret_cast<float4*>(smem + Q_HDR);
-    const char* ring2 = smem + Q_HDR;
+    float* law = reinterpret_cast<float*>(lab + QBS);   // (WGT only)
+    float4* stage = reinterpret_cast<float4*>(smem + HDR);
+    const char* ring2 = smem + HDR;
 
     const int B = a.B, N = a.N, d = a.d;
     const int tid = threadIdx.x, lane = tid & 63, i = lane & 15, g = lane >> 4;
@@ -160,6 +166,7 @@ __global__ __launch_bounds__(TILE_THREADS, 2) void nw_bwd_query_kernel(const Bwd
             ssc[t] = a.s_scale[j];
             const int64_t y = a.sy[j];
             lab[t] = ((uint64_t)y < (uint64_t)a.C) ? (int)y : -1;
+            if constexpr (WGT) law[t] = a.row_logw[j];
         }
         f32x4 acc[QRS];
         tile_dots_f16x2<QRS, true>(a.q, a.s, B, N, d, q0, s0, stage, acc, st % nk, qn2, qsc_s);
@@ -195,12 +202,17 @@ __global__ __launch_bounds__(TILE_THREADS, 2) void nw_bwd_query_kernel(const Bwd
                     if (NEED_NORM) n4 = *reinterpret_cast<const float4*>(sn2 + 16 * r + 4 * g);
                     const float4 s4 = *reinterpret_cast<const float4*>(ssc + 16 * r + 4 * g);
                     const float nn[4] = {n4.x, n4.y, n4.z, n4.w}, ss[4] = {s4.x, s4.y, s4.z, s4.w};
+                    float4 a4 = make_float4(0.f, 0.f, 0.f, 0.f);
+                    if constexpr (WGT) a4 = *reinterpret_cast<const float4*>(law + 16 * r + 4 * g);
+                    const float aw[4] = {a4.x, a4.y, a4.z, a4.w};
 #pragma unroll
                     for (int e = 0; e < 4; ++e) {
                         float K, Base;
                         SF::support(nn[e], ss[e], K, Base);
                         const float u = SF::finish(__builtin_fmaf(acc[r][e], K * Cq, Base + Bq));   // base-2 units, as the forward
-                        float W = __builtin_amdgcn_exp2f(u - lsev);
+                        // the weighted score (the forward's fused multiply-add) goes into W alone: bwd_pair_coeff below takes
+                        // the raw score, whose distance the kind's derivative is a function of
+                        float W = __builtin_amdgcn_exp2f((WGT ? __builtin_fmaf(aw[e], L2E, u) : u) - lsev);
                         if (check) {
                             const int t = 16 * r + e;
                             bool keep = s0 + 4 * g + t < N;
@@ -292,7 +304,7 @@ __global__ __launch_bounds__(TILE_THREADS, 2) void nw_bwd_query_kernel(const Bwd
             }
             const char* sb = reinterpret_cast<const char*>(a.s + (size_t)s0 * d) + (size_t)kc0 * BK * 4;
             auto issue = [&](int c) {
-                char* buf = smem + Q_HDR + (c % Q2_NBUF) * Q2_STAGE;
+                char* buf = smem + HDR + (c % Q2_NBUF) * Q2_STAGE;
 #pragma unroll
                 for (int m = 0; m < Q2_NI; ++m)
                     __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(sb + (size_t)c * BK * 4 + voff[m]),
@@ -422,17 +434,19 @@ size_t bwd_query_layout(int64_t B, int64_t d, int64_t C, const BwdQueryPlan& p, 
     return off;
 }
 
-template <int KIND, int NCH>
+template <int KIND, int NCH, bool WGT>
 int launch_bwd_query_kernel(const BwdQueryArgs& a, unsigned grid, hipStream_t st) {
-    static const bool attr = hipFuncSetAttribute(reinterpret_cast<const void*>(nw_bwd_query_kernel<KIND, NCH>),
-                                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)Q_LDS) == hipSuccess;
+    constexpr size_t LDS = WGT ? Q_LDS_W : Q_LDS;
+    static const bool attr = hipFuncSetAttribute(reinterpret_cast<const void*>(nw_bwd_query_kernel<KIND, NCH, WGT>),
+                                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS) == hipSuccess;
     if (!attr) return NW_ERR_LAUNCH;
-    hipLaunchKernelGGL((nw_bwd_query_kernel<KIND, NCH>), dim3(grid), dim3(TILE_THREADS), Q_LDS, st, a);
+    hipLaunchKernelGGL((nw_bwd_query_kernel<KIND, NCH, WGT>), dim3(grid), dim3(TILE_THREADS), LDS, st, a);
     return NW_OK;
 }
 template <int KIND>
 int launch_bwd_query_kind(const BwdQueryArgs& a, int nch, unsigned grid, hipStream_t st) {
-    return nch == 8 ? launch_bwd_query_kernel<KIND, 8>(a, grid, st) : launch_bwd_query_kernel<KIND, 4>(a, grid, st);
+    if (a.row_logw) return nch == 8 ? launch_bwd_query_kernel<KIND, 8, true>(a, grid, st) : launch_bwd_query_kernel<KIND, 4, true>(a, grid, st);
+    return nch == 8 ? launch_bwd_query_kernel<KIND, 8, false>(a, grid, st) : launch_bwd_query_kernel<KIND, 4, false>(a, grid, st);
 }
 
 }  // namespace
@@ -456,7 +470,7 @@ int launch_bwd_query(const BwdQueryCall& c) {
     const int64_t wgs = (int64_t)p.n_qtiles * p.nslabs * p.nchunks;
     if (wgs > 0x7fffffffLL || (c.B * c.d / 4 + 255) / 256 > 0x7fffffffLL) return NW_ERR_UNSUPPORTED;
     hipLaunchKernelGGL(nw_bwd_query_prologue_kernel, dim3((unsigned)c.B), dim3(256), 0, st, c.out, c.gout, ws.dptab, ws.tb, c.C);
-    const BwdQueryArgs a = {c.q, c.s_split, c.s_scale, c.s_norm2, c.sy, c.row_lo, c.row_hi, c.lse, c.logit_scale_dev, ws,
+    const BwdQueryArgs a = {c.q, c.s_split, c.s_scale, c.s_norm2, c.sy, c.row_lo, c.row_hi, c.lse, c.logit_scale_dev, c.row_logw, ws,
                             c.exclude, (int)c.B, (int)c.N, (int)c.d, (int)c.C, p.n_stiles, p.n_qtiles, p.nslabs, p.nchunks, p.tpc};
     int rc;
     switch (c.kind) {

@@ -287,6 +287,54 @@ extern "C" int nw_bwd_query_f32(const float* q, const float* s_split, const floa
                                  static_cast<hipStream_t>(stream)});
 }
 
+// The head and its query gradient with a log-weight per bank row (fused.hip OUT_WGT, bwd_query.hip WGT): the regimes,
+// workspaces and status codes of nw_fwd_window_f32 / nw_bwd_query_f32, the window optional in both.  row_logw is read in
+// float4s from row offsets that are multiples of four: it must be 16-byte aligned like the other operands.
+extern "C" int nw_fwd_weighted_f32(const float* q, const float* s_split, const float* s_scale, const float* s_norm2,
+                                   const int64_t* sy, const float* row_logw, const int32_t* row_lo, const int32_t* row_hi,
+                                   int exclude, float* out, float* lse_out, void* workspace, size_t workspace_bytes, int64_t B,
+                                   int64_t N, int64_t d, int64_t C, int kind, const float* logit_scale_dev, void* stream) {
+    if (B < 0 || N < 0 || d < 0 || C < 0) return NW_ERR_INVALID_ARG;
+    if ((row_lo != nullptr) != (row_hi != nullptr)) return NW_ERR_INVALID_ARG;
+    if (bad_kind(kind)) return NW_ERR_UNSUPPORTED;
+    if (N <= 25 || C < 1 || d < 32 || d % 32 != 0 || d > (1 << 20)) return NW_ERR_UNSUPPORTED;
+    if (B == 0) return NW_OK;
+    if (!q || !s_split || !s_scale || !s_norm2 || !sy || !row_logw || !out) return NW_ERR_INVALID_ARG;
+    if (kind == NW_SCORE_CLIP && !logit_scale_dev) return NW_ERR_INVALID_ARG;
+    if (!nw::fused_eligible(q, s_split, B, N, d, C)) return NW_ERR_UNSUPPORTED;   // alignment, sizes past the tile kernels
+    if (reinterpret_cast<uintptr_t>(row_logw) & 15) return NW_ERR_UNSUPPORTED;
+    const nw::FwdLayout L = nw::fwd_layout(B, N, d, C, workspace);
+    if (!L.fits(workspace_bytes)) return NW_ERR_WORKSPACE;
+    if (reinterpret_cast<uintptr_t>(workspace) & 15) return NW_ERR_UNSUPPORTED;
+    nw::FusedArgs a = {q, s_split, sy, s_norm2, s_scale, logit_scale_dev, out, nullptr, lse_out, nullptr, nullptr, nullptr,
+                       &L, (int)B, (int)N, (int)d, (int)C, static_cast<hipStream_t>(stream), nullptr,
+                       row_lo, row_hi, row_lo && exclude != 0, row_logw};
+    return nw::launch_fused(a, nw::FORM_SPLIT, kind);
+}
+
+extern "C" int nw_bwd_query_weighted_f32(const float* q, const float* s_split, const float* s_scale, const float* s_norm2,
+                                         const int64_t* sy, const float* row_logw, const int32_t* row_lo, const int32_t* row_hi,
+                                         int exclude, const float* lse, const float* out, const float* gout, float* gq,
+                                         float* glogit_scale, void* workspace, size_t workspace_bytes, int64_t B, int64_t N,
+                                         int64_t d, int64_t C, int kind, const float* logit_scale_dev, int row_chunks,
+                                         void* stream) {
+    if (B < 0 || N < 0 || d < 0 || C < 0 || row_chunks < 0) return NW_ERR_INVALID_ARG;
+    if ((row_lo != nullptr) != (row_hi != nullptr)) return NW_ERR_INVALID_ARG;
+    if (bad_kind(kind)) return NW_ERR_UNSUPPORTED;
+    if (!nw::bwd_query_shape_ok(B, N, d, C)) return NW_ERR_UNSUPPORTED;
+    if (B == 0) return NW_OK;
+    if (!q || !s_split || !s_scale || !s_norm2 || !sy || !row_logw || !lse || !out || !gout || !gq) return NW_ERR_INVALID_ARG;
+    if (kind == NW_SCORE_CLIP && !logit_scale_dev) return NW_ERR_INVALID_ARG;
+    if ((reinterpret_cast<uintptr_t>(q) | reinterpret_cast<uintptr_t>(s_split) | reinterpret_cast<uintptr_t>(gq) |
+         reinterpret_cast<uintptr_t>(row_logw)) & 15)
+        return NW_ERR_UNSUPPORTED;
+    if (!workspace || workspace_bytes < nw::bwd_query_workspace_bytes(B, N, d, C, row_chunks)) return NW_ERR_WORKSPACE;
+    if (reinterpret_cast<uintptr_t>(workspace) & 15) return NW_ERR_UNSUPPORTED;
+    return nw::launch_bwd_query({q, s_split, s_scale, s_norm2, sy, row_lo, row_hi, exclude, lse, out, gout, gq, glogit_scale,
+                                 workspace, workspace_bytes, B, N, d, C, kind, logit_scale_dev, row_chunks,
+                                 static_cast<hipStream_t>(stream), row_logw});
+}
+
 extern "C" int nw_fwd_partial_f32(const float* q, const float* s, const int64_t* sy,
                                   const float* s_norm2, const float* s_split, const float* s_scale,
                                   float* m, float* den, float* num, void* workspace, size_t workspace_bytes,

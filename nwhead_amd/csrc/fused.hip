@@ -631,8 +631,9 @@ FusedPlan plan_fused(int64_t B, int64_t N, int64_t d, int64_t C, int form, int o
     if (out == OUT_CAND && split && p.rs == 12) return refuse(NW_ERR_UNSUPPORTED);
     // the windowed head: split rows on nw_fused_kernel only (p.persistent above asks for OUT_NONE: never the persistent
     // kernels, so never run tables either), at the tile heights of the candidate form
-    if (out == OUT_WIN && form == FORM_F32) return refuse(NW_ERR_INVALID_ARG);
-    if (out == OUT_WIN && p.rs == 12) return refuse(NW_ERR_UNSUPPORTED);
+    // (OUT_WGT, the same with row weights: the same plan)
+    if (out_is_win(out) && form == FORM_F32) return refuse(NW_ERR_INVALID_ARG);
+    if (out_is_win(out) && p.rs == 12) return refuse(NW_ERR_UNSUPPORTED);
     if (p.persistent) {
         p.mode = MODE_F16;
         p.split_queries = true;
@@ -715,7 +716,7 @@ bool fused_eligible(const float* q, const float* s, int64_t B, int64_t N, int64_
 }
 
 int launch_fused(const FusedArgs& a, int form, int kind) {
-    const int out = a.cand ? OUT_CAND : (a.win_lo && a.win_hi) ? OUT_WIN : a.scores ? OUT_SCORES : OUT_NONE;
+    const int out = a.cand ? OUT_CAND : a.row_logw ? OUT_WGT : (a.win_lo && a.win_hi) ? OUT_WIN : a.scores ? OUT_SCORES : OUT_NONE;
     const FusedPlan p = plan_fused(a.B, a.N, a.d, a.C, form, out, a.cand ? a.cand->k : 0, a.s_norm2 != nullptr,
                                    kind == NW_SCORE_DOT, 0, fwd_opts());
 #define NW_KIND_CASE(K) case K: return launch_fused_kind<K>(a, p);

@@ -198,6 +198,29 @@ __device__ __forceinline__ void tile_candidates(const float (&sc)[RS][4], unsign
     }
 }
 
+// The head's row window on the scores of one tile (OUT_WIN, OUT_WGT): tile_candidates<RS, true>'s window arithmetic.  Rows
+// that the query's window does not admit leave the softmax like the rows past the bank.  A (query column, tile) pair that the
+// window leaves whole skips the per-element comparisons; lo / hi are clamped and never used as addresses.
+template <int RS>
+__device__ __forceinline__ void window_scores(float (&sc)[RS][4], const int* __restrict__ win_lo, const int* __restrict__ win_hi,
+                                              bool exclude, int b, int B, int N, int s0, int g) {
+    constexpr int BS = 16 * RS;
+    const int bb = b < B ? b : B - 1;
+    const int lo = min(max(win_lo[bb], 0), N), hi = min(max(win_hi[bb], 0), N);
+    const unsigned width = hi > lo ? (unsigned)(hi - lo) : 0u;
+    const int tile_end = s0 + BS < N ? s0 + BS : N;
+    const bool disjoint = width == 0u || hi <= s0 || lo >= tile_end;   // no row of the tile is in the window
+    const bool covered = lo <= s0 && hi >= tile_end;                    // every row of the tile is
+    if (!(exclude ? disjoint : covered)) {
+        const int rel = s0 + 4 * g - lo;   // tile row t = 16r + e of this lane is bank row lo + rel + t
+#pragma unroll
+        for (int r = 0; r < RS; ++r)
+#pragma unroll
+            for (int e = 0; e < 4; ++e)
+                if (((unsigned)(rel + 16 * r + e) < width) == exclude) sc[r][e] = -INFINITY;
+    }
+}
+
 #ifdef NW_DIAG_FUSED   // diagnostic build only (tools/bench_fused.hip): phase stamps go to `scores`
 #define NW_FSTAMP(k) if (threadIdx.x == 0) reinterpret_cast<unsigned long long*>(scores)[8 * blockIdx.x + (k)] = __builtin_amdgcn_s_memtime()
 #else
@@ -209,13 +232,16 @@ __device__ __forceinline__ void tile_candidates(const float (&sc)[RS][4], unsign
 // OUT_CAND_WIN: `ws_nrun` / `ws_m` are CandOut's window arrays besides, loaded in tile_candidates.
 // OUT_WIN: `scores` / `ws_den` are the row window's two arrays (the tile sums go to ws_m + fused_den_after_m), k carries
 // the kernel's C argument (WIN_EXCLUDE); everything else as for OUT_NONE.
+// OUT_WGT: OUT_WIN with `row_logw` (N natural-log weights of the bank rows, read from global memory here, behind the main
+// loop: no register is held across it and the LDS header stays what it is); the window's arrays may both be null.
 template <int RS, int KIND, int OUT, int MODE>
 __device__ __forceinline__ void fused_epilogue(
     f32x4 (&acc)[RS], const float* qn2, const float* sn2, const float* ssc, const int* runid,
     const int* runlab, const int* nrun_s, const float* qsc_s,
     const float* __restrict__ logit_scale, float* __restrict__ scores, float* __restrict__ ws_m,
     float* __restrict__ ws_den, int* __restrict__ ws_nrun, int* __restrict__ ws_lab,
-    float* __restrict__ ws_num, int B, int N, int q0, int s0, int qt, int st, int n_stiles = 0, int k = 0) {
+    float* __restrict__ ws_num, int B, int N, int q0, int s0, int qt, int st, int n_stiles = 0, int k = 0,
+    const float* __restrict__ row_logw = nullptr) {
     constexpr int BS = 16 * RS;
     constexpr bool WRITE_SCORES = OUT == OUT_SCORES;
     constexpr bool NEED_NORM = (KIND != NW_SCORE_DOT);
@@ -236,7 +262,7 @@ __device__ __forceinline__ void fused_epilogue(
     const float qsc = mode_is_f16(MODE) ? qsc_s[qrow] : 1.f;  // 2^-e of this lane's query row (LDS header)
     const bool partial_tile = s0 + BS > N;  // only the last support tile has rows past the bank
     const int *win_lo = nullptr, *win_hi = nullptr;
-    if constexpr (OUT == OUT_WIN) {   // the window's arrays ride in on `scores` / `ws_den`; the tile sums lie behind the maxima
+    if constexpr (out_is_win(OUT)) {   // the window's arrays ride in on `scores` / `ws_den`; the tile sums lie behind the maxima
         win_lo = reinterpret_cast<const int*>(scores);
         win_hi = reinterpret_cast<const int*>(ws_den);
         ws_den = ws_m + fused_den_after_m(n_stiles, B);
@@ -245,6 +271,18 @@ __device__ __forceinline__ void fused_epilogue(
     float sc[RS][4];
     float mloc = -INFINITY;
     if (consumer) {
+        // OUT_WGT: this lane's row weights, requested before the scores are finished.  The addresses of the partial last tile
+        // are clamped to the bank (those scores become -inf below whatever is added to them).
+        float4 lw[OUT == OUT_WGT ? RS : 1];
+        if constexpr (OUT == OUT_WGT) {
+#pragma unroll
+            for (int r = 0; r < RS; ++r) {
+                const int j = s0 + 16 * r + 4 * g;
+                if (!partial_tile) lw[r] = *reinterpret_cast<const float4*>(row_logw + j);
+                else lw[r] = make_float4(row_logw[min(j, N - 1)], row_logw[min(j + 1, N - 1)], row_logw[min(j + 2, N - 1)],
+                                         row_logw[min(j + 3, N - 1)]);
+            }
+        }
         // per-row score factors (nw_internal.h, ScoreFactors): x = acc * K * Cq + (Base + Bq)
         using SF = ScoreFactors<KIND>;
         float Cq, Bq;
@@ -259,7 +297,10 @@ __device__ __forceinline__ void fused_epilogue(
             for (int e = 0; e < 4; ++e) {
                 float K, Base;
                 SF::support(nn[e], ss[e], K, Base);
-                if constexpr (OUT == OUT_CAND_WIN) {
+                if constexpr (OUT == OUT_CAND_WIN || OUT == OUT_WGT) {
+                    // (OUT_WGT: with zero weights the weighted head returns the windowed head's bits, OUT_WIN's, which round
+                    // `Base + Bq` like the kernels without a window do; test_head_weighted_gpu.py holds the two to each other
+                    // at every tile height.)
                     // The windowed search returns nw_knn_f32's scores bit for bit, and in `Base + Bq` those depend on
                     // how the compiler contracts the sum in the kernels without a window: a fused multiply-add for every
                     // element but the lane's last one of the tile, whose product shares a packed multiply with the
@@ -269,6 +310,16 @@ __device__ __forceinline__ void fused_epilogue(
                 } else {
                     sc[r][e] = SF::finish(__builtin_fmaf(acc[r][e], K * Cq, Base + Bq));
                 }
+            }
+        }
+        if constexpr (OUT == OUT_WGT) {
+            // score + a in base-2 units, before every mask and the tile maximum: all of them see the weighted score
+            // (a = -inf: the row leaves numerator and denominator alike)
+#pragma unroll
+            for (int r = 0; r < RS; ++r) {
+                const float aw[4] = {lw[r].x, lw[r].y, lw[r].z, lw[r].w};
+#pragma unroll
+                for (int e = 0; e < 4; ++e) sc[r][e] = __builtin_fmaf(aw[e], L2E, sc[r][e]);
             }
         }
         if (partial_tile) {
@@ -287,25 +338,9 @@ __device__ __forceinline__ void fused_epilogue(
                                       reinterpret_cast<const int*>(ws_m));
             return;
         }
-        if constexpr (OUT == OUT_WIN) {
-            // tile_candidates<RS, true>'s window arithmetic, on the scores: rows that the query's window does not admit leave
-            // the softmax like the rows past the bank.  A (query column, tile) pair that the window leaves whole skips the
-            // per-element comparisons; lo / hi are clamped and never used as addresses.
-            const bool exclude = (k & WIN_EXCLUDE) != 0;
-            const int bb = b < B ? b : B - 1;
-            const int lo = min(max(win_lo[bb], 0), N), hi = min(max(win_hi[bb], 0), N);
-            const unsigned width = hi > lo ? (unsigned)(hi - lo) : 0u;
-            const int tile_end = s0 + BS < N ? s0 + BS : N;
-            const bool disjoint = width == 0u || hi <= s0 || lo >= tile_end;   // no row of the tile is in the window
-            const bool covered = lo <= s0 && hi >= tile_end;                    // every row of the tile is
-            if (!(exclude ? disjoint : covered)) {
-                const int rel = s0 + 4 * g - lo;   // tile row t = 16r + e of this lane is bank row lo + rel + t
-#pragma unroll
-                for (int r = 0; r < RS; ++r)
-#pragma unroll
-                    for (int e = 0; e < 4; ++e)
-                        if (((unsigned)(rel + 16 * r + e) < width) == exclude) sc[r][e] = -INFINITY;
-            }
+        if constexpr (OUT == OUT_WIN) window_scores<RS>(sc, win_lo, win_hi, (k & WIN_EXCLUDE) != 0, b, B, N, s0, g);
+        if constexpr (OUT == OUT_WGT) {   // (the window is optional beside the weights)
+            if (win_lo) window_scores<RS>(sc, win_lo, win_hi, (k & WIN_EXCLUDE) != 0, b, B, N, s0, g);
         }
 #pragma unroll
         for (int r = 0; r < RS; ++r) mloc = fmaxf(mloc, fmaxf(fmaxf(sc[r][0], sc[r][1]), fmaxf(sc[r][2], sc[r][3])));
@@ -341,9 +376,9 @@ __device__ __forceinline__ void fused_epilogue(
     if (consumer) {
         float dloc = 0.f;
         float msub = mloc;
-        if constexpr (OUT == OUT_WIN) {
-            // dead pairs (mloc = -inf: the window keeps no row of the tile for this query).  A wave all of whose sixteen
-            // queries are dead stores their zeros and goes; a dead query among live ones takes the sums below with
+        if constexpr (out_is_win(OUT)) {
+            // dead pairs (mloc = -inf: the window, or the weights, keep no row of the tile for this query).  A wave all of whose
+            // sixteen queries are dead stores their zeros and goes; a dead query among live ones takes the sums below with
             // 2^(-inf - 0) = 0 in every element (-inf - -inf would be NaN), which leaves the same zeros.
             const bool dead = mloc == -INFINITY;
             if (__all(dead)) {
@@ -459,6 +494,7 @@ __device__ __forceinline__ void fused_epilogue(
 // OUT_CAND: sy is not read, `scores` / `ws_lab` are CandOut's key / row arrays and `C` carries k.
 // OUT_CAND_WIN: `C` carries CAND_EXCLUDE besides and `ws_nrun` / `ws_m` are the row window's two arrays.
 // OUT_WIN: `scores` / `ws_den` are the row window's two arrays, `C` carries WIN_EXCLUDE besides the class count.
+// OUT_WGT: as OUT_WIN (both window arrays may be null), and `row_logw` holds the bank rows' log-weights; null otherwise.
 template <int RS, int KIND, int OUT, int MODE>
 __global__ __launch_bounds__(TILE_THREADS, (RS <= 5 ? 4 : 2)) void nw_fused_kernel(
     const float* __restrict__ q, const float* __restrict__ s, const int64_t* __restrict__ sy,
@@ -466,7 +502,8 @@ __global__ __launch_bounds__(TILE_THREADS, (RS <= 5 ? 4 : 2)) void nw_fused_kern
     const float* __restrict__ q_scale, const float* __restrict__ logit_scale,
     float* __restrict__ scores, float* __restrict__ ws_m,
     float* __restrict__ ws_den, int* __restrict__ ws_nrun, int* __restrict__ ws_lab,
-    float* __restrict__ ws_num, int B, int N, int d, int C, int n_stiles, int n_qtiles) {
+    float* __restrict__ ws_num, int B, int N, int d, int C, int n_stiles, int n_qtiles,
+    const float* __restrict__ row_logw) {
     using Cfg = TileCfg<RS>;
     constexpr int BS = Cfg::BS;
     constexpr bool NEED_NORM = (KIND != NW_SCORE_DOT);
@@ -506,7 +543,7 @@ __global__ __launch_bounds__(TILE_THREADS, (RS <= 5 ? 4 : 2)) void nw_fused_kern
     // ---- runs of equal consecutive labels inside this support tile (one wave)
     if (!out_is_cand(OUT) && wave == 0) {
         int lab[3];
-        load_tile_labels<BS>(sy, s0, N, OUT == OUT_WIN ? C & (WIN_EXCLUDE - 1) : C, lane, lab);
+        load_tile_labels<BS>(sy, s0, N, out_is_win(OUT) ? C & (WIN_EXCLUDE - 1) : C, lane, lab);
         run_scan_wave<BS>(lab, lane, runid, runlab, nrun_s);
     }
 
@@ -534,7 +571,7 @@ __global__ __launch_bounds__(TILE_THREADS, (RS <= 5 ? 4 : 2)) void nw_fused_kern
 
     NW_FSTAMP(2);
     fused_epilogue<RS, KIND, OUT, MODE>(acc, qn2, sn2, ssc, runid, runlab, nrun_s, qsc_s, logit_scale,
-                                        scores, ws_m, ws_den, ws_nrun, ws_lab, ws_num, B, N, q0, s0, qt, st, n_stiles, C);
+                                        scores, ws_m, ws_den, ws_nrun, ws_lab, ws_num, B, N, q0, s0, qt, st, n_stiles, C, row_logw);
     NW_FSTAMP(6);
 }
 
@@ -584,7 +621,8 @@ int launch_fused_rs(const FusedArgs& a, const FusedPlan& p) {
     // the run counts go.
     // OUT_WIN: the head's row window stands where the scores and the tile sums go, its flag beside the class count; the
     // kernel finds the tile sums behind the tile maxima (fused_den_after_m).
-    const bool head_window = p.out == OUT_WIN;
+    // OUT_WGT: the same, with the row weights in the kernel's last argument (null for every other output).
+    const bool head_window = out_is_win(p.out);
     float* scores = cand ? reinterpret_cast<float*>(cand->key) : head_window ? reinterpret_cast<float*>(const_cast<int*>(a.win_lo)) : a.scores;
     int* lab = cand ? cand->row : ws.lab;
     const bool window = cand && cand->win_lo && cand->win_hi;
@@ -597,7 +635,7 @@ int launch_fused_rs(const FusedArgs& a, const FusedPlan& p) {
 #define NW_TILE(OUT_, MODE_)                                                                                           \
     hipLaunchKernelGGL((nw_fused_kernel<RS, KIND, OUT_, MODE_>), dim3(p.grid), dim3(TILE_THREADS), p.lds_bytes, st, q.rows, \
                        a.s, a.sy, a.s_norm2, a.s_scale, q.norm2, q.scale, a.ls, scores, ws.m, ws.den, ws.nrun, lab, ws.num, \
-                       a.B, a.N, a.d, c_or_k, p.n_stiles, p.n_qtiles)
+                       a.B, a.N, a.d, c_or_k, p.n_stiles, p.n_qtiles, p.out == OUT_WGT ? a.row_logw : nullptr)
 #define NW_TILE_CASE(MODE_) \
     case MODE_: if (p.out == OUT_SCORES) NW_TILE(OUT_SCORES, MODE_); else NW_TILE(OUT_NONE, MODE_); break
     if (p.out == OUT_CAND && p.persistent) {   // half-precision rows: the 256-query kernel's candidate form (nw_knn_f16)
@@ -620,15 +658,21 @@ int launch_fused_rs(const FusedArgs& a, const FusedPlan& p) {
             return NW_OK;
         }
     }
-    if (p.out == OUT_WIN) {   // the windowed head: the tile kernel of the windowed search at this shape, then the run merge
+    if (out_is_win(p.out)) {   // the windowed head: the tile kernel of the windowed search at this shape, then the run merge
         if constexpr (RS == 12) {
             return NW_ERR_UNSUPPORTED;
         } else {
-            if (p.persistent || p.run_tables || !mode_is_f16(p.mode) || !a.win_lo || !a.win_hi) return NW_ERR_UNSUPPORTED;
+            const bool weighted = p.out == OUT_WGT;   // (its window is optional: both arrays or neither)
+            if (p.persistent || p.run_tables || !mode_is_f16(p.mode)) return NW_ERR_UNSUPPORTED;
+            if (weighted ? (!a.row_logw || !a.win_lo != !a.win_hi) : (!a.win_lo || !a.win_hi)) return NW_ERR_UNSUPPORTED;
             float* const den = ws.den;
             if (den != ws.m + fused_den_after_m(p.n_stiles, a.B) || a.C >= WIN_EXCLUDE) return NW_ERR_UNSUPPORTED;
             ws.den = reinterpret_cast<float*>(const_cast<int*>(a.win_hi));
-            if (p.mode == MODE_F16Q) NW_TILE(OUT_WIN, MODE_F16Q); else NW_TILE(OUT_WIN, MODE_F16);
+            if (weighted) {
+                if (p.mode == MODE_F16Q) NW_TILE(OUT_WGT, MODE_F16Q); else NW_TILE(OUT_WGT, MODE_F16);
+            } else {
+                if (p.mode == MODE_F16Q) NW_TILE(OUT_WIN, MODE_F16Q); else NW_TILE(OUT_WIN, MODE_F16);
+            }
             ws.den = den;
             NW_CHECK_LAUNCH();
             return launch_merge_runs(ws, a.out, a.lse, a.m, a.den, a.num, a.B, a.C, p.n_stiles, BS, st);

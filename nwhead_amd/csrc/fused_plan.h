@@ -32,7 +32,10 @@ constexpr bool mode_is_f16(int m) { return m == MODE_F16 || m == MODE_F16Q; }
 // block of the (B,N) score matrix, or its best k scores per query (CandOut; split or half-precision operands, no labels, no merge).
 // OUT_WIN: the softmax partials of OUT_NONE over the bank rows that a per-query row window admits (FusedArgs::win_lo / win_hi,
 // nw_fwd_window_f32; split operands on nw_fused_kernel only, never the persistent kernels).  (3 is OUT_CAND_WIN, fused_impl.h.)
-enum { OUT_NONE = 0, OUT_SCORES = 1, OUT_CAND = 2, OUT_WIN = 4 };
+// OUT_WGT: OUT_WIN with a log-weight per bank row added to the scores (FusedArgs::row_logw, nw_fwd_weighted_f32); the window
+// is optional there.  Same operands, kernels and plans as OUT_WIN.
+enum { OUT_NONE = 0, OUT_SCORES = 1, OUT_CAND = 2, OUT_WIN = 4, OUT_WGT = 5 };
+constexpr bool out_is_win(int out) { return out == OUT_WIN || out == OUT_WGT; }
 // The support operand: fp32 rows, split rows (nw_split_rows_f16x2) or half-precision rows (nw_pack_rows_f16).
 enum { FORM_F32 = 0, FORM_SPLIT = 1, FORM_HALF = 2 };
 
@@ -70,6 +73,7 @@ struct FusedArgs {
     const CandOut* cand;
     const int *win_lo, *win_hi;
     int win_exclude;
+    const float* row_logw;       // (N,) natural-log weight of every bank row (OUT_WGT), or null
 };
 int launch_fused(const FusedArgs& a, int form, int kind);   // plan_fused + the launcher of the score kind (fused.hip)
 

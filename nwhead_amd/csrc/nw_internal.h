@@ -86,6 +86,7 @@ struct BwdQueryCall {
     const float* logit_scale_dev;
     int row_chunks;
     hipStream_t st;
+    const float* row_logw;   // (N,) log-weights of the bank rows (nw_bwd_query_weighted_f32), or null
 };
 bool bwd_query_shape_ok(int64_t B, int64_t N, int64_t d, int64_t C);
 size_t bwd_query_workspace_bytes(int64_t B, int64_t N, int64_t d, int64_t C, int row_chunks);

@@ -58,8 +58,15 @@ class NWNet(nn.Module):
                  n_shot_random=1, n_shot_full=100, n_shot_cluster=1, n_neighbors=10,
                  env_array=None, debug_mode=False, device='cuda:0', return_mask=False, cluster_backend='auto',
                  loader_workers=0, pin_memory=False, knn_per_query=False, full_precision="fp32",
-                 search_precision="fp32"):
+                 search_precision="fp32", balance_full="truncate"):
         super().__init__()
+        # not in the reference: how the 'full' bank gets its flat class prior.  "truncate" (the reference): every class is cut
+        # to the rarest class's row count.  "weights": every class keeps its first min(n_shot_full, n_c) rows and precompute()
+        # sets support weights -log n_c (ops.class_balance_logw), which predict('full'), predict_loo and forward_bank honour
+        if balance_full not in ("truncate", "weights"):
+            raise ValueError(f"balance_full must be 'truncate' or 'weights', got {balance_full!r}")
+        self.balance_full = balance_full
+        self.support_weights = None
         # not in the reference: "fp16" serves predict(x, 'full') from a half-precision bank (ops.SplitBank(precision="fp16"):
         # bank and query features rounded to fp16, half the bytes, a third of the matrix-core work); "fp32" is the parity path
         if full_precision not in ("fp32", "fp16"):
@@ -149,7 +156,7 @@ class NWNet(nn.Module):
                                            n_neighbors=self.n_neighbors, env_array=self.env_array,
                                            knn_per_query=self.knn_per_query, search_precision=self.search_precision,
                                            cluster_backend=self.cluster_backend, loader_workers=self.loader_workers,
-                                           pin_memory=self.pin_memory)
+                                           pin_memory=self.pin_memory, balance_full=self.balance_full)
 
     @torch.no_grad()
     def _compute_all_support_feats(self):
@@ -177,6 +184,49 @@ class NWNet(nn.Module):
         self.full_norm2 = self.full_cache.norm2
         self.support_eval.build_infer_iters(*info)
         self.support_eval.knn.bank = self.support_eval.hnsw.bank = self.full_cache   # neighbour search over the same bank
+        self.support_weights = None                  # weights are per row of the bank they were set for
+        if self.balance_full == "weights":
+            self.set_support_weights(ops.class_balance_logw(self.full_y, self.n_classes))
+
+    def set_support_weights(self, log_w=None):
+        """Not in the reference: a prior weight per row of precompute()'s bank.  ``log_w``: (N,) float tensor over the rows of
+        ``full_feat``, the natural logs a_j = log w_j; ``None`` clears them.  The 'full' head becomes the head of
+        score + a (ops.nw_head_window has the formula): -inf switches a row off (soft deletion, label-noise screening after
+        predict_loo, "what if these supports were gone", a subgroup or environment of the bank -- any subset, no rebuild),
+        ops.class_balance_logw(full_y, n_classes) gives an unbalanced bank a flat class prior, finite values are
+        importance / confidence / recency weights.  Checked once, here (one device synchronisation): NaN or +inf raise
+        ValueError.  The weights are a constant: no gradient flows to them.
+
+        Honoured by predict(x, 'full') with and without leave_out, by predict_loo and by forward_bank.  Kept by
+        refresh_bank (rows keep their identity); cleared by precompute().  NOT seen by get_neighbors, explain and the
+        other inference modes ('random', 'cluster', 'ensemble', 'knn', 'hnsw'), which read the bank's features as they are.
+        A sharded bank is refused (NWHipError), as is a custom kernel module."""
+        if log_w is None:
+            self.support_weights = None
+            return
+        if getattr(self, 'sharded_bank', None) is not None and not hasattr(self, 'full_feat'):
+            raise ops.NWHipError("set_support_weights: a sharded bank is not served (the weights are rows of one resident "
+                                 "bank); call precompute()")
+        if not hasattr(self, 'full_feat'):
+            raise ops.NWHipError("set_support_weights needs the bank of precompute()")
+        if not isinstance(self.kernel, _ScoreModule):
+            raise ops.NWHipError("set_support_weights needs one of the built-in score kernels")
+        # (a copy of its own: later writes to the caller's tensor do not get past the check below)
+        w = torch.as_tensor(log_w).detach().to(device=self.full_feat.device, dtype=torch.float32, copy=True).contiguous()
+        if w.shape != (self.full_feat.shape[0],):
+            raise ValueError(f"set_support_weights: log_w must be ({self.full_feat.shape[0]},), one value per bank row; got "
+                             f"{tuple(w.shape)}")
+        if bool((torch.isnan(w) | (w == float("inf"))).any()):
+            raise ValueError("set_support_weights: log_w holds NaN or +inf (finite values and -inf only)")
+        self.support_weights = w
+
+    def _weights_for(self, what):
+        """The support weights for a call over precompute()'s resident bank, or None; a sharded bank in front of it refuses."""
+        w = getattr(self, 'support_weights', None)
+        if w is not None and getattr(self, 'sharded_bank', None) is not None:
+            raise ops.NWHipError(f"{what}: support weights are set and the bank is sharded; a sharded bank has no weights "
+                                 "(set_support_weights(None), or precompute())")
+        return w
 
     @torch.no_grad()
     def precompute_sharded(self, group=None, partial_fn=None, merge_fn=None, search_fn=None, knn_merge_fn=None):
@@ -254,7 +304,7 @@ class NWNet(nn.Module):
         window = self._leave_out_window(rows, qfeat, what)
         with torch.no_grad():
             return ops.nw_head(qfeat.detach(), sfeat, sy, self.n_classes, self.kernel.kind, self.kernel._logit_scale(),
-                               support_cache=cache, row_window=window, exclude=True)
+                               support_cache=cache, row_window=window, exclude=True, row_logw=self._weights_for(what))
 
     def forward_bank(self, x, leave_out=None):
         """Not in the reference: the 'full' head at TRAINING time -- log-probabilities of ``self.featurizer(x)`` over
@@ -265,7 +315,8 @@ class NWNet(nn.Module):
 
         The bank is a CONSTANT here: it holds the features of the weights precompute() saw and goes stale as the weights
         move; the caller decides when to call precompute() again, or writes each batch's features back with
-        refresh_bank(rows) -- they are kept, detached, in ``bank_features`` (a view, not a copy).  A sharded bank, a missing bank and a custom kernel
+        refresh_bank(rows) -- they are kept, detached, in ``bank_features`` (a view, not a copy).  Support weights
+        (set_support_weights) are honoured, as a constant.  A sharded bank, a missing bank and a custom kernel
         module are refused (NWHipError), like predict_loo.  A full_precision="fp16" bank or a bank whose labels are not
         class-sorted takes ops.nw_head's route through the score matrix without ``leave_out`` and is refused with it."""
         what = "forward_bank"
@@ -276,7 +327,7 @@ class NWNet(nn.Module):
         sfeat, sy, cache = self._resident_bank(what, qfeat.device)
         window = None if leave_out is None else self._leave_out_window(leave_out, qfeat, what)
         out = ops.nw_head_bank(qfeat, sfeat, sy, self.n_classes, cache, self.kernel.kind, self.kernel._logit_scale(),
-                               row_window=window, exclude=window is not None)
+                               row_window=window, exclude=window is not None, row_logw=self._weights_for(what))
         return (out, torch.full((len(x),), True)) if self.return_mask else out
 
     def refresh_bank(self, rows, feats=None, momentum=0.0):
@@ -332,6 +383,7 @@ class NWNet(nn.Module):
             return (out, torch.full((len(x),), True)) if self.return_mask else out
         qfeat = self._eval_featurizer()(x)
         if mode == 'full' and getattr(self, 'sharded_bank', None) is not None:
+            self._weights_for("predict(x, 'full')")    # (raises when weights are set: a sharded bank has none)
             out = self.sharded_bank.predict(qfeat.detach())
             return (out, torch.full((len(x),), True)) if self.return_mask else out
         if mode in ('knn', 'hnsw') and getattr(self, 'sharded_bank', None) is not None \
@@ -356,7 +408,11 @@ class NWNet(nn.Module):
             cache = getattr(self, 'full_cache', None)
             if cache is None or not cache.matches(sfeat):   # the bank was replaced or updated since precompute()
                 cache = self.full_cache = ops.SplitBank(sfeat, labels=sy, precision=self.full_precision)
-            out = self.nwhead(qfeat, sfeat, sy, support_cache=cache)
+            if getattr(self, 'support_weights', None) is not None:    # (set_support_weights: a built-in score kernel)
+                out = ops.nw_head_bank(qfeat, sfeat, sy, self.n_classes, cache, self.kernel.kind, self.kernel._logit_scale(),
+                                       row_logw=self.support_weights)
+            else:
+                out = self.nwhead(qfeat, sfeat, sy, support_cache=cache)
         else:
             out = self.nwhead(qfeat, sfeat.to(x.device), sy.to(x.device))
         if self.return_mask:

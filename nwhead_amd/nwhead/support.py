@@ -73,14 +73,14 @@ class SupportSetEval(SupportSet):
 
     def __init__(self, support_set, n_classes, n_shot_random, n_shot_full, n_shot_cluster=3,
                  n_neighbors=20, env_array=None, cluster_backend="auto", loader_workers=0, pin_memory=False,
-                 knn_per_query=False, search_precision="fp32"):
+                 knn_per_query=False, search_precision="fp32", balance_full="truncate"):
         super().__init__(support_set, n_classes, env_array)
         self.search_precision = search_precision      # utils.KNN(search_precision=): "fp16" = the rounded search of an fp16 bank
         self.knn_per_query = bool(knn_per_query)      # utils.KNN(per_query=): each query its own neighbours (not in the reference)
         self.cluster_backend = cluster_backend        # utils.compute_clusters: 'auto' | 'sklearn' | 'device'
         self.n_shot_random, self.n_shot_full = n_shot_random, n_shot_full
         self.n_shot_cluster, self.n_neighbors = n_shot_cluster, n_neighbors
-        self.full_datasets = [FullDataset(env, n_shot_full) for env in self.env_datasets]
+        self.full_datasets = [FullDataset(env, n_shot_full, balance=balance_full) for env in self.env_datasets]
         # the reference's loaders (support.py:164-165: batch 128, in order, num_workers = 0).  Decoding the bank's images is
         # what bounds precompute() on a real dataset, so the worker count and pinned staging buffers are the caller's to
         # raise (NWNet(..., loader_workers=, pin_memory=)); the row order does not depend on them (shuffle=False)

@@ -53,12 +53,17 @@ class FeatureDataset(Dataset):
 
 class FullDataset(Dataset):
     """Class-balanced prefix of a dataset: the first min(n_shot_full, smallest class) items of every
-    class, classes in ascending order -> the bank is class-sorted (utils.py:34-54)."""
+    class, classes in ascending order -> the bank is class-sorted (utils.py:34-54).
+    balance="weights" (not in the reference): the first min(n_shot_full, n_c) items of EVERY class instead -- nothing is cut
+    to the rarest class's count; the flat class prior then comes from support weights (ops.class_balance_logw), which
+    NWNet(balance_full="weights") sets in precompute()."""
 
-    def __init__(self, underlying_dataset, n_shot_full):
+    def __init__(self, underlying_dataset, n_shot_full, balance="truncate"):
+        if balance not in ("truncate", "weights"):
+            raise ValueError(f"balance must be 'truncate' or 'weights', got {balance!r}")
         self.underlying_dataset = underlying_dataset
         self.indices = get_separated_indices(underlying_dataset.targets)
-        keep = min(n_shot_full, min(len(ix) for ix in self.indices))
+        keep = min(n_shot_full, min(len(ix) for ix in self.indices)) if balance == "truncate" else n_shot_full
         self.keys = [i for ix in self.indices for i in ix[:keep]]
 
     def __len__(self):

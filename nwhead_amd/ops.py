@@ -386,6 +386,48 @@ def head_window_route(*, split, sorted_copy, shape, pad, width, B, n_classes):
     return "fused" if fused else "matrix"
 
 
+def head_weighted_route(*, split, sorted_copy, shape, pad, width, B, n_classes, grad=False):
+    """Which route serves a head with SUPPORT WEIGHTS (``row_logw``), beside head_window_route / head_bank_route and over the
+    same plain facts: "fused" (nw_fwd_weighted_f32, and nw_bwd_query_weighted_f32 for the gradient: the weight is added in the
+    tile epilogue, no score matrix) exactly when the windowed head would be fused -- both kernels take the same shapes, and
+    the measured cost of the weights is N more floats per query tile, so there is no size gate either; else
+    "matrix" for the forward (nw_scores + a (+ the window's mask) + nw_aggregate_f32, with the dead-query fix-up of
+    nw_head_window).  The gradient (``grad``) has no matrix route that knows the weights -- nw_head's saves the scores its
+    distance derivative is taken at, and they would be the weighted ones -- so it is None there, with a window or
+    without: the caller refuses."""
+    fused = head_window_route(split=split, sorted_copy=sorted_copy, shape=shape, pad=pad, width=width, B=B,
+                              n_classes=n_classes) == "fused"
+    return "fused" if fused else (None if grad else "matrix")
+
+
+def _row_logw(row_logw, N, device, what):
+    """``row_logw`` as the kernels read it: (N,) fp32, contiguous, 16-byte aligned, on ``device``.  No value is looked at."""
+    if not torch.is_tensor(row_logw) or not row_logw.is_floating_point() or row_logw.shape != (N,):
+        raise ValueError(f"{what}: row_logw is an ({N},) float tensor, the log-weight of every row of `s`")
+    if row_logw.device != device:
+        raise ValueError(f"{what}: row_logw must be on the queries' device")
+    a = _f32c(row_logw.detach())
+    return a if a.data_ptr() % 16 == 0 else a.clone()
+
+
+def class_balance_logw(labels, n_classes, prior=None):
+    """(N,) fp32 log-weights log(pi_c / n_c) for the rows of a bank with integer ``labels`` (N,): the weights of a class sum
+    to its prior pi_c whatever its row count n_c, so an unbalanced bank predicts with that class prior -- flat (1 / C) by
+    default, or ``prior`` (C,), positive entries.  Pass the result as ``row_logw`` / NWNet.set_support_weights.  Labels
+    outside [0, n_classes) get -inf (the kernels skip such rows anyway); so do the rows of a class whose prior is 0."""
+    C = int(n_classes)
+    y = labels.detach().to(torch.int64)
+    ok = (y >= 0) & (y < C)
+    yc = y.clamp(0, max(C - 1, 0))
+    counts = torch.bincount(yc[ok], minlength=C).to(torch.float64)
+    pi = torch.full((C,), 1.0 / max(C, 1), dtype=torch.float64, device=y.device) if prior is None else \
+        torch.as_tensor(prior, dtype=torch.float64, device=y.device)
+    if pi.shape != (C,):
+        raise ValueError(f"class_balance_logw: prior must be ({C},)")
+    logw = (pi.log() - counts.clamp(min=1).log())[yc]
+    return torch.where(ok, logw, logw.new_tensor(float("-inf"))).to(torch.float32)
+
+
 KNN_MERGE_MAX_K, KNN_MERGE_MAX_SHARDS = 32, 64
 
 
@@ -808,11 +850,13 @@ class _NWHeadFn(torch.autograd.Function):
 
 
 def nw_head(q, s, sy, n_classes, kind="euclidean", logit_scale=None, return_weights=False,
-            support_norm2=None, support_cache=None, validate_labels=False, row_window=None, exclude=False):
+            support_norm2=None, support_cache=None, validate_labels=False, row_window=None, exclude=False, row_logw=None):
     """NWHead.forward(x, sx, sy) -> (B,C) log-probs (and the (B,N) softmax weights on request).
     row_window=(lo, hi) (not the default, which it leaves as it is bit for bit; needs ``support_cache``, inference only):
     the head of query b over the rows lo[b] <= row < hi[b] of `s` alone, or with ``exclude=True`` over every other row --
     nw_head_window, which says more.
+    row_logw (same conditions; ``None`` leaves every call as it is): (N,) float log-weights of the rows of `s`, added to the
+    scores before the softmax; -inf removes a row.  nw_head_window says more; nw_head_bank is the call with gradients.
     support_norm2: optional cached ``row_norm2(s)`` for a shared (N,d) support.
     support_cache: optional ``SplitBank(s)`` (the fast 'full' inference path; its docstring says what the call then reads).
     validate_labels: the reference's F.one_hot (nw.py:276) REFUSES labels outside [0, n_classes); the kernels skip such
@@ -838,11 +882,11 @@ def nw_head(q, s, sy, n_classes, kind="euclidean", logit_scale=None, return_weig
         _check_label_range(None, support_cache.label_max, n_classes)
     grad = torch.is_grad_enabled()
     needs_grad = grad and (q.requires_grad or s.requires_grad or (logit_scale is not None and logit_scale.requires_grad))
-    if row_window is not None:
+    if row_window is not None or row_logw is not None:
         if needs_grad or return_weights or support_cache is None:
-            raise ValueError("nw_head(row_window=...) is inference over a prepared bank: it needs support_cache and has no "
-                             "gradients and no return_weights")
-        return nw_head_window(q, s, sy, n_classes, support_cache, row_window, exclude, kind, logit_scale)
+            raise ValueError("nw_head(row_window=... / row_logw=...) is inference over a prepared bank: it needs support_cache "
+                             "and has no gradients (nw_head_bank has the queries') and no return_weights")
+        return nw_head_window(q, s, sy, n_classes, support_cache, row_window, exclude, kind, logit_scale, row_logw=row_logw)
     call = _resolve(support_cache, q, s, sy, n_classes, return_weights, grad and s.requires_grad,
                     not (needs_grad or return_weights), 0, support_norm2, needs_grad)      # (by position: host-bound)
     if not needs_grad:   # inference: skip the autograd node (its bookkeeping costs more than the kernels at small sizes)
@@ -856,7 +900,8 @@ def _window_empty(lo, hi, exclude, N):
     return ((lo <= 0) & (hi >= N)) if exclude else (hi <= lo)
 
 
-def nw_head_window(q, s, sy, n_classes, bank, row_window, exclude=False, kind="euclidean", logit_scale=None, return_lse=False):
+def nw_head_window(q, s, sy, n_classes, bank, row_window, exclude=False, kind="euclidean", logit_scale=None, return_lse=False,
+                   row_logw=None):
     """``nw_head(q, s, sy, n_classes, support_cache=bank, row_window=(lo, hi), exclude=...)``: the head of every query over
     its own ROW WINDOW of the bank -> (B,C) log-probs (with ``return_lse`` also the (B,) log-sum-exp of the admitted scores).
     lo / hi: (B,) integer tensors on the device, rows of `s`, the tensor the bank was prepared from; query b sees the rows
@@ -870,7 +915,16 @@ def nw_head_window(q, s, sy, n_classes, bank, row_window, exclude=False, kind="e
     Route (head_window_route): nw_fwd_window_f32 -- the split-fp16 tile kernel with the window in its epilogue, no (B,N)
     matrix -- at every shape the kernel takes, whenever the bank holds split rows without a class-sorted copy and the
     queries pad to its width; otherwise (a ``precision="fp16"`` or norms-only bank, a bank built from unsorted labels,
-    N <= 25) nw_scores over the bank, a torch mask and nw_aggregate_f32: the same result through the (B,N) score matrix."""
+    N <= 25) nw_scores over the bank, a torch mask and nw_aggregate_f32: the same result through the (B,N) score matrix.
+
+    row_logw: SUPPORT WEIGHTS, (N,) float log-weights a_j = log w_j of the rows of `s` (``row_window`` may then be None: no
+    window).  The head becomes log(sum_{j admitted, y_j = c} w_j e^score / sum_{j admitted} w_j e^score + 1e-12): the head of
+    score + a.  a_j = -inf removes row j (soft deletion, any subset of a live bank), ops.class_balance_logw gives an unbalanced
+    bank a flat class prior, anything finite is an importance weight.  Values must be finite or -inf; NaN, +inf and magnitudes
+    above ~1e38 / 1.45 are outside the contract (undefined results for the queries that admit such a row, no fault; nothing is
+    checked here -- NWNet.set_support_weights checks once).  A query all of whose admitted rows have a = -inf is dead like one
+    with an empty window.  Route (head_weighted_route): nw_fwd_weighted_f32 wherever the windowed head is fused, the weight
+    added in the tile epilogue before the maximum; else nw_scores + a + the mask + nw_aggregate_f32."""
     _need_hip(q, s, sy, logit_scale)
     if not isinstance(bank, SplitBank):
         raise TypeError("nw_head_window runs over a prepared bank: pass ops.SplitBank(support)")
@@ -879,7 +933,10 @@ def nw_head_window(q, s, sy, n_classes, bank, row_window, exclude=False, kind="e
     lib = _lib.load()
     q = _f32c(q)
     B, N, C = q.shape[0], s.shape[0], int(n_classes)
-    lo, hi = _row_window(row_window, B, q.device)
+    if row_window is None and row_logw is None:
+        raise ValueError("nw_head_window: needs row_window=(lo, hi), row_logw, or both")
+    lo, hi = _row_window(row_window, B, q.device) if row_window is not None else (None, None)
+    logw = None if row_logw is None else _row_logw(row_logw, N, q.device, "nw_head_window")
     ls = None if logit_scale is None else _f32c(logit_scale)
     kid = _kind_id(kind)
     if kid == SCORE_KINDS["clip"] and ls is None:
@@ -887,26 +944,37 @@ def nw_head_window(q, s, sy, n_classes, bank, row_window, exclude=False, kind="e
     syc = sy if (sy.dtype == torch.int64 and sy.is_contiguous()) else sy.detach().to(torch.int64).contiguous()
     out = torch.empty(B, C, dtype=torch.float32, device=q.device)
     lse = torch.empty(B, dtype=torch.float32, device=q.device)
-    route = head_window_route(split=bank.split is not None, sorted_copy=bank.sorted_rows is not None, shape=bank.shape,
-                              pad=bank.pad, width=q.shape[1], B=B, n_classes=C)
+    facts = dict(split=bank.split is not None, sorted_copy=bank.sorted_rows is not None, shape=bank.shape, pad=bank.pad,
+                 width=q.shape[1], B=B, n_classes=C)
+    route = head_window_route(**facts) if logw is None else head_weighted_route(**facts)
     if route == "fused":
         call = _resolve_scores(bank, q)
         st, d = _stream(q), call.q.shape[1]
         ws, ws_bytes = _fwd_workspace(lib, B, N, d, C, q.device, st)
         with _OnDevice(q.device):
-            _lib.check(lib.nw_fwd_window_f32(_ptr(call.q), _ptr(call.operand), _ptr(call.scale), _ptr(call.norm2), _ptr(syc),
-                                             _ptr(lo), _ptr(hi), int(bool(exclude)), _ptr(out), _ptr(lse), _ptr(ws), ws_bytes,
-                                             B, N, d, C, kid, _ptr(ls), st), "nw_fwd_window_f32")
+            if logw is None:
+                _lib.check(lib.nw_fwd_window_f32(_ptr(call.q), _ptr(call.operand), _ptr(call.scale), _ptr(call.norm2), _ptr(syc),
+                                                 _ptr(lo), _ptr(hi), int(bool(exclude)), _ptr(out), _ptr(lse), _ptr(ws), ws_bytes,
+                                                 B, N, d, C, kid, _ptr(ls), st), "nw_fwd_window_f32")
+            else:
+                _lib.check(lib.nw_fwd_weighted_f32(_ptr(call.q), _ptr(call.operand), _ptr(call.scale), _ptr(call.norm2), _ptr(syc),
+                                                   _ptr(logw), _ptr(lo), _ptr(hi), int(bool(exclude)), _ptr(out), _ptr(lse),
+                                                   _ptr(ws), ws_bytes, B, N, d, C, kid, _ptr(ls), st), "nw_fwd_weighted_f32")
     elif B > 0:
-        cols = torch.arange(N, device=q.device)
-        keep = (cols >= lo[:, None]) & (cols < hi[:, None])
-        if exclude:
-            keep = ~keep
-        scores = nw_scores(q, s, kind, logit_scale, support_cache=bank).masked_fill_(~keep, float("-inf"))
+        scores = nw_scores(q, s, kind, logit_scale, support_cache=bank)
+        if logw is not None:
+            scores += logw
+        if lo is not None:
+            cols = torch.arange(N, device=q.device)
+            keep = (cols >= lo[:, None]) & (cols < hi[:, None])
+            if exclude:
+                keep = ~keep
+            scores.masked_fill_(~keep, float("-inf"))
         with _OnDevice(q.device):
             _lib.check(lib.nw_aggregate_f32(_ptr(scores), _ptr(syc), _ptr(out), _ptr(lse), None, B, N, C, 0, _stream(q)),
                        "nw_aggregate_f32")
-        empty = _window_empty(lo, hi, exclude, N)     # (a softmax over nothing: the kernel's answer is not defined)
+        # (a softmax over nothing: the kernel's answer is not defined)
+        empty = _window_empty(lo, hi, exclude, N) if logw is None else ~(scores > float("-inf")).any(dim=1)
         out = torch.where(empty[:, None], out.new_tensor(1e-12).log(), out)
         lse = lse.masked_fill(empty, float("-inf"))
     return (out, lse) if return_lse else out
@@ -966,9 +1034,11 @@ class _NWHeadBankFn(torch.autograd.Function):
     out and the window: nothing of size B x N."""
 
     @staticmethod
-    def forward(ctx, q, logit_scale, call, n_classes, kind_id, window, exclude, bank=None):
+    def forward(ctx, q, logit_scale, call, n_classes, kind_id, window, exclude, bank=None, logw=None, logw_src=None):
         """``call``: the _Call nw_head_bank resolved (``q`` is its queries, an argument of its own for autograd);
-        ``window``: None or (lo, hi) int32; ``bank``: the SplitBank the call reads, whose ``writes`` the backward checks."""
+        ``window``: None or (lo, hi) int32; ``bank``: the SplitBank the call reads, whose ``writes`` the backward checks;
+        ``logw``: None or the (N,) fp32 support weights as the kernels read them (_row_logw), ``logw_src`` the caller's tensor
+        they came from (the same one, or what a conversion copied), whose version the backward checks likewise."""
         _, sc, syc, sn2, ssplit, sscale, opts = call
         lib = _lib.load()
         qc = _f32c(q)
@@ -981,7 +1051,11 @@ class _NWHeadBankFn(torch.autograd.Function):
         ws, ws_bytes = _fwd_workspace(lib, B, N, d, n_classes, dev, st)
         lo, hi = window if window is not None else (None, None)
         with _OnDevice(dev):
-            if window is None:
+            if logw is not None:
+                _lib.check(lib.nw_fwd_weighted_f32(_ptr(qc), _ptr(ssplit), _ptr(sscale), _ptr(sn2), _ptr(syc), _ptr(logw), _ptr(lo),
+                                                   _ptr(hi), int(exclude), _ptr(out), _ptr(lse), _ptr(ws), ws_bytes, B, N, d,
+                                                   n_classes, kind_id, _ptr(ls), st), "nw_fwd_weighted_f32")
+            elif window is None:
                 _lib.check(lib.nw_fwd_f32(_ptr(qc), _ptr(sc), _ptr(syc), _ptr(sn2), _ptr(ssplit), _ptr(sscale), _ptr(out), None,
                                           _ptr(lse), None, _ptr(ws), ws_bytes, B, N, d, n_classes, kind_id, _ptr(ls), 0, 0, opts,
                                           st), "nw_fwd_f32")
@@ -993,6 +1067,8 @@ class _NWHeadBankFn(torch.autograd.Function):
         # the backward recomputes the scores from these: SplitBank.update_rows writes them in place and counts in `writes`
         ctx.bank = (ssplit, sscale, sn2, syc)
         ctx.bank_writes = (bank, bank.writes) if bank is not None else None
+        # ... and the weights, a constant of this node: the tensor itself and its version (an in-place write bumps it)
+        ctx.logw = None if logw is None else (logw, logw_src, logw_src._version)
         ctx.meta = (B, N, d, n_classes, kind_id, ls is not None, window is not None, int(exclude))
         return out
 
@@ -1009,20 +1085,30 @@ class _NWHeadBankFn(torch.autograd.Function):
         if ctx.bank_writes is not None and ctx.bank_writes[0].writes != ctx.bank_writes[1]:
             raise RuntimeError("nw_head_bank: the bank was written (SplitBank.update_rows) between this forward and its "
                                "backward, which recomputes the scores from the bank: call backward() first, then update")
+        if ctx.logw is not None and ctx.logw[1]._version != ctx.logw[2]:
+            raise RuntimeError("nw_head_bank: row_logw was written in place between this forward and its backward, which "
+                               "recomputes the weighted scores from it: call backward() first, then change the weights")
         dev = qc.device
         g = _f32c(gout)
         gq = torch.empty_like(qc)
         gls = torch.empty((), dtype=torch.float32, device=dev) if has_ls else None
         ws_bytes = lib.nw_bwd_query_workspace_bytes(B, N, d, C, 0)
         ws = _workspace(ws_bytes, dev)
+        if ctx.logw is not None:
+            with _OnDevice(dev):
+                _lib.check(lib.nw_bwd_query_weighted_f32(_ptr(qc), _ptr(ssplit), _ptr(sscale), _ptr(sn2), _ptr(syc), _ptr(ctx.logw[0]),
+                                                         _ptr(lo), _ptr(hi), exclude, _ptr(lse), _ptr(out), _ptr(g), _ptr(gq),
+                                                         _ptr(gls), _ptr(ws), ws_bytes, B, N, d, C, kind_id, _ptr(ls), 0,
+                                                         _stream(qc)), "nw_bwd_query_weighted_f32")
+            return gq, gls, None, None, None, None, None, None, None, None
         with _OnDevice(dev):
             _lib.check(lib.nw_bwd_query_f32(_ptr(qc), _ptr(ssplit), _ptr(sscale), _ptr(sn2), _ptr(syc), _ptr(lo), _ptr(hi), exclude,
                                             _ptr(lse), _ptr(out), _ptr(g), _ptr(gq), _ptr(gls), _ptr(ws), ws_bytes, B, N, d, C,
                                             kind_id, _ptr(ls), 0, _stream(qc)), "nw_bwd_query_f32")
-        return gq, gls, None, None, None, None, None, None
+        return gq, gls, None, None, None, None, None, None, None, None
 
 
-def nw_head_bank(q, s, sy, n_classes, bank, kind="euclidean", logit_scale=None, row_window=None, exclude=False):
+def nw_head_bank(q, s, sy, n_classes, bank, kind="euclidean", logit_scale=None, row_window=None, exclude=False, row_logw=None):
     """The head over a RESIDENT bank, differentiable in the queries (and a clip ``logit_scale``) with the bank a constant
     -> (B,C) log-probabilities.  For fine-tuning a featurizer against a frozen or periodically refreshed bank, a
     leave-one-out training loss (``row_window`` / ``exclude`` as in nw_head_window), input gradients of 'full' inference,
@@ -1034,7 +1120,12 @@ def nw_head_bank(q, s, sy, n_classes, bank, kind="euclidean", logit_scale=None, 
     bank rows in the same kernel: no (B,N) buffer is saved or filled (nw_head's route keeps three) and no support gradient
     is computed.  Route (head_bank_route): that kernel whenever the bank holds split rows without a class-sorted copy and
     the queries pad to its width; otherwise (an fp16 or norms-only bank, unsorted labels, N <= 25, a width that is no
-    multiple of 32 after padding) nw_head's route without a window, NWHipError with one."""
+    multiple of 32 after padding) nw_head's route without a window, NWHipError with one.
+
+    row_logw: SUPPORT WEIGHTS as in nw_head_window, a constant like the bank: no gradient flows to them, and writing the
+    tensor in place between forward and backward is refused like a bank update.  Forward nw_fwd_weighted_f32, backward
+    nw_bwd_query_weighted_f32, wherever the rule above gives the kernel (head_weighted_route); where it does not, the
+    gradient is refused with or without a window (NWHipError: nw_head's matrix route does not know the weights)."""
     if not isinstance(bank, SplitBank):
         raise TypeError("nw_head_bank runs over a prepared bank: pass ops.SplitBank(support)")
     grad = torch.is_grad_enabled()
@@ -1048,24 +1139,28 @@ def nw_head_bank(q, s, sy, n_classes, bank, kind="euclidean", logit_scale=None, 
     if kid == SCORE_KINDS["clip"] and logit_scale is None:
         raise ValueError("clip kernel needs logit_scale")
     if not (grad and (q.requires_grad or (logit_scale is not None and logit_scale.requires_grad))):
-        return nw_head(q, s, sy, n_classes, kind, logit_scale, support_cache=bank, row_window=row_window, exclude=exclude)
+        return nw_head(q, s, sy, n_classes, kind, logit_scale, support_cache=bank, row_window=row_window, exclude=exclude,
+                       row_logw=row_logw)
     C = int(n_classes)
     _check_label_range(None, bank.label_max, C)
+    logw = None if row_logw is None else _row_logw(row_logw, s.shape[0], q.device, "nw_head_bank")
     why = head_bank_refusal(split=bank.split is not None, sorted_copy=bank.sorted_rows is not None, shape=bank.shape,
                             pad=bank.pad, width=q.shape[1], B=q.shape[0], n_classes=C)
     if why is not None:
+        if logw is not None:
+            raise NWHipError(f"nw_head_bank(row_logw=...) has no gradient route here: {why}")
         if row_window is None:
             return nw_head(q, s, sy, C, kind, logit_scale, support_cache=bank)
         raise NWHipError(f"nw_head_bank(row_window=...) has no gradient route here: {why}")
-    if row_window is None:
+    if row_window is None and logw is None:
         call = _resolve(bank, q, s, sy, C, False, False, False, 0, None, False)       # nw_head's inference call
         window = None
     else:
         call = _resolve_scores(bank, q)
         syc = sy if (sy.dtype == torch.int64 and sy.is_contiguous()) else sy.detach().to(torch.int64).contiguous()
         call = call._replace(sy=syc)
-        window = tuple(_row_window(row_window, q.shape[0], q.device))
-    out = _NWHeadBankFn.apply(call.q, logit_scale, call, C, kid, window, bool(exclude), bank)
+        window = None if row_window is None else tuple(_row_window(row_window, q.shape[0], q.device))
+    out = _NWHeadBankFn.apply(call.q, logit_scale, call, C, kid, window, bool(exclude), bank, logw, row_logw)
     return out
 
 

@@ -88,14 +88,14 @@ int main(int argc, char** argv) {
         else if (qraw)
             hipLaunchKernelGGL((nw_fused_kernel<RS, 0, false, MODE_F16Q>), dim3(grid), dim3(TILE_THREADS), lds, 0, q, ssp, sy, sn, ssc,
                                (const float*)nullptr, (const float*)nullptr,
-                               (const float*)nullptr, (float*)dbg, m, den, nrun, lab, num, B, N, d, C, n_stiles, n_qtiles);
+                               (const float*)nullptr, (float*)dbg, m, den, nrun, lab, num, B, N, d, C, n_stiles, n_qtiles, (const float*)nullptr);
         else if (f16)
             hipLaunchKernelGGL((nw_fused_kernel<RS, 0, false, MODE_F16>), dim3(grid), dim3(TILE_THREADS), lds, 0, qsp, ssp, sy, sn, ssc, qn, qsc,
-                               (const float*)nullptr, (float*)dbg, m, den, nrun, lab, num, B, N, d, C, n_stiles, n_qtiles);
+                               (const float*)nullptr, (float*)dbg, m, den, nrun, lab, num, B, N, d, C, n_stiles, n_qtiles, (const float*)nullptr);
         else
             hipLaunchKernelGGL((nw_fused_kernel<RS, 0, false, MODE_DMA_SN>), dim3(grid), dim3(TILE_THREADS), lds, 0, q, s, sy, sn, (const float*)nullptr,
                                (const float*)nullptr, (const float*)nullptr, (const float*)nullptr, (float*)dbg, m, den, nrun, lab, num, B, N, d, C,
-                               n_stiles, n_qtiles);
+                               n_stiles, n_qtiles, (const float*)nullptr);
     };
     const int warm = argc > 6 ? atoi(argv[6]) : 5;   // e.g. 300: past the post-idle clock ramp (~40 ms)
     for (int i = 0; i < warm; ++i) launch();
