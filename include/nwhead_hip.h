@@ -431,6 +431,34 @@ int nw_bwd_query_weighted_f32(const float *q, const float *s_split, const float 
                               float *gq, float *glogit_scale, void *workspace, size_t workspace_bytes,
                               int64_t B, int64_t N, int64_t d, int64_t C, int kind, const float *logit_scale_dev,
                               int row_chunks, void *stream);
+/* LEARNABLE support weights: nw_bwd_query_weighted_f32 with the gradient of the weighted head w.r.t. row_logw as well,
+ *   glogw[j] = sum_b dS_bj,   dS_bj = W_bj (dP_b[sy_j] - t_b),   W_bj = exp(score_bj + a_j - lse_b)
+ * -- the column sum over the queries of the quantity whose row contraction with the bank is gq, taken in the same kernel
+ * from the same registers: no (B,N) buffer.  A row whose label is outside [0, C) has dP = 0 and gets -sum_b W_bj t_b.
+ *   glogw  (N,) fp32, required, 16-byte aligned.  EVERY element of glogw[0..N) is written by every successful call with
+ *          B > 0 (the caller never clears it); a row with a_j = -inf, a row that no query's window admits and the
+ *          contribution of a dead query (lse = -inf) are exactly +0.0, no NaN.
+ *   gq     (B,d) or NULL.  NULL is the weights-only variant (a frozen featurizer): the bank rows are not streamed a second
+ *          time, no second product, and the workspace holds no partial gq tiles.  glogw of the two variants is the same
+ *          bit for bit; with gq given, gq and glogit_scale are nw_bwd_query_weighted_f32's bits.
+ *   glogit_scale  optional scalar in both variants (0 unless clip).
+ * Reduction order: within a 64-query tile the 16 queries of a wave in a fixed exchange tree, then the four waves in
+ * order; then the query tiles in ascending order (a finishing kernel).  Chunks own disjoint rows, so row_chunks does not
+ * enter the sum: two calls, and calls with different row_chunks, give identical bits.  No float atomics.
+ * workspace: nw_bwd_logw_workspace_bytes(B, N, d, C, row_chunks, want_gq) with want_gq = (gq != NULL); at most
+ * ceil(B / 64) * 64 * ceil(N / 64) floats more than nw_bwd_query_workspace_bytes with gq, far fewer without.
+ * Regime, alignment, row_chunks, status codes and refusals before anything is launched are nw_bwd_query_weighted_f32's;
+ * glogw or row_logw NULL: NW_ERR_INVALID_ARG; a misaligned glogw: NW_ERR_UNSUPPORTED.  B == 0: NW_OK and NOTHING is
+ * touched, glogw included (there is no query to sum over and no launch to write it: a caller with an empty batch clears
+ * its own buffer). */
+size_t nw_bwd_logw_workspace_bytes(int64_t B, int64_t N, int64_t d, int64_t C, int row_chunks, int want_gq);
+int nw_bwd_query_logw_f32(const float *q, const float *s_split, const float *s_scale, const float *s_norm2,
+                          const int64_t *sy, const float *row_logw,
+                          const int32_t *row_lo, const int32_t *row_hi, int exclude,
+                          const float *lse, const float *out, const float *gout,
+                          float *gq, float *glogw, float *glogit_scale, void *workspace, size_t workspace_bytes,
+                          int64_t B, int64_t N, int64_t d, int64_t C, int kind, const float *logit_scale_dev,
+                          int row_chunks, void *stream);
 /* support_influence (util/metric.py:23-50) of k SELECTED supports per query, from the head's own outputs:
  *   vals (B,k) fp32 raw scores and rows (B,k) int64 bank rows (a search's val_out / idx_out),
  *   sy (N,) int64, qy (B,) int64, out (B,C) log-probabilities and lse (B,) of nw_fwd_f32 over the same bank;

@@ -1,5 +1,5 @@
 // bwd_query.hip -- gradient of the head w.r.t. the queries over a resident split bank, without a (B,N) matrix
-// (gfx950 / MI355X only; nw_bwd_query_f32, nw_bwd_query_weighted_f32).
+// (gfx950 / MI355X only; nw_bwd_query_f32, nw_bwd_query_weighted_f32), and w.r.t. the row weights (nw_bwd_query_logw_f32).
 //
 // backward.hip's closed form with the bank a constant.  For query b, bank row j, score s_bj = f(dot, |q_b|^2, |s_j|^2):
 //     dP_c = g_bc exp(-out_bc)                 dW_j = dP[y_j]  (0 for a label outside [0, C))
@@ -37,6 +37,22 @@
 //
 // Chunks over N fill the chip; each writes its partial gq / rq / gls, nw_bwd_query_finish_kernel adds them in chunk order:
 // no float atomics, two calls give the same bits.
+//
+// The gradient w.r.t. the row weights (GA; nw_bwd_query_logw_f32).  d out / d a_j is the column sum of the dS above,
+//     ga_j = sum_b dS_bj,
+// taken from the registers that hold dS for the row contraction: a consumer lane (i, g) of wave w holds dS for query
+// 16w + i and the 16 tile rows 16r + 4g + e.  Per support tile
+//   1. the 16 lanes i of a lane group reduce-scatter their 16 values in 15 DPP exchanges (partners i ^ 8, i ^ 7, i ^ 2,
+//      i ^ 1; a lane sends the half it does not keep): lane i ends with the sum over the wave's 16 queries of row
+//      16 (i >> 2) + 4g + (i & 3);
+//   2. the four consumer waves write their 64 sums to a 64 rows x 4 waves float area beside the header; behind the next
+//      workgroup barrier the first loader wave adds the four in wave order and stores the tile's 64 sums to
+//      gap[query tile][row].  With gq (GA = 1) that barrier is the first of the second product, which every wave passes
+//      anyway; without (GA = 2) it is the tile's only barrier behind the scores.
+// Only slab 0 writes (every slab recomputes the same scores); chunks own disjoint rows, so the chunk count does not enter
+// the sum; nw_bwd_logw_finish_kernel adds the query tiles in ascending order from +0: no float atomics, a row that nobody
+// admits is +0.0 exactly.  GA = 2 (gq == NULL, a frozen featurizer) drops the second stream of the bank rows, the second
+// product and the part / rqp / ascale areas; its dS and its reduction are GA = 1's, so ga is the same bit for bit.
 #include "nw_internal.h"
 #include "tile_dma.h"
 #include "tile_f16.h"
@@ -52,9 +68,11 @@ constexpr int QRS = 4;            // support blocks per tile
 constexpr int QBS = 16 * QRS;     // 64 bank rows per tile
 constexpr int Q_HDR = (3 * BQ + 3 * QBS) * 4;   // qn2[BQ] | qsc[BQ] | fac[BQ] | sn2[QBS] | ssc[QBS] | lab[QBS]
 constexpr int Q_HDR_W = Q_HDR + QBS * 4;        // ... | law[QBS]: the tile's row log-weights (the weighted kernels only)
-static_assert(Q_HDR % 16 == 0 && Q_HDR_W % 16 == 0, "stage buffers must stay 16-byte aligned");
+constexpr int Q_HDR_GA = Q_HDR_W + QBS * NCONS * 4;   // ... | gar[QBS][NCONS]: the waves' column sums of dS (the GA kernels only)
+static_assert(Q_HDR % 16 == 0 && Q_HDR_W % 16 == 0 && Q_HDR_GA % 16 == 0, "stage buffers must stay 16-byte aligned");
 constexpr size_t Q_LDS = Q_HDR + DmaCfg<QRS>::STAGE_BYTES, Q_LDS_W = Q_HDR_W + DmaCfg<QRS>::STAGE_BYTES;
-static_assert(Q_LDS_W <= 160 * 1024, "header + ring exceed LDS");
+constexpr size_t Q_LDS_GA = Q_HDR_GA + DmaCfg<QRS>::STAGE_BYTES;
+static_assert(Q_LDS_GA <= 80 * 1024, "header + ring exceed the LDS of two workgroups per CU");
 // the second product's ring (over the forward's, dead by then): 64 rows x 128 B per stage
 constexpr int Q2_STAGE = QBS * 128, Q2_NBUF = 4, Q2_NI = QBS / 8 / NLOAD;
 static_assert((size_t)Q2_NBUF * Q2_STAGE <= DmaCfg<QRS>::STAGE_BYTES, "second ring inside the first");
@@ -74,6 +92,8 @@ struct BwdQueryArgs {
     const float *lse, *logit_scale, *row_logw;
     BwdQueryWs ws;
     int exclude, B, N, d, C, n_stiles, n_qtiles, nslabs, nchunks, tpc;
+    // (behind everything the kernels without GA read, whose argument offsets stay what they were)
+    float* gap;   // (n_qtiles, 64 n_stiles) column sums of dS per query tile, the GA kernels only
 };
 
 // dP (B,C) and t_b: one workgroup per query.  (The block sum runs in a fixed order: deterministic.)
@@ -97,11 +117,40 @@ __global__ __launch_bounds__(256) void nw_bwd_query_prologue_kernel(const float*
     if (threadIdx.x == 0) tb[b] = t;
 }
 
+// One step of the reduce-scatter over the 16 lanes of a lane group: partner = the lane a DPP control CTL pairs this one
+// with (an involution that flips the lane bit `upper` is read from); a lane keeps the half of its 2 H values that its
+// bit selects, adds the partner's values of that half, and sends the other half.  Plain additions, never contracted with
+// the product that made an operand: GA = 1 and GA = 2 must round alike.
+template <int CTL, int H>
+__device__ __forceinline__ void colsum_step(const float (&in)[2 * H], float (&outv)[H], bool upper) {
+#pragma clang fp contract(off)
+#pragma unroll
+    for (int k = 0; k < H; ++k) {
+        const float keep = upper ? in[H + k] : in[k], send = upper ? in[k] : in[H + k];
+        outv[k] = keep + __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, send), CTL, 0xf, 0xf, false));
+    }
+}
+// v[4r + e] = dS of the lane's query for tile row 16r + 4g + e -> the sum over the 16 lanes i of the group of value i,
+// i.e. of tile row 16 (i >> 2) + 4g + (i & 3)
+__device__ __forceinline__ float colsum16(const float (&v)[16], int i) {
+    float v8[8], v4[4], v2[2], v1[1];
+    colsum_step<0x128, 8>(v, v8, (i & 8) != 0);    // row_ror:8            i ^ 8
+    colsum_step<0x141, 4>(v8, v4, (i & 4) != 0);   // row_half_mirror      i ^ 7
+    colsum_step<0x4e, 2>(v4, v2, (i & 2) != 0);    // quad_perm [2,3,0,1]  i ^ 2
+    colsum_step<0xb1, 1>(v2, v1, (i & 1) != 0);    // quad_perm [1,0,3,2]  i ^ 1
+    return v1[0];
+}
+
 // WGT: a.row_logw holds a natural-log weight per bank row, staged per tile beside the labels (a fourth header array).
-template <int KIND, int NCH, bool WGT>
+// GA (WGT only): 0 -- gq alone; 1 -- gq and the weights' gradient; 2 -- the weights' gradient alone (no second product:
+// NCH is 1 and names nothing, one slab).  See the header.
+template <int KIND, int NCH, bool WGT, int GA = 0>
 __global__ __launch_bounds__(TILE_THREADS, 2) void nw_bwd_query_kernel(const BwdQueryArgs a) {
+    static_assert(GA == 0 || WGT, "the weights' gradient belongs to the weighted head");
+    static_assert(GA != 2 || NCH == 1, "the weights-only kernel has no slab");
     constexpr bool NEED_NORM = (KIND != NW_SCORE_DOT);
-    constexpr int HDR = WGT ? Q_HDR_W : Q_HDR;
+    constexpr bool GQ = GA != 2;
+    constexpr int HDR = GA ? Q_HDR_GA : (WGT ? Q_HDR_W : Q_HDR);
     constexpr float L2E = 1.44269504088896340736f, LN2 = 0.693147180559945309417f;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     float* qn2 = reinterpret_cast<float*>(smem);
@@ -111,6 +160,7 @@ __global__ __launch_bounds__(TILE_THREADS, 2) void nw_bwd_query_kernel(const Bwd
     float* ssc = sn2 + QBS;
     int* lab = reinterpret_cast<int*>(ssc + QBS);
     float* law = reinterpret_cast<float*>(lab + QBS);   // (WGT only)
+    float* gar = law + QBS;                             // (GA only) [tile row][consumer wave]
     float4* stage = reinterpret_cast<float4*>(smem + HDR);
     const char* ring2 = smem + HDR;
 
@@ -125,6 +175,11 @@ __global__ __launch_bounds__(TILE_THREADS, 2) void nw_bwd_query_kernel(const Bwd
     const int kc0 = slab * NCH;
     const int nc = min(NCH, nk - kc0);                 // 32-column chunks of this slab
     const int st_begin = chunk * a.tpc, st_end = min(a.n_stiles, st_begin + a.tpc);
+    // the tile's 64 column sums, by the first loader wave behind the barrier that follows the consumers' writes of `gar`
+    auto store_colsums = [&](int s0) {
+        const float4 v = *reinterpret_cast<const float4*>(gar + NCONS * lane);
+        a.gap[(size_t)qt * ((size_t)a.n_stiles * QBS) + s0 + lane] = ((v.x + v.y) + v.z) + v.w;
+    };
 
     // ---- what a consumer lane knows of its query (query 16 wave + i on the lane)
     const int qrow = 16 * (wave & 3) + i;
@@ -187,6 +242,7 @@ __global__ __launch_bounds__(TILE_THREADS, 2) void nw_bwd_query_kernel(const Bwd
                 const bool check = !whole || tile_end < s0 + QBS;
                 const int rel = s0 + 4 * g - lo;
                 float dw[QRS][4], xr[QRS][4], amax = 0.f;
+                float dsv[GA ? 4 * QRS : 1];   // (GA) the lane's dS, for the column sums
 #pragma unroll
                 for (int r = 0; r < QRS; ++r) {
                     const int4 y4 = *reinterpret_cast<const int4*>(lab + 16 * r + 4 * g);
@@ -220,12 +276,18 @@ __global__ __launch_bounds__(TILE_THREADS, 2) void nw_bwd_query_kernel(const Bwd
                             W = keep ? W : 0.f;
                         }
                         const float dS = W * (dw[r][e] - tq);
+                        if constexpr (GA != 0) dsv[4 * r + e] = b < B ? dS : 0.f;   // (a lane past B repeats query B - 1)
                         float av, rs_unused;
                         bwd_pair_coeff<KIND>(u * LN2, dS, nn[e], scale, nq, inq2, av, rs_unused, rq_acc, gls_acc);
                         xr[r][e] = av * ss[e];
                         amax = fmaxf(amax, fabsf(xr[r][e]));
                     }
                 }
+                if constexpr (GA != 0) {
+                    // the column sums of dS over this wave's 16 queries -> gar[tile row][wave] (only slab 0 writes them out)
+                    if (GA == 2 || slab == 0) gar[NCONS * (16 * (i >> 2) + 4 * g + (i & 3)) + wave] = colsum16(dsv, i);
+                }
+                if constexpr (GQ) {
                 // the row's exponent: raised (a smaller E) when this tile holds a larger coefficient than any before it
                 amax = group4_max(amax);
                 float factor = 1.f;
@@ -261,7 +323,11 @@ __global__ __launch_bounds__(TILE_THREADS, 2) void nw_bwd_query_kernel(const Bwd
                         gacc[c][1] *= fv;
                     }
                 }
+                }   // GQ
             }
+            if constexpr (!GQ) {
+                tile_barrier();   // gar is whole; (behind it the first loader wave reads it, the next tile's header may be written)
+            } else {
             // ================================ consumers: gq tile += A' s' ================================
             auto tr8 = [&](const char* base, int off) {
                 const halfx4 v0 = __builtin_bit_cast(halfx4, __builtin_amdgcn_ds_read_tr16_b64_v4f16(
@@ -291,6 +357,11 @@ __global__ __launch_bounds__(TILE_THREADS, 2) void nw_bwd_query_kernel(const Bwd
                 }
             }
             tile_barrier();   // the ring is free for the next tile
+            }   // GQ
+        } else if constexpr (!GQ) {
+            // ================================ loaders, weights only: nothing to stream; the tile's column sums ================================
+            tile_barrier();
+            if (wave == NCONS) store_colsums(s0);
         } else {
             // ================================ loaders: the tile's rows again, this slab's columns ================================
             const int lw = wave - NCONS;
@@ -317,6 +388,11 @@ __global__ __launch_bounds__(TILE_THREADS, 2) void nw_bwd_query_kernel(const Bwd
             for (int c = 0; c < nc; ++c) {
                 if (c + AHEAD <= nc) wait_vmcnt<(AHEAD - 1) * Q2_NI>(); else wait_vmcnt<0>();
                 tile_barrier();   // stage c is published; the consumers have left stage c - 1
+                if constexpr (GA == 1) {
+                    // (gar was written in front of this product's first barrier.  The store is one more vector-memory
+                    // operation in flight: the counted waits above then wait for one more of the older loads, never fewer)
+                    if (c == 0 && slab == 0 && lw == 0) store_colsums(s0);
+                }
                 if (c + AHEAD < nc) issue(c + AHEAD);
             }
             tile_barrier();
@@ -324,6 +400,11 @@ __global__ __launch_bounds__(TILE_THREADS, 2) void nw_bwd_query_kernel(const Bwd
     }
 
     if (wave >= NCONS) return;
+    if constexpr (!GQ) {   // the weights alone: of the chunk's partial results only the logit scale's
+        gls_acc = group4_sum(gls_acc);
+        if (g == 0 && b < B) a.ws.glsp[(size_t)chunk * B + b] = gls_acc;
+        return;
+    }
     // ---- partial results of this chunk: acc[c][nb][e] of lane (i, g) = gq'[query 16 wave + 4g + e][column 32 (kc0 + c) + 16 nb + i]
 #pragma unroll
     for (int c = 0; c < NCH; ++c) {
@@ -384,6 +465,17 @@ __global__ __launch_bounds__(256) void nw_bwd_query_gls_kernel(const float* __re
     if (threadIdx.x == 0) *out = v;
 }
 
+// ga[j] = sum_qt gap[qt][j], query tiles in ascending order, from +0: a row whose every term is -0 (W = 0 times a
+// negative dW - t) comes out +0.0
+__global__ __launch_bounds__(256) void nw_bwd_logw_finish_kernel(const float* __restrict__ gap, float* __restrict__ ga, int n_qtiles,
+                                                                  int64_t stride, int64_t N) {
+    const int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (j >= N) return;
+    float v = 0.f;
+    for (int qt = 0; qt < n_qtiles; ++qt) v += gap[(int64_t)qt * stride + j];
+    ga[j] = v;
+}
+
 inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
 
 // Slab width and chunk count.  Cost of a workgroup per support tile, in matrix-core time: 3 d/32 for the scores (every
@@ -416,7 +508,21 @@ BwdQueryPlan bwd_query_plan(int64_t B, int64_t N, int64_t d, int row_chunks) {
     return best;
 }
 
-size_t bwd_query_layout(int64_t B, int64_t d, int64_t C, const BwdQueryPlan& p, char* base, BwdQueryWs* ws) {
+// The weights' gradient alone (gq == NULL): one slab and no second product, so a workgroup costs 3 d/32 per support tile
+// -- the scores -- whatever the split, and a chunk's partials are B floats (glsp): nothing for the workspace to cap.
+// Chunks only fill the chip: ceil(256 / n_qtiles) of them, at most the tile count; cost = rounds * tpc * 3 d/32.
+BwdQueryPlan bwd_logw_plan(int64_t B, int64_t N, int row_chunks) {
+    const int64_t n_stiles = (N + QBS - 1) / QBS, n_qtiles = (B + BQ - 1) / BQ;
+    int64_t want = row_chunks > 0 ? row_chunks : (Q_CUS + n_qtiles - 1) / n_qtiles;
+    if (want > n_stiles) want = n_stiles;
+    const int64_t tpc = (n_stiles + want - 1) / want, nchunks = (n_stiles + tpc - 1) / tpc;
+    return {(int)n_stiles, (int)n_qtiles, 1, 1, (int)nchunks, (int)tpc};
+}
+
+// dptab | tb | ascale | rqp | glsp | part | gap: the areas of the query gradient (`gq`: ascale, rqp, part), the chunks'
+// logit-scale terms, and the query tiles' column sums of the weights' gradient (`gap`, when `gap_out` is asked for)
+size_t bwd_query_layout(int64_t B, int64_t d, int64_t C, const BwdQueryPlan& p, char* base, BwdQueryWs* ws, bool gq = true,
+                        float** gap_out = nullptr) {
     size_t off = 0;
     auto take = [&](size_t nfloat) {
         float* ptr = base ? reinterpret_cast<float*>(base + off) : nullptr;
@@ -426,25 +532,30 @@ size_t bwd_query_layout(int64_t B, int64_t d, int64_t C, const BwdQueryPlan& p, 
     BwdQueryWs w;
     w.dptab = take((size_t)B * C);
     w.tb = take((size_t)B);
-    w.ascale = take((size_t)p.nchunks * B);
-    w.rqp = take((size_t)p.nchunks * B);
+    w.ascale = take(gq ? (size_t)p.nchunks * B : 0);
+    w.rqp = take(gq ? (size_t)p.nchunks * B : 0);
     w.glsp = take((size_t)p.nchunks * B);
-    w.part = take((size_t)p.nchunks * B * d);
+    w.part = take(gq ? (size_t)p.nchunks * B * d : 0);
+    float* gap = take(gap_out ? (size_t)p.n_qtiles * QBS * p.n_stiles : 0);
     if (ws) *ws = w;
+    if (gap_out) *gap_out = gap;
     return off;
 }
 
-template <int KIND, int NCH, bool WGT>
+template <int KIND, int NCH, bool WGT, int GA = 0>
 int launch_bwd_query_kernel(const BwdQueryArgs& a, unsigned grid, hipStream_t st) {
-    constexpr size_t LDS = WGT ? Q_LDS_W : Q_LDS;
-    static const bool attr = hipFuncSetAttribute(reinterpret_cast<const void*>(nw_bwd_query_kernel<KIND, NCH, WGT>),
+    constexpr size_t LDS = GA ? Q_LDS_GA : (WGT ? Q_LDS_W : Q_LDS);
+    static const bool attr = hipFuncSetAttribute(reinterpret_cast<const void*>(nw_bwd_query_kernel<KIND, NCH, WGT, GA>),
                                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS) == hipSuccess;
     if (!attr) return NW_ERR_LAUNCH;
-    hipLaunchKernelGGL((nw_bwd_query_kernel<KIND, NCH, WGT>), dim3(grid), dim3(TILE_THREADS), LDS, st, a);
+    hipLaunchKernelGGL((nw_bwd_query_kernel<KIND, NCH, WGT, GA>), dim3(grid), dim3(TILE_THREADS), LDS, st, a);
     return NW_OK;
 }
+// ga: 0 -- gq alone; 1 -- gq and the weights' gradient; 2 -- the weights' gradient alone (the kernel's GA)
 template <int KIND>
-int launch_bwd_query_kind(const BwdQueryArgs& a, int nch, unsigned grid, hipStream_t st) {
+int launch_bwd_query_kind(const BwdQueryArgs& a, int nch, unsigned grid, hipStream_t st, int ga) {
+    if (ga == 2) return launch_bwd_query_kernel<KIND, 1, true, 2>(a, grid, st);
+    if (ga == 1) return nch == 8 ? launch_bwd_query_kernel<KIND, 8, true, 1>(a, grid, st) : launch_bwd_query_kernel<KIND, 4, true, 1>(a, grid, st);
     if (a.row_logw) return nch == 8 ? launch_bwd_query_kernel<KIND, 8, true>(a, grid, st) : launch_bwd_query_kernel<KIND, 4, true>(a, grid, st);
     return nch == 8 ? launch_bwd_query_kernel<KIND, 8, false>(a, grid, st) : launch_bwd_query_kernel<KIND, 4, false>(a, grid, st);
 }
@@ -461,28 +572,45 @@ size_t bwd_query_workspace_bytes(int64_t B, int64_t N, int64_t d, int64_t C, int
     return bwd_query_layout(B, d, C, bwd_query_plan(B, N, d, row_chunks), nullptr, nullptr);
 }
 
+size_t bwd_logw_workspace_bytes(int64_t B, int64_t N, int64_t d, int64_t C, int row_chunks, bool want_gq) {
+    if (B <= 0 || !bwd_query_shape_ok(B, N, d, C)) return 0;
+    float* gap;
+    return bwd_query_layout(B, d, C, want_gq ? bwd_query_plan(B, N, d, row_chunks) : bwd_logw_plan(B, N, row_chunks), nullptr, nullptr,
+                            want_gq, &gap);
+}
+
+// c.glogw: the weights' gradient as well (nw_bwd_query_logw_f32), with the plan, the areas and the launches of the query
+// gradient when c.gq is set -- its bits are then those of the call without glogw -- and the weights-only plan when not
 int launch_bwd_query(const BwdQueryCall& c) {
     hipStream_t st = c.st;
-    const BwdQueryPlan p = bwd_query_plan(c.B, c.N, c.d, c.row_chunks);
+    const bool want_gq = c.gq != nullptr;
+    const int ga = !c.glogw ? 0 : (want_gq ? 1 : 2);
+    const BwdQueryPlan p = want_gq ? bwd_query_plan(c.B, c.N, c.d, c.row_chunks) : bwd_logw_plan(c.B, c.N, c.row_chunks);
     BwdQueryWs ws;
-    const size_t need = bwd_query_layout(c.B, c.d, c.C, p, static_cast<char*>(c.workspace), &ws);
+    float* gap = nullptr;
+    const size_t need = bwd_query_layout(c.B, c.d, c.C, p, static_cast<char*>(c.workspace), &ws, want_gq, ga ? &gap : nullptr);
     if (!c.workspace || c.workspace_bytes < need) return NW_ERR_WORKSPACE;
     const int64_t wgs = (int64_t)p.n_qtiles * p.nslabs * p.nchunks;
     if (wgs > 0x7fffffffLL || (c.B * c.d / 4 + 255) / 256 > 0x7fffffffLL) return NW_ERR_UNSUPPORTED;
     hipLaunchKernelGGL(nw_bwd_query_prologue_kernel, dim3((unsigned)c.B), dim3(256), 0, st, c.out, c.gout, ws.dptab, ws.tb, c.C);
     const BwdQueryArgs a = {c.q, c.s_split, c.s_scale, c.s_norm2, c.sy, c.row_lo, c.row_hi, c.lse, c.logit_scale_dev, c.row_logw, ws,
-                            c.exclude, (int)c.B, (int)c.N, (int)c.d, (int)c.C, p.n_stiles, p.n_qtiles, p.nslabs, p.nchunks, p.tpc};
+                            c.exclude, (int)c.B, (int)c.N, (int)c.d, (int)c.C, p.n_stiles, p.n_qtiles, p.nslabs, p.nchunks, p.tpc,
+                            gap};
     int rc;
     switch (c.kind) {
-        case NW_SCORE_EUCLIDEAN: rc = launch_bwd_query_kind<NW_SCORE_EUCLIDEAN>(a, p.nch, (unsigned)wgs, st); break;
-        case NW_SCORE_HYPERSPHERE: rc = launch_bwd_query_kind<NW_SCORE_HYPERSPHERE>(a, p.nch, (unsigned)wgs, st); break;
-        case NW_SCORE_COSINE: rc = launch_bwd_query_kind<NW_SCORE_COSINE>(a, p.nch, (unsigned)wgs, st); break;
-        case NW_SCORE_DOT: rc = launch_bwd_query_kind<NW_SCORE_DOT>(a, p.nch, (unsigned)wgs, st); break;
-        default: rc = launch_bwd_query_kind<NW_SCORE_CLIP>(a, p.nch, (unsigned)wgs, st); break;
+        case NW_SCORE_EUCLIDEAN: rc = launch_bwd_query_kind<NW_SCORE_EUCLIDEAN>(a, p.nch, (unsigned)wgs, st, ga); break;
+        case NW_SCORE_HYPERSPHERE: rc = launch_bwd_query_kind<NW_SCORE_HYPERSPHERE>(a, p.nch, (unsigned)wgs, st, ga); break;
+        case NW_SCORE_COSINE: rc = launch_bwd_query_kind<NW_SCORE_COSINE>(a, p.nch, (unsigned)wgs, st, ga); break;
+        case NW_SCORE_DOT: rc = launch_bwd_query_kind<NW_SCORE_DOT>(a, p.nch, (unsigned)wgs, st, ga); break;
+        default: rc = launch_bwd_query_kind<NW_SCORE_CLIP>(a, p.nch, (unsigned)wgs, st, ga); break;
     }
     if (rc != NW_OK) return rc;
-    hipLaunchKernelGGL(nw_bwd_query_finish_kernel, dim3((unsigned)((c.B * c.d / 4 + 255) / 256)), dim3(256), 0, st, ws.part, ws.rqp,
-                       ws.ascale, c.q, c.gq, p.nchunks, c.B, c.d);
+    if (want_gq)
+        hipLaunchKernelGGL(nw_bwd_query_finish_kernel, dim3((unsigned)((c.B * c.d / 4 + 255) / 256)), dim3(256), 0, st, ws.part,
+                           ws.rqp, ws.ascale, c.q, c.gq, p.nchunks, c.B, c.d);
+    if (ga)
+        hipLaunchKernelGGL(nw_bwd_logw_finish_kernel, dim3((unsigned)((c.N + 255) / 256)), dim3(256), 0, st, gap, c.glogw, p.n_qtiles,
+                           (int64_t)p.n_stiles * QBS, c.N);
     if (c.glogit_scale) {
         if (c.kind == NW_SCORE_CLIP)
             hipLaunchKernelGGL(nw_bwd_query_gls_kernel, dim3(1), dim3(256), 0, st, ws.glsp, c.glogit_scale, p.nchunks, c.B);

@@ -188,7 +188,19 @@ class NWNet(nn.Module):
         if self.balance_full == "weights":
             self.set_support_weights(ops.class_balance_logw(self.full_y, self.n_classes))
 
-    def set_support_weights(self, log_w=None):
+    @property
+    def support_weights(self):
+        """The (N,) fp32 log-weights in force, or None -- as a constant: of a learnable set (set_support_weights(...,
+        learnable=True)) the current values of the parameter ``support_logw``, detached."""
+        p = self._parameters.get('support_logw')
+        return p.detach() if p is not None else self.__dict__.get('_support_weights')
+
+    @support_weights.setter
+    def support_weights(self, w):
+        self._parameters.pop('support_logw', None)       # a learnable set ends with the weights it was registered for
+        self.__dict__['_support_weights'] = w
+
+    def set_support_weights(self, log_w=None, learnable=False):
         """Not in the reference: a prior weight per row of precompute()'s bank.  ``log_w``: (N,) float tensor over the rows of
         ``full_feat``, the natural logs a_j = log w_j; ``None`` clears them.  The 'full' head becomes the head of
         score + a (ops.nw_head_window has the formula): -inf switches a row off (soft deletion, label-noise screening after
@@ -196,6 +208,17 @@ class NWNet(nn.Module):
         ops.class_balance_logw(full_y, n_classes) gives an unbalanced bank a flat class prior, finite values are
         importance / confidence / recency weights.  Checked once, here (one device synchronisation): NaN or +inf raise
         ValueError.  The weights are a constant: no gradient flows to them.
+
+        ``learnable=True`` makes them LEARNED instead (importance / confidence weights against label noise, data valuation,
+        a recency decay): they are registered as the nn.Parameter ``support_logw`` -- in parameters() and state_dict() from
+        this call on, not before -- forward_bank passes the parameter with its graph, so a loss on its output puts a
+        gradient on ``support_logw`` (ops.nw_head_bank: no (B, N) matrix; only the weights learning skips the second pass
+        over the bank), while predict('full'), predict_loo and leave_out read the current values detached;
+        ``support_weights`` is that detached view.  The values must be finite: an optimizer's weight decay turns -inf
+        into NaN -- to switch rows off, keep a constant -inf mask OUTSIDE the parameter (ops.nw_head_bank(...,
+        row_logw=net.support_logw + mask)).  precompute() clears learnable weights like any others, parameter included:
+        set them again afterwards and rebuild the optimizer's parameter group.  A full_precision="fp16" bank has no route
+        for this gradient: forward_bank raises NWHipError.  ``learnable=False`` is the behaviour described above, unchanged.
 
         Honoured by predict(x, 'full') with and without leave_out, by predict_loo and by forward_bank.  Kept by
         refresh_bank (rows keep their identity); cleared by precompute().  NOT seen by get_neighbors, explain and the
@@ -218,11 +241,19 @@ class NWNet(nn.Module):
                              f"{tuple(w.shape)}")
         if bool((torch.isnan(w) | (w == float("inf"))).any()):
             raise ValueError("set_support_weights: log_w holds NaN or +inf (finite values and -inf only)")
-        self.support_weights = w
+        if learnable and not bool(torch.isfinite(w).all()):
+            raise ValueError("set_support_weights(learnable=True): log_w must be finite -- an optimizer's weight decay turns "
+                             "-inf into NaN; switch rows off by adding a constant -inf mask outside the parameter")
+        self.support_weights = None if learnable else w   # (drops a parameter of an earlier call)
+        if learnable:
+            self.support_logw = nn.Parameter(w)           # the values live in the parameter alone
 
-    def _weights_for(self, what):
-        """The support weights for a call over precompute()'s resident bank, or None; a sharded bank in front of it refuses."""
-        w = getattr(self, 'support_weights', None)
+    def _weights_for(self, what, graph=False):
+        """The support weights for a call over precompute()'s resident bank, or None; a sharded bank in front of it refuses.
+        ``graph``: learnable weights as the parameter itself, for a call that differentiates (forward_bank)."""
+        w = self._parameters.get('support_logw') if graph else None
+        if w is None:
+            w = getattr(self, 'support_weights', None)
         if w is not None and getattr(self, 'sharded_bank', None) is not None:
             raise ops.NWHipError(f"{what}: support weights are set and the bank is sharded; a sharded bank has no weights "
                                  "(set_support_weights(None), or precompute())")
@@ -316,7 +347,8 @@ class NWNet(nn.Module):
         The bank is a CONSTANT here: it holds the features of the weights precompute() saw and goes stale as the weights
         move; the caller decides when to call precompute() again, or writes each batch's features back with
         refresh_bank(rows) -- they are kept, detached, in ``bank_features`` (a view, not a copy).  Support weights
-        (set_support_weights) are honoured, as a constant.  A sharded bank, a missing bank and a custom kernel
+        (set_support_weights) are honoured: as a constant, or, set with learnable=True, as the parameter ``support_logw``
+        with its graph (a gradient lands on it).  A sharded bank, a missing bank and a custom kernel
         module are refused (NWHipError), like predict_loo.  A full_precision="fp16" bank or a bank whose labels are not
         class-sorted takes ops.nw_head's route through the score matrix without ``leave_out`` and is refused with it."""
         what = "forward_bank"
@@ -327,7 +359,7 @@ class NWNet(nn.Module):
         sfeat, sy, cache = self._resident_bank(what, qfeat.device)
         window = None if leave_out is None else self._leave_out_window(leave_out, qfeat, what)
         out = ops.nw_head_bank(qfeat, sfeat, sy, self.n_classes, cache, self.kernel.kind, self.kernel._logit_scale(),
-                               row_window=window, exclude=window is not None, row_logw=self._weights_for(what))
+                               row_window=window, exclude=window is not None, row_logw=self._weights_for(what, graph=True))
         return (out, torch.full((len(x),), True)) if self.return_mask else out
 
     def refresh_bank(self, rows, feats=None, momentum=0.0):

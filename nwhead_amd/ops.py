@@ -386,7 +386,7 @@ def head_window_route(*, split, sorted_copy, shape, pad, width, B, n_classes):
     return "fused" if fused else "matrix"
 
 
-def head_weighted_route(*, split, sorted_copy, shape, pad, width, B, n_classes, grad=False):
+def head_weighted_route(*, split, sorted_copy, shape, pad, width, B, n_classes, grad=False, grad_logw=False):
     """Which route serves a head with SUPPORT WEIGHTS (``row_logw``), beside head_window_route / head_bank_route and over the
     same plain facts: "fused" (nw_fwd_weighted_f32, and nw_bwd_query_weighted_f32 for the gradient: the weight is added in the
     tile epilogue, no score matrix) exactly when the windowed head would be fused -- both kernels take the same shapes, and
@@ -394,10 +394,14 @@ def head_weighted_route(*, split, sorted_copy, shape, pad, width, B, n_classes, 
     "matrix" for the forward (nw_scores + a (+ the window's mask) + nw_aggregate_f32, with the dead-query fix-up of
     nw_head_window).  The gradient (``grad``) has no matrix route that knows the weights -- nw_head's saves the scores its
     distance derivative is taken at, and they would be the weighted ones -- so it is None there, with a window or
-    without: the caller refuses."""
+    without: the caller refuses.  ``grad_logw`` -- the gradient to the WEIGHTS is wanted (nw_bwd_query_logw_f32, with or
+    without ``grad`` for the queries) -- is served exactly where the query gradient is, "fused", and None elsewhere (an
+    fp16 or norms-only bank, a class-sorted copy, N <= 25, a width that is no multiple of 32): the caller refuses and names
+    nw_scores + a + nw_aggregate.  No size gate: at both shapes measured the fused weights-only step is faster than that
+    composition and never holds a (B, N) buffer."""
     fused = head_window_route(split=split, sorted_copy=sorted_copy, shape=shape, pad=pad, width=width, B=B,
                               n_classes=n_classes) == "fused"
-    return "fused" if fused else (None if grad else "matrix")
+    return "fused" if fused else (None if (grad or grad_logw) else "matrix")
 
 
 def _row_logw(row_logw, N, device, what):
@@ -1030,8 +1034,9 @@ def bank_update_refusal(*, split, packed, sorted_copy, shape, pad, width, R):
 
 
 class _NWHeadBankFn(torch.autograd.Function):
-    """autograd node of nw_head_bank: today's inference call forward, nw_bwd_query_f32 backward.  Saves the queries, lse,
-    out and the window: nothing of size B x N."""
+    """autograd node of nw_head_bank: today's inference call forward, nw_bwd_query_f32 backward (with support weights
+    nw_bwd_query_weighted_f32, or nw_bwd_query_logw_f32 when the weights need a gradient too: it goes to the 10th input, the
+    caller's tensor).  Saves the queries, lse, out and the window: nothing of size B x N."""
 
     @staticmethod
     def forward(ctx, q, logit_scale, call, n_classes, kind_id, window, exclude, bank=None, logw=None, logw_src=None):
@@ -1090,6 +1095,20 @@ class _NWHeadBankFn(torch.autograd.Function):
                                "recomputes the weighted scores from it: call backward() first, then change the weights")
         dev = qc.device
         g = _f32c(gout)
+        if ctx.logw is not None and ctx.needs_input_grad[9]:
+            # the weights' gradient as well: one entry, without gq (no second pass over the bank) when only the weights learn
+            want_gq = ctx.needs_input_grad[0] or (has_ls and ctx.needs_input_grad[1])
+            gq = torch.empty_like(qc) if want_gq else None
+            gls = torch.empty((), dtype=torch.float32, device=dev) if has_ls else None
+            ga = torch.empty(N, dtype=torch.float32, device=dev)
+            ws_bytes = lib.nw_bwd_logw_workspace_bytes(B, N, d, C, 0, int(want_gq))
+            ws = _workspace(ws_bytes, dev)
+            with _OnDevice(dev):
+                _lib.check(lib.nw_bwd_query_logw_f32(_ptr(qc), _ptr(ssplit), _ptr(sscale), _ptr(sn2), _ptr(syc), _ptr(ctx.logw[0]),
+                                                     _ptr(lo), _ptr(hi), exclude, _ptr(lse), _ptr(out), _ptr(g), _ptr(gq), _ptr(ga),
+                                                     _ptr(gls), _ptr(ws), ws_bytes, B, N, d, C, kind_id, _ptr(ls), 0, _stream(qc)),
+                           "nw_bwd_query_logw_f32")
+            return gq, gls, None, None, None, None, None, None, None, ga.to(ctx.logw[1].dtype)
         gq = torch.empty_like(qc)
         gls = torch.empty((), dtype=torch.float32, device=dev) if has_ls else None
         ws_bytes = lib.nw_bwd_query_workspace_bytes(B, N, d, C, 0)
@@ -1122,10 +1141,18 @@ def nw_head_bank(q, s, sy, n_classes, bank, kind="euclidean", logit_scale=None, 
     the queries pad to its width; otherwise (an fp16 or norms-only bank, unsorted labels, N <= 25, a width that is no
     multiple of 32 after padding) nw_head's route without a window, NWHipError with one.
 
-    row_logw: SUPPORT WEIGHTS as in nw_head_window, a constant like the bank: no gradient flows to them, and writing the
-    tensor in place between forward and backward is refused like a bank update.  Forward nw_fwd_weighted_f32, backward
-    nw_bwd_query_weighted_f32, wherever the rule above gives the kernel (head_weighted_route); where it does not, the
-    gradient is refused with or without a window (NWHipError: nw_head's matrix route does not know the weights)."""
+    row_logw: SUPPORT WEIGHTS as in nw_head_window.  A tensor that does not require grad is a constant like the bank;
+    writing it in place between forward and backward is refused like a bank update, either way.  Forward
+    nw_fwd_weighted_f32, backward nw_bwd_query_weighted_f32, wherever the rule above gives the kernel
+    (head_weighted_route); where it does not, the gradient is refused with or without a window (NWHipError: nw_head's
+    matrix route does not know the weights).
+    LEARNABLE weights: when ``row_logw.requires_grad`` -- a leaf or any graph tensor, ``beta[labels]``, ``param + mask`` --
+    the gradient flows to it as well, in its dtype: ga_j = sum_b W_bj (dP_b[y_j] - t_b), the column sums of what the query
+    gradient contracts with the bank rows, from the same kernel (nw_bwd_query_logw_f32, DESIGN 4.8i: no (B, N) matrix; a
+    row at -inf and a row no query admits get exactly 0).  One backward entry per case: that one when the weights need a
+    gradient -- without gq, i.e. without the second pass over the bank rows, when neither `q` nor a clip scale does --
+    and the entries above, unchanged, otherwise.  Where the kernel does not serve (the cases above) the gradient to the
+    weights is refused (NWHipError); without a window nw_scores + a + nw_aggregate is the way through the score matrix."""
     if not isinstance(bank, SplitBank):
         raise TypeError("nw_head_bank runs over a prepared bank: pass ops.SplitBank(support)")
     grad = torch.is_grad_enabled()
@@ -1138,7 +1165,8 @@ def nw_head_bank(q, s, sy, n_classes, bank, kind="euclidean", logit_scale=None, 
     kid = _kind_id(kind)
     if kid == SCORE_KINDS["clip"] and logit_scale is None:
         raise ValueError("clip kernel needs logit_scale")
-    if not (grad and (q.requires_grad or (logit_scale is not None and logit_scale.requires_grad))):
+    grad_logw = grad and torch.is_tensor(row_logw) and row_logw.requires_grad
+    if not (grad and (q.requires_grad or (logit_scale is not None and logit_scale.requires_grad) or grad_logw)):
         return nw_head(q, s, sy, n_classes, kind, logit_scale, support_cache=bank, row_window=row_window, exclude=exclude,
                        row_logw=row_logw)
     C = int(n_classes)
@@ -1147,6 +1175,10 @@ def nw_head_bank(q, s, sy, n_classes, bank, kind="euclidean", logit_scale=None, 
     why = head_bank_refusal(split=bank.split is not None, sorted_copy=bank.sorted_rows is not None, shape=bank.shape,
                             pad=bank.pad, width=q.shape[1], B=q.shape[0], n_classes=C)
     if why is not None:
+        if grad_logw:
+            raise NWHipError(f"nw_head_bank(row_logw=...) has no route for the gradient to the weights here: {why}.  Without "
+                             "a window the composition ops.nw_aggregate(ops.nw_scores(q, s, support_cache=bank) + a, sy, C) "
+                             "(nw_scores + a + nw_aggregate) differentiates in a through the (B, N) score matrix")
         if logw is not None:
             raise NWHipError(f"nw_head_bank(row_logw=...) has no gradient route here: {why}")
         if row_window is None:
