@@ -563,8 +563,7 @@ int launch_bwd_query_kind(const BwdQueryArgs& a, int nch, unsigned grid, hipStre
 }  // namespace
 
 bool bwd_query_shape_ok(int64_t B, int64_t N, int64_t d, int64_t C) {
-    return N > 25 && C >= 1 && d >= 32 && d % 32 == 0 && d <= (1 << 20) && B <= 0x7fffffffLL - BQ && N <= 0x7fffffffLL - QBS
-           && C < (1 << 30);
+    return bank_head_shape_ok(N, d, C) && B <= 0x7fffffffLL - BQ && N <= 0x7fffffffLL - QBS && C < (1 << 30);
 }
 
 size_t bwd_query_workspace_bytes(int64_t B, int64_t N, int64_t d, int64_t C, int row_chunks) {

@@ -237,33 +237,98 @@ extern "C" int nw_fwd_f32(const float* q, const float* s, const int64_t* sy, con
                    B, N, d, C, kind, logit_scale_dev, sup_batched, labels_batched, static_cast<hipStream_t>(stream));
 }
 
-// The head over a per-query row window of a split bank (fused.hip, OUT_WIN): nw_knn_window_f32's regime, nw_fwd_f32's
-// workspace, no options (nothing of nw_fwd_opts applies: split rows at every size, no run tables, no persistent kernel).
+// The head over a resident split bank and its gradients (fused.hip OUT_WIN / OUT_WGT, bwd_query.hip WGT / GA): one argument
+// rule for the two forward entries and one for the three backward ones.  An entry builds its call record and names the
+// optional operands it REQUIRES; the order of the checks, which decides the status of a call with several faults, is here.
+// The regime of all five, stated here and nowhere else (bwd_query_shape_ok adds the integer ranges of the backward's index
+// arithmetic; the forward leaves its own to fused_eligible, asked after B == 0 has answered):
+bool nw::bank_head_shape_ok(int64_t N, int64_t d, int64_t C) { return N > 25 && C >= 1 && d >= 32 && d % 32 == 0 && d <= (1 << 20); }
+
+namespace {
+enum { NEED_WINDOW = 1, NEED_LOGW = 2, NEED_GQ = 4, NEED_GLOGW = 8 };
+inline uintptr_t addr(const void* p) { return reinterpret_cast<uintptr_t>(p); }
+
+// The forward: nw_fwd_f32's workspace, no options (nothing of nw_fwd_opts applies: split rows at every size, no run tables,
+// no persistent kernel).  row_logw is read in float4s from row offsets that are multiples of four: 16-byte aligned
+struct BankFwdCall {
+    const float *q, *s_split, *s_scale, *s_norm2;
+    const int64_t* sy;
+    const float* row_logw;            // or null
+    const int32_t *row_lo, *row_hi;   // both or neither; exclude reaches the kernel only with them
+    int exclude;
+    float *out, *lse_out;
+    void* workspace;
+    size_t workspace_bytes;
+    int64_t B, N, d, C;
+    int kind;
+    const float* logit_scale_dev;
+    void* stream;
+};
+int bank_fwd_checked(const BankFwdCall& c, int needs) {
+    if (c.B < 0 || c.N < 0 || c.d < 0 || c.C < 0) return NW_ERR_INVALID_ARG;
+    if ((c.row_lo != nullptr) != (c.row_hi != nullptr) || ((needs & NEED_WINDOW) && !c.row_lo)) return NW_ERR_INVALID_ARG;
+    if (bad_kind(c.kind)) return NW_ERR_UNSUPPORTED;
+    if (!nw::bank_head_shape_ok(c.N, c.d, c.C)) return NW_ERR_UNSUPPORTED;
+    if (c.B == 0) return NW_OK;       // before any pointer is looked at
+    if (!c.q || !c.s_split || !c.s_scale || !c.s_norm2 || !c.sy || !c.out || ((needs & NEED_LOGW) && !c.row_logw))
+        return NW_ERR_INVALID_ARG;
+    if (c.kind == NW_SCORE_CLIP && !c.logit_scale_dev) return NW_ERR_INVALID_ARG;
+    if (!nw::fused_eligible(c.q, c.s_split, c.B, c.N, c.d, c.C)) return NW_ERR_UNSUPPORTED;   // alignment, sizes past the tile kernels
+    if (addr(c.row_logw) & 15) return NW_ERR_UNSUPPORTED;
+    const nw::FwdLayout L = nw::fwd_layout(c.B, c.N, c.d, c.C, c.workspace);
+    if (!L.fits(c.workspace_bytes)) return NW_ERR_WORKSPACE;
+    if (addr(c.workspace) & 15) return NW_ERR_UNSUPPORTED;
+    nw::FusedArgs a = {c.q, c.s_split, c.sy, c.s_norm2, c.s_scale, c.logit_scale_dev, c.out, nullptr, c.lse_out, nullptr, nullptr,
+                       nullptr, &L, (int)c.B, (int)c.N, (int)c.d, (int)c.C, static_cast<hipStream_t>(c.stream), nullptr,
+                       c.row_lo, c.row_hi, c.row_lo && c.exclude != 0, c.row_logw};
+    return nw::launch_fused(a, nw::FORM_SPLIT, c.kind);
+}
+
+// The backward, over the launcher's own record: a null gq / glogw / row_logw adds nothing to the alignment test; with glogw
+// the workspace is the weights' (smaller without gq)
+int bank_bwd_checked(const nw::BwdQueryCall& c, int needs) {
+    if (c.B < 0 || c.N < 0 || c.d < 0 || c.C < 0 || c.row_chunks < 0) return NW_ERR_INVALID_ARG;
+    if ((c.row_lo != nullptr) != (c.row_hi != nullptr)) return NW_ERR_INVALID_ARG;
+    if (bad_kind(c.kind)) return NW_ERR_UNSUPPORTED;
+    if (!nw::bwd_query_shape_ok(c.B, c.N, c.d, c.C)) return NW_ERR_UNSUPPORTED;
+    if (c.B == 0) return NW_OK;       // before any pointer is looked at: nothing is touched, glogw included
+    if (!c.q || !c.s_split || !c.s_scale || !c.s_norm2 || !c.sy || !c.lse || !c.out || !c.gout ||
+        ((needs & NEED_LOGW) && !c.row_logw) || ((needs & NEED_GQ) && !c.gq) || ((needs & NEED_GLOGW) && !c.glogw))
+        return NW_ERR_INVALID_ARG;
+    if (c.kind == NW_SCORE_CLIP && !c.logit_scale_dev) return NW_ERR_INVALID_ARG;
+    if ((addr(c.q) | addr(c.s_split) | addr(c.gq) | addr(c.row_logw) | addr(c.glogw)) & 15) return NW_ERR_UNSUPPORTED;
+    const size_t need = c.glogw ? nw::bwd_logw_workspace_bytes(c.B, c.N, c.d, c.C, c.row_chunks, c.gq != nullptr)
+                                : nw::bwd_query_workspace_bytes(c.B, c.N, c.d, c.C, c.row_chunks);
+    if (!c.workspace || c.workspace_bytes < need) return NW_ERR_WORKSPACE;
+    if (addr(c.workspace) & 15) return NW_ERR_UNSUPPORTED;
+    return nw::launch_bwd_query(c);
+}
+}  // namespace
+
 extern "C" int nw_fwd_window_f32(const float* q, const float* s_split, const float* s_scale, const float* s_norm2,
                                  const int64_t* sy, const int32_t* row_lo, const int32_t* row_hi, int exclude, float* out,
                                  float* lse_out, void* workspace, size_t workspace_bytes, int64_t B, int64_t N, int64_t d,
                                  int64_t C, int kind, const float* logit_scale_dev, void* stream) {
-    if (B < 0 || N < 0 || d < 0 || C < 0) return NW_ERR_INVALID_ARG;
-    if (!row_lo || !row_hi) return NW_ERR_INVALID_ARG;   // (the head without a window is nw_fwd_f32)
-    if (bad_kind(kind)) return NW_ERR_UNSUPPORTED;
-    if (N <= 25 || C < 1 || d < 32 || d % 32 != 0 || d > (1 << 20)) return NW_ERR_UNSUPPORTED;
-    if (B == 0) return NW_OK;
-    if (!q || !s_split || !s_scale || !s_norm2 || !sy || !out) return NW_ERR_INVALID_ARG;
-    if (kind == NW_SCORE_CLIP && !logit_scale_dev) return NW_ERR_INVALID_ARG;
-    if (!nw::fused_eligible(q, s_split, B, N, d, C)) return NW_ERR_UNSUPPORTED;   // alignment, sizes past the tile kernels
-    const nw::FwdLayout L = nw::fwd_layout(B, N, d, C, workspace);
-    if (!L.fits(workspace_bytes)) return NW_ERR_WORKSPACE;
-    if (reinterpret_cast<uintptr_t>(workspace) & 15) return NW_ERR_UNSUPPORTED;
-    nw::FusedArgs a = {q, s_split, sy, s_norm2, s_scale, logit_scale_dev, out, nullptr, lse_out, nullptr, nullptr, nullptr,
-                       &L, (int)B, (int)N, (int)d, (int)C, static_cast<hipStream_t>(stream), nullptr,
-                       row_lo, row_hi, exclude != 0};
-    return nw::launch_fused(a, nw::FORM_SPLIT, kind);
+    return bank_fwd_checked({q, s_split, s_scale, s_norm2, sy, nullptr, row_lo, row_hi, exclude, out, lse_out, workspace,
+                             workspace_bytes, B, N, d, C, kind, logit_scale_dev, stream}, NEED_WINDOW);
 }
 
-// The query gradient over a resident split bank (bwd_query.hip): nw_fwd_window_f32's regime, a workspace of its own.
+extern "C" int nw_fwd_weighted_f32(const float* q, const float* s_split, const float* s_scale, const float* s_norm2,
+                                   const int64_t* sy, const float* row_logw, const int32_t* row_lo, const int32_t* row_hi,
+                                   int exclude, float* out, float* lse_out, void* workspace, size_t workspace_bytes, int64_t B,
+                                   int64_t N, int64_t d, int64_t C, int kind, const float* logit_scale_dev, void* stream) {
+    return bank_fwd_checked({q, s_split, s_scale, s_norm2, sy, row_logw, row_lo, row_hi, exclude, out, lse_out, workspace,
+                             workspace_bytes, B, N, d, C, kind, logit_scale_dev, stream}, NEED_LOGW);
+}
+
 extern "C" size_t nw_bwd_query_workspace_bytes(int64_t B, int64_t N, int64_t d, int64_t C, int row_chunks) {
     if (B <= 0 || N < 0 || d < 0 || C < 0) return 0;
     return nw::bwd_query_workspace_bytes(B, N, d, C, row_chunks);
+}
+
+extern "C" size_t nw_bwd_logw_workspace_bytes(int64_t B, int64_t N, int64_t d, int64_t C, int row_chunks, int want_gq) {
+    if (B <= 0 || N < 0 || d < 0 || C < 0) return 0;
+    return nw::bwd_logw_workspace_bytes(B, N, d, C, row_chunks, want_gq != 0);
 }
 
 extern "C" int nw_bwd_query_f32(const float* q, const float* s_split, const float* s_scale, const float* s_norm2,
@@ -271,45 +336,9 @@ extern "C" int nw_bwd_query_f32(const float* q, const float* s_split, const floa
                                 const float* lse, const float* out, const float* gout, float* gq, float* glogit_scale,
                                 void* workspace, size_t workspace_bytes, int64_t B, int64_t N, int64_t d, int64_t C,
                                 int kind, const float* logit_scale_dev, int row_chunks, void* stream) {
-    if (B < 0 || N < 0 || d < 0 || C < 0 || row_chunks < 0) return NW_ERR_INVALID_ARG;
-    if ((row_lo != nullptr) != (row_hi != nullptr)) return NW_ERR_INVALID_ARG;
-    if (bad_kind(kind)) return NW_ERR_UNSUPPORTED;
-    if (!nw::bwd_query_shape_ok(B, N, d, C)) return NW_ERR_UNSUPPORTED;
-    if (B == 0) return NW_OK;
-    if (!q || !s_split || !s_scale || !s_norm2 || !sy || !lse || !out || !gout || !gq) return NW_ERR_INVALID_ARG;
-    if (kind == NW_SCORE_CLIP && !logit_scale_dev) return NW_ERR_INVALID_ARG;
-    if ((reinterpret_cast<uintptr_t>(q) | reinterpret_cast<uintptr_t>(s_split) | reinterpret_cast<uintptr_t>(gq)) & 15)
-        return NW_ERR_UNSUPPORTED;
-    if (!workspace || workspace_bytes < nw::bwd_query_workspace_bytes(B, N, d, C, row_chunks)) return NW_ERR_WORKSPACE;
-    if (reinterpret_cast<uintptr_t>(workspace) & 15) return NW_ERR_UNSUPPORTED;
-    return nw::launch_bwd_query({q, s_split, s_scale, s_norm2, sy, row_lo, row_hi, exclude, lse, out, gout, gq, glogit_scale,
-                                 workspace, workspace_bytes, B, N, d, C, kind, logit_scale_dev, row_chunks,
-                                 static_cast<hipStream_t>(stream)});
-}
-
-// The head and its query gradient with a log-weight per bank row (fused.hip OUT_WGT, bwd_query.hip WGT): the regimes,
-// workspaces and status codes of nw_fwd_window_f32 / nw_bwd_query_f32, the window optional in both.  row_logw is read in
-// float4s from row offsets that are multiples of four: it must be 16-byte aligned like the other operands.
-extern "C" int nw_fwd_weighted_f32(const float* q, const float* s_split, const float* s_scale, const float* s_norm2,
-                                   const int64_t* sy, const float* row_logw, const int32_t* row_lo, const int32_t* row_hi,
-                                   int exclude, float* out, float* lse_out, void* workspace, size_t workspace_bytes, int64_t B,
-                                   int64_t N, int64_t d, int64_t C, int kind, const float* logit_scale_dev, void* stream) {
-    if (B < 0 || N < 0 || d < 0 || C < 0) return NW_ERR_INVALID_ARG;
-    if ((row_lo != nullptr) != (row_hi != nullptr)) return NW_ERR_INVALID_ARG;
-    if (bad_kind(kind)) return NW_ERR_UNSUPPORTED;
-    if (N <= 25 || C < 1 || d < 32 || d % 32 != 0 || d > (1 << 20)) return NW_ERR_UNSUPPORTED;
-    if (B == 0) return NW_OK;
-    if (!q || !s_split || !s_scale || !s_norm2 || !sy || !row_logw || !out) return NW_ERR_INVALID_ARG;
-    if (kind == NW_SCORE_CLIP && !logit_scale_dev) return NW_ERR_INVALID_ARG;
-    if (!nw::fused_eligible(q, s_split, B, N, d, C)) return NW_ERR_UNSUPPORTED;   // alignment, sizes past the tile kernels
-    if (reinterpret_cast<uintptr_t>(row_logw) & 15) return NW_ERR_UNSUPPORTED;
-    const nw::FwdLayout L = nw::fwd_layout(B, N, d, C, workspace);
-    if (!L.fits(workspace_bytes)) return NW_ERR_WORKSPACE;
-    if (reinterpret_cast<uintptr_t>(workspace) & 15) return NW_ERR_UNSUPPORTED;
-    nw::FusedArgs a = {q, s_split, sy, s_norm2, s_scale, logit_scale_dev, out, nullptr, lse_out, nullptr, nullptr, nullptr,
-                       &L, (int)B, (int)N, (int)d, (int)C, static_cast<hipStream_t>(stream), nullptr,
-                       row_lo, row_hi, row_lo && exclude != 0, row_logw};
-    return nw::launch_fused(a, nw::FORM_SPLIT, kind);
+    return bank_bwd_checked({q, s_split, s_scale, s_norm2, sy, row_lo, row_hi, exclude, lse, out, gout, gq, glogit_scale,
+                             workspace, workspace_bytes, B, N, d, C, kind, logit_scale_dev, row_chunks,
+                             static_cast<hipStream_t>(stream), nullptr, nullptr}, NEED_GQ);
 }
 
 extern "C" int nw_bwd_query_weighted_f32(const float* q, const float* s_split, const float* s_scale, const float* s_norm2,
@@ -318,28 +347,9 @@ extern "C" int nw_bwd_query_weighted_f32(const float* q, const float* s_split, c
                                          float* glogit_scale, void* workspace, size_t workspace_bytes, int64_t B, int64_t N,
                                          int64_t d, int64_t C, int kind, const float* logit_scale_dev, int row_chunks,
                                          void* stream) {
-    if (B < 0 || N < 0 || d < 0 || C < 0 || row_chunks < 0) return NW_ERR_INVALID_ARG;
-    if ((row_lo != nullptr) != (row_hi != nullptr)) return NW_ERR_INVALID_ARG;
-    if (bad_kind(kind)) return NW_ERR_UNSUPPORTED;
-    if (!nw::bwd_query_shape_ok(B, N, d, C)) return NW_ERR_UNSUPPORTED;
-    if (B == 0) return NW_OK;
-    if (!q || !s_split || !s_scale || !s_norm2 || !sy || !row_logw || !lse || !out || !gout || !gq) return NW_ERR_INVALID_ARG;
-    if (kind == NW_SCORE_CLIP && !logit_scale_dev) return NW_ERR_INVALID_ARG;
-    if ((reinterpret_cast<uintptr_t>(q) | reinterpret_cast<uintptr_t>(s_split) | reinterpret_cast<uintptr_t>(gq) |
-         reinterpret_cast<uintptr_t>(row_logw)) & 15)
-        return NW_ERR_UNSUPPORTED;
-    if (!workspace || workspace_bytes < nw::bwd_query_workspace_bytes(B, N, d, C, row_chunks)) return NW_ERR_WORKSPACE;
-    if (reinterpret_cast<uintptr_t>(workspace) & 15) return NW_ERR_UNSUPPORTED;
-    return nw::launch_bwd_query({q, s_split, s_scale, s_norm2, sy, row_lo, row_hi, exclude, lse, out, gout, gq, glogit_scale,
-                                 workspace, workspace_bytes, B, N, d, C, kind, logit_scale_dev, row_chunks,
-                                 static_cast<hipStream_t>(stream), row_logw});
-}
-
-// ... and the gradient w.r.t. the weights (bwd_query.hip GA): nw_bwd_query_weighted_f32's checks in its order, gq optional,
-// glogw required.  B == 0 returns before any pointer is looked at: nothing is touched, glogw included.
-extern "C" size_t nw_bwd_logw_workspace_bytes(int64_t B, int64_t N, int64_t d, int64_t C, int row_chunks, int want_gq) {
-    if (B <= 0 || N < 0 || d < 0 || C < 0) return 0;
-    return nw::bwd_logw_workspace_bytes(B, N, d, C, row_chunks, want_gq != 0);
+    return bank_bwd_checked({q, s_split, s_scale, s_norm2, sy, row_lo, row_hi, exclude, lse, out, gout, gq, glogit_scale,
+                             workspace, workspace_bytes, B, N, d, C, kind, logit_scale_dev, row_chunks,
+                             static_cast<hipStream_t>(stream), row_logw, nullptr}, NEED_LOGW | NEED_GQ);
 }
 
 extern "C" int nw_bwd_query_logw_f32(const float* q, const float* s_split, const float* s_scale, const float* s_norm2,
@@ -347,21 +357,9 @@ extern "C" int nw_bwd_query_logw_f32(const float* q, const float* s_split, const
                                      int exclude, const float* lse, const float* out, const float* gout, float* gq, float* glogw,
                                      float* glogit_scale, void* workspace, size_t workspace_bytes, int64_t B, int64_t N,
                                      int64_t d, int64_t C, int kind, const float* logit_scale_dev, int row_chunks, void* stream) {
-    if (B < 0 || N < 0 || d < 0 || C < 0 || row_chunks < 0) return NW_ERR_INVALID_ARG;
-    if ((row_lo != nullptr) != (row_hi != nullptr)) return NW_ERR_INVALID_ARG;
-    if (bad_kind(kind)) return NW_ERR_UNSUPPORTED;
-    if (!nw::bwd_query_shape_ok(B, N, d, C)) return NW_ERR_UNSUPPORTED;
-    if (B == 0) return NW_OK;
-    if (!q || !s_split || !s_scale || !s_norm2 || !sy || !row_logw || !lse || !out || !gout || !glogw) return NW_ERR_INVALID_ARG;
-    if (kind == NW_SCORE_CLIP && !logit_scale_dev) return NW_ERR_INVALID_ARG;
-    if ((reinterpret_cast<uintptr_t>(q) | reinterpret_cast<uintptr_t>(s_split) | reinterpret_cast<uintptr_t>(gq) |
-         reinterpret_cast<uintptr_t>(row_logw) | reinterpret_cast<uintptr_t>(glogw)) & 15)
-        return NW_ERR_UNSUPPORTED;
-    if (!workspace || workspace_bytes < nw::bwd_logw_workspace_bytes(B, N, d, C, row_chunks, gq != nullptr)) return NW_ERR_WORKSPACE;
-    if (reinterpret_cast<uintptr_t>(workspace) & 15) return NW_ERR_UNSUPPORTED;
-    return nw::launch_bwd_query({q, s_split, s_scale, s_norm2, sy, row_lo, row_hi, exclude, lse, out, gout, gq, glogit_scale,
-                                 workspace, workspace_bytes, B, N, d, C, kind, logit_scale_dev, row_chunks,
-                                 static_cast<hipStream_t>(stream), row_logw, glogw});
+    return bank_bwd_checked({q, s_split, s_scale, s_norm2, sy, row_lo, row_hi, exclude, lse, out, gout, gq, glogit_scale,
+                             workspace, workspace_bytes, B, N, d, C, kind, logit_scale_dev, row_chunks,
+                             static_cast<hipStream_t>(stream), row_logw, glogw}, NEED_LOGW | NEED_GLOGW);
 }
 
 extern "C" int nw_fwd_partial_f32(const float* q, const float* s, const int64_t* sy,

@@ -89,7 +89,8 @@ struct BwdQueryCall {
     const float* row_logw;   // (N,) log-weights of the bank rows (nw_bwd_query_weighted_f32), or null
     float* glogw;            // (N,) the gradient w.r.t. row_logw (nw_bwd_query_logw_f32; gq may then be null), or null
 };
-bool bwd_query_shape_ok(int64_t B, int64_t N, int64_t d, int64_t C);
+bool bank_head_shape_ok(int64_t N, int64_t d, int64_t C);   // capi.hip: the regime of the head over a resident bank
+bool bwd_query_shape_ok(int64_t B, int64_t N, int64_t d, int64_t C);   // ... and the backward's integer ranges
 size_t bwd_query_workspace_bytes(int64_t B, int64_t N, int64_t d, int64_t C, int row_chunks);
 size_t bwd_logw_workspace_bytes(int64_t B, int64_t N, int64_t d, int64_t C, int row_chunks, bool want_gq);
 int launch_bwd_query(const BwdQueryCall& c);

@@ -88,6 +88,11 @@ def _f32c(t):
     return t.detach().to(torch.float32).contiguous()
 
 
+def _i64c(t):
+    """Labels (or rows) as the library reads them: int64, contiguous; the caller's own tensor when it already is."""
+    return t if (t.dtype == torch.int64 and t.is_contiguous()) else t.detach().to(torch.int64).contiguous()
+
+
 def _kind_id(kind):
     if isinstance(kind, int):
         return kind
@@ -374,16 +379,38 @@ def knn_route_for(bank, width, B, k, matches=None, **policy):
 HEAD_WINDOW_MAX_CLASSES = 160 * 1024 // 4 - 8     # the run merge's accumulators (fused_eligible)
 
 
+def head_bank_refusal(*, split, sorted_copy, shape, pad, width, B, n_classes):
+    """Why ``nw_head_bank`` cannot take nw_bwd_query_f32 for B queries of ``width`` columns over a prepared bank, over
+    head_window_route's plain facts -- a sentence for the error text, or None when it can: the bank holds ``split`` rows
+    that are the caller's (no class-sorted copy), the queries pad to its width, and the shape is one the kernel takes.
+    The one statement of the regime of the head over a resident bank, forward and backward: head_window_route,
+    head_weighted_route and head_bank_route read it."""
+    N, d = shape
+    if not split:
+        return "the bank holds no split rows (a precision='fp16' or norms-only bank)"
+    if sorted_copy:
+        return "the bank was built from unsorted labels and keeps a class-sorted copy, whose rows are not the caller's"
+    if width + pad != d:
+        return f"queries of width {width} do not pad to the bank's width {d}"
+    if N <= 25:
+        return f"a bank of {N} rows is below the tile kernels (N > 25)"
+    if d % 32 or not 32 <= d <= 1 << 20:
+        return f"a bank of width {d} is not a multiple of 32 columns"
+    if not 1 <= n_classes <= HEAD_WINDOW_MAX_CLASSES:
+        return f"{n_classes} classes are outside [1, {HEAD_WINDOW_MAX_CLASSES}]"
+    if B <= 0:
+        return "an empty query batch"
+    return None
+
+
 def head_window_route(*, split, sorted_copy, shape, pad, width, B, n_classes):
     """Which route serves ``nw_head(..., row_window=...)`` for B queries of ``width`` columns over a prepared bank, over plain
     facts like knn_route: "fused" (nw_fwd_window_f32: the window is applied in the tile epilogue, no score matrix) at EVERY
     shape the kernel takes -- no size gate, the alternative is never the cheaper one -- that is whenever the bank holds
     ``split`` rows that are the caller's (no class-sorted copy), the queries pad to them (_resolve_scores' conditions) and
     N > 25; else "matrix" (nw_scores, a torch mask, nw_aggregate_f32): an fp16 or norms-only bank, a sorted copy, N <= 25."""
-    N, d = shape
-    fused = (split and not sorted_copy and width + pad == d and N > 25 and d % 32 == 0 and 32 <= d <= 1 << 20 and B > 0
-             and 1 <= n_classes <= HEAD_WINDOW_MAX_CLASSES)
-    return "fused" if fused else "matrix"
+    return "fused" if head_bank_refusal(split=split, sorted_copy=sorted_copy, shape=shape, pad=pad, width=width, B=B,
+                                        n_classes=n_classes) is None else "matrix"
 
 
 def head_weighted_route(*, split, sorted_copy, shape, pad, width, B, n_classes, grad=False, grad_logw=False):
@@ -630,8 +657,7 @@ class SplitBank:
         xc = _f32c(x)
         if xc.untyped_storage().data_ptr() == support.untyped_storage().data_ptr():
             xc = xc.clone()            # (rows of the bank itself, e.g. support[perm]: read while they are written)
-        rc = rows.detach()
-        rc = rc if (rc.dtype == torch.int64 and rc.is_contiguous()) else rc.to(torch.int64).contiguous()
+        rc = _i64c(rows.detach())
         N, d = self.shape
         padded = self.rows is not None
         s_rows = self.rows if padded else support.detach()
@@ -655,8 +681,7 @@ class SplitBank:
         """Run tables of this bank under ``labels`` (nw_bank_tables_build): the forward then skips building them on
         every large launch.  They are used only for calls that pass this very label tensor, unmodified."""
         lib = _lib.load()
-        lab = labels.detach()
-        lab64 = lab if (lab.dtype == torch.int64 and lab.is_contiguous()) else lab.to(torch.int64).contiguous()
+        lab64 = _i64c(labels.detach())
         N = self.shape[0]
         if lab64.dim() != 1 or lab64.numel() != N or N == 0 or not lab64.is_cuda:
             return
@@ -762,7 +787,7 @@ def _resolve(bank, q, s, sy, n_classes, positional=False, s_in_graph=False, half
             # the two extra torch ops than the kernels gain: d = 100, 168 -> 232 us); autograd slices the gradients back
             pad = (-d) % 32
             q, s = torch.nn.functional.pad(q, (0, pad)), torch.nn.functional.pad(s, (0, pad))
-    syc = sy if (sy.dtype == torch.int64 and sy.is_contiguous()) else sy.detach().to(torch.int64).contiguous()
+    syc = _i64c(sy)
     if bank is None:
         return _new_call(_Call, (q, s, syc, norm2, None, None, _default_opts(persistent_wgs)))
     norm2, operand, scale, form = bank.norm2, bank.split, bank.scale, 0
@@ -904,6 +929,45 @@ def _window_empty(lo, hi, exclude, N):
     return ((lo <= 0) & (hi >= N)) if exclude else (hi <= lo)
 
 
+def _bank_head_fwd(q, call, syc, logw, lo, hi, exclude, out, lse, kind_id, ls):
+    """The one launch of the head over a resident bank with a row window, support weights or both, into ``out`` / ``lse``:
+    nw_fwd_window_f32 without weights (``logw`` None), nw_fwd_weighted_f32 with them.  ``q``: the fp32 queries padded to the
+    bank, ``call``: the _Call of its split rows (_resolve_scores), ``syc``: int64 labels, ``lo`` / ``hi``: int32 or None."""
+    lib = _lib.load()
+    (B, d), N, C, st = q.shape, call.operand.shape[0], out.shape[1], _stream(q)
+    ws, ws_bytes = _fwd_workspace(lib, B, N, d, C, q.device, st)
+    entry = "nw_fwd_window_f32" if logw is None else "nw_fwd_weighted_f32"
+    with _OnDevice(q.device):
+        _lib.check(getattr(lib, entry)(_ptr(q), _ptr(call.operand), _ptr(call.scale), _ptr(call.norm2), _ptr(syc),
+                                       *(() if logw is None else (_ptr(logw),)), _ptr(lo), _ptr(hi), int(bool(exclude)),
+                                       _ptr(out), _ptr(lse), _ptr(ws), ws_bytes, B, N, d, C, kind_id, _ptr(ls), st), entry)
+
+
+def _bank_head_bwd(q, operands, logw, lo, hi, exclude, lse, out, gout, kind_id, ls, want_gq=True, want_glogw=False):
+    """The one launch of the gradients of that head -> (gq, glogit_scale, glogw), None where not asked for (glogit_scale:
+    whenever there is a clip scale ``ls``).  nw_bwd_query_f32 without weights, nw_bwd_query_weighted_f32 with constant ones,
+    nw_bwd_query_logw_f32 with its own workspace size when their gradient is wanted (``want_glogw``; gq is then optional).
+    ``operands``: the bank's (split, scale, norm2) and the int64 labels, as the forward read them."""
+    lib = _lib.load()
+    ssplit, sscale, sn2, syc = operands
+    (B, d), N, C, dev = q.shape, ssplit.shape[0], out.shape[1], q.device
+    gq = torch.empty_like(q) if want_gq else None
+    gls = torch.empty((), dtype=torch.float32, device=dev) if ls is not None else None
+    glogw = torch.empty(N, dtype=torch.float32, device=dev) if want_glogw else None
+    if want_glogw:
+        entry, ws_bytes = "nw_bwd_query_logw_f32", lib.nw_bwd_logw_workspace_bytes(B, N, d, C, 0, int(want_gq))
+    else:
+        entry = "nw_bwd_query_f32" if logw is None else "nw_bwd_query_weighted_f32"
+        ws_bytes = lib.nw_bwd_query_workspace_bytes(B, N, d, C, 0)
+    ws = _workspace(ws_bytes, dev)
+    with _OnDevice(dev):
+        _lib.check(getattr(lib, entry)(_ptr(q), _ptr(ssplit), _ptr(sscale), _ptr(sn2), _ptr(syc),
+                                       *(() if logw is None else (_ptr(logw),)), _ptr(lo), _ptr(hi), int(exclude), _ptr(lse),
+                                       _ptr(out), _ptr(gout), _ptr(gq), *((_ptr(glogw),) if want_glogw else ()), _ptr(gls),
+                                       _ptr(ws), ws_bytes, B, N, d, C, kind_id, _ptr(ls), 0, _stream(q)), entry)
+    return gq, gls, glogw
+
+
 def nw_head_window(q, s, sy, n_classes, bank, row_window, exclude=False, kind="euclidean", logit_scale=None, return_lse=False,
                    row_logw=None):
     """``nw_head(q, s, sy, n_classes, support_cache=bank, row_window=(lo, hi), exclude=...)``: the head of every query over
@@ -945,7 +1009,7 @@ def nw_head_window(q, s, sy, n_classes, bank, row_window, exclude=False, kind="e
     kid = _kind_id(kind)
     if kid == SCORE_KINDS["clip"] and ls is None:
         raise ValueError("clip kernel needs logit_scale")
-    syc = sy if (sy.dtype == torch.int64 and sy.is_contiguous()) else sy.detach().to(torch.int64).contiguous()
+    syc = _i64c(sy)
     out = torch.empty(B, C, dtype=torch.float32, device=q.device)
     lse = torch.empty(B, dtype=torch.float32, device=q.device)
     facts = dict(split=bank.split is not None, sorted_copy=bank.sorted_rows is not None, shape=bank.shape, pad=bank.pad,
@@ -953,17 +1017,7 @@ def nw_head_window(q, s, sy, n_classes, bank, row_window, exclude=False, kind="e
     route = head_window_route(**facts) if logw is None else head_weighted_route(**facts)
     if route == "fused":
         call = _resolve_scores(bank, q)
-        st, d = _stream(q), call.q.shape[1]
-        ws, ws_bytes = _fwd_workspace(lib, B, N, d, C, q.device, st)
-        with _OnDevice(q.device):
-            if logw is None:
-                _lib.check(lib.nw_fwd_window_f32(_ptr(call.q), _ptr(call.operand), _ptr(call.scale), _ptr(call.norm2), _ptr(syc),
-                                                 _ptr(lo), _ptr(hi), int(bool(exclude)), _ptr(out), _ptr(lse), _ptr(ws), ws_bytes,
-                                                 B, N, d, C, kid, _ptr(ls), st), "nw_fwd_window_f32")
-            else:
-                _lib.check(lib.nw_fwd_weighted_f32(_ptr(call.q), _ptr(call.operand), _ptr(call.scale), _ptr(call.norm2), _ptr(syc),
-                                                   _ptr(logw), _ptr(lo), _ptr(hi), int(bool(exclude)), _ptr(out), _ptr(lse),
-                                                   _ptr(ws), ws_bytes, B, N, d, C, kid, _ptr(ls), st), "nw_fwd_weighted_f32")
+        _bank_head_fwd(call.q, call, syc, logw, lo, hi, exclude, out, lse, kid, ls)
     elif B > 0:
         scores = nw_scores(q, s, kind, logit_scale, support_cache=bank)
         if logw is not None:
@@ -982,28 +1036,6 @@ def nw_head_window(q, s, sy, n_classes, bank, row_window, exclude=False, kind="e
         out = torch.where(empty[:, None], out.new_tensor(1e-12).log(), out)
         lse = lse.masked_fill(empty, float("-inf"))
     return (out, lse) if return_lse else out
-
-
-def head_bank_refusal(*, split, sorted_copy, shape, pad, width, B, n_classes):
-    """Why ``nw_head_bank`` cannot take nw_bwd_query_f32 for B queries of ``width`` columns over a prepared bank, over
-    head_window_route's plain facts -- a sentence for the error text, or None when it can: the bank holds ``split`` rows
-    that are the caller's (no class-sorted copy), the queries pad to its width, and the shape is one the kernel takes."""
-    N, d = shape
-    if not split:
-        return "the bank holds no split rows (a precision='fp16' or norms-only bank)"
-    if sorted_copy:
-        return "the bank was built from unsorted labels and keeps a class-sorted copy, whose rows are not the caller's"
-    if width + pad != d:
-        return f"queries of width {width} do not pad to the bank's width {d}"
-    if N <= 25:
-        return f"a bank of {N} rows is below the tile kernels (N > 25)"
-    if d % 32 or not 32 <= d <= 1 << 20:
-        return f"a bank of width {d} is not a multiple of 32 columns"
-    if not 1 <= n_classes <= HEAD_WINDOW_MAX_CLASSES:
-        return f"{n_classes} classes are outside [1, {HEAD_WINDOW_MAX_CLASSES}]"
-    if B <= 0:
-        return "an empty query batch"
-    return None
 
 
 def head_bank_route(*, split, sorted_copy, shape, pad, width, B, n_classes):
@@ -1052,79 +1084,45 @@ class _NWHeadBankFn(torch.autograd.Function):
         out = torch.empty(B, n_classes, dtype=torch.float32, device=dev)
         lse = torch.empty(B, dtype=torch.float32, device=dev)
         ls = None if logit_scale is None else _f32c(logit_scale)
-        st = _stream(qc)
-        ws, ws_bytes = _fwd_workspace(lib, B, N, d, n_classes, dev, st)
         lo, hi = window if window is not None else (None, None)
-        with _OnDevice(dev):
-            if logw is not None:
-                _lib.check(lib.nw_fwd_weighted_f32(_ptr(qc), _ptr(ssplit), _ptr(sscale), _ptr(sn2), _ptr(syc), _ptr(logw), _ptr(lo),
-                                                   _ptr(hi), int(exclude), _ptr(out), _ptr(lse), _ptr(ws), ws_bytes, B, N, d,
-                                                   n_classes, kind_id, _ptr(ls), st), "nw_fwd_weighted_f32")
-            elif window is None:
+        if logw is None and window is None:
+            st = _stream(qc)
+            ws, ws_bytes = _fwd_workspace(lib, B, N, d, n_classes, dev, st)
+            with _OnDevice(dev):
                 _lib.check(lib.nw_fwd_f32(_ptr(qc), _ptr(sc), _ptr(syc), _ptr(sn2), _ptr(ssplit), _ptr(sscale), _ptr(out), None,
                                           _ptr(lse), None, _ptr(ws), ws_bytes, B, N, d, n_classes, kind_id, _ptr(ls), 0, 0, opts,
                                           st), "nw_fwd_f32")
-            else:
-                _lib.check(lib.nw_fwd_window_f32(_ptr(qc), _ptr(ssplit), _ptr(sscale), _ptr(sn2), _ptr(syc), _ptr(lo), _ptr(hi),
-                                                 int(exclude), _ptr(out), _ptr(lse), _ptr(ws), ws_bytes, B, N, d, n_classes,
-                                                 kind_id, _ptr(ls), st), "nw_fwd_window_f32")
+        else:
+            _bank_head_fwd(qc, call, syc, logw, lo, hi, exclude, out, lse, kind_id, ls)
         ctx.save_for_backward(qc, lse, out, *([ls] if ls is not None else []), *([lo, hi] if window is not None else []))
         # the backward recomputes the scores from these: SplitBank.update_rows writes them in place and counts in `writes`
         ctx.bank = (ssplit, sscale, sn2, syc)
         ctx.bank_writes = (bank, bank.writes) if bank is not None else None
         # ... and the weights, a constant of this node: the tensor itself and its version (an in-place write bumps it)
         ctx.logw = None if logw is None else (logw, logw_src, logw_src._version)
-        ctx.meta = (B, N, d, n_classes, kind_id, ls is not None, window is not None, int(exclude))
+        ctx.meta = (kind_id, ls is not None, window is not None, exclude)
         return out
 
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, gout):
-        lib = _lib.load()
-        B, N, d, C, kind_id, has_ls, windowed, exclude = ctx.meta
+        kind_id, has_ls, windowed, exclude = ctx.meta
         saved = list(ctx.saved_tensors)
         qc, lse, out = saved[:3]
         ls = saved[3] if has_ls else None
         lo, hi = saved[-2:] if windowed else (None, None)
-        ssplit, sscale, sn2, syc = ctx.bank
         if ctx.bank_writes is not None and ctx.bank_writes[0].writes != ctx.bank_writes[1]:
             raise RuntimeError("nw_head_bank: the bank was written (SplitBank.update_rows) between this forward and its "
                                "backward, which recomputes the scores from the bank: call backward() first, then update")
         if ctx.logw is not None and ctx.logw[1]._version != ctx.logw[2]:
             raise RuntimeError("nw_head_bank: row_logw was written in place between this forward and its backward, which "
                                "recomputes the weighted scores from it: call backward() first, then change the weights")
-        dev = qc.device
-        g = _f32c(gout)
-        if ctx.logw is not None and ctx.needs_input_grad[9]:
-            # the weights' gradient as well: one entry, without gq (no second pass over the bank) when only the weights learn
-            want_gq = ctx.needs_input_grad[0] or (has_ls and ctx.needs_input_grad[1])
-            gq = torch.empty_like(qc) if want_gq else None
-            gls = torch.empty((), dtype=torch.float32, device=dev) if has_ls else None
-            ga = torch.empty(N, dtype=torch.float32, device=dev)
-            ws_bytes = lib.nw_bwd_logw_workspace_bytes(B, N, d, C, 0, int(want_gq))
-            ws = _workspace(ws_bytes, dev)
-            with _OnDevice(dev):
-                _lib.check(lib.nw_bwd_query_logw_f32(_ptr(qc), _ptr(ssplit), _ptr(sscale), _ptr(sn2), _ptr(syc), _ptr(ctx.logw[0]),
-                                                     _ptr(lo), _ptr(hi), exclude, _ptr(lse), _ptr(out), _ptr(g), _ptr(gq), _ptr(ga),
-                                                     _ptr(gls), _ptr(ws), ws_bytes, B, N, d, C, kind_id, _ptr(ls), 0, _stream(qc)),
-                           "nw_bwd_query_logw_f32")
-            return gq, gls, None, None, None, None, None, None, None, ga.to(ctx.logw[1].dtype)
-        gq = torch.empty_like(qc)
-        gls = torch.empty((), dtype=torch.float32, device=dev) if has_ls else None
-        ws_bytes = lib.nw_bwd_query_workspace_bytes(B, N, d, C, 0)
-        ws = _workspace(ws_bytes, dev)
-        if ctx.logw is not None:
-            with _OnDevice(dev):
-                _lib.check(lib.nw_bwd_query_weighted_f32(_ptr(qc), _ptr(ssplit), _ptr(sscale), _ptr(sn2), _ptr(syc), _ptr(ctx.logw[0]),
-                                                         _ptr(lo), _ptr(hi), exclude, _ptr(lse), _ptr(out), _ptr(g), _ptr(gq),
-                                                         _ptr(gls), _ptr(ws), ws_bytes, B, N, d, C, kind_id, _ptr(ls), 0,
-                                                         _stream(qc)), "nw_bwd_query_weighted_f32")
-            return gq, gls, None, None, None, None, None, None, None, None
-        with _OnDevice(dev):
-            _lib.check(lib.nw_bwd_query_f32(_ptr(qc), _ptr(ssplit), _ptr(sscale), _ptr(sn2), _ptr(syc), _ptr(lo), _ptr(hi), exclude,
-                                            _ptr(lse), _ptr(out), _ptr(g), _ptr(gq), _ptr(gls), _ptr(ws), ws_bytes, B, N, d, C,
-                                            kind_id, _ptr(ls), 0, _stream(qc)), "nw_bwd_query_f32")
-        return gq, gls, None, None, None, None, None, None, None, None
+        # the weights' gradient as well: then without gq (no second pass over the bank) when only the weights learn
+        want_glogw = ctx.logw is not None and ctx.needs_input_grad[9]
+        want_gq = not want_glogw or ctx.needs_input_grad[0] or (has_ls and ctx.needs_input_grad[1])
+        gq, gls, ga = _bank_head_bwd(qc, ctx.bank, ctx.logw and ctx.logw[0], lo, hi, exclude, lse, out, _f32c(gout), kind_id, ls,
+                                     want_gq, want_glogw)
+        return gq, gls, None, None, None, None, None, None, None, ga if ga is None else ga.to(ctx.logw[1].dtype)
 
 
 def nw_head_bank(q, s, sy, n_classes, bank, kind="euclidean", logit_scale=None, row_window=None, exclude=False, row_logw=None):
@@ -1188,9 +1186,7 @@ def nw_head_bank(q, s, sy, n_classes, bank, kind="euclidean", logit_scale=None, 
         call = _resolve(bank, q, s, sy, C, False, False, False, 0, None, False)       # nw_head's inference call
         window = None
     else:
-        call = _resolve_scores(bank, q)
-        syc = sy if (sy.dtype == torch.int64 and sy.is_contiguous()) else sy.detach().to(torch.int64).contiguous()
-        call = call._replace(sy=syc)
+        call = _resolve_scores(bank, q)._replace(sy=_i64c(sy))
         window = None if row_window is None else tuple(_row_window(row_window, q.shape[0], q.device))
     out = _NWHeadBankFn.apply(call.q, logit_scale, call, C, kid, window, bool(exclude), bank, logw, row_logw)
     return out
@@ -1458,7 +1454,7 @@ class _AggregateFn(torch.autograd.Function):
     def forward(ctx, scores, sy, n_classes):
         lib = _lib.load()
         sc = _f32c(scores)
-        syc = sy if (sy.dtype == torch.int64 and sy.is_contiguous()) else sy.detach().to(torch.int64).contiguous()
+        syc = _i64c(sy)
         B, N = sc.shape
         out = torch.empty(B, n_classes, dtype=torch.float32, device=sc.device)
         lse = torch.empty(B, dtype=torch.float32, device=sc.device)
