@@ -162,7 +162,13 @@ __global__ __launch_bounds__(TK_THREADS) void nw_topk_kernel(const float* __rest
         unsigned cg = 0, ce = 0;
 #pragma unroll
         for (int e = 0; e < TK_REGS; ++e) {
-            // (slots past the row hold 0, below every image and so below T: they drop out by themselves)
+            // (register slots past the wave's segment or the row hold 0, below every image: with T > 0 they are below T
+            //  and drop out by themselves.  PAD with T = 0 -- fewer than k candidates -- ranks them among the row's own
+            //  empty slots as "equal to T", and some of the n_eq places can go to them, with an index i that is past the
+            //  row or inside the next wave's segment: harmless, because nothing is read through that index -- emit writes
+            //  (-1, -inf) for EVERY key of 0 whatever its index, the histogram passes counted the row's own empty slots
+            //  only, so n_gt + n_eq = k slots are filled all the same, and every element above T, the valid ones, keeps
+            //  its place)
             cg += (unsigned)__builtin_popcountll(__ballot(ureg[e] > T));
             ce += (unsigned)__builtin_popcountll(__ballot(ureg[e] == T));
             __builtin_amdgcn_sched_barrier(0);   // (one ballot pair at a time: hoisted together they spill the scalar file)
