@@ -7,12 +7,83 @@ Differences that are deliberate (and documented in DESIGN.md):
   * 'hnsw' mode is an exact search (hnswlib is not available);
   * there is no CPU execution path: tensors must live on the MI355X.
 """
+from typing import NamedTuple
+
 import torch
 import torch.nn as nn
 
 from .. import ops
 from .kernel import _ScoreModule, get_kernel
 from .support import SupportSetEval, SupportSetTrain
+from .utils import routed_search
+
+
+# ---------------------------------------------------------------------- which bank serves a call (DESIGN.md 4.8j has the table)
+class Refusal(NamedTuple):
+    """bank_rule's "no": the exception to raise, and whether it comes before the entry point does any work (its featurizer
+    pass, predict_loo's first batch) or after."""
+    kind: type
+    text: str
+    early: bool = True
+
+
+# entry point -> how its messages name it
+WHAT = {"predict": "predict(x, 'full')", "predict_leave_out": "predict(x, 'full', leave_out=...)", "predict_loo": "predict_loo",
+        "forward_bank": "forward_bank", "refresh_bank": "refresh_bank", "get_neighbors": "get_neighbors", "explain": "explain",
+        "set_support_weights": "set_support_weights", "weights_for": None}
+# entry point -> why it needs ONE resident bank: the head over a row window, the top-influence windows, one weight per row
+_ROWS_OF = {"explain": "the row windows of ops.nw_top_influence are rows", "set_support_weights": "the weights are rows"}
+
+
+def bank_rule(entry, what=None, *, resident, sharded, searchable=False, builtin_kernel=True, weights="none", mode="full",
+              knn_per_query=False, leave_out=False, k_given=True):
+    """Which bank serves a call of NWNet: "resident" (precompute()'s full_feat / full_y / full_cache), "sharded"
+    (precompute_sharded()'s ShardedBank), "supports" (what support_eval builds per call), "missing" (no bank: the read of
+    the attribute fails with AttributeError) -- or the Refusal to raise.  Over plain facts: ``resident`` (full_feat is
+    there), ``sharded`` (sharded_bank is set), ``searchable`` (support_eval has its knn: precompute() has run),
+    ``builtin_kernel`` (a get_kernel score module), ``weights`` ("none" | "constant" | "learnable"), and of the call
+    ``mode``, ``knn_per_query``, ``leave_out`` (given or not) and ``k_given`` (get_neighbors).  ``entry``: a key of WHAT;
+    ``what`` names the caller in a message where the entry has no name of its own ("weights_for")."""
+    what = what or WHAT[entry]
+    if entry == "predict" and leave_out:
+        if mode != 'full':
+            return Refusal(ops.NWHipError, f"predict(x, '{mode}', leave_out=...): only mode='full' over precompute()'s bank "
+                                           "leaves rows out (the other modes build their support per call)")
+        entry, what = "predict_leave_out", WHAT["predict_leave_out"]
+    if entry == "predict":
+        if mode == 'full' and sharded:
+            return bank_rule("weights_for", what, resident=resident, sharded=sharded, weights=weights)._replace(early=False) \
+                if weights != "none" else "sharded"
+        if mode in ('knn', 'hnsw') and sharded and not searchable:
+            # a sharded bank and no precompute(): every query over its own neighbours of the whole bank
+            return "sharded" if knn_per_query else Refusal(
+                ops.NWHipError, f"predict(x, '{mode}') over a sharded bank needs NWNet(knn_per_query=True): the shared-support "
+                "form, which pools every query's neighbours, would have to gather their feature rows across the ranks", False)
+        # (the rows come from support_eval, which has them once precompute() has run: 'full' hands on ITS full_feat)
+        return "missing" if not searchable else "resident" if mode == 'full' else "supports"
+    if entry == "get_neighbors":
+        if sharded and not resident:
+            return "sharded" if k_given else Refusal(
+                ops.NWHipError, "get_neighbors over a sharded bank needs k (1 <= k <= 32): the full ordering of a sharded bank "
+                "is not available", False)
+        return "resident" if resident else "missing"
+    if entry == "weights_for":
+        if weights != "none" and sharded:
+            return Refusal(ops.NWHipError, f"{what}: support weights are set and the bank is sharded; a sharded bank has no "
+                                           "weights (set_support_weights(None), or precompute())")
+        return "resident"
+    # the entry points over ONE resident bank.  explain and set_support_weights look past a sharded bank when there is a
+    # resident one as well; the head over a row window (predict_loo, leave_out, forward_bank, refresh_bank) does not
+    if sharded and not (resident and entry in _ROWS_OF):
+        return Refusal(ops.NWHipError, f"{what}: a sharded bank is not served ({_ROWS_OF.get(entry, 'a row window is rows')} of "
+                                       "one resident bank); call precompute()")
+    if not resident:
+        return Refusal(ops.NWHipError, f"{what} needs the bank of precompute()")
+    if not builtin_kernel:
+        # (late: the bank getter says it, after the featurizer pass of forward_bank and leave_out, with predict_loo's first
+        # batch -- none for no rows; explain and set_support_weights ask once, before anything else)
+        return Refusal(ops.NWHipError, f"{what} needs one of the built-in score kernels", False)
+    return "resident"
 
 
 class _ChannelsLast(nn.Module):
@@ -119,8 +190,8 @@ class NWNet(nn.Module):
         """Changes whenever a parameter or buffer of the featurizer is written in place (optimizer step,
         load_state_dict, BatchNorm statistics) or replaced: the folded inference copy is rebuilt then.  (torch's fused
         optimizers do not advance version counters; train(), which every training loop passes through, drops the copy.)"""
-        ts = list(self.featurizer.parameters()) + list(self.featurizer.buffers())
-        return (len(ts), sum(0 if t.is_inference() else t._version for t in ts), sum(t.data_ptr() & 0xffff for t in ts))
+        from ..model.backbones import tensor_signature
+        return tensor_signature(self.featurizer)
 
     def _eval_featurizer(self, rebuild=False):
         if not getattr(self, '_fold_bn', False) or self.featurizer.training:
@@ -128,12 +199,9 @@ class NWNet(nn.Module):
         sig = self._weights_signature()
         if rebuild or getattr(self, '_folded', None) is None or getattr(self, '_folded_sig', None) != sig:
             object.__setattr__(self, '_folded_sig', sig)
-            from ..model import fold_batchnorm
-            from ..model.backbones import Conv1x1Fused, Conv3x3Fused, ScaleShiftReLU
+            from ..model.backbones import fold_batchnorm, folded_stays_nchw
             folded = fold_batchnorm(self.featurizer)
-            # DenseNet's folded copy runs its BatchNorm -> ReLU pairs in an NCHW HIP kernel on channel
-            # prefixes of the dense-block slab: it stays NCHW (11.2 -> 7.8 ms over 64 images @224)
-            if getattr(self, '_fold_cl', False) and not any(isinstance(m, (ScaleShiftReLU, Conv1x1Fused, Conv3x3Fused)) for m in folded.modules()):
+            if getattr(self, '_fold_cl', False) and not folded_stays_nchw(folded):
                 folded = _ChannelsLast(folded)
             object.__setattr__(self, '_folded', folded)
         return self._folded
@@ -227,13 +295,7 @@ class NWNet(nn.Module):
         if log_w is None:
             self.support_weights = None
             return
-        if getattr(self, 'sharded_bank', None) is not None and not hasattr(self, 'full_feat'):
-            raise ops.NWHipError("set_support_weights: a sharded bank is not served (the weights are rows of one resident "
-                                 "bank); call precompute()")
-        if not hasattr(self, 'full_feat'):
-            raise ops.NWHipError("set_support_weights needs the bank of precompute()")
-        if not isinstance(self.kernel, _ScoreModule):
-            raise ops.NWHipError("set_support_weights needs one of the built-in score kernels")
+        self._served("set_support_weights")
         # (a copy of its own: later writes to the caller's tensor do not get past the check below)
         w = torch.as_tensor(log_w).detach().to(device=self.full_feat.device, dtype=torch.float32, copy=True).contiguous()
         if w.shape != (self.full_feat.shape[0],):
@@ -251,13 +313,31 @@ class NWNet(nn.Module):
     def _weights_for(self, what, graph=False):
         """The support weights for a call over precompute()'s resident bank, or None; a sharded bank in front of it refuses.
         ``graph``: learnable weights as the parameter itself, for a call that differentiates (forward_bank)."""
+        self._served("weights_for", what)
+        return self._weights(graph)
+
+    def _weights(self, graph=False):
+        """_weights_for without the question: for the entry points, which have asked bank_rule for their bank already."""
         w = self._parameters.get('support_logw') if graph else None
-        if w is None:
-            w = getattr(self, 'support_weights', None)
-        if w is not None and getattr(self, 'sharded_bank', None) is not None:
-            raise ops.NWHipError(f"{what}: support weights are set and the bank is sharded; a sharded bank has no weights "
-                                 "(set_support_weights(None), or precompute())")
-        return w
+        return self.support_weights if w is None else w
+
+    def _served(self, entry, what=None, early_only=False, **call):
+        """bank_rule's answer for this net and this call (``call``: the call's own facts -- mode, leave_out, k_given); the
+        net's facts are gathered here and nowhere else.  A Refusal is raised (``early_only``: one that comes before the
+        featurizer pass; any other is left to the same question after it)."""
+        weights = "learnable" if self._parameters.get('support_logw') is not None else \
+            "none" if self.__dict__.get('_support_weights') is None else "constant"
+        served = bank_rule(entry, what, resident=hasattr(self, 'full_feat'), sharded=getattr(self, 'sharded_bank', None) is not None,
+                           searchable=hasattr(getattr(self, 'support_eval', None), 'knn'),
+                           builtin_kernel=isinstance(self._modules['kernel'], _ScoreModule),    # (self.kernel, without __getattr__)
+                           weights=weights, knn_per_query=self.knn_per_query, **call)
+        if isinstance(served, Refusal) and (served.early or not early_only):
+            raise served.kind(served.text)
+        return served
+
+    def _result(self, out):
+        """``out`` as the entry points return it: with return_mask, beside the mask of queries that were served (all)."""
+        return (out, torch.full((len(out),), True)) if self.return_mask else out
 
     @torch.no_grad()
     def precompute_sharded(self, group=None, partial_fn=None, merge_fn=None, search_fn=None, knn_merge_fn=None):
@@ -301,20 +381,22 @@ class NWNet(nn.Module):
                                         knn_merge_fn=knn_merge_fn, search_precision=self.search_precision)
         return self.sharded_bank
 
-    def _resident_bank(self, what, device):
-        """precompute()'s bank as ``what`` needs it -- (full_feat, full_y, SplitBank) on ``device`` -- or NWHipError with the
-        reason: a sharded bank, no bank, a custom kernel module.  The SplitBank is rebuilt when full_feat was replaced or
-        updated since precompute(), as predict does."""
-        if getattr(self, 'sharded_bank', None) is not None:
-            raise ops.NWHipError(f"{what}: a sharded bank is not served (a row window is rows of one resident bank); call "
-                                 "precompute()")
-        if not hasattr(self, 'full_feat'):
-            raise ops.NWHipError(f"{what} needs the bank of precompute()")
-        if not isinstance(self.kernel, _ScoreModule):
-            raise ops.NWHipError(f"{what} needs one of the built-in score kernels")
-        sfeat, sy = self.full_feat.to(device), self.full_y.to(device)
+    def _resident_bank(self, entry=None, device=None, rebuild=True, rows=None):
+        """precompute()'s bank -- (full_feat, full_y, SplitBank), on ``device`` when one is given -- for an entry point
+        bank_rule serves from it; ``entry``: the rule is asked here (NWHipError with the reason: a sharded bank, no bank, a
+        custom kernel module), None: the caller has asked.  ``rows``: the (features, labels) predict('full') got from
+        support_eval.  The one reader of ``full_cache``: a SplitBank that is not of these rows as they stand (full_feat
+        was replaced or updated since precompute()) is rebuilt -- or, with ``rebuild=False`` (get_neighbors, explain, which
+        have a route without a bank), left alone and None comes back in its place."""
+        if entry is not None:
+            self._served(entry)
+        sfeat, sy = (self.full_feat, self.full_y) if rows is None else rows
+        if device is not None:
+            sfeat, sy = sfeat.to(device), sy.to(device)
         cache = getattr(self, 'full_cache', None)
-        if cache is None or not cache.matches(sfeat):   # the bank was replaced or updated since precompute()
+        if cache is not None and not cache.matches(sfeat):
+            cache = None
+        if cache is None and rebuild:
             cache = self.full_cache = ops.SplitBank(sfeat, labels=sy, precision=self.full_precision)
         return sfeat, sy, cache
 
@@ -328,14 +410,15 @@ class NWNet(nn.Module):
         lo = rows.clamp(min=0)
         return lo, torch.where(rows < 0, lo, lo + 1)
 
-    def _predict_leave_out(self, qfeat, rows, what):
+    def _predict_leave_out(self, qfeat, rows, entry):
         """The 'full' head of the featurised queries ``qfeat`` over precompute()'s bank, query b without bank row rows[b]
         (-1: with every row): ops.nw_head's row window [row, row + 1), excluded."""
-        sfeat, sy, cache = self._resident_bank(what, None if qfeat is None else qfeat.device)
+        what = WHAT[entry]
+        sfeat, sy, cache = self._resident_bank(entry, qfeat.device)
         window = self._leave_out_window(rows, qfeat, what)
         with torch.no_grad():
             return ops.nw_head(qfeat.detach(), sfeat, sy, self.n_classes, self.kernel.kind, self.kernel._logit_scale(),
-                               support_cache=cache, row_window=window, exclude=True, row_logw=self._weights_for(what))
+                               support_cache=cache, row_window=window, exclude=True, row_logw=self._weights())
 
     def forward_bank(self, x, leave_out=None):
         """Not in the reference: the 'full' head at TRAINING time -- log-probabilities of ``self.featurizer(x)`` over
@@ -351,16 +434,15 @@ class NWNet(nn.Module):
         with its graph (a gradient lands on it).  A sharded bank, a missing bank and a custom kernel
         module are refused (NWHipError), like predict_loo.  A full_precision="fp16" bank or a bank whose labels are not
         class-sorted takes ops.nw_head's route through the score matrix without ``leave_out`` and is refused with it."""
-        what = "forward_bank"
-        if getattr(self, 'sharded_bank', None) is not None or not hasattr(self, 'full_feat'):
-            self._resident_bank(what, None)    # (raises: says why)
+        what = WHAT["forward_bank"]
+        self._served("forward_bank", early_only=True)      # (a sharded or missing bank: no featurizer pass)
         qfeat = self.featurizer(x)
         self.bank_features = qfeat.detach()
-        sfeat, sy, cache = self._resident_bank(what, qfeat.device)
+        sfeat, sy, cache = self._resident_bank("forward_bank", qfeat.device)
         window = None if leave_out is None else self._leave_out_window(leave_out, qfeat, what)
         out = ops.nw_head_bank(qfeat, sfeat, sy, self.n_classes, cache, self.kernel.kind, self.kernel._logit_scale(),
-                               row_window=window, exclude=window is not None, row_logw=self._weights_for(what, graph=True))
-        return (out, torch.full((len(x),), True)) if self.return_mask else out
+                               row_window=window, exclude=window is not None, row_logw=self._weights(graph=True))
+        return self._result(out)
 
     def refresh_bank(self, rows, feats=None, momentum=0.0):
         """Not in the reference: write fresh features into rows of precompute()'s bank IN PLACE (ops.SplitBank.update_rows:
@@ -375,12 +457,11 @@ class NWNet(nn.Module):
         What follows the refresh: predict('full') (with leave_out too), forward_bank and predict_loo; get_neighbors and
         explain over the bank; the 'knn' / 'hnsw' / 'random' modes, which read the same tensor.  What does not: the cluster
         centroids and the per-environment copies of 'ensemble' keep precompute()'s features until it runs again."""
-        what = "refresh_bank"
         if feats is None:
             feats, self.bank_features = getattr(self, 'bank_features', None), None
             if feats is None:
-                raise ops.NWHipError(f"{what}: no features to write: call forward_bank first, or pass feats")
-        sfeat, _sy, cache = self._resident_bank(what, feats.device)
+                raise ops.NWHipError(f"{WHAT['refresh_bank']}: no features to write: call forward_bank first, or pass feats")
+        sfeat, _sy, cache = self._resident_bank("refresh_bank", feats.device)
         cache.update_rows(sfeat, torch.as_tensor(rows, device=sfeat.device), feats.detach(), momentum)
 
     def predict_loo(self, rows=None, batch_size=256):
@@ -392,41 +473,24 @@ class NWNet(nn.Module):
         nearest other row is far.  A full_precision="fp16" bank, and a bank whose labels are not class-sorted (several
         environments), take ops.nw_head_window's score-matrix route: same result, a (batch, N) matrix per batch.
         Honours return_mask like predict.  A sharded bank is not served: NWHipError."""
-        if getattr(self, 'sharded_bank', None) is None and hasattr(self, 'full_feat'):
-            N = self.full_feat.shape[0]
-            rows = torch.arange(N, device=self.full_feat.device) if rows is None else torch.as_tensor(rows, device=self.full_feat.device)
-            outs = [self._predict_leave_out(self.full_feat[r], r, 'predict_loo') for r in rows.split(max(int(batch_size), 1))]
-            out = torch.cat(outs) if outs else torch.empty(0, self.n_classes, device=self.full_feat.device)
-        else:
-            out = self._predict_leave_out(None, None, 'predict_loo')    # (raises: says why)
-        return (out, torch.full((len(out),), True)) if self.return_mask else out
+        self._served("predict_loo", early_only=True)     # (a custom kernel module is refused by the first batch, if any)
+        N = self.full_feat.shape[0]
+        rows = torch.arange(N, device=self.full_feat.device) if rows is None else torch.as_tensor(rows, device=self.full_feat.device)
+        outs = [self._predict_leave_out(self.full_feat[r], r, 'predict_loo') for r in rows.split(max(int(batch_size), 1))]
+        out = torch.cat(outs) if outs else torch.empty(0, self.n_classes, device=self.full_feat.device)
+        return self._result(out)
 
     def predict(self, x, mode='random', leave_out=None):
         """leave_out (not in the reference; mode='full' over precompute()'s bank only): (B,) int64, the bank row of each
         query or -1 for none -- query b is predicted without that row (see predict_loo).  Any other mode or a sharded bank:
         NWHipError."""
         if leave_out is not None:
-            if mode != 'full':
-                raise ops.NWHipError(f"predict(x, '{mode}', leave_out=...): only mode='full' over precompute()'s bank leaves "
-                                     "rows out (the other modes build their support per call)")
-            if getattr(self, 'sharded_bank', None) is not None or not hasattr(self, 'full_feat'):
-                self._predict_leave_out(None, None, "predict(x, 'full', leave_out=...)")    # (raises: says why)
-            out = self._predict_leave_out(self._eval_featurizer()(x).detach(), leave_out, "predict(x, 'full', leave_out=...)")
-            return (out, torch.full((len(x),), True)) if self.return_mask else out
+            self._served("predict", early_only=True, mode=mode, leave_out=True)    # (another mode, a sharded or missing bank)
+            return self._result(self._predict_leave_out(self._eval_featurizer()(x).detach(), leave_out, "predict_leave_out"))
         qfeat = self._eval_featurizer()(x)
-        if mode == 'full' and getattr(self, 'sharded_bank', None) is not None:
-            self._weights_for("predict(x, 'full')")    # (raises when weights are set: a sharded bank has none)
-            out = self.sharded_bank.predict(qfeat.detach())
-            return (out, torch.full((len(x),), True)) if self.return_mask else out
-        if mode in ('knn', 'hnsw') and getattr(self, 'sharded_bank', None) is not None \
-                and not hasattr(self.support_eval, 'knn'):
-            # a sharded bank and no precompute(): every query over its own neighbours of the whole bank
-            if not self.knn_per_query:
-                raise ops.NWHipError(
-                    f"predict(x, '{mode}') over a sharded bank needs NWNet(knn_per_query=True): the shared-support form, which "
-                    "pools every query's neighbours, would have to gather their feature rows across the ranks")
-            out = self.sharded_bank.predict_knn(qfeat.detach(), self.n_neighbors)
-            return (out, torch.full((len(x),), True)) if self.return_mask else out
+        if self._served("predict", mode=mode) == "sharded":
+            bank = self.sharded_bank
+            return self._result(bank.predict(qfeat.detach()) if mode == 'full' else bank.predict_knn(qfeat.detach(), self.n_neighbors))
         sfeat, sy = self.support_eval.get_support(mode, x=qfeat)
         if self.debug_mode:
             print('qx shape:', x.shape)
@@ -436,20 +500,15 @@ class NWNet(nn.Module):
             probs = sum(self.nwhead(qfeat, f.to(x.device), y.to(x.device)).exp() for f, y in zip(sfeat, sy))
             out = torch.log(probs / len(sfeat))
         elif mode == 'full':
-            sfeat, sy = sfeat.to(x.device), sy.to(x.device)
-            cache = getattr(self, 'full_cache', None)
-            if cache is None or not cache.matches(sfeat):   # the bank was replaced or updated since precompute()
-                cache = self.full_cache = ops.SplitBank(sfeat, labels=sy, precision=self.full_precision)
-            if getattr(self, 'support_weights', None) is not None:    # (set_support_weights: a built-in score kernel)
-                out = ops.nw_head_bank(qfeat, sfeat, sy, self.n_classes, cache, self.kernel.kind, self.kernel._logit_scale(),
-                                       row_logw=self.support_weights)
+            sfeat, sy, cache = self._resident_bank(device=x.device, rows=(sfeat, sy))
+            w = self._weights()
+            if w is not None:    # (set_support_weights: a built-in score kernel)
+                out = ops.nw_head_bank(qfeat, sfeat, sy, self.n_classes, cache, self.kernel.kind, self.kernel._logit_scale(), row_logw=w)
             else:
                 out = self.nwhead(qfeat, sfeat, sy, support_cache=cache)
         else:
             out = self.nwhead(qfeat, sfeat.to(x.device), sy.to(x.device))
-        if self.return_mask:
-            return out, torch.full((len(x),), True)
-        return out
+        return self._result(out)
 
     def get_neighbors(self, x, k=None):
         """Support indices ordered from nearest to farthest under the configured kernel.  k (not in the reference): only the
@@ -461,27 +520,19 @@ class NWNet(nn.Module):
         bank (ops.nw_knn(rounded=True)) whenever the bank can serve it, at every size; k > 32 or k=None falls back to the
         routes above."""
         qfeat = self._eval_featurizer()(x).detach()
-        if getattr(self, 'sharded_bank', None) is not None and not hasattr(self, 'full_feat'):
-            if k is None:
-                raise ops.NWHipError("get_neighbors over a sharded bank needs k (1 <= k <= 32): the full ordering of a "
-                                     "sharded bank is not available")
+        if self._served("get_neighbors", k_given=k is not None) == "sharded":
             return self.sharded_bank.neighbors(qfeat, k)
         N = self.full_feat.shape[0]
         if k is not None:
             k = int(k)
             if not 1 <= k <= N:
                 raise ops.NWHipError(f"get_neighbors: k = {k} outside [1, N = {N}]")
-            bank = getattr(self, 'full_cache', None)
-            if isinstance(self.kernel, _ScoreModule) and bank is not None and qfeat.is_cuda and self.full_feat.is_cuda \
-                    and bank.matches(self.full_feat):
-                # size_gate: below it the (B, N) score matrix and the argsort below are the cheaper route (DESIGN 4.8c)
-                # need_n4: for other N the lines below rank the fp32 scores kernel's scores: not nw_knn's to the last bit
-                route = ops.knn_route_for(bank, qfeat.shape[1], qfeat.shape[0], k, True, search_precision=self.search_precision,
-                                          size_gate=True, need_n4=True)
-                if route == "rounded":
-                    return ops.nw_knn(qfeat, bank, k, self.kernel.kind, self.kernel._logit_scale(), rounded=True)
-                if route in ("fused", "matrix"):    # nw_knn's; None: the gates keep the search for the lines below
-                    return ops.nw_knn(qfeat, bank, k, self.kernel.kind, self.kernel._logit_scale(), support=self.full_feat)
+            if isinstance(self.kernel, _ScoreModule):
+                sfeat, _sy, bank = self._resident_bank(rebuild=False)
+                idx = routed_search(qfeat, bank, sfeat, k, self.kernel.kind, self.kernel._logit_scale(), self.search_precision)
+                if idx is not None:
+                    return idx
+        # (a custom kernel module, k=None, or the gates of the routed search keep it: the scores, ranked whole)
         scores = self.kernel(qfeat, self.full_feat.to(qfeat.device))
         order = torch.argsort(scores, dim=-1, descending=True)
         return order if k is None else order[:, :k]
@@ -492,18 +543,10 @@ class NWNet(nn.Module):
         precompute()'s bank -- ops.nw_top_influence of the featurised queries over full_feat / full_y with the configured
         kernel, no (B, N) matrix.  k defaults to n_neighbors (1 <= k <= 32).  Rows are rows of full_feat.  A sharded bank
         (precompute_sharded() without precompute()) is not served: NWHipError."""
-        if not hasattr(self, 'full_feat'):
-            if getattr(self, 'sharded_bank', None) is not None:
-                raise ops.NWHipError("explain: a sharded bank is not served (the row windows of ops.nw_top_influence are rows "
-                                     "of one resident bank); call precompute()")
-            raise ops.NWHipError("explain needs the bank of precompute()")
-        if not isinstance(self.kernel, _ScoreModule):
-            raise ops.NWHipError("explain needs one of the built-in score kernels")
+        self._served("explain")
         qfeat = self._eval_featurizer()(x).detach()
-        bank = getattr(self, 'full_cache', None)
-        if bank is not None and not bank.matches(self.full_feat):
-            bank = None
-        return ops.nw_top_influence(qfeat, self.full_feat, self.full_y, self.n_classes, y.to(qfeat.device),
+        sfeat, sy, bank = self._resident_bank(rebuild=False)
+        return ops.nw_top_influence(qfeat, sfeat, sy, self.n_classes, y.to(qfeat.device),
                                     self.n_neighbors if k is None else int(k), self.kernel.kind, self.kernel._logit_scale(),
                                     support_cache=bank)
 

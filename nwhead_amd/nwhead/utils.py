@@ -110,6 +110,24 @@ class InfiniteUniformClassLoader:
         return self.collate_fn([self.dataset[i] for i in picks])
 
 
+def routed_search(q, bank, data, k, kind, logit_scale, search_precision):
+    """The k nearest rows of ``data`` (N, d) for every query by ops.nw_knn, where ``bank`` is data's ops.SplitBank as it
+    stands, both are on the device and ops.knn_route gives the search to nw_knn -- or None: the gates keep the search for the
+    caller's own scores (KNN.indices: nw_scores and nw_topk; NWNet.get_neighbors: the kernel module's and an argsort)."""
+    if bank is None or not (q.is_cuda and data.is_cuda) or data.dim() != 2 or not bank.matches(data):
+        return None
+    # size_gate: below it the (B, N) score matrix and the caller's ranking are the cheaper route (DESIGN 4.8c)
+    # need_n4: for other N the callers rank the fp32 scores kernel's scores, which the fused search does not reproduce to the
+    # last bit
+    route = ops.knn_route_for(bank, q.shape[1], q.shape[0], k, True, search_precision=search_precision, size_gate=True,
+                              need_n4=True)
+    if route == "rounded":
+        return ops.nw_knn(q, bank, k, kind, logit_scale, rounded=True)
+    if route in ("fused", "matrix"):    # nw_knn's; None: the gates keep the search for the caller
+        return ops.nw_knn(q, bank, k, kind, logit_scale, support=data)
+    return None
+
+
 class KNN:
     """Exact nearest supports by Euclidean distance (utils.py:178-193).  As in the reference, the k
     rows of ALL queries are concatenated into one shared (B*k, d) support -- every query attends to every query's
@@ -131,16 +149,10 @@ class KNN:
     def indices(self, x):
         data = self.data.to(x.device)
         k = min(self.n_neighbors, data.shape[0])
-        if self.bank is not None and data.is_cuda and data.dim() == 2 and self.bank.matches(data):
-            # size_gate: below it the (B, N) score matrix is the cheaper route
-            # need_n4: at N % 4 == 0 the lines below rank the bank route's scores, whose rows nw_knn returns bit for bit; for
-            # other N they rank the fp32 scores kernel's, which the fused search does not reproduce to the last bit
-            route = ops.knn_route_for(self.bank, x.shape[1], x.shape[0], k, True, search_precision=self.search_precision,
-                                      size_gate=True, need_n4=True)
-            if route == "rounded":
-                return ops.nw_knn(x, self.bank, k, "euclidean", rounded=True)
-            if route in ("fused", "matrix"):    # nw_knn's; None: the gates keep the search for the lines below
-                return ops.nw_knn(x, self.bank, k, "euclidean", support=data)
+        idx = routed_search(x, self.bank, data, k, "euclidean", None, self.search_precision)
+        if idx is not None:
+            return idx
+        # (at N % 4 == 0 these lines rank the bank route's scores, whose rows nw_knn returns bit for bit)
         scores = ops.nw_scores(x, data, "euclidean", support_cache=self.bank if data.is_cuda else None)
         k = min(self.n_neighbors, scores.shape[1])
         # descending score == ascending distance; ties resolve like a stable argsort would
