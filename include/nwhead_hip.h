@@ -459,6 +459,42 @@ int nw_bwd_query_logw_f32(const float *q, const float *s_split, const float *s_s
                           float *gq, float *glogw, float *glogit_scale, void *workspace, size_t workspace_bytes,
                           int64_t B, int64_t N, int64_t d, int64_t C, int kind, const float *logit_scale_dev,
                           int row_chunks, void *stream);
+/* VALUE HEAD: Nadaraya-Watson regression over a resident split bank, a real-valued target row per support instead of a label,
+ *   out[b,t] = sum_{j admitted} exp(score_bj + a_j - lse_b) v_jt,
+ * i.e. softmax(scores) @ values with no (B,N) buffer anywhere: regression targets, soft / smoothed / multi-hot labels, any
+ * per-row attribute carried through the softmax.  The scores are recomputed tile by tile on the split-fp16 matrix cores and
+ * contracted with the value rows in the same kernel (nw_bwd_query_f32's work split with the value rows in the bank's place).
+ *   q (B,d) fp32; s_split / s_scale / s_norm2: the bank of nw_split_rows_f16x2;
+ *   v_split / v_scale  (N,T), (N,): the VALUES as nw_split_rows_f16x2 leaves them (its norms output is not needed), T a
+ *             multiple of 32 -- callers pad with zero columns.  Every value is FINITE, in every row, admitted or not: a row
+ *             that takes no part has an exact 0 coefficient, and 0 x inf is NaN on the matrix pipe.  Nothing is checked on
+ *             the device;
+ *   row_logw  optional (N,) natural-log weights a_j, 16-byte aligned, under nw_fwd_weighted_f32's contract (finite or -inf);
+ *             NULL: a = 0;
+ *   row_lo / row_hi (B,) int32: both NULL (no window) or both set, with `exclude` as in nw_fwd_window_f32 (clamped to
+ *             [0, N], never used as an address; exclude is ignored without a window);
+ *   lse (B,): the log-sum-exp the forward returned for the SAME operands, weights and window (nw_fwd_window_f32 or
+ *             nw_fwd_weighted_f32 with lse_out; a caller without labels passes all-zero labels and C = 1, one without a
+ *             window the kept window [0, N)).  The weight is that forward's fused multiply-add, so the weights of a row sum
+ *             to 1 to its tolerance;
+ *   out (B,T) fp32: EVERY element is written by a successful call with B > 0;
+ *   row_chunks: as in nw_bwd_query_f32 (0: the library chooses; a positive value is clamped to the 64-row tile count).
+ * A dead query (lse = -inf) gets a zero row; a row at a = -inf, a row outside the window and the rows past N of the last tile
+ * contribute exactly 0.  A finishing kernel adds the chunks' partial tiles in chunk order, scaled by exact powers of two: no
+ * float atomics, two calls give identical bits.
+ * Regime: nw_fwd_window_f32's for the operands -- d % 32 == 0, 32 <= d, N > 25 -- and T % 32 == 0, 32 <= T <= 16384; q,
+ * s_split, v_split, out, row_logw and workspace 16-byte aligned; anything else is NW_ERR_UNSUPPORTED before anything is
+ * launched, and the workspace size is then 0.  Null required pointers, one of row_lo / row_hi alone, a negative size or
+ * row_chunks, clip without logit_scale_dev: NW_ERR_INVALID_ARG.  A short or NULL workspace
+ * (nw_fwd_values_workspace_bytes(B, N, d, T, row_chunks)): NW_ERR_WORKSPACE.  B == 0: NW_OK.  No allocation, no
+ * synchronisation, no environment. */
+size_t nw_fwd_values_workspace_bytes(int64_t B, int64_t N, int64_t d, int64_t T, int row_chunks);
+int nw_fwd_values_f32(const float *q, const float *s_split, const float *s_scale, const float *s_norm2,
+                      const float *v_split, const float *v_scale, const float *row_logw,
+                      const int32_t *row_lo, const int32_t *row_hi, int exclude,
+                      const float *lse, float *out, void *workspace, size_t workspace_bytes,
+                      int64_t B, int64_t N, int64_t d, int64_t T, int kind, const float *logit_scale_dev,
+                      int row_chunks, void *stream);
 /* support_influence (util/metric.py:23-50) of k SELECTED supports per query, from the head's own outputs:
  *   vals (B,k) fp32 raw scores and rows (B,k) int64 bank rows (a search's val_out / idx_out),
  *   sy (N,) int64, qy (B,) int64, out (B,C) log-probabilities and lse (B,) of nw_fwd_f32 over the same bank;

@@ -95,6 +95,28 @@ size_t bwd_query_workspace_bytes(int64_t B, int64_t N, int64_t d, int64_t C, int
 size_t bwd_logw_workspace_bytes(int64_t B, int64_t N, int64_t d, int64_t C, int row_chunks, bool want_gq);
 int launch_bwd_query(const BwdQueryCall& c);
 
+// fwd_values.hip: the value head over a resident split bank, out = softmax(scores) @ values with no (B,N) matrix
+// (nw_fwd_values_f32)
+struct FwdValuesCall {
+    const float *q, *s_split, *s_scale, *s_norm2;
+    const float *v_split, *v_scale;   // (N,T), (N,): nw_split_rows_f16x2 of the values
+    const float* row_logw;            // (N,) log-weights of the bank rows, or null
+    const int32_t *row_lo, *row_hi;   // both or neither
+    int exclude;
+    const float* lse;
+    float* out;
+    void* workspace;
+    size_t workspace_bytes;
+    int64_t B, N, d, T;
+    int kind;
+    const float* logit_scale_dev;
+    int row_chunks;
+    hipStream_t st;
+};
+bool fwd_values_shape_ok(int64_t B, int64_t N, int64_t d, int64_t T);   // the bank head's regime, T's, the integer ranges
+size_t fwd_values_workspace_bytes(int64_t B, int64_t N, int64_t d, int64_t T, int row_chunks);
+int launch_fwd_values(const FwdValuesCall& c);
+
 // Options of the forward call in progress on this thread (nw_fwd_opts of the ABI, set for the duration of the call by
 // the entry point): explicit arguments, not process state.
 struct FwdOpts {

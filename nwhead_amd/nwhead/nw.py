@@ -30,9 +30,11 @@ class Refusal(NamedTuple):
 # entry point -> how its messages name it
 WHAT = {"predict": "predict(x, 'full')", "predict_leave_out": "predict(x, 'full', leave_out=...)", "predict_loo": "predict_loo",
         "forward_bank": "forward_bank", "refresh_bank": "refresh_bank", "get_neighbors": "get_neighbors", "explain": "explain",
-        "set_support_weights": "set_support_weights", "weights_for": None}
+        "set_support_weights": "set_support_weights", "weights_for": None, "set_support_values": "set_support_values",
+        "predict_values": "predict_values", "predict_loo_values": "predict_loo_values"}
 # entry point -> why it needs ONE resident bank: the head over a row window, the top-influence windows, one weight per row
-_ROWS_OF = {"explain": "the row windows of ops.nw_top_influence are rows", "set_support_weights": "the weights are rows"}
+_ROWS_OF = {"explain": "the row windows of ops.nw_top_influence are rows", "set_support_weights": "the weights are rows",
+            "set_support_values": "the values are rows"}
 
 
 def bank_rule(entry, what=None, *, resident, sharded, searchable=False, builtin_kernel=True, weights="none", mode="full",
@@ -73,7 +75,8 @@ def bank_rule(entry, what=None, *, resident, sharded, searchable=False, builtin_
                                            "weights (set_support_weights(None), or precompute())")
         return "resident"
     # the entry points over ONE resident bank.  explain and set_support_weights look past a sharded bank when there is a
-    # resident one as well; the head over a row window (predict_loo, leave_out, forward_bank, refresh_bank) does not
+    # resident one as well, and so does set_support_values; the head over a row window (predict_loo, leave_out, forward_bank,
+    # refresh_bank) and the value head (predict_values, predict_loo_values) do not
     if sharded and not (resident and entry in _ROWS_OF):
         return Refusal(ops.NWHipError, f"{what}: a sharded bank is not served ({_ROWS_OF.get(entry, 'a row window is rows')} of "
                                        "one resident bank); call precompute()")
@@ -138,6 +141,7 @@ class NWNet(nn.Module):
             raise ValueError(f"balance_full must be 'truncate' or 'weights', got {balance_full!r}")
         self.balance_full = balance_full
         self.support_weights = None
+        self.support_values = None     # ops.BankValues over the rows of precompute()'s bank (set_support_values), or None
         # not in the reference: "fp16" serves predict(x, 'full') from a half-precision bank (ops.SplitBank(precision="fp16"):
         # bank and query features rounded to fp16, half the bytes, a third of the matrix-core work); "fp32" is the parity path
         if full_precision not in ("fp32", "fp16"):
@@ -253,6 +257,7 @@ class NWNet(nn.Module):
         self.support_eval.build_infer_iters(*info)
         self.support_eval.knn.bank = self.support_eval.hnsw.bank = self.full_cache   # neighbour search over the same bank
         self.support_weights = None                  # weights are per row of the bank they were set for
+        self.support_values = None                   # ... and so are values
         if self.balance_full == "weights":
             self.set_support_weights(ops.class_balance_logw(self.full_y, self.n_classes))
 
@@ -288,7 +293,8 @@ class NWNet(nn.Module):
         set them again afterwards and rebuild the optimizer's parameter group.  A full_precision="fp16" bank has no route
         for this gradient: forward_bank raises NWHipError.  ``learnable=False`` is the behaviour described above, unchanged.
 
-        Honoured by predict(x, 'full') with and without leave_out, by predict_loo and by forward_bank.  Kept by
+        Honoured by predict(x, 'full') with and without leave_out, by predict_loo, by forward_bank and by the value head
+        (predict_values, predict_loo_values).  Kept by
         refresh_bank (rows keep their identity); cleared by precompute().  NOT seen by get_neighbors, explain and the
         other inference modes ('random', 'cluster', 'ensemble', 'knn', 'hnsw'), which read the bank's features as they are.
         A sharded bank is refused (NWHipError), as is a custom kernel module."""
@@ -479,6 +485,69 @@ class NWNet(nn.Module):
         outs = [self._predict_leave_out(self.full_feat[r], r, 'predict_loo') for r in rows.split(max(int(batch_size), 1))]
         out = torch.cat(outs) if outs else torch.empty(0, self.n_classes, device=self.full_feat.device)
         return self._result(out)
+
+    def set_support_values(self, values=None):
+        """Not in the reference: a real-valued TARGET ROW per row of precompute()'s bank, for predict_values /
+        predict_loo_values -- Nadaraya-Watson regression over the resident bank (an age, a pose, a box, an embedding to
+        retrieve), soft / smoothed / mixup / distilled or multi-hot labels, or any per-row attribute carried through the
+        softmax (expected metadata or loss of the neighbours).  ``values``: (N, T) float tensor over the rows of
+        ``full_feat``, every entry finite; ``None`` clears them.  Prepared once, here, as an ops.BankValues (``support_values``:
+        an fp32 copy and its split-fp16 form) from a copy of the caller's tensor: later writes to that tensor are not seen;
+        to change value rows, call this again.  Kept by refresh_bank (rows keep their identity); cleared by precompute().
+        A sharded bank, a missing bank and a custom kernel module are refused (NWHipError), like set_support_weights."""
+        if values is None:
+            self.support_values = None
+            return
+        self._served("set_support_values")
+        sfeat, _sy, cache = self._resident_bank()
+        v = torch.as_tensor(values)
+        if v.dim() != 2 or v.shape[0] != sfeat.shape[0] or v.shape[1] < 1 or not v.is_floating_point():
+            raise ValueError(f"set_support_values: values must be ({sfeat.shape[0]}, T) floats, T >= 1: one row per bank row; got "
+                             f"{tuple(v.shape)} {v.dtype}")
+        self.support_values = ops.BankValues(v.detach().to(device=sfeat.device, copy=True), cache)
+
+    def _values_head(self, qfeat, rows, log, entry):
+        """ops.nw_head_values of the featurised queries ``qfeat`` over precompute()'s bank and the values set for it, query b
+        without bank row rows[b] (None: no window); constant support weights are honoured, learnable ones read detached."""
+        what = WHAT[entry]
+        sfeat, _sy, cache = self._resident_bank(entry, qfeat.device)
+        vals = getattr(self, 'support_values', None)
+        if vals is None:
+            raise ops.NWHipError(f"{what}: no values are set for the bank: call set_support_values (precompute() clears them)")
+        window = None if rows is None else self._leave_out_window(rows, qfeat, what)
+        with torch.no_grad():
+            return ops.nw_head_values(qfeat.detach(), sfeat, cache, vals, self.kernel.kind, self.kernel._logit_scale(),
+                                      row_window=window, exclude=window is not None, row_logw=self._weights(), log=log)
+
+    def predict_values(self, x, leave_out=None, log=False):
+        """Not in the reference: the VALUE head over precompute()'s bank -- (B, T) fp32, the softmax-weighted mean of the
+        value rows of set_support_values under the configured kernel (ops.nw_head_values: no (B, N) matrix on the fused
+        route; a full_precision="fp16" bank or one whose labels are not class-sorted goes through the score matrix).  The
+        eval featurizer runs on ``x``.  ``leave_out``: (B,) int64, the bank row of each query or -1 for none, as in
+        predict(x, 'full', leave_out=...).  ``log``: log(out + 1e-12), for soft labels.  Honours set_support_weights (as a
+        constant; learnable weights are read detached) and return_mask.  Inference only.  A sharded bank, a missing bank,
+        a custom kernel module and a bank without values are refused (NWHipError)."""
+        self._served("predict_values", early_only=True)
+        if getattr(self, 'support_values', None) is None:
+            raise ops.NWHipError(f"{WHAT['predict_values']}: no values are set for the bank: call set_support_values "
+                                 "(precompute() clears them)")
+        return self._result(self._values_head(self._eval_featurizer()(x).detach(), leave_out, log, "predict_values"))
+
+    def predict_loo_values(self, rows=None, batch_size=256, log=False):
+        """Not in the reference: leave-one-out value estimates of the bank's own rows, (len(rows), T) -- row i's value
+        predicted from every row but itself (LOO regression error, bandwidth / kernel selection, screening of noisy
+        targets), mirroring predict_loo: the queries are full_feat[rows], no featurizer pass, batches of ``batch_size``,
+        the exclusion inside the kernel before the softmax.  ``rows``: (R,) int64 bank rows, default all.  Honours
+        set_support_weights, return_mask and ``log`` like predict_values; refuses what it refuses."""
+        self._served("predict_loo_values", early_only=True)
+        vals = getattr(self, 'support_values', None)
+        if vals is None:
+            raise ops.NWHipError(f"{WHAT['predict_loo_values']}: no values are set for the bank: call set_support_values "
+                                 "(precompute() clears them)")
+        dev = self.full_feat.device
+        rows = torch.arange(self.full_feat.shape[0], device=dev) if rows is None else torch.as_tensor(rows, device=dev)
+        outs = [self._values_head(self.full_feat[r], r, log, 'predict_loo_values') for r in rows.split(max(int(batch_size), 1))]
+        return self._result(torch.cat(outs) if outs else torch.empty(0, vals.T, device=dev))
 
     def predict(self, x, mode='random', leave_out=None):
         """leave_out (not in the reference; mode='full' over precompute()'s bank only): (B,) int64, the bank row of each

@@ -7,6 +7,7 @@ from __future__ import annotations
 import collections
 import ctypes
 import os
+import weakref
 
 import torch
 from torch.autograd.function import once_differentiable
@@ -558,6 +559,8 @@ class SplitBank:
       scores -- split rows without a class-sorted copy, whose rows are the caller's -- else through the score matrix.
     * the head's query gradient over the bank as a constant (nw_head_bank; head_bank_route): fused on the same terms again,
       else nw_head's route without a window and a refusal with one.
+    * the value head (nw_head_values, BankValues; head_values_route): fused on the same terms as the head over a row window,
+      for values of 1 to 16384 columns, else through the score matrix, torch.softmax and a matmul.
     * searches, rounded (nw_knn(rounded=True); _resolve_scores): only fp16-packed rows without a class-sorted copy; the
       queries are padded to the bank's width like everywhere else.
     * run tables (build_tables): named in the call's options only when its labels are the tensor the tables were built
@@ -1044,6 +1047,174 @@ def head_bank_route(*, split, sorted_copy, shape, pad, width, B, n_classes):
     has nothing to say; else "matrix": nw_head's route through the score matrix without a window, a refusal with one."""
     return "fused" if head_bank_refusal(split=split, sorted_copy=sorted_copy, shape=shape, pad=pad, width=width, B=B,
                                         n_classes=n_classes) is None else "matrix"
+
+
+HEAD_VALUES_MAX_T = 16384        # nw_fwd_values_f32: value columns per row (after padding to a multiple of 32)
+
+
+def head_values_route(*, split, sorted_copy, shape, pad, width, B, T):
+    """Which route serves the VALUE head ``nw_head_values`` for B queries of ``width`` columns and values of ``T`` columns over
+    a prepared bank, beside head_window_route and over the same plain facts: "fused" (the forward's lse pass, then
+    nw_fwd_values_f32: no (B, N) matrix) exactly where head_bank_refusal is silent -- the bank holds split rows that are the
+    caller's, the queries pad to its width, N > 25, B > 0 -- and 1 <= T <= HEAD_VALUES_MAX_T (the values pad to a multiple
+    of 32 columns themselves); else "matrix": nw_scores over the bank, + row_logw, the window's mask, torch.softmax and a
+    matmul with the values -- an fp16 or norms-only bank, a class-sorted copy, N <= 25, widths that do not pad.  No size
+    gate: the matrix route holds the (B, N) matrix twice, which is the reason for the fused one at every shape it was timed
+    at (DESIGN 4.8k has the times)."""
+    fused = 1 <= T <= HEAD_VALUES_MAX_T and head_bank_refusal(split=split, sorted_copy=sorted_copy, shape=shape, pad=pad,
+                                                              width=width, B=B, n_classes=1) is None
+    return "fused" if fused else "matrix"
+
+
+class BankValues:
+    """Real-valued targets for the rows of a SplitBank, prepared once for ``nw_head_values``: ``values`` (N, T), any float
+    dtype, row j the target of row j of the tensor ``bank`` was prepared from (regression targets, soft / smoothed / multi-hot
+    labels, per-row attributes).  Keeps an fp32 copy zero-padded to a multiple of 32 columns (``rows``, (N, ``width``)) and
+    its split-fp16 form (``split``, ``scale``: nw_split_rows_f16x2 over the padded copy, the norms dropped) -- 8 N width
+    bytes; ``T`` is the caller's column count.  Every value must be FINITE, in every row (a row that a window or a -inf
+    weight removes still meets the matrix pipe with a 0 coefficient, and 0 x inf is NaN); nothing is checked.  The split
+    format scales by ROW: an element keeps 22 bits down to 2^-18 of its row's largest magnitude, an absolute error of 2^-38
+    of that below -- columns of very different magnitude belong in separate BankValues.
+    ``matches(values)``: the very tensor, not written since; ``stale()``: that tensor is alive and was written.  There is no in-place update of value rows: build a new
+    BankValues.  T above HEAD_VALUES_MAX_T keeps the fp32 copy only (the matrix route)."""
+
+    def __init__(self, values, bank):
+        if not isinstance(bank, SplitBank):
+            raise TypeError("BankValues: `bank` is the ops.SplitBank whose rows the values belong to")
+        if not torch.is_tensor(values) or not values.is_floating_point() or values.dim() != 2 or values.shape[1] < 1:
+            raise ValueError("BankValues: values is an (N, T) float tensor, T >= 1: one target row per bank row")
+        if values.shape[0] != bank.shape[0]:
+            raise ValueError(f"BankValues: {values.shape[0]} value rows for a bank of {bank.shape[0]} rows")
+        _need_hip(values)
+        self._src, self._ref = _sig(values), weakref.ref(values)      # (no hold on the caller's tensor)
+        self.requires_grad = bool(values.requires_grad)
+        N, T = values.shape
+        self.T, self.width = T, T + (-T) % 32
+        vc = _f32c(values)
+        self.rows = torch.nn.functional.pad(vc, (0, self.width - T)) if self.width != T else (vc.clone() if vc.data_ptr() == values.data_ptr() else vc)
+        self.split = self.scale = None
+        if N > 0 and self.width <= HEAD_VALUES_MAX_T:
+            self.split = torch.empty_like(self.rows)
+            self.scale = torch.empty(N, dtype=torch.float32, device=vc.device)
+            norm2 = torch.empty(N, dtype=torch.float32, device=vc.device)      # (the packer's third output: not needed)
+            with _OnDevice(vc.device):
+                _lib.check(_lib.load().nw_split_rows_f16x2(_ptr(self.rows), _ptr(self.split), _ptr(self.scale), _ptr(norm2),
+                                                           N, self.width, _stream(vc)), "nw_split_rows_f16x2")
+
+    def matches(self, values):
+        """True when ``values`` is the very tensor (storage, shape, no in-place update since) this object was prepared from."""
+        return _sig(values) == self._src
+
+    def stale(self):
+        """True when the source tensor is still alive and was written in place since: what nw_head_values refuses."""
+        t = self._ref()
+        return t is not None and _sig(t) != self._src
+
+
+def nw_head_values(q, s, bank, values, kind="euclidean", logit_scale=None, row_window=None, exclude=False, row_logw=None,
+                   log=False, return_lse=False):
+    """The VALUE head (Nadaraya-Watson regression) over a prepared bank: q (B,d), ``s`` (N,d) the tensor ``bank`` (a SplitBank)
+    was prepared from, ``values`` the targets of its rows -> (B,T) fp32
+        out[b] = sum_{j admitted} softmax_j(score_bj + a_j) values[j]
+    (with ``return_lse`` also the (B,) log-sum-exp of the admitted weighted scores).  ``values``: a BankValues (prepared
+    once), or a raw (N,T) float tensor, which is prepared on the fly -- an fp32 copy, the padding and one split launch over
+    N x T values per call: prepare it once for repeated calls.  ``row_window`` / ``exclude`` / ``row_logw`` mean what they
+    mean for nw_head_window: the softmax runs over the admitted rows alone (leave-one-out regression is the window
+    [i, i+1), excluded), a_j = -inf removes a row.  Every value must be finite, in every row.  ``log``: log(out + 1e-12), for
+    soft-label classification -- one-hot values of the labels reproduce nw_head_window.  A dead query (no admitted row)
+    gets 0 in every column (``log``: log(1e-12)) and lse = -inf.
+
+    Inference only: a ``q``, ``values`` or ``row_logw`` that requires grad while grad mode is enabled raises NWHipError --
+    the differentiable route is the composition nw_scores + softmax + matmul (torch autograd).
+
+    Route (head_values_route): "fused" -- the forward's lse pass (nw_fwd_window_f32 / nw_fwd_weighted_f32 over all-zero
+    labels, one class, the kept window [0, N) when there is none) and nw_fwd_values_f32, no (B,N) matrix -- wherever the
+    windowed head is fused and T <= 16384; else "matrix": nw_scores, + row_logw, the mask, torch.softmax, @ values.  A
+    BankValues whose tensor was written since it was prepared is REFUSED (ValueError), not rebuilt."""
+    _need_hip(q, s, logit_scale)
+    if not isinstance(bank, SplitBank):
+        raise TypeError("nw_head_values runs over a prepared bank: pass ops.SplitBank(support)")
+    if s.dim() != 2 or not bank.matches(s):
+        raise ValueError("nw_head_values: `s` (N,d) must be the tensor the bank was prepared from")
+    raw = values if torch.is_tensor(values) else None
+    if torch.is_grad_enabled() and (q.requires_grad or (raw.requires_grad if raw is not None else getattr(values, "requires_grad", False))
+                                    or (torch.is_tensor(row_logw) and row_logw.requires_grad)):
+        raise NWHipError("nw_head_values is inference only and does not detach silently: q, values or row_logw requires grad. "
+                         "The differentiable route is the composition nw_scores + softmax + matmul")
+    if raw is not None:
+        values = BankValues(raw, bank)
+    elif not isinstance(values, BankValues):
+        raise TypeError("nw_head_values: values is an ops.BankValues or an (N,T) float tensor")
+    N, T = s.shape[0], values.T
+    if values.rows.shape[0] != N or values.rows.device != q.device:
+        raise ValueError(f"nw_head_values: the values hold {values.rows.shape[0]} rows on {values.rows.device} for a bank of {N} "
+                         f"rows and queries on {q.device}")
+    if values.stale():
+        raise ValueError("nw_head_values: the tensor this BankValues was prepared from was written since; build a new "
+                         "ops.BankValues")
+    q = _f32c(q)
+    if q.data_ptr() % 16:
+        q = q.clone()
+    B = q.shape[0]
+    lo, hi = _row_window(row_window, B, q.device) if row_window is not None else (None, None)
+    logw = None if row_logw is None else _row_logw(row_logw, N, q.device, "nw_head_values")
+    ls = None if logit_scale is None else _f32c(logit_scale)
+    kid = _kind_id(kind)
+    if kid == SCORE_KINDS["clip"] and ls is None:
+        raise ValueError("clip kernel needs logit_scale")
+    route = head_values_route(split=bank.split is not None, sorted_copy=bank.sorted_rows is not None, shape=bank.shape,
+                              pad=bank.pad, width=q.shape[1], B=B, T=T)
+    if route == "fused":
+        lib = _lib.load()
+        call = _resolve_scores(bank, q, s)
+        qp, d, Tp, st = call.q, call.q.shape[1], values.width, _stream(q)
+        lse = torch.empty(B, dtype=torch.float32, device=q.device)
+        out1 = torch.empty(B, 1, dtype=torch.float32, device=q.device)
+        flo, fhi = (lo, hi) if lo is not None or logw is not None else _whole_window(bank, B, N, q.device)
+        _bank_head_fwd(qp, call, call.sy, logw, flo, fhi, exclude and lo is not None, out1, lse, kid, ls)
+        out = torch.empty(B, Tp, dtype=torch.float32, device=q.device)
+        ws_bytes = lib.nw_fwd_values_workspace_bytes(B, N, d, Tp, 0)
+        ws = _workspace(ws_bytes, q.device, st)
+        with _OnDevice(q.device):
+            _lib.check(lib.nw_fwd_values_f32(_ptr(qp), _ptr(call.operand), _ptr(call.scale), _ptr(call.norm2), _ptr(values.split),
+                                             _ptr(values.scale), _ptr(logw), _ptr(lo), _ptr(hi), int(bool(exclude)), _ptr(lse),
+                                             _ptr(out), _ptr(ws), ws_bytes, B, N, d, Tp, kid, _ptr(ls), 0, st), "nw_fwd_values_f32")
+        if Tp != T:
+            out = out[:, :T]
+    else:
+        vals = values.rows[:, :T]
+        if B == 0 or N == 0:
+            out = torch.zeros(B, T, dtype=torch.float32, device=q.device)
+            lse = torch.full((B,), float("-inf"), dtype=torch.float32, device=q.device)
+        else:
+            scores = nw_scores(q, s, kind, logit_scale, support_cache=bank)
+            if logw is not None:
+                scores += logw
+            if lo is not None:
+                cols = torch.arange(N, device=q.device)
+                keep = (cols >= lo[:, None]) & (cols < hi[:, None])
+                if exclude:
+                    keep = ~keep
+                scores.masked_fill_(~keep, float("-inf"))
+            # (a softmax over nothing is NaN: a dead query gets weight 0 in every row)
+            dead = ~(scores > float("-inf")).any(dim=1)
+            lse = torch.logsumexp(scores, dim=1).masked_fill(dead, float("-inf"))
+            out = torch.softmax(scores, dim=1).masked_fill(dead[:, None], 0.0) @ vals
+    if log:
+        out = torch.log(out + 1e-12)
+    elif not out.is_contiguous():
+        out = out.contiguous()
+    return (out, lse) if return_lse else out
+
+
+def _whole_window(bank, B, N, device):
+    """The kept window [0, N) of B queries as two (B,) int32 tensors, cached on the bank (the lse pass of a value head
+    without a window or weights goes through nw_fwd_window_f32, which wants one)."""
+    cached = getattr(bank, "_whole", None)
+    if cached is None or cached[0].shape[0] != B or cached[0].device != device:
+        cached = bank._whole = (torch.zeros(B, dtype=torch.int32, device=device),
+                                torch.full((B,), N, dtype=torch.int32, device=device))
+    return cached
 
 
 BANK_UPDATE_MAX_ROWS = 16384     # nw_bank_update_rows_f32: every wave scans the rest of `rows` for its own row
