@@ -495,6 +495,34 @@ int nw_fwd_values_f32(const float *q, const float *s_split, const float *s_scale
                       const float *lse, float *out, void *workspace, size_t workspace_bytes,
                       int64_t B, int64_t N, int64_t d, int64_t T, int kind, const float *logit_scale_dev,
                       int row_chunks, void *stream);
+/* The VALUE HEAD AT TRAINING TIME: the gradient of nw_fwd_values_f32 w.r.t. the QUERIES, the bank, the values and the
+ * weights constants -- no (B,N) buffer anywhere, no gradient to the supports, the values or row_logw.  With g = gout,
+ *   c_bj = g_b . v_j,   m_b = g_b . out_b,   dS_bj = W_bj (c_bj - m_b),   W_bj = exp(score_bj + a_j - lse_b),
+ *   gq_b = sum_j dS_bj dscore_bj/dq_b          (the derivative taken at the raw score, as in nw_bwd_query_weighted_f32):
+ * per 64-row support tile the scores are recomputed on the split-fp16 matrix cores, c is a second product of the same
+ * kind over (gout, v_split, T), and dS is contracted with the bank rows in the same kernel (nw_bwd_query_f32's work split).
+ *   q, s_split / s_scale / s_norm2, v_split / v_scale, row_logw, row_lo / row_hi / exclude: nw_fwd_values_f32's operands;
+ *   lse (B,): the log-sum-exp that forward read;  out (B,T): the RAW output it wrote (not a logarithm of it);
+ *   gout (B,T) fp32, 16-byte aligned: the upstream gradient w.r.t. out, zero in the padding columns of T;
+ *   gq (B,d): the result, EVERY element written by a successful call with B > 0;  glogit_scale: optional scalar (0 unless clip);
+ *   row_chunks: as in nw_bwd_query_f32.
+ * A dead query (lse = -inf), a row outside the window, a row at a = -inf and the rows past N of the last tile contribute
+ * exactly 0; an all-zero row of gout gives an all-zero row of gq; scaling a row of gout by a power of two scales its row of gq
+ * exactly.  The value rows are finite in every row, as for the forward.  Chunks are added in chunk order by finishing kernels:
+ * no float atomics, two calls give identical bits.
+ * Accuracy: c - m cancels.  The error of c is ~2.4e-7 sum_t |g_t v_jt| whatever the spread of the values among the rows, so
+ * value columns with a large common offset lose that many bits of the gradient: centre such columns.
+ * Regime, alignment (gout and gq as well), status codes and refusals before anything is launched are nw_fwd_values_f32's;
+ * out, gout or gq NULL: NW_ERR_INVALID_ARG.  workspace: nw_bwd_values_query_workspace_bytes(B, N, d, T, row_chunks), 0 for
+ * a shape outside the regime; short or NULL: NW_ERR_WORKSPACE.  B == 0: NW_OK. */
+size_t nw_bwd_values_query_workspace_bytes(int64_t B, int64_t N, int64_t d, int64_t T, int row_chunks);
+int nw_bwd_values_query_f32(const float *q, const float *s_split, const float *s_scale, const float *s_norm2,
+                            const float *v_split, const float *v_scale, const float *row_logw,
+                            const int32_t *row_lo, const int32_t *row_hi, int exclude,
+                            const float *lse, const float *out, const float *gout,
+                            float *gq, float *glogit_scale, void *workspace, size_t workspace_bytes,
+                            int64_t B, int64_t N, int64_t d, int64_t T, int kind, const float *logit_scale_dev,
+                            int row_chunks, void *stream);
 /* support_influence (util/metric.py:23-50) of k SELECTED supports per query, from the head's own outputs:
  *   vals (B,k) fp32 raw scores and rows (B,k) int64 bank rows (a search's val_out / idx_out),
  *   sy (N,) int64, qy (B,) int64, out (B,C) log-probabilities and lse (B,) of nw_fwd_f32 over the same bank;

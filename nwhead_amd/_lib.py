@@ -60,6 +60,9 @@ SIGNATURES = {
                                      _p, _int, _p]),
     "nw_fwd_values_workspace_bytes": (_sz, [_i64, _i64, _i64, _i64, _int]),
     "nw_fwd_values_f32": (_int, [_p, _p, _p, _p, _p, _p, _p, _p, _p, _int, _p, _p, _p, _sz, _i64, _i64, _i64, _i64, _int, _p, _int, _p]),
+    "nw_bwd_values_query_workspace_bytes": (_sz, [_i64, _i64, _i64, _i64, _int]),
+    "nw_bwd_values_query_f32": (_int, [_p, _p, _p, _p, _p, _p, _p, _p, _p, _int, _p, _p, _p, _p, _p, _p, _sz, _i64, _i64, _i64, _i64,
+                                       _int, _p, _int, _p]),
     "nw_influence_select_f32": (_int, [_p] * 8 + [_i64, _i64, _i64, _i64, _p]),
     "nw_knn_f16_workspace_bytes": (_sz, [_i64, _i64, _i64, _i64]),
     "nw_knn_f16": (_int, [_p, _p, _p, _p, _p, _p, _p, _sz, _i64, _i64, _i64, _i64, _int, _p, _p, _p]),

@@ -117,6 +117,28 @@ bool fwd_values_shape_ok(int64_t B, int64_t N, int64_t d, int64_t T);   // the b
 size_t fwd_values_workspace_bytes(int64_t B, int64_t N, int64_t d, int64_t T, int row_chunks);
 int launch_fwd_values(const FwdValuesCall& c);
 
+// bwd_values.hip: the value head's gradient w.r.t. the queries over the same operands, no (B,N) matrix
+// (nw_bwd_values_query_f32)
+struct BwdValuesCall {
+    const float *q, *s_split, *s_scale, *s_norm2;
+    const float *v_split, *v_scale;   // (N,T), (N,): nw_split_rows_f16x2 of the values
+    const float* row_logw;            // (N,) log-weights of the bank rows, or null
+    const int32_t *row_lo, *row_hi;   // both or neither
+    int exclude;
+    const float *lse, *out, *gout;    // (B,), (B,T) the forward's raw output, (B,T) the upstream gradient
+    float *gq, *glogit_scale;
+    void* workspace;
+    size_t workspace_bytes;
+    int64_t B, N, d, T;
+    int kind;
+    const float* logit_scale_dev;
+    int row_chunks;
+    hipStream_t st;
+};
+bool bwd_values_shape_ok(int64_t B, int64_t N, int64_t d, int64_t T);   // fwd_values_shape_ok's regime
+size_t bwd_values_workspace_bytes(int64_t B, int64_t N, int64_t d, int64_t T, int row_chunks);
+int launch_bwd_values(const BwdValuesCall& c);
+
 // Options of the forward call in progress on this thread (nw_fwd_opts of the ABI, set for the duration of the call by
 // the entry point): explicit arguments, not process state.
 struct FwdOpts {

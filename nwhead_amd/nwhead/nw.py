@@ -31,7 +31,7 @@ class Refusal(NamedTuple):
 WHAT = {"predict": "predict(x, 'full')", "predict_leave_out": "predict(x, 'full', leave_out=...)", "predict_loo": "predict_loo",
         "forward_bank": "forward_bank", "refresh_bank": "refresh_bank", "get_neighbors": "get_neighbors", "explain": "explain",
         "set_support_weights": "set_support_weights", "weights_for": None, "set_support_values": "set_support_values",
-        "predict_values": "predict_values", "predict_loo_values": "predict_loo_values"}
+        "predict_values": "predict_values", "predict_loo_values": "predict_loo_values", "forward_values": "forward_values"}
 # entry point -> why it needs ONE resident bank: the head over a row window, the top-influence windows, one weight per row
 _ROWS_OF = {"explain": "the row windows of ops.nw_top_influence are rows", "set_support_weights": "the weights are rows",
             "set_support_values": "the values are rows"}
@@ -76,7 +76,7 @@ def bank_rule(entry, what=None, *, resident, sharded, searchable=False, builtin_
         return "resident"
     # the entry points over ONE resident bank.  explain and set_support_weights look past a sharded bank when there is a
     # resident one as well, and so does set_support_values; the head over a row window (predict_loo, leave_out, forward_bank,
-    # refresh_bank) and the value head (predict_values, predict_loo_values) do not
+    # refresh_bank) and the value head (predict_values, predict_loo_values, forward_values) do not
     if sharded and not (resident and entry in _ROWS_OF):
         return Refusal(ops.NWHipError, f"{what}: a sharded bank is not served ({_ROWS_OF.get(entry, 'a row window is rows')} of "
                                        "one resident bank); call precompute()")
@@ -532,6 +532,33 @@ class NWNet(nn.Module):
             raise ops.NWHipError(f"{WHAT['predict_values']}: no values are set for the bank: call set_support_values "
                                  "(precompute() clears them)")
         return self._result(self._values_head(self._eval_featurizer()(x).detach(), leave_out, log, "predict_values"))
+
+    def forward_values(self, x, leave_out=None, log=False):
+        """Not in the reference: the VALUE head at TRAINING time, the twin of predict_values as forward_bank is of predict --
+        (B, T) fp32 estimates of ``self.featurizer(x)`` over precompute()'s bank and the value rows of set_support_values,
+        differentiable in the featurizer, the projection and a clip scale (ops.nw_head_values_bank: the query gradient is
+        computed without a (B, N) matrix; a full_precision="fp16" bank or one whose labels are not class-sorted goes
+        through the score matrix).  The featurizer is taken as it is, not the folded eval copy.  ``leave_out``: (B,) int64,
+        the bank row of each query or -1 for none (a leave-one-out regression loss over the bank's own samples).  ``log``:
+        log(out + 1e-12), for soft labels under a KL or cross-entropy loss.  Honours return_mask.
+
+        The bank and the values are CONSTANTS here, as in forward_bank: ``bank_features`` keeps the batch's features,
+        detached, for refresh_bank(rows).  Support weights (set_support_weights) are honoured as a constant; LEARNABLE
+        weights are read detached -- no gradient reaches ``support_logw`` from this head.  Value columns with a large
+        common offset lose that many bits of the gradient (ops.nw_head_values_bank): centre them.  A sharded bank, a missing
+        bank, a custom kernel module and a bank without values are refused (NWHipError), like predict_values."""
+        what = WHAT["forward_values"]
+        self._served("forward_values", early_only=True)    # (a sharded or missing bank: no featurizer pass)
+        vals = getattr(self, 'support_values', None)
+        if vals is None:
+            raise ops.NWHipError(f"{what}: no values are set for the bank: call set_support_values (precompute() clears them)")
+        qfeat = self.featurizer(x)
+        self.bank_features = qfeat.detach()
+        sfeat, _sy, cache = self._resident_bank("forward_values", qfeat.device)
+        window = None if leave_out is None else self._leave_out_window(leave_out, qfeat, what)
+        out = ops.nw_head_values_bank(qfeat, sfeat, cache, vals, self.kernel.kind, self.kernel._logit_scale(), row_window=window,
+                                      exclude=window is not None, row_logw=self._weights(), log=log)
+        return self._result(out)
 
     def predict_loo_values(self, rows=None, batch_size=256, log=False):
         """Not in the reference: leave-one-out value estimates of the bank's own rows, (len(rows), T) -- row i's value

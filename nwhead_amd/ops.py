@@ -1125,7 +1125,8 @@ def nw_head_values(q, s, bank, values, kind="euclidean", logit_scale=None, row_w
     gets 0 in every column (``log``: log(1e-12)) and lse = -inf.
 
     Inference only: a ``q``, ``values`` or ``row_logw`` that requires grad while grad mode is enabled raises NWHipError --
-    the differentiable route is the composition nw_scores + softmax + matmul (torch autograd).
+    the differentiable route is the composition nw_scores + softmax + matmul (torch autograd); for the gradient to the
+    queries alone, without a (B, N) matrix, nw_head_values_bank.
 
     Route (head_values_route): "fused" -- the forward's lse pass (nw_fwd_window_f32 / nw_fwd_weighted_f32 over all-zero
     labels, one class, the kept window [0, N) when there is none) and nw_fwd_values_f32, no (B,N) matrix -- wherever the
@@ -1165,21 +1166,8 @@ def nw_head_values(q, s, bank, values, kind="euclidean", logit_scale=None, row_w
     route = head_values_route(split=bank.split is not None, sorted_copy=bank.sorted_rows is not None, shape=bank.shape,
                               pad=bank.pad, width=q.shape[1], B=B, T=T)
     if route == "fused":
-        lib = _lib.load()
-        call = _resolve_scores(bank, q, s)
-        qp, d, Tp, st = call.q, call.q.shape[1], values.width, _stream(q)
-        lse = torch.empty(B, dtype=torch.float32, device=q.device)
-        out1 = torch.empty(B, 1, dtype=torch.float32, device=q.device)
-        flo, fhi = (lo, hi) if lo is not None or logw is not None else _whole_window(bank, B, N, q.device)
-        _bank_head_fwd(qp, call, call.sy, logw, flo, fhi, exclude and lo is not None, out1, lse, kid, ls)
-        out = torch.empty(B, Tp, dtype=torch.float32, device=q.device)
-        ws_bytes = lib.nw_fwd_values_workspace_bytes(B, N, d, Tp, 0)
-        ws = _workspace(ws_bytes, q.device, st)
-        with _OnDevice(q.device):
-            _lib.check(lib.nw_fwd_values_f32(_ptr(qp), _ptr(call.operand), _ptr(call.scale), _ptr(call.norm2), _ptr(values.split),
-                                             _ptr(values.scale), _ptr(logw), _ptr(lo), _ptr(hi), int(bool(exclude)), _ptr(lse),
-                                             _ptr(out), _ptr(ws), ws_bytes, B, N, d, Tp, kid, _ptr(ls), 0, st), "nw_fwd_values_f32")
-        if Tp != T:
+        out, lse = _values_head_fwd(_resolve_scores(bank, q, s), bank, values, logw, lo, hi, exclude, kid, ls)
+        if values.width != T:
             out = out[:, :T]
     else:
         vals = values.rows[:, :T]
@@ -1205,6 +1193,27 @@ def nw_head_values(q, s, bank, values, kind="euclidean", logit_scale=None, row_w
     elif not out.is_contiguous():
         out = out.contiguous()
     return (out, lse) if return_lse else out
+
+
+def _values_head_fwd(call, bank, values, logw, lo, hi, exclude, kind_id, ls):
+    """The two launches of the fused value head -> (out (B, values.width), lse (B,)): the forward's lse pass (_bank_head_fwd
+    over all-zero labels and one class; the kept window [0, N) when there is neither a window nor weights), then
+    nw_fwd_values_f32.  ``call``: _resolve_scores' _Call of the fp32 queries padded to the bank (``call.q``)."""
+    lib = _lib.load()
+    qp, N, Tp = call.q, call.operand.shape[0], values.width
+    (B, d), dev, st = qp.shape, qp.device, _stream(qp)
+    lse = torch.empty(B, dtype=torch.float32, device=dev)
+    out1 = torch.empty(B, 1, dtype=torch.float32, device=dev)
+    flo, fhi = (lo, hi) if lo is not None or logw is not None else _whole_window(bank, B, N, dev)
+    _bank_head_fwd(qp, call, call.sy, logw, flo, fhi, exclude and lo is not None, out1, lse, kind_id, ls)
+    out = torch.empty(B, Tp, dtype=torch.float32, device=dev)
+    ws_bytes = lib.nw_fwd_values_workspace_bytes(B, N, d, Tp, 0)
+    ws = _workspace(ws_bytes, dev, st)
+    with _OnDevice(dev):
+        _lib.check(lib.nw_fwd_values_f32(_ptr(qp), _ptr(call.operand), _ptr(call.scale), _ptr(call.norm2), _ptr(values.split),
+                                         _ptr(values.scale), _ptr(logw), _ptr(lo), _ptr(hi), int(bool(exclude)), _ptr(lse),
+                                         _ptr(out), _ptr(ws), ws_bytes, B, N, d, Tp, kind_id, _ptr(ls), 0, st), "nw_fwd_values_f32")
+    return out, lse
 
 
 def _whole_window(bank, B, N, device):
@@ -1361,6 +1370,202 @@ def nw_head_bank(q, s, sy, n_classes, bank, kind="euclidean", logit_scale=None, 
         window = None if row_window is None else tuple(_row_window(row_window, q.shape[0], q.device))
     out = _NWHeadBankFn.apply(call.q, logit_scale, call, C, kid, window, bool(exclude), bank, logw, row_logw)
     return out
+
+
+def head_values_grad_route(*, split, sorted_copy, shape, pad, width, B, T):
+    """Which route serves the gradients of ``nw_head_values_bank``, beside head_values_route and over the same plain facts:
+    "fused" (the value head's two launches forward, nw_bwd_values_query_f32 backward: no (B, N) buffer) exactly where
+    head_values_route says "fused"; else "matrix": the differentiable composition nw_scores over the bank, + row_logw, the
+    window's mask, torch.softmax and a matmul with the values -- windows and weights included, so no shape is refused."""
+    return head_values_route(split=split, sorted_copy=sorted_copy, shape=shape, pad=pad, width=width, B=B, T=T)
+
+
+class _ScoresFn(torch.autograd.Function):
+    """``nw_scores`` with a gradient to the queries and to a clip ``logit_scale``, the supports a constant: the score matrix
+    of the "matrix" route of nw_head_values_bank.  Forward: nw_scores, as it is.  Backward: the closed forms of bwd_coeff.h in
+    torch ops over the saved (B, N) scores -- a = g df/ddot, gq = a @ s + 2 rq q -- two (B, N) x (N, d) products; the
+    zero sub-gradient at distance 0 and F.normalize's clamp are those of the kernels."""
+
+    @staticmethod
+    def forward(ctx, q, logit_scale, s, kind, bank):
+        sc = nw_scores(q, s, kind, logit_scale, support_cache=bank)
+        ctx.save_for_backward(q, s, sc, *([logit_scale] if logit_scale is not None else []))
+        ctx.kind = _kind_id(kind)
+        return sc
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        q, s, sc = ctx.saved_tensors[:3]
+        q, s, kid, gls = q.float(), s.float(), ctx.kind, None
+        if kid == SCORE_KINDS["dotproduct"]:
+            return g @ s, None, None, None, None
+        if kid == SCORE_KINDS["euclidean"]:
+            a = torch.where(sc == 0, torch.zeros_like(g), g / -sc)
+            return a @ s - a.sum(1, keepdim=True) * q, None, None, None, None
+        nq, ns = q.norm(dim=1, keepdim=True), s.norm(dim=1, keepdim=True).clamp_min(1e-12)
+        nqc = nq.clamp_min(1e-12)
+        if kid == SCORE_KINDS["hypersphere_euclidean"]:
+            gc, c = torch.where(sc == 0, torch.zeros_like(g), g / -sc), 1.0 - 0.5 * sc * sc
+        elif kid == SCORE_KINDS["cosine"]:
+            gc, c = g, sc
+        else:
+            scale = ctx.saved_tensors[3].float().exp()
+            gc, c, gls = g * scale, sc / scale, (g * sc).sum().to(ctx.saved_tensors[3].dtype)
+        through_norm = torch.where(nq > 1e-12, (gc * c).sum(1, keepdim=True), torch.zeros_like(nq))   # (the clamp passes none)
+        return (gc @ (s / ns) - through_norm * (q / nqc)) / nqc, gls, None, None, None
+
+
+def _values_head_matrix(q, s, bank, vals, kind, logit_scale, logw, lo, hi, exclude):
+    """The differentiable "matrix" composition of the value head -> (B, T): nw_scores over the bank (_ScoresFn), + ``logw``,
+    the window's mask, torch.softmax, @ ``vals`` ((N, T) fp32), a dead query 0 in every column.  Autograd keeps the (B, N)
+    matrices."""
+    N = s.shape[0]
+    x = _ScoresFn.apply(q, logit_scale, s, kind, bank)
+    if logw is not None:
+        x = x + logw
+    if lo is not None:
+        cols = torch.arange(N, device=q.device)
+        keep = (cols >= lo[:, None]) & (cols < hi[:, None])
+        x = x.masked_fill(keep if exclude else ~keep, float("-inf"))
+    dead = ~(x > float("-inf")).any(dim=1, keepdim=True)       # (a softmax over nothing is NaN, and so is its gradient)
+    return torch.softmax(x.masked_fill(dead, 0.0), dim=1).masked_fill(dead, 0.0) @ vals
+
+
+class _NWValuesBankFn(torch.autograd.Function):
+    """autograd node of nw_head_values_bank on the fused route: the inference launches forward (_values_head_fwd: the lse pass,
+    nw_fwd_values_f32), ONE call of nw_bwd_values_query_f32 backward.  Returns the padded (B, values.width) raw output; the
+    slice to T and the logarithm are torch ops behind it.  Saves the queries, lse, out and the window: nothing of size B x N."""
+
+    @staticmethod
+    def forward(ctx, q, logit_scale, call, bank, values, kind_id, window, exclude, logw=None, logw_src=None):
+        """``call``: _resolve_scores' _Call (``q`` is its queries, an argument of its own for autograd); ``values``: the
+        BankValues; ``window``: None or (lo, hi) int32; ``logw`` / ``logw_src``: as in _NWHeadBankFn."""
+        qc = _f32c(q)
+        if qc.data_ptr() % 16:
+            qc = qc.clone()
+        ls = None if logit_scale is None else _f32c(logit_scale)
+        lo, hi = window if window is not None else (None, None)
+        out, lse = _values_head_fwd(call._replace(q=qc), bank, values, logw, lo, hi, exclude, kind_id, ls)
+        ctx.save_for_backward(qc, lse, out, *([ls] if ls is not None else []), *([lo, hi] if window is not None else []))
+        # the backward recomputes the scores and c from these: constants of this node, each with what tells a write
+        ctx.bank = (call.operand, call.scale, call.norm2)
+        ctx.bank_writes = (bank, bank.writes)
+        ctx.values = values
+        ctx.logw = None if logw is None else (logw, logw_src, logw_src._version)
+        ctx.meta = (kind_id, ls is not None, window is not None, exclude)
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gout):
+        kind_id, has_ls, windowed, exclude = ctx.meta
+        saved = list(ctx.saved_tensors)
+        qc, lse, out = saved[:3]
+        ls = saved[3] if has_ls else None
+        lo, hi = saved[-2:] if windowed else (None, None)
+        if ctx.bank_writes[0].writes != ctx.bank_writes[1]:
+            raise RuntimeError("nw_head_values_bank: the bank was written (SplitBank.update_rows) between this forward and its "
+                               "backward, which recomputes the scores from the bank: call backward() first, then update")
+        if ctx.logw is not None and ctx.logw[1]._version != ctx.logw[2]:
+            raise RuntimeError("nw_head_values_bank: row_logw was written in place between this forward and its backward, which "
+                               "recomputes the weighted scores from it: call backward() first, then change the weights")
+        if ctx.values.stale():
+            raise RuntimeError("nw_head_values_bank: the tensor the BankValues was prepared from was written between this forward "
+                               "and its backward (the prepared rows no longer stand for it): build a new ops.BankValues")
+        lib = _lib.load()
+        ssplit, sscale, sn2 = ctx.bank
+        logw = ctx.logw and ctx.logw[0]
+        (B, d), N, Tp, dev = qc.shape, ssplit.shape[0], out.shape[1], qc.device
+        g = _f32c(gout)
+        if g.data_ptr() % 16:
+            g = g.clone()
+        gq = torch.empty_like(qc)
+        gls = torch.empty((), dtype=torch.float32, device=dev) if ls is not None else None
+        ws_bytes = lib.nw_bwd_values_query_workspace_bytes(B, N, d, Tp, 0)
+        ws = _workspace(ws_bytes, dev)
+        with _OnDevice(dev):
+            _lib.check(lib.nw_bwd_values_query_f32(_ptr(qc), _ptr(ssplit), _ptr(sscale), _ptr(sn2), _ptr(ctx.values.split),
+                                                   _ptr(ctx.values.scale), _ptr(logw), _ptr(lo), _ptr(hi), int(bool(exclude)),
+                                                   _ptr(lse), _ptr(out), _ptr(g), _ptr(gq), _ptr(gls), _ptr(ws), ws_bytes, B, N, d,
+                                                   Tp, kind_id, _ptr(ls), 0, _stream(qc)), "nw_bwd_values_query_f32")
+        return gq, gls, None, None, None, None, None, None, None, None
+
+
+def nw_head_values_bank(q, s, bank, values, kind="euclidean", logit_scale=None, row_window=None, exclude=False, row_logw=None,
+                        log=False):
+    """The VALUE head over a RESIDENT bank at training time: ``nw_head_values``, differentiable in the queries (and a clip
+    ``logit_scale``) with the bank, the values and the weights constants -> (B, T) fp32.  For fine-tuning a featurizer against
+    a frozen or periodically refreshed bank with regression targets, soft / mixup / distilled labels (``log=True`` and a KL or
+    cross-entropy loss), embeddings to retrieve, or a leave-one-out regression loss over the bank's own rows (``row_window`` /
+    ``exclude``).  The counterpart of nw_head_bank; arguments as in nw_head_values.
+
+    With nothing requiring grad, or grad mode off, this IS nw_head_values(...): the same call, the same bits.  Otherwise, on
+    the fused route, the forward is the inference launches as they are (the lse pass, nw_fwd_values_f32: bit-equal to
+    nw_head_values under no_grad) and the backward ONE call of nw_bwd_values_query_f32, which recomputes the scores and
+    c = gout @ values^T tile by tile on the split-fp16 matrix cores and contracts dS = W (c - gout . out) with the bank rows
+    in the same kernel: the node saves q, lse, out and the window, nothing of size B x N.  The slice to T
+    columns and ``log`` (log(out + 1e-12)) are torch ops behind the node.
+    Route (head_values_grad_route): that kernel exactly where nw_head_values is fused; else (an fp16 or norms-only bank, a
+    class-sorted copy, N <= 25, widths that do not pad, T > 16384) "matrix": nw_scores over the bank, + row_logw, the
+    window's mask, torch.softmax and a matmul, through torch autograd and three (B, N) matrices -- no shape is refused.
+
+    Constants: `s` must not require grad (ValueError); ``values`` or ``row_logw`` that requires grad raises NWHipError (no
+    gradient to either is computed here: the composition nw_scores + softmax + matmul differentiates in them through the
+    (B, N) matrix).  On the fused route a bank written (SplitBank.update_rows), a ``row_logw`` written in place, or a
+    BankValues gone stale between forward and backward is refused at backward (RuntimeError).
+
+    Accuracy: c - gout . out cancels.  The error of c is ~2.4e-7 sum_t |gout_t values_jt| whatever the spread of the values
+    among the rows, so value columns with a large common offset lose that many bits of the gradient: CENTRE such columns
+    (the forward is linear in the values: add the offset back to the output).  Every value must be finite, in every row."""
+    _need_hip(q, s, logit_scale)
+    if not isinstance(bank, SplitBank):
+        raise TypeError("nw_head_values_bank runs over a prepared bank: pass ops.SplitBank(support)")
+    grad = torch.is_grad_enabled()
+    if grad and s.requires_grad:
+        raise ValueError("nw_head_values_bank: the bank is a constant here and `s` requires grad")
+    raw = values if torch.is_tensor(values) else None
+    if grad and ((raw.requires_grad if raw is not None else getattr(values, "requires_grad", False))
+                 or (torch.is_tensor(row_logw) and row_logw.requires_grad)):
+        raise NWHipError("nw_head_values_bank differentiates in the queries and a clip scale alone and does not detach silently: "
+                         "values or row_logw requires grad.  The composition nw_scores + softmax + matmul differentiates in them")
+    if not (grad and (q.requires_grad or (logit_scale is not None and logit_scale.requires_grad))):
+        return nw_head_values(q, s, bank, values, kind, logit_scale, row_window=row_window, exclude=exclude, row_logw=row_logw,
+                              log=log)
+    if s.dim() != 2 or not bank.matches(s):
+        raise ValueError("nw_head_values_bank: `s` (N,d) must be the tensor the bank was prepared from")
+    if raw is not None:
+        values = BankValues(raw, bank)
+    elif not isinstance(values, BankValues):
+        raise TypeError("nw_head_values_bank: values is an ops.BankValues or an (N,T) float tensor")
+    N, T = s.shape[0], values.T
+    if values.rows.shape[0] != N or values.rows.device != q.device:
+        raise ValueError(f"nw_head_values_bank: the values hold {values.rows.shape[0]} rows on {values.rows.device} for a bank of "
+                         f"{N} rows and queries on {q.device}")
+    if values.stale():
+        raise ValueError("nw_head_values_bank: the tensor this BankValues was prepared from was written since; build a new "
+                         "ops.BankValues")
+    if q.dtype != torch.float32:
+        q = q.float()
+    B = q.shape[0]
+    window = None if row_window is None else tuple(_row_window(row_window, B, q.device))
+    logw = None if row_logw is None else _row_logw(row_logw, N, q.device, "nw_head_values_bank")
+    kid = _kind_id(kind)
+    if kid == SCORE_KINDS["clip"] and logit_scale is None:
+        raise ValueError("clip kernel needs logit_scale")
+    route = head_values_grad_route(split=bank.split is not None, sorted_copy=bank.sorted_rows is not None, shape=bank.shape,
+                                   pad=bank.pad, width=q.shape[1], B=B, T=T)
+    if route == "fused":
+        call = _resolve_scores(bank, q, s)                      # (queries padded by a torch op: autograd slices gq back)
+        out = _NWValuesBankFn.apply(call.q, logit_scale, call, bank, values, kid, window, bool(exclude), logw, row_logw)
+        if values.width != T:
+            out = out[:, :T]
+    elif B == 0 or N == 0:
+        out = torch.zeros(B, T, dtype=torch.float32, device=q.device) + 0.0 * q.sum()
+    else:
+        lo, hi = window if window is not None else (None, None)
+        out = _values_head_matrix(q, s, bank, values.rows[:, :T], kind, logit_scale, logw, lo, hi, bool(exclude))
+    return torch.log(out + 1e-12) if log else out
 
 
 def nw_partials(q, s, sy, n_classes, kind="euclidean", logit_scale=None, support_cache=None):
