@@ -523,6 +523,36 @@ int nw_bwd_values_query_f32(const float *q, const float *s_split, const float *s
                             float *gq, float *glogit_scale, void *workspace, size_t workspace_bytes,
                             int64_t B, int64_t N, int64_t d, int64_t T, int kind, const float *logit_scale_dev,
                             int row_chunks, void *stream);
+/* LEARNABLE VALUES AND SUPPORT WEIGHTS of the value head: the gradients of nw_fwd_values_f32 w.r.t. the VALUES and row_logw,
+ *   gvalues[j,t] = sum_b W_bj g_bt,
+ *   glogw[j]     = sum_b W_bj (g_b . v_j - m_b) = gvalues[j] . v_j - sum_b W_bj m_b,     m_b = g_b . out_b,
+ * contractions over the QUERIES of the weights W_bj = exp(score_bj + a_j - lse_b) that nw_bwd_values_query_f32 recomputes:
+ * a workgroup owns a 64-row support tile and a slab of value columns and loops over the 64-query tiles.  No (B,N) buffer,
+ * no G V^T product, no float atomics.
+ *   q, s_split / s_scale / s_norm2, row_logw, row_lo / row_hi / exclude, lse, out, gout: nw_bwd_values_query_f32's operands;
+ *   v_rows   (N,T) the fp32 VALUES themselves (not split), 16-byte aligned, finite; read for glogw only, may be NULL without;
+ *   gvalues  (N,T) fp32 or NULL, 16-byte aligned;  glogw (N,) fp32 or NULL, 16-byte aligned: at least one.  glogw requires
+ *            row_logw and v_rows.  With gvalues == NULL (the weights-only mode) nothing of size N x T is stored or needed;
+ *   query_chunks: 0 lets the library split the query loop when the support tiles alone cannot fill the chip; a positive
+ *            value is clamped to the number of 64-query tiles.  Chunk partials are added in chunk order by a finish kernel.
+ * EVERY element of gvalues[0..N) x [0..T) and of glogw[0..N) is written by a successful call with B > 0, nothing past them.
+ * A row at a = -inf, a row no query's window admits and the share of a dead query (lse = -inf) are exactly +0.0 in every
+ * column and in glogw; a zero column of gout gives a zero column of gvalues; the value rows do not enter gvalues.  Scaling
+ * gout by a power of two scales gvalues exactly.  Two calls with the same arguments give the same bits.
+ * Accuracy: W 2^15 and gout 2^E (E from max |gout|) are split into fp16 halves, products exact, sums fp32:
+ *   |error of gvalues[j,t]| <~ (2^-21 + B 2^-24) sum_b W_bj |g_bt| + 2^-38 max|gout| sum_b W_bj.
+ * Regime, alignment, status codes and refusals before anything is launched are nw_bwd_values_query_f32's; gvalues and glogw
+ * both NULL, glogw without row_logw or v_rows: NW_ERR_INVALID_ARG.  workspace:
+ * nw_bwd_values_support_workspace_bytes(B, N, d, T, query_chunks, want_gvalues) with want_gvalues = (gvalues != NULL), 0
+ * for a shape outside the regime; short or NULL: NW_ERR_WORKSPACE.  B == 0: NW_OK and NOTHING is touched. */
+size_t nw_bwd_values_support_workspace_bytes(int64_t B, int64_t N, int64_t d, int64_t T, int query_chunks, int want_gvalues);
+int nw_bwd_values_support_f32(const float *q, const float *s_split, const float *s_scale, const float *s_norm2,
+                              const float *v_rows, const float *row_logw,
+                              const int32_t *row_lo, const int32_t *row_hi, int exclude,
+                              const float *lse, const float *out, const float *gout,
+                              float *gvalues, float *glogw, void *workspace, size_t workspace_bytes,
+                              int64_t B, int64_t N, int64_t d, int64_t T, int kind, const float *logit_scale_dev,
+                              int query_chunks, void *stream);
 /* support_influence (util/metric.py:23-50) of k SELECTED supports per query, from the head's own outputs:
  *   vals (B,k) fp32 raw scores and rows (B,k) int64 bank rows (a search's val_out / idx_out),
  *   sy (N,) int64, qy (B,) int64, out (B,C) log-probabilities and lse (B,) of nw_fwd_f32 over the same bank;

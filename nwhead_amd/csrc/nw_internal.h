@@ -139,6 +139,27 @@ bool bwd_values_shape_ok(int64_t B, int64_t N, int64_t d, int64_t T);   // fwd_v
 size_t bwd_values_workspace_bytes(int64_t B, int64_t N, int64_t d, int64_t T, int row_chunks);
 int launch_bwd_values(const BwdValuesCall& c);
 
+// bwd_values_support.hip: the value head's gradients w.r.t. the values and the row weights, contractions over the queries of
+// the same recomputed weights, no (B,N) matrix (nw_bwd_values_support_f32)
+struct BwdValuesSupportCall {
+    const float *q, *s_split, *s_scale, *s_norm2;
+    const float* v_rows;              // (N,T) the fp32 values, read for glogw only
+    const float* row_logw;            // (N,) log-weights of the bank rows, or null
+    const int32_t *row_lo, *row_hi;   // both or neither
+    int exclude;
+    const float *lse, *out, *gout;
+    float *gvalues, *glogw;           // (N,T), (N,): at least one
+    void* workspace;
+    size_t workspace_bytes;
+    int64_t B, N, d, T;
+    int kind;
+    const float* logit_scale_dev;
+    int query_chunks;
+    hipStream_t st;
+};
+size_t bwd_values_support_workspace_bytes(int64_t B, int64_t N, int64_t d, int64_t T, int query_chunks, bool want_gvalues);
+int launch_bwd_values_support(const BwdValuesSupportCall& c);
+
 // Options of the forward call in progress on this thread (nw_fwd_opts of the ABI, set for the duration of the call by
 // the entry point): explicit arguments, not process state.
 struct FwdOpts {

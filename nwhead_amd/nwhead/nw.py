@@ -258,6 +258,7 @@ class NWNet(nn.Module):
         self.support_eval.knn.bank = self.support_eval.hnsw.bank = self.full_cache   # neighbour search over the same bank
         self.support_weights = None                  # weights are per row of the bank they were set for
         self.support_values = None                   # ... and so are values
+        self._parameters.pop('support_targets', None)   # ... learnable ones with their parameter
         if self.balance_full == "weights":
             self.set_support_weights(ops.class_balance_logw(self.full_y, self.n_classes))
 
@@ -486,7 +487,7 @@ class NWNet(nn.Module):
         out = torch.cat(outs) if outs else torch.empty(0, self.n_classes, device=self.full_feat.device)
         return self._result(out)
 
-    def set_support_values(self, values=None):
+    def set_support_values(self, values=None, learnable=False):
         """Not in the reference: a real-valued TARGET ROW per row of precompute()'s bank, for predict_values /
         predict_loo_values -- Nadaraya-Watson regression over the resident bank (an age, a pose, a box, an embedding to
         retrieve), soft / smoothed / mixup / distilled or multi-hot labels, or any per-row attribute carried through the
@@ -494,24 +495,46 @@ class NWNet(nn.Module):
         ``full_feat``, every entry finite; ``None`` clears them.  Prepared once, here, as an ops.BankValues (``support_values``:
         an fp32 copy and its split-fp16 form) from a copy of the caller's tensor: later writes to that tensor are not seen;
         to change value rows, call this again.  Kept by refresh_bank (rows keep their identity); cleared by precompute().
-        A sharded bank, a missing bank and a custom kernel module are refused (NWHipError), like set_support_weights."""
+        A sharded bank, a missing bank and a custom kernel module are refused (NWHipError), like set_support_weights.
+
+        ``learnable=True`` makes the values LEARNED (soft labels corrected against label noise, target prototypes, distilled
+        targets): they are registered as the nn.Parameter ``support_targets``, (N, T) fp32 -- in parameters() and
+        state_dict() from this call on, not before, like ``support_logw`` -- forward_values passes them with their graph
+        (ops.nw_head_values_bank(support_grad=True): no (B, N) matrix), and every value entry point re-prepares the
+        BankValues in place (BankValues.refresh) when the parameter was written since -- an optimizer step, a
+        load_state_dict.  predict_values / predict_loo_values read the current values detached.  precompute() and
+        set_support_values(None) drop the parameter: set the values again and rebuild the optimizer's parameter group."""
         if values is None:
+            self._parameters.pop('support_targets', None)
             self.support_values = None
             return
         self._served("set_support_values")
+        self._parameters.pop('support_targets', None)    # a learnable set ends with the values it was registered for
         sfeat, _sy, cache = self._resident_bank()
         v = torch.as_tensor(values)
         if v.dim() != 2 or v.shape[0] != sfeat.shape[0] or v.shape[1] < 1 or not v.is_floating_point():
             raise ValueError(f"set_support_values: values must be ({sfeat.shape[0]}, T) floats, T >= 1: one row per bank row; got "
                              f"{tuple(v.shape)} {v.dtype}")
-        self.support_values = ops.BankValues(v.detach().to(device=sfeat.device, copy=True), cache)
+        if learnable:
+            self.support_targets = nn.Parameter(v.detach().to(device=sfeat.device, dtype=torch.float32, copy=True).contiguous())
+            self.support_values = ops.BankValues(self.support_targets, cache)
+        else:
+            self.support_values = ops.BankValues(v.detach().to(device=sfeat.device, copy=True), cache)
+
+    def _values(self):
+        """``support_values`` for a call, or None: learnable values written since they were prepared (an optimizer step) are
+        re-prepared in place first."""
+        vals = getattr(self, 'support_values', None)
+        if vals is not None and self._parameters.get('support_targets') is not None and vals.stale():
+            vals.refresh()
+        return vals
 
     def _values_head(self, qfeat, rows, log, entry):
         """ops.nw_head_values of the featurised queries ``qfeat`` over precompute()'s bank and the values set for it, query b
         without bank row rows[b] (None: no window); constant support weights are honoured, learnable ones read detached."""
         what = WHAT[entry]
         sfeat, _sy, cache = self._resident_bank(entry, qfeat.device)
-        vals = getattr(self, 'support_values', None)
+        vals = self._values()
         if vals is None:
             raise ops.NWHipError(f"{what}: no values are set for the bank: call set_support_values (precompute() clears them)")
         window = None if rows is None else self._leave_out_window(rows, qfeat, what)
@@ -533,7 +556,7 @@ class NWNet(nn.Module):
                                  "(precompute() clears them)")
         return self._result(self._values_head(self._eval_featurizer()(x).detach(), leave_out, log, "predict_values"))
 
-    def forward_values(self, x, leave_out=None, log=False):
+    def forward_values(self, x, leave_out=None, log=False, weights_grad=False):
         """Not in the reference: the VALUE head at TRAINING time, the twin of predict_values as forward_bank is of predict --
         (B, T) fp32 estimates of ``self.featurizer(x)`` over precompute()'s bank and the value rows of set_support_values,
         differentiable in the featurizer, the projection and a clip scale (ops.nw_head_values_bank: the query gradient is
@@ -546,18 +569,25 @@ class NWNet(nn.Module):
         detached, for refresh_bank(rows).  Support weights (set_support_weights) are honoured as a constant; LEARNABLE
         weights are read detached -- no gradient reaches ``support_logw`` from this head.  Value columns with a large
         common offset lose that many bits of the gradient (ops.nw_head_values_bank): centre them.  A sharded bank, a missing
-        bank, a custom kernel module and a bank without values are refused (NWHipError), like predict_values."""
+        bank, a custom kernel module and a bank without values are refused (NWHipError), like predict_values.
+
+        LEARNABLE values (set_support_values(..., learnable=True)) are passed with their graph: a loss on the output puts a
+        gradient on ``support_targets``.  ``weights_grad=True`` passes learnable support weights with their graph as well,
+        so that ``support_logw`` learns from this head too; the default keeps the detached read described above.  Both go
+        through ops.nw_head_values_bank(support_grad=True) (no (B, N) matrix)."""
         what = WHAT["forward_values"]
         self._served("forward_values", early_only=True)    # (a sharded or missing bank: no featurizer pass)
-        vals = getattr(self, 'support_values', None)
+        vals = self._values()
         if vals is None:
             raise ops.NWHipError(f"{what}: no values are set for the bank: call set_support_values (precompute() clears them)")
         qfeat = self.featurizer(x)
         self.bank_features = qfeat.detach()
         sfeat, _sy, cache = self._resident_bank("forward_values", qfeat.device)
         window = None if leave_out is None else self._leave_out_window(leave_out, qfeat, what)
+        support = {"support_grad": True} if weights_grad or self._parameters.get('support_targets') is not None else {}
         out = ops.nw_head_values_bank(qfeat, sfeat, cache, vals, self.kernel.kind, self.kernel._logit_scale(), row_window=window,
-                                      exclude=window is not None, row_logw=self._weights(), log=log)
+                                      exclude=window is not None, row_logw=self._weights(graph=bool(weights_grad)), log=log,
+                                      **support)
         return self._result(out)
 
     def predict_loo_values(self, rows=None, batch_size=256, log=False):
@@ -567,7 +597,7 @@ class NWNet(nn.Module):
         the exclusion inside the kernel before the softmax.  ``rows``: (R,) int64 bank rows, default all.  Honours
         set_support_weights, return_mask and ``log`` like predict_values; refuses what it refuses."""
         self._served("predict_loo_values", early_only=True)
-        vals = getattr(self, 'support_values', None)
+        vals = self._values()
         if vals is None:
             raise ops.NWHipError(f"{WHAT['predict_loo_values']}: no values are set for the bank: call set_support_values "
                                  "(precompute() clears them)")

@@ -1075,8 +1075,8 @@ class BankValues:
     weight removes still meets the matrix pipe with a 0 coefficient, and 0 x inf is NaN); nothing is checked.  The split
     format scales by ROW: an element keeps 22 bits down to 2^-18 of its row's largest magnitude, an absolute error of 2^-38
     of that below -- columns of very different magnitude belong in separate BankValues.
-    ``matches(values)``: the very tensor, not written since; ``stale()``: that tensor is alive and was written.  There is no in-place update of value rows: build a new
-    BankValues.  T above HEAD_VALUES_MAX_T keeps the fp32 copy only (the matrix route)."""
+    ``matches(values)``: the very tensor, not written since; ``stale()``: that tensor is alive and was written.  After such a write ``refresh()`` re-prepares in place from the live tensor (no
+    allocation); there is no update of single value rows.  T above HEAD_VALUES_MAX_T keeps the fp32 copy only (the matrix route)."""
 
     def __init__(self, values, bank):
         if not isinstance(bank, SplitBank):
@@ -1096,10 +1096,35 @@ class BankValues:
         if N > 0 and self.width <= HEAD_VALUES_MAX_T:
             self.split = torch.empty_like(self.rows)
             self.scale = torch.empty(N, dtype=torch.float32, device=vc.device)
-            norm2 = torch.empty(N, dtype=torch.float32, device=vc.device)      # (the packer's third output: not needed)
+            norm2 = self._norm2 = torch.empty(N, dtype=torch.float32, device=vc.device)      # (the packer's third output: not needed)
             with _OnDevice(vc.device):
                 _lib.check(_lib.load().nw_split_rows_f16x2(_ptr(self.rows), _ptr(self.split), _ptr(self.scale), _ptr(norm2),
                                                            N, self.width, _stream(vc)), "nw_split_rows_f16x2")
+
+    def source(self):
+        """The tensor this object was prepared from, or None when it is gone (only a weak reference is kept)."""
+        return self._ref()
+
+    def refresh(self):
+        """Re-prepare IN PLACE from the live source tensor after it was written (an optimiser step on learnable values): the
+        copy into the padded fp32 rows and one nw_split_rows_f16x2 into the existing buffers -- no allocation -- and the
+        staleness signature moves to the tensor's present version.  A training loop that steps the values calls this once
+        per step instead of building a new BankValues.  The source gone: NWHipError."""
+        t = self._ref()
+        if t is None:
+            raise NWHipError("BankValues.refresh: the tensor this object was prepared from is gone; build a new ops.BankValues")
+        if t.data_ptr() != self._src[0] or tuple(t.shape) != self._src[1]:
+            raise NWHipError("BankValues.refresh: the source tensor was replaced or reshaped; build a new ops.BankValues")
+        with torch.no_grad():
+            self.rows[:, :self.T].copy_(t.detach())
+        if self.split is not None:
+            with _OnDevice(self.rows.device):
+                _lib.check(_lib.load().nw_split_rows_f16x2(_ptr(self.rows), _ptr(self.split), _ptr(self.scale), _ptr(self._norm2),
+                                                           self.rows.shape[0], self.width, _stream(self.rows)),
+                           "nw_split_rows_f16x2")
+        self._src = _sig(t)
+        self.requires_grad = bool(t.requires_grad)
+        return self
 
     def matches(self, values):
         """True when ``values`` is the very tensor (storage, shape, no in-place update since) this object was prepared from."""
@@ -1492,8 +1517,149 @@ class _NWValuesBankFn(torch.autograd.Function):
         return gq, gls, None, None, None, None, None, None, None, None
 
 
+def _values_support_bwd(qc, operands, values, logw, lo, hi, exclude, lse, out, g, kind_id, ls, want_gvalues, want_glogw,
+                        query_chunks=0):
+    """ONE call of nw_bwd_values_support_f32 -> (gvalues (N, values.width) or None, glogw (N,) or None).  ``operands``: the
+    bank's (split rows, scales, norms); ``g``: the fp32 upstream gradient, 16-byte aligned.  Without ``want_gvalues`` nothing
+    of size N x T is allocated."""
+    lib = _lib.load()
+    ssplit, sscale, sn2 = operands
+    (B, d), N, Tp, dev = qc.shape, ssplit.shape[0], out.shape[1], qc.device
+    gv = torch.empty(N, Tp, dtype=torch.float32, device=dev) if want_gvalues else None
+    ga = torch.empty(N, dtype=torch.float32, device=dev) if want_glogw else None
+    ws_bytes = lib.nw_bwd_values_support_workspace_bytes(B, N, d, Tp, query_chunks, int(want_gvalues))
+    ws = _workspace(ws_bytes, dev)
+    with _OnDevice(dev):
+        _lib.check(lib.nw_bwd_values_support_f32(_ptr(qc), _ptr(ssplit), _ptr(sscale), _ptr(sn2),
+                                                 _ptr(values.rows) if want_glogw else None, _ptr(logw), _ptr(lo), _ptr(hi),
+                                                 int(bool(exclude)), _ptr(lse), _ptr(out), _ptr(g), _ptr(gv), _ptr(ga), _ptr(ws),
+                                                 ws_bytes, B, N, d, Tp, kind_id, _ptr(ls), query_chunks, _stream(qc)),
+                   "nw_bwd_values_support_f32")
+    return gv, ga
+
+
+class _NWValuesSupportFn(torch.autograd.Function):
+    """autograd node of nw_head_values_bank(support_grad=True) on the fused route: _NWValuesBankFn's forward (the inference
+    launches as they are); backward nw_bwd_values_query_f32 when the queries or a clip scale need it (the same call, the same
+    bits) and ONE call of nw_bwd_values_support_f32 for the values' source tensor (3rd input) and the caller's row_logw (last
+    input), each in its dtype.  When only the weights learn nothing of size N x T is allocated.  Saves what _NWValuesBankFn
+    saves: nothing of size B x N."""
+
+    @staticmethod
+    def forward(ctx, q, logit_scale, vsrc, call, bank, values, kind_id, window, exclude, logw=None, logw_src=None):
+        qc = _f32c(q)
+        if qc.data_ptr() % 16:
+            qc = qc.clone()
+        ls = None if logit_scale is None else _f32c(logit_scale)
+        lo, hi = window if window is not None else (None, None)
+        out, lse = _values_head_fwd(call._replace(q=qc), bank, values, logw, lo, hi, exclude, kind_id, ls)
+        ctx.save_for_backward(qc, lse, out, *([ls] if ls is not None else []), *([lo, hi] if window is not None else []))
+        ctx.bank = (call.operand, call.scale, call.norm2)
+        ctx.bank_writes = (bank, bank.writes)
+        ctx.values = values
+        ctx.vsrc = None if vsrc is None else (vsrc.dtype, tuple(vsrc.shape))
+        ctx.logw = None if logw is None else (logw, logw_src, logw_src._version)
+        ctx.meta = (kind_id, ls is not None, window is not None, exclude)
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gout):
+        kind_id, has_ls, windowed, exclude = ctx.meta
+        saved = list(ctx.saved_tensors)
+        qc, lse, out = saved[:3]
+        ls = saved[3] if has_ls else None
+        lo, hi = saved[-2:] if windowed else (None, None)
+        if ctx.bank_writes[0].writes != ctx.bank_writes[1]:
+            raise RuntimeError("nw_head_values_bank: the bank was written (SplitBank.update_rows) between this forward and its "
+                               "backward, which recomputes the scores from the bank: call backward() first, then update")
+        if ctx.logw is not None and ctx.logw[1]._version != ctx.logw[2]:
+            raise RuntimeError("nw_head_values_bank: row_logw was written in place between this forward and its backward, which "
+                               "recomputes the weighted scores from it: call backward() first, then change the weights")
+        if ctx.values.stale():
+            raise RuntimeError("nw_head_values_bank: the tensor the BankValues was prepared from was written between this forward "
+                               "and its backward (the prepared rows no longer stand for it): build a new ops.BankValues")
+        lib = _lib.load()
+        ssplit, sscale, sn2 = ctx.bank
+        logw = ctx.logw and ctx.logw[0]
+        (B, d), N, Tp, dev = qc.shape, ssplit.shape[0], out.shape[1], qc.device
+        g = _f32c(gout)
+        if g.data_ptr() % 16:
+            g = g.clone()
+        gq = gls = None
+        if ctx.needs_input_grad[0] or (has_ls and ctx.needs_input_grad[1]):
+            gq = torch.empty_like(qc)
+            gls = torch.empty((), dtype=torch.float32, device=dev) if ls is not None else None
+            ws_bytes = lib.nw_bwd_values_query_workspace_bytes(B, N, d, Tp, 0)
+            ws = _workspace(ws_bytes, dev)
+            with _OnDevice(dev):
+                _lib.check(lib.nw_bwd_values_query_f32(_ptr(qc), _ptr(ssplit), _ptr(sscale), _ptr(sn2), _ptr(ctx.values.split),
+                                                       _ptr(ctx.values.scale), _ptr(logw), _ptr(lo), _ptr(hi), int(bool(exclude)),
+                                                       _ptr(lse), _ptr(out), _ptr(g), _ptr(gq), _ptr(gls), _ptr(ws), ws_bytes, B, N,
+                                                       d, Tp, kind_id, _ptr(ls), 0, _stream(qc)), "nw_bwd_values_query_f32")
+        want_gv = ctx.vsrc is not None and ctx.needs_input_grad[2]
+        want_ga = ctx.logw is not None and ctx.needs_input_grad[10]
+        gv = ga = None
+        if want_gv or want_ga:
+            gv, ga = _values_support_bwd(qc, ctx.bank, ctx.values, logw, lo, hi, exclude, lse, out, g, kind_id, ls, want_gv, want_ga)
+        if gv is not None:
+            T = ctx.vsrc[1][1]
+            gv = (gv if T == Tp else gv[:, :T]).to(ctx.vsrc[0])
+        if ga is not None:
+            ga = ga.to(ctx.logw[1].dtype)
+        return gq, gls, gv, None, None, None, None, None, None, None, ga
+
+
+def _values_support_entry(q, s, bank, values, kind, logit_scale, row_window, exclude, row_logw, log, grad_v, grad_a):
+    """nw_head_values_bank(support_grad=True) with something on the support side requiring grad."""
+    if s.dim() != 2 or not bank.matches(s):
+        raise ValueError("nw_head_values_bank: `s` (N,d) must be the tensor the bank was prepared from")
+    if torch.is_tensor(values):
+        vsrc, values = values, BankValues(values, bank)
+    elif isinstance(values, BankValues):
+        vsrc = values.source()
+        if grad_v and vsrc is None:
+            raise NWHipError("nw_head_values_bank(support_grad=True): the tensor this BankValues was prepared from is gone, so "
+                             "there is nothing for the gradient to the values to go to; build a new ops.BankValues")
+    else:
+        raise TypeError("nw_head_values_bank: values is an ops.BankValues or an (N,T) float tensor")
+    N, T = s.shape[0], values.T
+    if values.rows.shape[0] != N or values.rows.device != q.device:
+        raise ValueError(f"nw_head_values_bank: the values hold {values.rows.shape[0]} rows on {values.rows.device} for a bank of "
+                         f"{N} rows and queries on {q.device}")
+    if values.stale():
+        raise ValueError("nw_head_values_bank: the tensor this BankValues was prepared from was written since; build a new "
+                         "ops.BankValues (or BankValues.refresh())")
+    if q.dtype != torch.float32:
+        q = q.float()
+    B = q.shape[0]
+    window = None if row_window is None else tuple(_row_window(row_window, B, q.device))
+    logw = None if row_logw is None else _row_logw(row_logw, N, q.device, "nw_head_values_bank")
+    kid = _kind_id(kind)
+    if kid == SCORE_KINDS["clip"] and logit_scale is None:
+        raise ValueError("clip kernel needs logit_scale")
+    route = head_values_grad_route(split=bank.split is not None, sorted_copy=bank.sorted_rows is not None, shape=bank.shape,
+                                   pad=bank.pad, width=q.shape[1], B=B, T=T)
+    if route == "fused":
+        call = _resolve_scores(bank, q, s)
+        out = _NWValuesSupportFn.apply(call.q, logit_scale, vsrc if grad_v else None, call, bank, values, kid, window,
+                                       bool(exclude), logw, row_logw)
+        if values.width != T:
+            out = out[:, :T]
+    else:
+        # the matrix composition differentiates in the graph tensors themselves
+        vals = vsrc.float() if grad_v else values.rows[:, :T]
+        a = row_logw.float() if grad_a else logw
+        if B == 0 or N == 0:
+            out = torch.zeros(B, T, dtype=torch.float32, device=q.device) + 0.0 * (vals.sum() + (a.sum() if grad_a else 0.0))
+        else:
+            lo, hi = window if window is not None else (None, None)
+            out = _values_head_matrix(q, s, bank, vals, kind, logit_scale, a, lo, hi, bool(exclude))
+    return torch.log(out + 1e-12) if log else out
+
+
 def nw_head_values_bank(q, s, bank, values, kind="euclidean", logit_scale=None, row_window=None, exclude=False, row_logw=None,
-                        log=False):
+                        log=False, support_grad=False):
     """The VALUE head over a RESIDENT bank at training time: ``nw_head_values``, differentiable in the queries (and a clip
     ``logit_scale``) with the bank, the values and the weights constants -> (B, T) fp32.  For fine-tuning a featurizer against
     a frozen or periodically refreshed bank with regression targets, soft / mixup / distilled labels (``log=True`` and a KL or
@@ -1517,7 +1683,17 @@ def nw_head_values_bank(q, s, bank, values, kind="euclidean", logit_scale=None, 
 
     Accuracy: c - gout . out cancels.  The error of c is ~2.4e-7 sum_t |gout_t values_jt| whatever the spread of the values
     among the rows, so value columns with a large common offset lose that many bits of the gradient: CENTRE such columns
-    (the forward is linear in the values: add the offset back to the output).  Every value must be finite, in every row."""
+    (the forward is linear in the values: add the offset back to the output).  Every value must be finite, in every row.
+
+    ``support_grad=True``: LEARNABLE values and support weights.  Gradients flow to whichever of ``values`` and
+    ``row_logw`` requires grad instead of the refusal above; `q` and ``logit_scale`` may require grad too, or not.  ``values``:
+    the raw (N, T) tensor, or a BankValues whose source tensor is alive -- the gradient goes to that tensor, in its dtype (the
+    source gone: NWHipError; after an optimiser step call ``BankValues.refresh()``).  ``row_logw``: a leaf or any graph
+    tensor, any float dtype, as in nw_head_bank.  Fused route: the same forward; backward nw_bwd_values_query_f32 when the
+    queries or the clip scale need it (gq's bits are those of the call without ``support_grad``) and ONE call of
+    nw_bwd_values_support_f32, gvalues_j = sum_b W_bj gout_b and glogw_j = gvalues_j . values_j - sum_b W_bj (gout_b . out_b):
+    no (B, N) buffer; when only the weights learn, nothing of size N x T either.  Matrix route: the graph tensors go through
+    the composition.  With nothing on the support side requiring grad the keyword changes nothing."""
     _need_hip(q, s, logit_scale)
     if not isinstance(bank, SplitBank):
         raise TypeError("nw_head_values_bank runs over a prepared bank: pass ops.SplitBank(support)")
@@ -1525,6 +1701,12 @@ def nw_head_values_bank(q, s, bank, values, kind="euclidean", logit_scale=None, 
     if grad and s.requires_grad:
         raise ValueError("nw_head_values_bank: the bank is a constant here and `s` requires grad")
     raw = values if torch.is_tensor(values) else None
+    if grad and support_grad:
+        grad_v = bool(raw.requires_grad if raw is not None else getattr(values, "requires_grad", False))
+        grad_a = torch.is_tensor(row_logw) and row_logw.requires_grad
+        if grad_v or grad_a:
+            _need_hip(values if raw is not None else None, row_logw if torch.is_tensor(row_logw) else None)
+            return _values_support_entry(q, s, bank, values, kind, logit_scale, row_window, exclude, row_logw, log, grad_v, grad_a)
     if grad and ((raw.requires_grad if raw is not None else getattr(values, "requires_grad", False))
                  or (torch.is_tensor(row_logw) and row_logw.requires_grad)):
         raise NWHipError("nw_head_values_bank differentiates in the queries and a clip scale alone and does not detach silently: "
