@@ -240,7 +240,7 @@ __global__ __launch_bounds__(TILE_THREADS, TWO ? 4 : 2) void nw_fused_f16p_kerne
     const int cu = tiles.cu, n_cu = tiles.n_cu, n_local = tiles.n_local;
 
     if (wave >= P::NCW) {
-        persistent_loader<P>(tiles, wave - P::NCW, lane, hdr0, stage, q, s, s_norm2, s_scale, q_norm2, q_scale, ws_runid, B, N,
+        persistent_loader<P>(tiles, wave - P::NCW, lane, hdr0, nullptr, stage, q, s, s_norm2, s_scale, q_norm2, q_scale, ws_runid, B, N,
                              d);
     } else {
         // ================================ CONSUMER ================================

@@ -17,6 +17,9 @@
 //     it was waited for in front of the barrier), waiting for all but the youngest stage;
 //   * the same arithmetic, element for element: per accumulator the products al x bh, ah x bl, ah x bh of a stage in this
 //     order, k chunks rotated by the support tile, support tiles of 128 rows, workspace layout and run tables unchanged.
+//   * tile turnaround: a tile's first eight fragment reads are issued from the previous tile's epilogue, in front of its
+//     partial stores, so a tile opens with MFMAs; the per-support-row score factors are made once per tile by a loader wave
+//     (persistent_loader, FKIND) and read by the epilogue one 16-row block ahead of the block being scored.
 // Configuration interface, tile order and loader role: persistent_pipe.h, shared with fused_f16p.h.
 // Requires d / 32 >= 3 (the header of a tile rides with its first stage, two stages ahead).
 //
@@ -38,17 +41,20 @@ namespace {
 
 struct P12 : PipeCfg<128, 256, 8, 4, 3> {
     static constexpr int RS = BS / 16, QB = BQP / (16 * NCW);
-    static_assert(LDS_BYTES <= 160 * 1024, "LDS of one CU");
+    static constexpr int FAC_F = NHB * NH;  // the kernel's static LDS: one array of row factors (Base) per header buffer
+    static_assert(LDS_BYTES + FAC_F * 4 <= 160 * 1024, "LDS of one CU");
 };
 
 // epilogue_p<8, KIND, 2, 8> (fused_f16p.h) for a wave that has 168 registers: the same operations on the same values, but
 // the support factors are made per 16-row block and the scores of both query blocks are formed while the accumulators
 // die, so that never more than 64 accumulator / score registers and one block's factors are live together.
-template <int KIND, bool CAND = false>
-__device__ __forceinline__ void epilogue_p12(f32x4 (&acc)[P12::QB][P12::RS], const float* hdr, int nrun, int2 bnd,
+// late(): called once, in front of the partial stores (CAND: behind the selection), where the score registers are dead.
+template <int KIND, bool CAND = false, class Late>
+__device__ __forceinline__ void epilogue_p12(f32x4 (&acc)[P12::QB][P12::RS], const float* hdr, const float* fac, int nrun, int2 bnd,
                                              float scale, float* __restrict__ ws_m,
                                              float* __restrict__ ws_den, float* __restrict__ ws_num, int B, int N,
-                                             int q0, int s0, int st, int wave, int lane, int n_stiles, int k
+                                             int q0, int s0, int st, int wave, int lane, int n_stiles, int k,
+                                             Late&& late
 #ifdef NW_DIAG_FUSED
                                              , unsigned long long (&diag_)[8], unsigned long long& last_
 #endif
@@ -72,8 +78,50 @@ __device__ __forceinline__ void epilogue_p12(f32x4 (&acc)[P12::QB][P12::RS], con
     }
     NW_PSTAMP(1);
     float sc[QB][RS][4];
+    // Split and half forms: the row factors come from LDS, made once per tile by a loader wave (persistent_loader, FKIND):
+    // ssc holds K, sn2 Base's norm term t, the factor array Base = t * L2E^2.  The distance kinds read them one block ahead,
+    // so that a block's arithmetic covers the next block's reads (the other kinds' split form spills at 168 registers with
+    // the look-ahead: they read each block's K in front of its arithmetic).
+    struct Fac { float4 K, t, P; };
+    auto factors = [&](int r) {
+        const float4 zero = make_float4(0.f, 0.f, 0.f, 0.f);
+        Fac f;
+        f.K = *reinterpret_cast<const float4*>(ssc + 16 * r + 4 * g);
+        f.t = SF::DIST ? *reinterpret_cast<const float4*>(sn2 + 16 * r + 4 * g) : zero;
+        f.P = SF::DIST ? *reinterpret_cast<const float4*>(fac + 16 * r + 4 * g) : zero;
+        return f;
+    };
+    constexpr bool AHEAD = SF::DIST;
+    Fac nxt = {};
+    if constexpr (!CAND && AHEAD) nxt = factors(0);
 #pragma unroll
     for (int r = 0; r < RS; ++r) {
+        if constexpr (!CAND) {
+            constexpr float L2E2 = SF::L2E * SF::L2E;
+            const Fac cur = AHEAD ? nxt : factors(r);
+            if (AHEAD && r + 1 < RS) nxt = factors(r + 1);
+#pragma unroll
+            for (int j = 0; j < QB; ++j) {  // x = acc * (K * Cq) + (Base + Bq): three packed fp32 ops per pair
+                const f32x2 cq = {Cq[j], Cq[j]}, bq = {Bq[j], Bq[j]}, l2 = {L2E2, L2E2};
+                // Base + Bq bit for bit as epilogue_p is compiled (see B4r below): one fma from t for the wave's FIRST query
+                // block, the rounded product plus Bq for the second
+                f32x2 a01 = {0.f, 0.f}, a23 = {0.f, 0.f};
+                if (SF::DIST) {
+                    a01 = (j == 0) ? __builtin_elementwise_fma(f32x2{cur.t.x, cur.t.y}, l2, bq) : f32x2{cur.P.x, cur.P.y} + bq;
+                    a23 = (j == 0) ? __builtin_elementwise_fma(f32x2{cur.t.z, cur.t.w}, l2, bq) : f32x2{cur.P.z, cur.P.w} + bq;
+                }
+                const f32x2 d01 = __builtin_elementwise_fma(f32x2{acc[j][r][0], acc[j][r][1]}, f32x2{cur.K.x, cur.K.y} * cq, a01);
+                const f32x2 d23 = __builtin_elementwise_fma(f32x2{acc[j][r][2], acc[j][r][3]}, f32x2{cur.K.z, cur.K.w} * cq, a23);
+                sc[j][r][0] = SF::finish_abs(d01.x);
+                sc[j][r][1] = SF::finish_abs(d01.y);
+                sc[j][r][2] = SF::finish_abs(d23.x);
+                sc[j][r][3] = SF::finish_abs(d23.y);
+                asm volatile("" : "+v"(sc[j][r][0]), "+v"(sc[j][r][1]), "+v"(sc[j][r][2]), "+v"(sc[j][r][3]));  // as below
+            }
+            __builtin_amdgcn_sched_barrier(0);
+            continue;
+        }
+        // candidate form: the header as the DMAs left it, the factors made here
         const float4 n4 = NEED_NORM ? *reinterpret_cast<const float4*>(sn2 + 16 * r + 4 * g) : make_float4(0.f, 0.f, 0.f, 0.f);
         const float4 s4 = *reinterpret_cast<const float4*>(ssc + 16 * r + 4 * g);
         float4 K4, B4;
@@ -123,6 +171,7 @@ __device__ __forceinline__ void epilogue_p12(f32x4 (&acc)[P12::QB][P12::RS], con
                                 q0 + 16 * (QB * wave + j) + ci, s0, cg, st, n_stiles, k);
             __builtin_amdgcn_sched_barrier(0);
         }
+        late();
         return;
     }
     // Both query blocks go through every phase together (extrema, lane-group reductions, exp2, run sums, reductions): the
@@ -266,6 +315,7 @@ __device__ __forceinline__ void epilogue_p12(f32x4 (&acc)[P12::QB][P12::RS], con
     // compare the same two operands), and the wave's two query blocks are 32 consecutive b: lane group g carries block
     // g & 1 of array g >> 1, so one full-wave store writes two 128-byte segments where 16-lane stores wrote four of 64.
     static_assert(QB == 2, "lane groups 0 / 1 carry query blocks 0 / 1, groups 2 / 3 the same blocks of the next array");
+    late();
     int ln = lane;  // made per tile: hoisted out of the tile loop, the selected pointers and offsets cost the main loop registers
     asm volatile("" : "+v"(ln));
     const int b = q0 + 16 * QB * wave + (ln & 31);
@@ -294,6 +344,9 @@ __global__ __launch_bounds__(P12::THREADS, 3) void nw_fused_f16p_kernel_w12(
     using P = P12;
     constexpr int RS = P::RS, QB = P::QB, BS = P::BS, BQP = P::BQP, NB = P::NB;
     extern __shared__ __attribute__((aligned(16))) char smem[];
+    // Base of the tile's 128 support rows, by tile index mod NHB like the headers (distance kinds of the split and half forms;
+    // written by loader wave 0, read by the epilogue).  Static, so the launch's dynamic LDS stays P::LDS_BYTES.
+    __shared__ __attribute__((aligned(16))) float fac0[P12::FAC_F];
     float* hdr0 = reinterpret_cast<float*>(smem);  // NHB header buffers of HDR_F floats, by tile index mod NHB
     float4* stage = reinterpret_cast<float4*>(smem + P::HDR_BYTES);
 
@@ -304,7 +357,7 @@ __global__ __launch_bounds__(P12::THREADS, 3) void nw_fused_f16p_kernel_w12(
     const int cu = tiles.cu, n_cu = tiles.n_cu, n_local = tiles.n_local;
 
     if (wave >= P::NCW) {
-        persistent_loader<P, !CAND>(tiles, wave - P::NCW, lane, hdr0, stage, q, s, s_norm2, s_scale, q_norm2, q_scale, ws_runid, B, N,
+        persistent_loader<P, !CAND, CAND ? -1 : KIND>(tiles, wave - P::NCW, lane, hdr0, fac0, stage, q, s, s_norm2, s_scale, q_norm2, q_scale, ws_runid, B, N,
                              d);
     } else {
         // ================================ CONSUMER ================================
@@ -390,10 +443,18 @@ __global__ __launch_bounds__(P12::THREADS, 3) void nw_fused_f16p_kernel_w12(
         // One stage.  fp = the previous stage's query fragments, fc = this stage's (read here).  The last pair of the
         // previous stage (in wb) is multiplied right behind the barrier: its operands are in registers, so the matrix pipe
         // starts at once for both waves of a SIMD, and this stage's first eight reads go out one behind each of those MFMAs
-        // (a tile's first stage has no held pair: its reads come first).  The reads of pair p + 1 lie behind the first four
+        // (a tile's first stage has no held pair: its eight reads were issued by read_ahead, below, and it starts with pair
+        // 0's MFMAs).  The reads of pair p + 1 lie behind the first four
         // MFMAs of pair p, the four address updates behind MFMAs 4 .. 7 of the last pair but one, after the stage's last
         // read.  No VALU or LDS instruction stands between the barrier and the first MFMA.  This stage's last pair is
         // left in wb.
+#ifdef NW_DIAG_TURN  // diagnostic build only: the ticks from the end of a tile's epilogue to the issue of the next tile's first
+                     // MFMA, summed in diag_[6]
+        unsigned long long t0_ = 0, t1_ = 0;
+#define NW_TURN_STAMP(t) asm volatile("s_memtime %0" : "=s"(t))
+#else
+#define NW_TURN_STAMP(t)
+#endif
         auto run_stage = [&](const QF& fp, QF& fc, int slot, auto first) {
             constexpr bool FIRST = decltype(first)::value;
 #ifdef NW_ABL_NORD   // timing experiment: no fragment reads in the loop (the fragments of a tile's first stage are reused)
@@ -401,13 +462,7 @@ __global__ __launch_bounds__(P12::THREADS, 3) void nw_fused_f16p_kernel_w12(
 #else
             constexpr bool RD = true;
 #endif
-            if constexpr (FIRST) {
-#pragma unroll
-                for (int n = 0; n < 8; ++n) {
-                    rd_first(fc, wa, n);
-                    pin();
-                }
-            } else {
+            if constexpr (!FIRST) {
                 NW_HEAD_STAMP(h0_);
                 mm_w(wb, fp, NW_ - 1, [&](int m) {
                     if (m == 0) NW_HEAD_STAMP(h1_);
@@ -422,6 +477,7 @@ __global__ __launch_bounds__(P12::THREADS, 3) void nw_fused_f16p_kernel_w12(
             for (int p = 0; p + 1 < NW_; ++p) {
                 SW& wr = (p & 1) ? wa : wb;
                 mm_w((p & 1) ? wb : wa, fc, p, [&](int m) {
+                    if (FIRST && p == 0 && m == 0) NW_TURN_STAMP(t1_);
                     if (m < 4) {
                         pin();
                         if (RD) rd_pair(wr, p + 1, m);
@@ -437,6 +493,9 @@ __global__ __launch_bounds__(P12::THREADS, 3) void nw_fused_f16p_kernel_w12(
             tile_barrier();  // every read of this stage's buffer has returned: the loaders may refill it
 #ifdef NW_DIAG_HEAD
             if (!FIRST) diag_[6] += h1_ - h0_;
+#endif
+#ifdef NW_DIAG_TURN
+            if (FIRST && t0_) diag_[6] += t1_ - t0_;
 #endif
         };
         using Yes = std::integral_constant<bool, true>;
@@ -459,7 +518,27 @@ __global__ __launch_bounds__(P12::THREADS, 3) void nw_fused_f16p_kernel_w12(
         last_ = __builtin_amdgcn_s_memtime();
         const unsigned long long first_ = last_, first_rt_ = __builtin_amdgcn_s_memrealtime();
 #endif
+        // A tile's first eight fragment reads (its first stage's query fragments and pair 0, into f0 and wa) are issued from
+        // the previous tile's epilogue.  At that tile's last stage barrier only the youngest stage the loaders have issued may
+        // still be in flight (wait_landed, persistent_pipe.h), and that is the next tile's SECOND stage: its first stage and
+        // its header have landed.  The four lane addresses point at that stage's ring slot already (advance in the last
+        // stage), and f0 and wa are dead in the epilogue.  A workgroup's first tile reads behind barrier P.
+        QF f0, f1;
+        auto read_ahead = [&]() {
+#pragma unroll
+            for (int n = 0; n < 8; ++n) {
+                rd_first(f0, wa, n);
+                pin();
+            }
+        };
+        if (cu < n_local) read_ahead();
         for (int T = cu; T < n_local; T += n_cu) {
+            const bool more = T + n_cu < n_local;  // the workgroup's last tile has no successor
+            auto late = [&]() {
+                pin();
+                if (more) read_ahead();
+                pin();
+            };
             int qt, st;
             tiles.decode(T, qt, st);
             const int q0 = qt * BQP, s0 = st * BS;
@@ -473,7 +552,6 @@ __global__ __launch_bounds__(P12::THREADS, 3) void nw_fused_f16p_kernel_w12(
             for (int j = 0; j < QB; ++j)
 #pragma unroll
                 for (int r = 0; r < RS; ++r) acc[j][r] = f32x4{0.f, 0.f, 0.f, 0.f};
-            QF f0, f1;
 #ifdef NW_ABL_NORD
 #pragma unroll
             for (int n = 0; n < 8; ++n) rd_first(f1, wa, n);
@@ -492,17 +570,21 @@ __global__ __launch_bounds__(P12::THREADS, 3) void nw_fused_f16p_kernel_w12(
             }
             NW_PSTAMP(0);
 #ifndef NW_ABL_NOEPI
-            epilogue_p12<KIND, CAND>(acc, hdr0 + par * P::HDR_F, nrun, bnd, scale, ws_m, ws_den, ws_num, B, N, q0, s0, st, wave,
-                                     lane, n_stiles, k
+            epilogue_p12<KIND, CAND>(acc, hdr0 + par * P::HDR_F, fac0 + par * P::NH, nrun, bnd, scale, ws_m, ws_den, ws_num, B, N, q0, s0, st, wave,
+                                     lane, n_stiles, k, late
 #ifdef NW_DIAG_FUSED
                                      , diag_, last_
 #endif
                                      );
 #else
             keep_acc_alive(acc, ws_m, nrun, bnd);
+            late();
 #endif
             par = (par + 1 == P::NHB) ? 0 : par + 1;
-#ifndef NW_DIAG_HEAD
+#ifdef NW_DIAG_TURN
+            asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t0_));  // carried over the loop's back edge: landed first
+#endif
+#if !defined(NW_DIAG_HEAD) && !defined(NW_DIAG_TURN)
             NW_PSTAMP(6);
 #endif
         }

@@ -411,6 +411,15 @@ struct ScoreFactors {
         K = sscale * in * (DIST ? -2.f * L2E * L2E : L2E);
         Base = DIST ? (NORMALISED ? n2 * in * in : n2) * (L2E * L2E) : 0.f;
     }
+    // support() in parts, every product rounded on its own, for a kernel that makes a row's factors once and finishes
+    // Base + Bq elsewhere (fused_f16p12.h): K as support() makes it, t = Base's norm term, Bp = Base = t * L2E^2 rounded.
+    // Whoever adds Bq chooses fma(t, L2E^2, Bq) or Bp + Bq (base_plus below: the two differ in the last bit).
+    static __device__ __forceinline__ void support_parts(float n2, float sscale, float& K, float& t, float& Bp) {
+        const float in = NORMALISED ? inv_norm(n2) : 1.f;
+        K = __fmul_rn(__fmul_rn(sscale, in), DIST ? -2.f * L2E * L2E : L2E);
+        t = DIST ? (NORMALISED ? __fmul_rn(__fmul_rn(n2, in), in) : n2) : 0.f;
+        Bp = DIST ? __fmul_rn(t, L2E * L2E) : 0.f;
+    }
     static __device__ __forceinline__ void query(float n2, float qscale, float clip_scale, float& Cq, float& Bq) {
         const float in = NORMALISED ? inv_norm(n2) : 1.f;
         Cq = qscale * in * (KIND == NW_SCORE_CLIP ? clip_scale : 1.f);

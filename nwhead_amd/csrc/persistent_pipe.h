@@ -80,34 +80,59 @@ struct PipeCfg {
 // (qt = x mod 8) instead, so every XCD gets the same number of tiles to within n_stiles % 8: with 49
 // support tiles (a shard of the K3 bank at 8 ranks) one XCD would otherwise walk 7 and seven XCDs 6.
 // Workgroup `cu` of its XCD takes the entries cu, cu + n_cu, ... < n_local of the XCD's list.
+// n / dv for 0 <= n < 2^31 and a divisor that is fixed for the launch, without the float reciprocal of hipcc's own expansion
+// (a v_rcp_iflag_f32 and a v_readfirstlane in a chain of scalar instructions): rcp = floor((2^32 - 1) / dv) is made once per
+// launch, and because 0 <= 2^32 / dv - rcp <= 1 the high half of n * rcp is short of n / dv by less than n / 2^32 < 1: it is
+// the quotient or one below it, and one step corrects it.  A divisor of 0 (a list part that is empty, never decoded) counts as 1.
+struct TileDiv {
+    unsigned dv, rcp;
+    __device__ __forceinline__ void set(int d) {
+        dv = (unsigned)max(d, 1);
+        rcp = 0xFFFFFFFFu / dv;
+    }
+    static __device__ __forceinline__ void divmod(unsigned n, unsigned dv, unsigned rcp, int& quo, int& rem) {
+        unsigned q = __umulhi(n, rcp), r = n - q * dv;
+        if (r >= dv) ++q, r -= dv;
+        quo = (int)q, rem = (int)r;
+    }
+    __device__ __forceinline__ void divmod(int n, int& quo, int& rem) const { divmod((unsigned)n, dv, rcp, quo, rem); }
+};
+
 struct PersistentTiles {
     int xcd, cu, n_cu;
     int n_qtiles, qg;
     int ns_x;       // full rounds: support tiles st = stl * 8 + x
     int n_full;
-    int nq_x;       // query tiles of this XCD in the leftover part
     int n_local;    // tiles of this XCD
-    int grp_tiles;
+    TileDiv by_nq;  // nq_x: query tiles of this XCD in the leftover part
+    TileDiv by_grp; // qg * ns_x: tiles of a group of query tiles
+    TileDiv by_qg;  // a group's query tiles: qg, ...
+    TileDiv by_last;  // ... but n_qtiles % qg in the last group when that is not 0
     __device__ __forceinline__ PersistentTiles(unsigned block, unsigned grid, int n_stiles, int n_qtiles_, int qg_)
         : xcd(block & 7), cu(block >> 3), n_cu(grid >> 3), n_qtiles(n_qtiles_), qg(qg_) {
         ns_x = n_stiles >> 3;
         n_full = ns_x * n_qtiles;
         const int rem = n_stiles & 7;  // leftover support tiles 8 * ns_x .. n_stiles - 1
-        nq_x = (n_qtiles - xcd + 7) >> 3;
+        const int nq_x = (n_qtiles - xcd + 7) >> 3;
         n_local = n_full + rem * nq_x;
-        grp_tiles = qg * ns_x;
+        by_nq.set(nq_x);
+        by_grp.set(qg * ns_x);
+        by_qg.set(qg);
+        by_last.set(n_qtiles % max(qg, 1));
     }
     __device__ __forceinline__ void decode(int L, int& qt, int& st) const {
         if (L >= n_full) {  // leftover part, support-tile major
-            const int r = L - n_full, j = r / nq_x;
+            int j, r;
+            by_nq.divmod(L - n_full, j, r);
             st = 8 * ns_x + j;
-            qt = xcd + 8 * (r - j * nq_x);
+            qt = xcd + 8 * r;
             return;
         }
-        const int gi = L / grp_tiles, r = L - gi * grp_tiles;
-        const int g = min(qg, n_qtiles - gi * qg);
-        const int stl = r / g;
-        qt = gi * qg + (r - stl * g);
+        int gi, r, stl, qi;
+        by_grp.divmod(L, gi, r);
+        const int g = min(qg, n_qtiles - gi * qg);  // one of two values per launch: the last group may be short
+        TileDiv::divmod((unsigned)r, (unsigned)g, g == qg ? by_qg.rcp : by_last.rcp, stl, qi);
+        qt = gi * qg + qi;
         st = stl * 8 + xcd;
     }
 };
@@ -118,8 +143,12 @@ struct PersistentTiles {
 // matched by the consumers.  -DNW_ABL_NODMA (timing experiment, results wrong): the stages are not filled.
 // RUNID = false (the candidate-output form, which reads no run tables: ws_runid is null): the run-id pieces repeat the row
 // scales' pieces instead (same bytes to the same place), so that every stage keeps its count of DMAs.
-template <class P, bool RUNID = true>
-__device__ __forceinline__ void persistent_loader(const PersistentTiles& tiles, int lw, int lane, float* hdr0, float4* stage,
+// FKIND >= 0 (a score kind; P has the factor array): once a tile's header has landed, loader wave 0 rewrites its support side
+// into the factors the tile epilogue would otherwise make in every multiplying wave and lane group
+// (ScoreFactors<FKIND>::support_parts): ssc becomes K, sn2 becomes Base's norm term t, and Base = t * L2E^2 goes to
+// fac0, the kernel's own NHB arrays of NH floats beside the headers (static LDS: the launch's dynamic LDS is unchanged).
+template <class P, bool RUNID = true, int FKIND = -1>
+__device__ __forceinline__ void persistent_loader(const PersistentTiles& tiles, int lw, int lane, float* hdr0, float* fac0, float4* stage,
                                                   const float* __restrict__ q, const float* __restrict__ s,
                                                   const float* __restrict__ s_norm2, const float* __restrict__ s_scale,
                                                   const float* __restrict__ q_norm2, const float* __restrict__ q_scale,
@@ -212,6 +241,38 @@ __device__ __forceinline__ void persistent_loader(const PersistentTiles& tiles, 
         else if (young_hdr) wait_vmcnt<YOUNG + P::HPW>();
         else wait_vmcnt<YOUNG>();
     };
+    // The header of the tile whose first stage the consumers are about to multiply landed with that stage, so it was
+    // published by the barrier before (wait_landed: everything but the youngest stage).  Its readers are the tile's epilogue,
+    // nk barriers later; the writes are complete at the next one (tile_barrier waits lgkmcnt(0)).  LDS is read and written
+    // by hand: hipcc would put a vmcnt(0) in front of a ds_read that may alias an LDS-DMA and drain the stages in flight.
+    int cpar = 0;  // header buffer of that tile
+    auto make_factors = [&]() {
+        if constexpr (FKIND >= 0) {
+            static_assert(P::NH == 128, "two rows per lane of one wave");
+            using SF = ScoreFactors<FKIND>;
+            if (lw == 0) {
+                const unsigned a = (unsigned)(uintptr_t)(__attribute__((address_space(3))) float*)(hdr0 + cpar * P::HDR_F) + 4u * lane;
+                const unsigned af = (unsigned)(uintptr_t)(__attribute__((address_space(3))) float*)(fac0 + cpar * P::NH) + 4u * lane;
+                float n2[2], sc[2];
+                asm volatile("ds_read_b32 %0, %4\n\tds_read_b32 %1, %4 offset:256\n\t"
+                             "ds_read_b32 %2, %4 offset:%5\n\tds_read_b32 %3, %4 offset:%6\n\ts_waitcnt lgkmcnt(0)"
+                             : "=&v"(n2[0]), "=&v"(n2[1]), "=&v"(sc[0]), "=&v"(sc[1])
+                             : "v"(a), "n"(4 * P::NH), "n"(4 * P::NH + 256)
+                             : "memory");
+#pragma unroll
+                for (int h = 0; h < 2; ++h) {
+                    float K, t, Bp;
+                    SF::support_parts(n2[h], sc[h], K, t, Bp);
+                    asm volatile("ds_write_b32 %0, %1 offset:%2" ::"v"(a), "v"(K), "n"(4 * P::NH + 256 * h) : "memory");
+                    if constexpr (SF::DIST) {
+                        if constexpr (SF::NORMALISED) asm volatile("ds_write_b32 %0, %1 offset:%2" ::"v"(a), "v"(t), "n"(256 * h) : "memory");
+                        asm volatile("ds_write_b32 %0, %1 offset:%2" ::"v"(af), "v"(Bp), "n"(256 * h) : "memory");
+                    }
+                }
+            }
+            cpar = (cpar + 1 == P::NHB) ? 0 : cpar + 1;
+        }
+    };
     if (iT < n_local) set_tile(iT);
     bool more = true;
 #pragma unroll
@@ -221,6 +282,7 @@ __device__ __forceinline__ void persistent_loader(const PersistentTiles& tiles, 
     for (int T = tiles.cu; T < n_local; T += n_cu) {
         for (int kt = 0; kt < nk; ++kt) {
             more = issue_next();
+            if (kt == 0) make_factors();
             wait_landed(more);
             tile_barrier();
         }

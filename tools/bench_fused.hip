@@ -2,7 +2,8 @@
 // Persistent kernels (argv[5] = 2; they exist for tiles of 128 supports only: build with -DNW_BENCH_RS=8, at another height
 // the mode is refused): NW_PVAR=0 / 1 / 2 pick the variants of fused_f16p.h, NW_PVAR=3 the 256-query kernel of
 // fused_f16p12.h; both take -DNW_ABL_NODMA / -DNW_ABL_NORD / -DNW_ABL_NOEPI.  -DNW_DIAG_HEAD (NW_PVAR=3 only): the last
-// slot sums the ticks from each stage barrier to the issue of the stage's first MFMA instead of the tile loop's rest.
+// slot sums the ticks from each stage barrier to the issue of the stage's first MFMA instead of the tile loop's rest;
+// -DNW_DIAG_TURN (NW_PVAR=3 only): the ticks from the end of each tile's epilogue to the issue of the next tile's first MFMA.
 // Build: hipcc -O3 --offload-arch=gfx950 -I nwhead_amd/csrc -DNW_DIAG_FUSED [-DNW_BENCH_RS=8] tools/bench_fused.hip
 //        nwhead_amd/csrc/split.hip -o tools/bench_fused      (tile height in 16-row blocks; 10 when not given)
 #include <hip/hip_runtime.h>
@@ -120,6 +121,8 @@ int main(int argc, char** argv) {
         }
 #ifdef NW_DIAG_HEAD  // the 256-query kernel only: the last slot sums barrier release -> first MFMA issued over the stages
         const char* last_slot = "stage heads (barrier -> first MFMA issued; inside main loops)";
+#elif defined(NW_DIAG_TURN)
+        const char* last_slot = "tile turnarounds (end of epilogue -> next tile's first MFMA issued)";
 #else
         const char* last_slot = "rest";
 #endif
