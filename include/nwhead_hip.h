@@ -553,6 +553,31 @@ int nw_bwd_values_support_f32(const float *q, const float *s_split, const float 
                               float *gvalues, float *glogw, void *workspace, size_t workspace_bytes,
                               int64_t B, int64_t N, int64_t d, int64_t T, int kind, const float *logit_scale_dev,
                               int query_chunks, void *stream);
+/* Gradient of the CLASS head over a resident split bank w.r.t. the BANK ROWS, without a (B,N) matrix (bwd_support.hip):
+ *   gs_j = sum_b A_bj q_b + 2 (sum_b r_bj) s_j,  (A_bj, r_bj) the per-pair coefficients of nw_bwd_query_f32 (df/ddot and
+ *   df/d|s|^2 times dS_bj = W_bj (dP_b[y_j] - t_b), the derivative taken at the RAW score, W carrying row_logw).
+ *   q (B,d), s (N,d) the fp32 rows the split forms were prepared from (read for the 2 r s term only), s_split / s_scale /
+ *   s_norm2 / sy / row_lo / row_hi / exclude / row_logw (or NULL) / lse / out / gout as nw_bwd_query_logw_f32;
+ *   gs (N,d) fp32, 16-byte aligned;
+ *   query_chunks: 0 lets the library split the query loop when the support tiles alone cannot fill the chip; a positive
+ *            value is clamped to the number of 64-query tiles.  Chunk partials are added in chunk order by a finish kernel.
+ * EVERY element of gs[0..N) x [0..d) is written by a successful call with B > 0, nothing past it.  A row at a = -inf, a row
+ * no query's window admits and the share of a dead query (lse = -inf) are exactly 0.0 in every column.  Scaling gout by a
+ * power of two scales gs exactly.  Two calls with the same arguments give the same bits.
+ * Accuracy: A 2^E (E from the largest |A| a 64-row support tile has shown so far, accumulators rescaled exactly when it
+ * rises) and q 2^F (F from max |q|) are split into fp16 halves, products exact, sums fp32; with Amax the tile's largest |A|:
+ *   |error of gs[j,k]| <~ (2^-21 + B 2^-24) sum_b |A_bj| |q_bk| + 2^-38 (Amax sum_b |q_bk| + max|q| sum_b |A_bj|).
+ * Regime, alignment, status codes and refusals before anything is launched are nw_bwd_query_f32's.  workspace:
+ * nw_bwd_bank_support_workspace_bytes(B, N, d, C, query_chunks), 0 for a shape outside the regime; short or NULL:
+ * NW_ERR_WORKSPACE.  B == 0: NW_OK and NOTHING is touched. */
+size_t nw_bwd_bank_support_workspace_bytes(int64_t B, int64_t N, int64_t d, int64_t C, int query_chunks);
+int nw_bwd_bank_support_f32(const float *q, const float *s, const float *s_split, const float *s_scale, const float *s_norm2,
+                            const int64_t *sy, const float *row_logw,
+                            const int32_t *row_lo, const int32_t *row_hi, int exclude,
+                            const float *lse, const float *out, const float *gout,
+                            float *gs, void *workspace, size_t workspace_bytes,
+                            int64_t B, int64_t N, int64_t d, int64_t C, int kind, const float *logit_scale_dev,
+                            int query_chunks, void *stream);
 /* support_influence (util/metric.py:23-50) of k SELECTED supports per query, from the head's own outputs:
  *   vals (B,k) fp32 raw scores and rows (B,k) int64 bank rows (a search's val_out / idx_out),
  *   sy (N,) int64, qy (B,) int64, out (B,C) log-probabilities and lse (B,) of nw_fwd_f32 over the same bank;

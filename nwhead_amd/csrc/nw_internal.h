@@ -160,6 +160,28 @@ struct BwdValuesSupportCall {
 size_t bwd_values_support_workspace_bytes(int64_t B, int64_t N, int64_t d, int64_t T, int query_chunks, bool want_gvalues);
 int launch_bwd_values_support(const BwdValuesSupportCall& c);
 
+// bwd_support.hip: the class head's gradient w.r.t. the bank rows, a contraction over the queries of the recomputed
+// coefficients of bwd_query.hip, no (B,N) matrix (nw_bwd_bank_support_f32)
+struct BwdBankSupportCall {
+    const float *q, *s;               // (B,d) queries; (N,d) the fp32 bank rows, read for the 2 r s term only
+    const float *s_split, *s_scale, *s_norm2;
+    const int64_t* sy;
+    const float* row_logw;            // (N,) log-weights of the bank rows, or null
+    const int32_t *row_lo, *row_hi;   // both or neither
+    int exclude;
+    const float *lse, *out, *gout;
+    float* gs;                        // (N,d)
+    void* workspace;
+    size_t workspace_bytes;
+    int64_t B, N, d, C;
+    int kind;
+    const float* logit_scale_dev;
+    int query_chunks;
+    hipStream_t st;
+};
+size_t bwd_bank_support_workspace_bytes(int64_t B, int64_t N, int64_t d, int64_t C, int query_chunks);
+int launch_bwd_bank_support(const BwdBankSupportCall& c);
+
 // Options of the forward call in progress on this thread (nw_fwd_opts of the ABI, set for the duration of the call by
 // the entry point): explicit arguments, not process state.
 struct FwdOpts {

@@ -259,6 +259,7 @@ class NWNet(nn.Module):
         self.support_weights = None                  # weights are per row of the bank they were set for
         self.support_values = None                   # ... and so are values
         self._parameters.pop('support_targets', None)   # ... learnable ones with their parameter
+        self._parameters.pop('support_bank', None)      # ... and learnable rows belong to the bank they were registered for
         if self.balance_full == "weights":
             self.set_support_weights(ops.class_balance_logw(self.full_y, self.n_classes))
 
@@ -316,6 +317,24 @@ class NWNet(nn.Module):
         self.support_weights = None if learnable else w   # (drops a parameter of an earlier call)
         if learnable:
             self.support_logw = nn.Parameter(w)           # the values live in the parameter alone
+
+    def set_bank_learnable(self, on=True):
+        """Not in the reference: make the ROWS of precompute()'s bank LEARNED (prototypes, a condensed support set, a memory
+        bank trained end to end rather than by momentum refresh).  After precompute(): registers the nn.Parameter
+        ``support_bank``, which shares ``full_feat``'s storage -- in parameters() and state_dict() from this call on, not
+        before; rebuild the optimizer's parameter group.  forward_bank then passes the parameter with its graph
+        (ops.nw_head_bank(support_grad=True): no (B, N) matrix), so a loss on its output puts a gradient on
+        ``support_bank``, with ``leave_out`` too.  After the optimizer wrote the rows, every entry point that reads the bank
+        re-prepares it in place first (ops.SplitBank.refresh: no rebuild, no allocation); predict('full'), predict_loo,
+        get_neighbors and explain read the rows detached, and refresh_bank keeps working (it writes in place).  Cleared by
+        precompute() and by ``set_bank_learnable(False)``, like ``support_logw``.  A sharded bank, a missing bank and a custom
+        kernel module are refused (NWHipError) as for forward_bank; a full_precision="fp16" bank or one whose labels are not
+        class-sorted takes ops.nw_head's matrix route without ``leave_out`` or weights and is refused with them."""
+        self._parameters.pop('support_bank', None)
+        if not on:
+            return
+        self._served("forward_bank")
+        self.support_bank = nn.Parameter(self.full_feat)     # (the same storage and the same in-place version counter)
 
     def _weights_for(self, what, graph=False):
         """The support weights for a call over precompute()'s resident bank, or None; a sharded bank in front of it refuses.
@@ -402,7 +421,12 @@ class NWNet(nn.Module):
             sfeat, sy = sfeat.to(device), sy.to(device)
         cache = getattr(self, 'full_cache', None)
         if cache is not None and not cache.matches(sfeat):
-            cache = None
+            # learnable rows the optimizer wrote (the same tensor, a later version): every prepared form again, in place
+            if (self._parameters.get('support_bank') is not None and cache.sorted_rows is None
+                    and cache._src[:2] == (sfeat.data_ptr(), tuple(sfeat.shape))):
+                cache.refresh(sfeat)
+            else:
+                cache = None
         if cache is None and rebuild:
             cache = self.full_cache = ops.SplitBank(sfeat, labels=sy, precision=self.full_precision)
         return sfeat, sy, cache
@@ -438,7 +462,8 @@ class NWNet(nn.Module):
         move; the caller decides when to call precompute() again, or writes each batch's features back with
         refresh_bank(rows) -- they are kept, detached, in ``bank_features`` (a view, not a copy).  Support weights
         (set_support_weights) are honoured: as a constant, or, set with learnable=True, as the parameter ``support_logw``
-        with its graph (a gradient lands on it).  A sharded bank, a missing bank and a custom kernel
+        with its graph (a gradient lands on it).  After set_bank_learnable() the rows themselves are the parameter
+        ``support_bank`` and get a gradient as well.  A sharded bank, a missing bank and a custom kernel
         module are refused (NWHipError), like predict_loo.  A full_precision="fp16" bank or a bank whose labels are not
         class-sorted takes ops.nw_head's route through the score matrix without ``leave_out`` and is refused with it."""
         what = WHAT["forward_bank"]
@@ -447,8 +472,11 @@ class NWNet(nn.Module):
         self.bank_features = qfeat.detach()
         sfeat, sy, cache = self._resident_bank("forward_bank", qfeat.device)
         window = None if leave_out is None else self._leave_out_window(leave_out, qfeat, what)
-        out = ops.nw_head_bank(qfeat, sfeat, sy, self.n_classes, cache, self.kernel.kind, self.kernel._logit_scale(),
-                               row_window=window, exclude=window is not None, row_logw=self._weights(graph=True))
+        rows = self._parameters.get('support_bank')     # learnable rows: the parameter with its graph
+        learn = {} if rows is None else {"support_grad": True}
+        out = ops.nw_head_bank(qfeat, sfeat if rows is None else rows, sy, self.n_classes, cache, self.kernel.kind,
+                               self.kernel._logit_scale(), row_window=window, exclude=window is not None,
+                               row_logw=self._weights(graph=True), **learn)
         return self._result(out)
 
     def refresh_bank(self, rows, feats=None, momentum=0.0):

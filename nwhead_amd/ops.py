@@ -566,8 +566,12 @@ class SplitBank:
     * run tables (build_tables): named in the call's options only when its labels are the tensor the tables were built
       from, unmodified; n_classes must then exceed every label of the tables.
 
+    * the gradient to the bank rows (nw_head_bank(support_grad=True); head_bank_support_route): fused on the same terms as the
+      query gradient, else nw_head's route without a window and weights and a refusal with either.
+
     The bank's tensors are written again only by ``update_rows``, which replaces rows of the support and of every prepared
-    form in place and keeps the bank matching its tensor."""
+    form in place and keeps the bank matching its tensor, and by ``refresh``, which re-prepares every row in place after
+    the support was written by something else (an optimizer step on learnable rows)."""
 
     def __init__(self, s, labels=None, precision="fp32"):
         if precision not in ("fp32", "fp16"):
@@ -672,6 +676,43 @@ class SplitBank:
                 "nw_bank_update_rows_f32")
         if not support.is_inference():
             torch.autograd.graph.increment_version(support)
+        self._src = _sig(support)
+        self.writes += 1
+
+    def refresh(self, support):
+        """Re-prepare EVERY row of the bank from ``support`` IN PLACE, after something other than ``update_rows`` wrote the
+        tensor (an optimizer step on learnable rows): the padded fp32 copy, split rows and scales, norms, fp16-packed rows with
+        their scales and norms are written again into the buffers the bank already holds -- the launches of the constructor,
+        so every prepared tensor is bit for bit what ``SplitBank(support, labels, precision)`` would build, at the same
+        addresses and with no allocation (a ``support`` that is not contiguous fp32 is converted first, which allocates).
+        ``support`` must have the shape and device the bank was prepared for; the bank ``matches`` it afterwards and
+        ``writes`` counts the call (a pending nw_head_bank backward refuses, as after update_rows).  The labels, the run
+        tables and the cached call options stay as they are.  Refused with NWHipError for a bank built from unsorted labels,
+        whose class-sorted copy holds rows that are not the caller's."""
+        _need_hip(support)
+        if self.sorted_rows is not None:
+            raise NWHipError("SplitBank.refresh: the bank was built from unsorted labels and keeps a class-sorted copy, whose "
+                             "rows are not the caller's (build a new ops.SplitBank)")
+        N, d = self.shape
+        if support.dim() != 2 or tuple(support.shape) != (N, d - self.pad) or support.device != self.norm2.device:
+            raise ValueError(f"SplitBank.refresh: `support` must be an ({N}, {d - self.pad}) tensor on the bank's device")
+        lib = _lib.load()
+        if self.rows is not None:
+            self.rows[:, :d - self.pad].copy_(support.detach())      # (the zero columns stay)
+            sc = self.rows
+        else:
+            sc = _f32c(support)
+        with _OnDevice(sc.device):
+            st = _stream(sc)
+            if self.packed is not None:
+                _lib.check(lib.nw_pack_rows_f16(_ptr(sc), _ptr(self.packed), _ptr(self.packed_scale), _ptr(self.packed_norm2),
+                                                N, d, st), "nw_pack_rows_f16")
+                _lib.check(lib.nw_row_norm2_f32(_ptr(sc), _ptr(self.norm2), N, d, st), "nw_row_norm2_f32")
+            elif self.split is not None:
+                _lib.check(lib.nw_split_rows_f16x2(_ptr(sc), _ptr(self.split), _ptr(self.scale), _ptr(self.norm2), N, d, st),
+                           "nw_split_rows_f16x2")
+            elif N > 0:
+                _lib.check(lib.nw_row_norm2_f32(_ptr(sc), _ptr(self.norm2), N, d, st), "nw_row_norm2_f32")
         self._src = _sig(support)
         self.writes += 1
 
@@ -1049,6 +1090,23 @@ def head_bank_route(*, split, sorted_copy, shape, pad, width, B, n_classes):
                                         n_classes=n_classes) is None else "matrix"
 
 
+def head_bank_support_route(*, split, sorted_copy, shape, pad, width, B, n_classes, window=False, weights=False):
+    """Which route serves the gradient to the BANK ROWS of ``nw_head_bank(..., support_grad=True)``, beside head_bank_route
+    and over the same plain facts (``window`` / ``weights``: the call has a row window / support weights): "fused"
+    (nw_bwd_bank_support_f32: the coefficients recomputed tile by tile and contracted with the queries, no (B, N) buffer)
+    whenever head_bank_refusal has nothing to say -- no size gate, the keyword is the caller's choice and the route is kept
+    for its memory where it is the slower one; else "matrix", nw_head's route through the score matrix, which
+    computes gs already, when the call has neither a window nor weights, and NWHipError with either: that route knows
+    neither."""
+    why = head_bank_refusal(split=split, sorted_copy=sorted_copy, shape=shape, pad=pad, width=width, B=B, n_classes=n_classes)
+    if why is None:
+        return "fused"
+    if window or weights:
+        what = "row_window" if window else "row_logw"
+        raise NWHipError(f"nw_head_bank({what}=..., support_grad=True) has no gradient route here: {why}")
+    return "matrix"
+
+
 HEAD_VALUES_MAX_T = 16384        # nw_fwd_values_f32: value columns per row (after padding to a multiple of 32)
 
 
@@ -1330,7 +1388,70 @@ class _NWHeadBankFn(torch.autograd.Function):
         return gq, gls, None, None, None, None, None, None, None, ga if ga is None else ga.to(ctx.logw[1].dtype)
 
 
-def nw_head_bank(q, s, sy, n_classes, bank, kind="euclidean", logit_scale=None, row_window=None, exclude=False, row_logw=None):
+def _bank_support_bwd(q, s_rows, operands, logw, lo, hi, exclude, lse, out, gout, kind_id, ls, query_chunks=0):
+    """The one call of the gradient of the head over a resident bank w.r.t. the bank rows (nw_bwd_bank_support_f32) -> gs (N, d)
+    fp32.  ``s_rows``: the fp32 rows the bank's forms were prepared from, at the bank's width; the rest as _bank_head_bwd."""
+    lib = _lib.load()
+    ssplit, sscale, sn2, syc = operands
+    (B, d), N, C, dev = q.shape, ssplit.shape[0], out.shape[1], q.device
+    gs = torch.empty(N, d, dtype=torch.float32, device=dev)
+    ws_bytes = lib.nw_bwd_bank_support_workspace_bytes(B, N, d, C, int(query_chunks))
+    ws = _workspace(ws_bytes, dev)
+    with _OnDevice(dev):
+        _lib.check(lib.nw_bwd_bank_support_f32(_ptr(q), _ptr(s_rows), _ptr(ssplit), _ptr(sscale), _ptr(sn2), _ptr(syc), _ptr(logw),
+                                               _ptr(lo), _ptr(hi), int(exclude), _ptr(lse), _ptr(out), _ptr(gout), _ptr(gs),
+                                               _ptr(ws), ws_bytes, B, N, d, C, kind_id, _ptr(ls), int(query_chunks), _stream(q)),
+                   "nw_bwd_bank_support_f32")
+    return gs
+
+
+class _NWHeadBankSupportFn(torch.autograd.Function):
+    """autograd node of nw_head_bank(..., support_grad=True): _NWHeadBankFn with the bank rows `s` a third input.  Forward:
+    that node's.  Backward: its one query / weights call when q, the clip scale or row_logw needs it -- the same arguments,
+    the same bits -- and none otherwise, plus nw_bwd_bank_support_f32 for the rows.  Nothing of size B x N."""
+
+    @staticmethod
+    def forward(ctx, q, logit_scale, s, call, n_classes, kind_id, window, exclude, bank, logw=None, logw_src=None):
+        out = _NWHeadBankFn.forward(ctx, q, logit_scale, call, n_classes, kind_id, window, exclude, bank, logw, logw_src)
+        # the fp32 rows the bank's forms were prepared from, at the bank's width (read for the 2 r s term), and what `s` is
+        ctx.s_rows = bank.rows if bank.rows is not None else _f32c(s)
+        ctx.s_meta = (s.shape[1], s.dtype)
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gout):
+        kind_id, has_ls, windowed, exclude = ctx.meta
+        saved = list(ctx.saved_tensors)
+        qc, lse, out = saved[:3]
+        ls = saved[3] if has_ls else None
+        lo, hi = saved[-2:] if windowed else (None, None)
+        if ctx.bank_writes[0].writes != ctx.bank_writes[1]:
+            raise RuntimeError("nw_head_bank: the bank was written (SplitBank.update_rows) between this forward and its "
+                               "backward, which recomputes the scores from the bank: call backward() first, then update")
+        if ctx.logw is not None and ctx.logw[1]._version != ctx.logw[2]:
+            raise RuntimeError("nw_head_bank: row_logw was written in place between this forward and its backward, which "
+                               "recomputes the weighted scores from it: call backward() first, then change the weights")
+        g = _f32c(gout)
+        logw = ctx.logw and ctx.logw[0]
+        want_glogw = ctx.logw is not None and ctx.needs_input_grad[10]
+        need_q = ctx.needs_input_grad[0] or (has_ls and ctx.needs_input_grad[1])
+        gq = gls = ga = gs = None
+        if want_glogw or need_q:      # _NWHeadBankFn's call: without gq when only the weights (and the rows) learn
+            gq, gls, ga = _bank_head_bwd(qc, ctx.bank, logw, lo, hi, exclude, lse, out, g, kind_id, ls,
+                                         not want_glogw or need_q, want_glogw)
+        if ctx.needs_input_grad[2]:
+            gs = _bank_support_bwd(qc, ctx.s_rows, ctx.bank, logw, lo, hi, exclude, lse, out, g, kind_id, ls)
+            width, dtype = ctx.s_meta
+            if width != gs.shape[1]:
+                gs = gs[:, :width]
+            gs = gs.to(dtype)
+        return (gq if ctx.needs_input_grad[0] else None, gls if has_ls and ctx.needs_input_grad[1] else None, gs, None, None,
+                None, None, None, None, None, ga if ga is None else ga.to(ctx.logw[1].dtype))
+
+
+def nw_head_bank(q, s, sy, n_classes, bank, kind="euclidean", logit_scale=None, row_window=None, exclude=False, row_logw=None,
+                 support_grad=False):
     """The head over a RESIDENT bank, differentiable in the queries (and a clip ``logit_scale``) with the bank a constant
     -> (B,C) log-probabilities.  For fine-tuning a featurizer against a frozen or periodically refreshed bank, a
     leave-one-out training loss (``row_window`` / ``exclude`` as in nw_head_window), input gradients of 'full' inference,
@@ -1355,10 +1476,22 @@ def nw_head_bank(q, s, sy, n_classes, bank, kind="euclidean", logit_scale=None, 
     row at -inf and a row no query admits get exactly 0).  One backward entry per case: that one when the weights need a
     gradient -- without gq, i.e. without the second pass over the bank rows, when neither `q` nor a clip scale does --
     and the entries above, unchanged, otherwise.  Where the kernel does not serve (the cases above) the gradient to the
-    weights is refused (NWHipError); without a window nw_scores + a + nw_aggregate is the way through the score matrix."""
+    weights is refused (NWHipError); without a window nw_scores + a + nw_aggregate is the way through the score matrix.
+
+    support_grad: LEARNABLE BANK ROWS (prototypes, a condensed support set, a bank trained end to end).  With
+    ``support_grad=True`` and ``s.requires_grad`` the gradient flows to `s` as well, in its dtype (on a padded bank: the
+    caller's columns): gs_j = sum_b A_bj q_b + 2 (sum_b r_bj) s_j from nw_bwd_bank_support_f32, which recomputes
+    the coefficients of the query gradient tile by tile and contracts them with the queries: no (B, N) matrix; a row at -inf
+    and a row no query admits get exactly 0.  The forward and the gradients to q, the clip scale and row_logw are those of
+    the call without the keyword, bit for bit, and when only the rows learn no query-gradient call is made.  The bank must
+    be brought up to date after the optimizer wrote `s` (``SplitBank.refresh``).  Route (head_bank_support_route): that
+    kernel wherever the rule above gives the kernels; else nw_head's matrix route without a window and weights, NWHipError
+    with either.  Without the keyword, or with an `s` that does not require grad, nothing changes."""
     if not isinstance(bank, SplitBank):
         raise TypeError("nw_head_bank runs over a prepared bank: pass ops.SplitBank(support)")
     grad = torch.is_grad_enabled()
+    if support_grad and grad and s.requires_grad:
+        return _head_bank_support(q, s, sy, n_classes, bank, kind, logit_scale, row_window, exclude, row_logw)
     if grad and s.requires_grad:
         raise ValueError("nw_head_bank: the bank is a constant here and `s` requires grad; nw_head(q, s, sy, ..., "
                          "support_cache=bank) is the call for support gradients")
@@ -1395,6 +1528,33 @@ def nw_head_bank(q, s, sy, n_classes, bank, kind="euclidean", logit_scale=None, 
         window = None if row_window is None else tuple(_row_window(row_window, q.shape[0], q.device))
     out = _NWHeadBankFn.apply(call.q, logit_scale, call, C, kid, window, bool(exclude), bank, logw, row_logw)
     return out
+
+
+def _head_bank_support(q, s, sy, n_classes, bank, kind, logit_scale, row_window, exclude, row_logw):
+    """nw_head_bank(..., support_grad=True) with an `s` that requires grad: nw_head_bank's checks, then
+    head_bank_support_route's answer."""
+    _need_hip(q, s, sy, logit_scale)
+    if s.dim() != 2 or sy.dim() != 1 or sy.shape[0] != s.shape[0] or not bank.matches(s):
+        raise ValueError("nw_head_bank: `s` (N,d) must be the tensor the bank was prepared from and `sy` its (N,) labels")
+    kid = _kind_id(kind)
+    if kid == SCORE_KINDS["clip"] and logit_scale is None:
+        raise ValueError("clip kernel needs logit_scale")
+    C = int(n_classes)
+    _check_label_range(None, bank.label_max, C)
+    logw = None if row_logw is None else _row_logw(row_logw, s.shape[0], q.device, "nw_head_bank")
+    route = head_bank_support_route(split=bank.split is not None, sorted_copy=bank.sorted_rows is not None, shape=bank.shape,
+                                    pad=bank.pad, width=q.shape[1], B=q.shape[0], n_classes=C, window=row_window is not None,
+                                    weights=logw is not None)
+    if route == "matrix":
+        return nw_head(q, s, sy, C, kind, logit_scale, support_cache=bank)
+    if row_window is None and logw is None:
+        # nw_head's inference call over the bank (the rows are the bank's: `s` is not handed to the graph here)
+        call = _resolve(bank, q, s.detach(), sy, C, False, False, False, 0, None, False)
+        window = None
+    else:
+        call = _resolve_scores(bank, q)._replace(sy=_i64c(sy))
+        window = None if row_window is None else tuple(_row_window(row_window, q.shape[0], q.device))
+    return _NWHeadBankSupportFn.apply(call.q, logit_scale, s, call, C, kid, window, bool(exclude), bank, logw, row_logw)
 
 
 def head_values_grad_route(*, split, sorted_copy, shape, pad, width, B, T):
