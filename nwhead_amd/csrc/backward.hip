@@ -511,8 +511,6 @@ __global__ __launch_bounds__(256) void nw_sum_kernel(const float* __restrict__ x
     if (threadIdx.x == 0) *out = a;
 }
 
-inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
-
 }  // namespace
 
 // The one statement of the backward's route rule, launch sizes and workspace map (bwd_plan.h).

@@ -476,8 +476,6 @@ __global__ __launch_bounds__(256) void nw_bwd_logw_finish_kernel(const float* __
     ga[j] = v;
 }
 
-inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
-
 // Slab width and chunk count.  Cost of a workgroup per support tile, in matrix-core time: 3 d/32 for the scores (every
 // slab recomputes them) + 4 per 32 columns of the slab (3 MFMAs per block and the transposed reads, which bound it);
 // the grid runs in ceil(workgroups / CUs) rounds.  The partial tiles are what the workspace holds: the library's own

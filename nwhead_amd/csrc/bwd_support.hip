@@ -33,27 +33,20 @@
 // Query chunks fill the chip when there are few support tiles.  Each writes its tile still scaled, with the exponent beside
 // it -- into gs itself when there is one chunk --; the finish kernel unscales, adds the chunks in ascending order from +0
 // and adds 2 r s.  No float atomics: two calls give the same bits.
-#include "nw_internal.h"
-#include "tile_dma.h"
-#include "tile_f16.h"
+// The skeleton -- plan, q's exponent and pack, the window rule and W, the h + l write, the MFMA block, the exchange of the r
+// sums, the launch -- is bwd_support_core.h's, shared with bwd_values_support.hip; X there is A here.
+#include "bwd_support_core.h"
 #include "bwd_coeff.h"
+#include "fused_plan.h"   // NW_FOR_EACH_KIND
 
 namespace nw {
 namespace {
 
-constexpr int SRS = 4;            // support blocks per tile
-constexpr int SBS = 16 * SRS;     // 64 bank rows per tile
 // qn2[BQ] | qsc[BQ] | sn2[SBS] | ssc[SBS] | law[SBS] | lab[SBS] | wmx[NCONS]
 constexpr int S_HDR = (2 * BQ + 4 * SBS + NCONS) * 4;
 static_assert(S_HDR % 16 == 0, "stage buffers must stay 16-byte aligned");
 constexpr size_t S_LDS = S_HDR + DmaCfg<SRS>::STAGE_BYTES;
 static_assert(S_LDS <= 80 * 1024, "header + ring exceed the LDS of two workgroups per CU");
-constexpr int A_STRIDE = BQ + 8;  // halves per row of the exchanged A: 144 bytes
-static_assert((size_t)2 * SBS * A_STRIDE * 2 <= DmaCfg<SRS>::STAGE_BYTES, "A halves inside the ring");
-static_assert((size_t)BQ * SBS * 4 <= DmaCfg<SRS>::STAGE_BYTES, "the r exchange inside the ring");
-constexpr int S_CUS = 256;        // workgroups that fill the chip
-constexpr float HALF_MAX = 60000.f;
-constexpr int S_NCH_MAX = 8, S_NCH_MIN = 4;   // the slab widths that are shipped (Makefile: no scratch in either)
 
 struct SupWs {
     float *dptab, *tb, *qmax;
@@ -62,9 +55,6 @@ struct SupWs {
     float* rp;         // [chunk][row]: rows padded to the tile
     int* esc;          // [chunk][support tile]: the exponent that unscales the chunk's tile
     float* part;       // [chunk][N][d], only with more than one chunk
-};
-struct SupPlan {
-    int n_stiles, n_qtiles, nch, nslabs, nchunks, tpc;
 };
 struct SupArgs {
     const float *q, *s, *s_scale, *s_norm2;
@@ -103,46 +93,10 @@ __global__ __launch_bounds__(256) void nw_bwd_bank_support_prologue_kernel(const
     if (threadIdx.x == 0) tb[b] = t, qmax[b] = mx;
 }
 
-// the one exponent of q: split_exponent of the largest magnitude (0 for an all-zero q)
-__global__ __launch_bounds__(256) void nw_bwd_bank_support_qexp_kernel(const float* __restrict__ qmax, int* __restrict__ qexp,
-                                                                        int64_t B) {
-    __shared__ float red[8];
-    float mx = 0.f;
-    for (int64_t b = threadIdx.x; b < B; b += 256) mx = fmaxf(mx, qmax[b]);
-    mx = block_max(mx, red);
-    if (threadIdx.x == 0) *qexp = split_exponent(mx);
-}
-
-// q 2^E -> fp16 halves in the B-operand order of the main kernel: thread (query tile, column block, step, lane (i, g))
-// packs queries 32 step + 8g .. + 7 of column 16 block + i.  A query past B is a zero.
-__global__ __launch_bounds__(256) void nw_bwd_bank_support_pack_kernel(const float* __restrict__ q, const int* __restrict__ qexp,
-                                                                        half8* __restrict__ qpack, int64_t B, int64_t d,
-                                                                        int64_t total) {
-    const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (idx >= total) return;
-    const int lane = (int)(idx & 63), i = lane & 15, g = lane >> 4;
-    const int ks = (int)((idx >> 6) & 1);
-    const int64_t ncb = d / 16, blk = idx >> 7;
-    const int64_t cb = blk % ncb, qt = blk / ncb;
-    const float up = __builtin_ldexpf(1.f, *qexp);
-    half8 h, l;
-#pragma unroll
-    for (int k = 0; k < 8; ++k) {
-        const int64_t b = qt * BQ + 32 * ks + 8 * g + k;
-        float x = b < B ? q[b * d + 16 * cb + i] * up : 0.f;
-        x = __builtin_amdgcn_fmed3f(x, -HALF_MAX, HALF_MAX);   // (only a non-finite input gets here)
-        h[k] = (_Float16)x;
-        l[k] = (_Float16)(x - (float)h[k]);
-    }
-    half8* dst = qpack + ((blk * 2 + ks) * 2) * 64 + lane;
-    dst[0] = h;
-    dst[64] = l;
-}
-
 template <int KIND, int NCH>
 __global__ __launch_bounds__(TILE_THREADS, 2) void nw_bwd_bank_support_kernel(const SupArgs a) {
     constexpr bool NEED_NORM = (KIND != NW_SCORE_DOT);
-    constexpr float L2E = 1.44269504088896340736f, LN2 = 0.693147180559945309417f;
+    constexpr float LN2 = 0.693147180559945309417f;
     constexpr int NCC = NCH / 2;     // 32-column chunks per wave
     extern __shared__ __attribute__((aligned(16))) char smem[];
     float* qn2 = reinterpret_cast<float*>(smem);
@@ -154,7 +108,7 @@ __global__ __launch_bounds__(TILE_THREADS, 2) void nw_bwd_bank_support_kernel(co
     float* wmx = reinterpret_cast<float*>(lab + SBS);   // the consumer waves' largest |A| of the query tile
     float4* stage = reinterpret_cast<float4*>(smem + S_HDR);
     _Float16* Ahs = reinterpret_cast<_Float16*>(smem + S_HDR);
-    _Float16* Als = Ahs + SBS * A_STRIDE;
+    _Float16* Als = Ahs + SBS * X_STRIDE;
     float* pmx = reinterpret_cast<float*>(smem + S_HDR);   // the r exchange at the end, over the same bytes
 
     const int B = a.B, N = a.N, d = a.d;
@@ -169,7 +123,6 @@ __global__ __launch_bounds__(TILE_THREADS, 2) void nw_bwd_bank_support_kernel(co
     const int nc = min(NCH, nk - kc0);                 // 32-column chunks of this slab
     const int qt_begin = chunk * a.tpc, qt_end = min(a.n_qtiles, qt_begin + a.tpc);
     const int rb = wave & 3, hf = wave >> 2;          // the second product: rows 16 rb .. + 15, chunks hf, hf + 2, ...
-    const bool windowed = a.win_lo != nullptr;
     const bool weighted = a.row_logw != nullptr;
     const bool exclude = a.exclude != 0;
 
@@ -205,28 +158,17 @@ __global__ __launch_bounds__(TILE_THREADS, 2) void nw_bwd_bank_support_kernel(co
         float xr[SRS][4];
         if (wave < NCONS) {
             // ================================ consumers: A in registers, its r sums, its maximum ================================
-            using SF = ScoreFactors<KIND>;
             const int qrow = 16 * wave + i;
-            const int b = q0 + qrow, bb = b < B ? b : B - 1;
-            const float lse = a.lse[bb];
-            // a dead query and a lane past B: W = 2^(u - inf) = 0 in every row
-            const float lsev = (lse == -INFINITY || b >= B) ? INFINITY : lse * L2E;
-            const float tq = a.ws.tb[bb];
+            const float qn = NEED_NORM ? qn2[qrow] : 0.f;
+            float scale, nq, inq2;
+            bwd_query_factors<KIND>(qn, a.logit_scale, scale, nq, inq2);
+            const SupQuery Q = sup_query<KIND>(a.lse, a.win_lo, a.win_hi, exclude, B, N, q0, qrow, g, s0, tile_end, qn,
+                                               qsc_s[qrow], scale);
+            const float tq = a.ws.tb[Q.bb];
             // an all-zero query adds nothing to A^T Q whatever its coefficients are, and those of the cosine kinds are of the
             // order 1 / NW_NORM_EPS there: they are kept away from the exponent
-            const bool qzero = a.ws.qmax[bb] == 0.f;
-            const float* dprow = a.ws.dptab + (size_t)bb * a.C;
-            int lo = 0, hi = N;
-            if (windowed) lo = min(max(a.win_lo[bb], 0), N), hi = min(max(a.win_hi[bb], 0), N);   // never used as addresses
-            const unsigned width = hi > lo ? (unsigned)(hi - lo) : 0u;
-            const float qn = NEED_NORM ? qn2[qrow] : 0.f;
-            float scale, nq, inq2, Cq, Bq;
-            bwd_query_factors<KIND>(qn, a.logit_scale, scale, nq, inq2);
-            SF::query(qn, qsc_s[qrow], scale, Cq, Bq);
-            // the window's rule of the forward (fused_impl.h, OUT_WIN): a pair the window leaves whole skips the comparisons
-            const bool whole = !windowed || (exclude ? (width == 0u || hi <= s0 || lo >= tile_end) : (lo <= s0 && hi >= tile_end));
-            const bool check = !whole || tile_end < s0 + SBS || b >= B;
-            const int rel = s0 + 4 * g - lo;
+            const bool qzero = a.ws.qmax[Q.bb] == 0.f;
+            const float* dprow = a.ws.dptab + (size_t)Q.bb * a.C;
             float dw[SRS][4], amax = 0.f, rq_unused = 0.f, gls_unused = 0.f;
 #pragma unroll
             for (int r = 0; r < SRS; ++r) {
@@ -247,17 +189,9 @@ __global__ __launch_bounds__(TILE_THREADS, 2) void nw_bwd_bank_support_kernel(co
                 const float aw[4] = {a4.x, a4.y, a4.z, a4.w};
 #pragma unroll
                 for (int e = 0; e < 4; ++e) {
-                    float K, Base;
-                    SF::support(nn[e], ss[e], K, Base);
-                    const float u = SF::finish(__builtin_fmaf(acc[r][e], K * Cq, Base + Bq));   // base-2 units, as the forward
-                    // the weighted score goes into W alone: bwd_pair_coeff takes the raw score (bwd_query.hip)
-                    float W = __builtin_amdgcn_exp2f(__builtin_fmaf(aw[e], L2E, u) - lsev);
-                    if (check) {
-                        const int t = 16 * r + e;
-                        bool keep = s0 + 4 * g + t < N && b < B;
-                        if (windowed) keep = keep && (((unsigned)(rel + t) < width) != exclude);
-                        W = keep ? W : 0.f;
-                    }
+                    // the weighted score goes into W alone: bwd_pair_coeff takes the raw score u (bwd_query.hip)
+                    float u;
+                    const float W = sup_weight<KIND>(Q, acc[r][e], nn[e], ss[e], aw[e], 16 * r + e, B, N, u);
                     const float dS = W * (dw[r][e] - tq);
                     float av, rs;
                     bwd_pair_coeff<KIND>(u * LN2, dS, nn[e], scale, nq, inq2, av, rs, rq_unused, gls_unused);
@@ -295,13 +229,7 @@ __global__ __launch_bounds__(TILE_THREADS, 2) void nw_bwd_bank_support_kernel(co
 #pragma unroll
             for (int r = 0; r < SRS; ++r)
 #pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    const float x = __builtin_amdgcn_fmed3f(xr[r][e] * up, -HALF_MAX, HALF_MAX);   // (only a non-finite input gets here)
-                    const _Float16 h = (_Float16)x;
-                    const int row = 16 * r + 4 * g + e;
-                    Ahs[row * A_STRIDE + qrow] = h;
-                    Als[row * A_STRIDE + qrow] = (_Float16)(x - (float)h);
-                }
+                for (int e = 0; e < 4; ++e) sup_put_halves(Ahs, Als, 16 * r + 4 * g + e, qrow, xr[r][e], up, -HALF_MAX);
         }
         if (factor != 1.f) {   // (uniform over the workgroup)
 #pragma unroll
@@ -313,40 +241,7 @@ __global__ __launch_bounds__(TILE_THREADS, 2) void nw_bwd_bank_support_kernel(co
         __syncthreads();   // A is in LDS
 
         // ================================ all waves: gs tile += A^T Q ================================
-        {
-            half8 Ah[2], Al[2];
-#pragma unroll
-            for (int ks = 0; ks < 2; ++ks) {
-                Ah[ks] = *reinterpret_cast<const half8*>(Ahs + (16 * rb + i) * A_STRIDE + 32 * ks + 8 * g);
-                Al[ks] = *reinterpret_cast<const half8*>(Als + (16 * rb + i) * A_STRIDE + 32 * ks + 8 * g);
-            }
-            auto mm = [](const half8& x, const half8& y, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x32_f16(x, y, c, 0, 0, 0); };
-            const half8* qp = a.ws.qpack + (size_t)qt * ncb * 256 + lane;
-#pragma unroll
-            for (int cc = 0; cc < NCC; ++cc) {
-                const int c = 2 * cc + hf;
-                if (c < nc) {
-                    half8 Qf[2][2][2];   // [column block][step][h, l]
-#pragma unroll
-                    for (int nb = 0; nb < 2; ++nb)
-#pragma unroll
-                        for (int ks = 0; ks < 2; ++ks)
-#pragma unroll
-                            for (int hl = 0; hl < 2; ++hl)
-                                Qf[nb][ks][hl] = qp[((size_t)(2 * (kc0 + c) + nb) * 2 + ks) * 128 + hl * 64];
-                    // small terms first, the dominant h*h product last; the two column blocks alternate
-#pragma unroll
-                    for (int ks = 0; ks < 2; ++ks) {
-                        gacc[cc][0] = mm(Al[ks], Qf[0][ks][0], gacc[cc][0]);
-                        gacc[cc][1] = mm(Al[ks], Qf[1][ks][0], gacc[cc][1]);
-                        gacc[cc][0] = mm(Ah[ks], Qf[0][ks][1], gacc[cc][0]);
-                        gacc[cc][1] = mm(Ah[ks], Qf[1][ks][1], gacc[cc][1]);
-                        gacc[cc][0] = mm(Ah[ks], Qf[0][ks][0], gacc[cc][0]);
-                        gacc[cc][1] = mm(Ah[ks], Qf[1][ks][0], gacc[cc][1]);
-                    }
-                }
-            }
-        }
+        sup_mfma_tile<NCC>(gacc, Ahs, Als, a.ws.qpack, qt, ncb, kc0, nc, rb, hf, lane);
         __syncthreads();   // the ring is free for the next tile
     }
 
@@ -368,18 +263,7 @@ __global__ __launch_bounds__(TILE_THREADS, 2) void nw_bwd_bank_support_kernel(co
     }
     if (slab == 0) {   // (uniform over the workgroup: every slab holds the same r sums and the same exponent)
         if (tid == 0) a.ws.esc[(size_t)chunk * a.n_stiles + stile] = -(Erun + *a.ws.qexp);
-        if (wave < NCONS) {
-#pragma unroll
-            for (int r = 0; r < SRS; ++r)
-#pragma unroll
-                for (int e = 0; e < 4; ++e) pmx[(16 * wave + i) * SBS + 16 * r + 4 * g + e] = pm[r][e];
-        }
-        __syncthreads();
-        if (tid < SBS) {
-            float v = 0.f;
-            for (int k = 0; k < BQ; ++k) v += pmx[k * SBS + tid];   // the tile's 64 query slots in order
-            a.ws.rp[(size_t)chunk * ((size_t)a.n_stiles * SBS) + s0 + tid] = v;
-        }
+        sup_row_sums(pm, pmx, a.ws.rp + (size_t)chunk * ((size_t)a.n_stiles * SBS) + s0, tid, wave);
     }
 }
 
@@ -408,61 +292,21 @@ __global__ __launch_bounds__(256) void nw_bwd_bank_support_finish_kernel(const f
     *reinterpret_cast<float4*>(gs + idx * 4) = v;
 }
 
-inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
-
-// Slab width: the narrow one when it takes all of d.  Query chunks: one when the support tiles and slabs alone fill the
-// chip, otherwise as many as do (at most the query tiles); a positive query_chunks is taken, clamped to the query tiles.
-SupPlan sup_plan(int64_t B, int64_t N, int64_t d, int query_chunks) {
-    const int64_t n_stiles = (N + SBS - 1) / SBS, n_qtiles = (B + BQ - 1) / BQ, nk = d / BK;
-    const int nch = nk <= S_NCH_MIN ? S_NCH_MIN : S_NCH_MAX;
-    const int64_t nslabs = (nk + nch - 1) / nch;
-    int64_t want;
-    if (query_chunks > 0) {
-        want = query_chunks;
-    } else {
-        const int64_t wgs = n_stiles * nslabs;
-        want = wgs >= S_CUS ? 1 : (S_CUS + wgs - 1) / wgs;
-    }
-    if (want > n_qtiles) want = n_qtiles;
-    if (want < 1) want = 1;
-    const int64_t tpc = (n_qtiles + want - 1) / want, nchunks = (n_qtiles + tpc - 1) / tpc;
-    return {(int)n_stiles, (int)n_qtiles, nch, (int)nslabs, (int)nchunks, (int)tpc};
-}
-
 // dptab | tb | qmax | qexp | qpack | rp | esc | part
 size_t sup_layout(int64_t B, int64_t N, int64_t d, int64_t C, const SupPlan& p, char* base, SupWs* ws) {
-    size_t off = 0;
-    auto take = [&](size_t bytes) {
-        char* ptr = base ? base + off : nullptr;
-        off += align256(bytes);
-        return ptr;
-    };
+    SupCarve ws_{base};
     const size_t npad = (size_t)p.n_stiles * SBS;
     SupWs w;
-    w.dptab = reinterpret_cast<float*>(take((size_t)B * C * 4));
-    w.tb = reinterpret_cast<float*>(take((size_t)B * 4));
-    w.qmax = reinterpret_cast<float*>(take((size_t)B * 4));
-    w.qexp = reinterpret_cast<int*>(take(4));
-    w.qpack = reinterpret_cast<half8*>(take((size_t)p.n_qtiles * BQ * d * 4));
-    w.rp = reinterpret_cast<float*>(take((size_t)p.nchunks * npad * 4));
-    w.esc = reinterpret_cast<int*>(take((size_t)p.nchunks * p.n_stiles * 4));
-    w.part = reinterpret_cast<float*>(take(p.nchunks > 1 ? (size_t)p.nchunks * N * d * 4 : 0));
+    w.dptab = ws_.take<float>((size_t)B * C * 4);
+    w.tb = ws_.take<float>((size_t)B * 4);
+    w.qmax = ws_.take<float>((size_t)B * 4);
+    w.qexp = ws_.take<int>(4);
+    w.qpack = ws_.take<half8>((size_t)p.n_qtiles * BQ * d * 4);
+    w.rp = ws_.take<float>((size_t)p.nchunks * npad * 4);
+    w.esc = ws_.take<int>((size_t)p.nchunks * p.n_stiles * 4);
+    w.part = ws_.take<float>(p.nchunks > 1 ? (size_t)p.nchunks * N * d * 4 : 0);
     if (ws) *ws = w;
-    return off;
-}
-
-template <int KIND, int NCH>
-int launch_sup_kernel(const SupArgs& a, unsigned grid, hipStream_t st) {
-    static const bool attr = hipFuncSetAttribute(reinterpret_cast<const void*>(nw_bwd_bank_support_kernel<KIND, NCH>),
-                                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)S_LDS) == hipSuccess;
-    if (!attr) return NW_ERR_LAUNCH;
-    hipLaunchKernelGGL((nw_bwd_bank_support_kernel<KIND, NCH>), dim3(grid), dim3(TILE_THREADS), S_LDS, st, a);
-    return NW_OK;
-}
-template <int KIND>
-int launch_sup_kind(const SupArgs& a, int nch, unsigned grid, hipStream_t st) {
-    if (nch == S_NCH_MAX) return launch_sup_kernel<KIND, S_NCH_MAX>(a, grid, st);
-    return launch_sup_kernel<KIND, S_NCH_MIN>(a, grid, st);
+    return ws_.off;
 }
 
 }  // namespace
@@ -479,25 +323,23 @@ int launch_bwd_bank_support(const BwdBankSupportCall& c) {
     const size_t need = sup_layout(c.B, c.N, c.d, c.C, p, static_cast<char*>(c.workspace), &ws);
     if (!c.workspace || c.workspace_bytes < need) return NW_ERR_WORKSPACE;
     const int64_t wgs = (int64_t)p.n_stiles * p.nslabs * p.nchunks;
-    const int64_t npack = (int64_t)p.n_qtiles * (c.d / 16) * 128, total4 = c.N * c.d / 4;
+    const int64_t npack = sup_pack_threads(p, c.d), total4 = c.N * c.d / 4;
     if (wgs > 0x7fffffffLL || (npack + 255) / 256 > 0x7fffffffLL || (total4 + 255) / 256 > 0x7fffffffLL) return NW_ERR_UNSUPPORTED;
     hipLaunchKernelGGL(nw_bwd_bank_support_prologue_kernel, dim3((unsigned)c.B), dim3(256), 0, st, c.out, c.gout, c.q, ws.dptab,
                        ws.tb, ws.qmax, c.C, c.d);
-    hipLaunchKernelGGL(nw_bwd_bank_support_qexp_kernel, dim3(1), dim3(256), 0, st, ws.qmax, ws.qexp, c.B);
-    hipLaunchKernelGGL(nw_bwd_bank_support_pack_kernel, dim3((unsigned)((npack + 255) / 256)), dim3(256), 0, st, c.q, ws.qexp,
-                       ws.qpack, c.B, c.d, npack);
+    launch_sup_pack(c.q, ws.qmax, ws.qexp, ws.qpack, c.B, c.d, p, st);
     float* part = p.nchunks > 1 ? ws.part : c.gs;
     const SupArgs a = {c.q, c.s_split, c.s_scale, c.s_norm2, c.sy, c.row_lo, c.row_hi, c.lse, c.logit_scale_dev, c.row_logw, part, ws,
                        c.row_lo && c.exclude != 0, (int)c.B, (int)c.N, (int)c.d, (int)c.C, p.n_stiles, p.n_qtiles, p.nslabs,
                        p.nchunks, p.tpc};
-    int rc;
-    switch (c.kind) {
-        case NW_SCORE_EUCLIDEAN: rc = launch_sup_kind<NW_SCORE_EUCLIDEAN>(a, p.nch, (unsigned)wgs, st); break;
-        case NW_SCORE_HYPERSPHERE: rc = launch_sup_kind<NW_SCORE_HYPERSPHERE>(a, p.nch, (unsigned)wgs, st); break;
-        case NW_SCORE_COSINE: rc = launch_sup_kind<NW_SCORE_COSINE>(a, p.nch, (unsigned)wgs, st); break;
-        case NW_SCORE_DOT: rc = launch_sup_kind<NW_SCORE_DOT>(a, p.nch, (unsigned)wgs, st); break;
-        default: rc = launch_sup_kind<NW_SCORE_CLIP>(a, p.nch, (unsigned)wgs, st); break;
-    }
+    int rc = NW_ERR_UNSUPPORTED;   // (the entry admits the five kinds alone)
+#define NW_KIND_CASE(K)                                                                                           \
+    case K:                                                                                                       \
+        rc = launch_sup_kind<nw_bwd_bank_support_kernel<K, S_NCH_MAX>, nw_bwd_bank_support_kernel<K, S_NCH_MIN>>( \
+            a, S_LDS, p.nch, (unsigned)wgs, st);                                                                  \
+        break;
+    switch (c.kind) { NW_FOR_EACH_KIND(NW_KIND_CASE) }
+#undef NW_KIND_CASE
     if (rc != NW_OK) return rc;
     hipLaunchKernelGGL(nw_bwd_bank_support_finish_kernel, dim3((unsigned)((total4 + 255) / 256)), dim3(256), 0, st, part, ws.esc,
                        ws.rp, c.s, c.gs, p.nchunks, p.n_stiles, c.N, c.d);

@@ -364,8 +364,6 @@ __global__ __launch_bounds__(256) void nw_bwd_values_gls_kernel(const float* __r
     if (threadIdx.x == 0) *out = v;
 }
 
-inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
-
 // Slab width and chunk count, by bwd_query_plan's model with the extra product: per support tile a workgroup costs
 // 3 d/32 for the scores + 3 T/32 for c (every slab recomputes both) + 4 per 32 columns of its slab; the grid runs in
 // ceil(workgroups / CUs) rounds.  The workspace cap is the query gradient's: the library's own choice keeps the partial

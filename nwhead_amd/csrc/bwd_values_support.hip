@@ -34,27 +34,20 @@
 // A zero column of gout gives a zero column of gvalues.  The value rows enter ga only, and must be finite there.
 // Query chunks fill the chip when there are few support tiles; each writes partial tiles, a finish kernel adds them in
 // chunk order: no float atomics, two calls give the same bits.
-#include "nw_internal.h"
-#include "tile_dma.h"
-#include "tile_f16.h"
+// The skeleton -- plan, gout's exponent and pack, the window rule and W, the h + l write, the MFMA block, the exchange of the
+// W m sums, the launch -- is bwd_support_core.h's, shared with bwd_support.hip; X there is W here.
+#include "bwd_support_core.h"
+#include "fused_plan.h"   // NW_FOR_EACH_KIND
 
 namespace nw {
 namespace {
 
-constexpr int SRS = 4;            // support blocks per tile
-constexpr int SBS = 16 * SRS;     // 64 bank rows per tile
 // qn2[BQ] | qsc[BQ] | sn2[SBS] | ssc[SBS] | law[SBS]
 constexpr int S_HDR = (2 * BQ + 3 * SBS) * 4;
 static_assert(S_HDR % 16 == 0, "stage buffers must stay 16-byte aligned");
 constexpr size_t S_LDS = S_HDR + DmaCfg<SRS>::STAGE_BYTES;
 static_assert(S_LDS <= 80 * 1024, "header + ring exceed the LDS of two workgroups per CU");
-constexpr int W_STRIDE = BQ + 8;  // halves per row of the exchanged W: 144 bytes
-static_assert((size_t)2 * SBS * W_STRIDE * 2 <= DmaCfg<SRS>::STAGE_BYTES, "W halves inside the ring");
-static_assert((size_t)BQ * SBS * 4 <= DmaCfg<SRS>::STAGE_BYTES, "the W m exchange inside the ring");
-constexpr int S_CUS = 256;        // workgroups that fill the chip
-constexpr float HALF_MAX = 60000.f;
 constexpr int W_SHIFT = 15;       // W 2^15 <= 32768: inside fp16
-constexpr int S_NCH_MAX = 8, S_NCH_MIN = 4;   // the slab widths that are shipped (Makefile: no scratch in either)
 
 struct SupWs {
     float *mb, *gmax;
@@ -62,9 +55,6 @@ struct SupWs {
     half8* gpack;      // [query tile][16-column block][32-query step][h, l][lane]: 8 halves each
     float *glp, *pmp;  // [chunk][slab, wave half][row], [chunk][row]: rows padded to the tile
     float* part;       // [chunk][N][T], only with gvalues and more than one chunk
-};
-struct SupPlan {
-    int n_stiles, n_qtiles, nch, nslabs, nchunks, tpc;
 };
 struct SupArgs {
     const float *q, *s, *s_scale, *s_norm2, *v_rows;
@@ -94,46 +84,9 @@ __global__ __launch_bounds__(256) void nw_bwd_values_support_prologue_kernel(con
     if (threadIdx.x == 0) mb[b] = t, gmax[b] = mx;
 }
 
-// the one exponent of gout: split_exponent of the largest magnitude
-__global__ __launch_bounds__(256) void nw_bwd_values_support_gexp_kernel(const float* __restrict__ gmax, int* __restrict__ gexp,
-                                                                          int64_t B) {
-    __shared__ float red[8];
-    float mx = 0.f;
-    for (int64_t b = threadIdx.x; b < B; b += 256) mx = fmaxf(mx, gmax[b]);
-    mx = block_max(mx, red);
-    if (threadIdx.x == 0) *gexp = split_exponent(mx);
-}
-
-// gout 2^E -> fp16 halves in the B-operand order of the main kernel: thread (query tile, column block, step, lane (i, g))
-// packs queries 32 step + 8g .. + 7 of column 16 block + i.  A query past B is a zero.
-__global__ __launch_bounds__(256) void nw_bwd_values_support_pack_kernel(const float* __restrict__ gout, const int* __restrict__ gexp,
-                                                                          half8* __restrict__ gpack, int64_t B, int64_t T,
-                                                                          int64_t total) {
-    const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (idx >= total) return;
-    const int lane = (int)(idx & 63), i = lane & 15, g = lane >> 4;
-    const int ks = (int)((idx >> 6) & 1);
-    const int64_t ncb = T / 16, blk = idx >> 7;
-    const int64_t cb = blk % ncb, qt = blk / ncb;
-    const float up = __builtin_ldexpf(1.f, *gexp);
-    half8 h, l;
-#pragma unroll
-    for (int k = 0; k < 8; ++k) {
-        const int64_t b = qt * BQ + 32 * ks + 8 * g + k;
-        float x = b < B ? gout[b * T + 16 * cb + i] * up : 0.f;
-        x = __builtin_amdgcn_fmed3f(x, -HALF_MAX, HALF_MAX);   // (only a non-finite input gets here)
-        h[k] = (_Float16)x;
-        l[k] = (_Float16)(x - (float)h[k]);
-    }
-    half8* dst = gpack + ((blk * 2 + ks) * 2) * 64 + lane;
-    dst[0] = h;
-    dst[64] = l;
-}
-
 template <int KIND, int NCH>
 __global__ __launch_bounds__(TILE_THREADS, 2) void nw_bwd_values_support_kernel(const SupArgs a) {
     constexpr bool NEED_NORM = (KIND != NW_SCORE_DOT);
-    constexpr float L2E = 1.44269504088896340736f;
     constexpr int NCC = NCH / 2;     // 32-column chunks per wave
     extern __shared__ __attribute__((aligned(16))) char smem[];
     float* qn2 = reinterpret_cast<float*>(smem);
@@ -143,7 +96,7 @@ __global__ __launch_bounds__(TILE_THREADS, 2) void nw_bwd_values_support_kernel(
     float* law = ssc + SBS;          // the tile's row log-weights (0 without them: the fused multiply-add is then exact)
     float4* stage = reinterpret_cast<float4*>(smem + S_HDR);
     _Float16* Wh = reinterpret_cast<_Float16*>(smem + S_HDR);
-    _Float16* Wl = Wh + SBS * W_STRIDE;
+    _Float16* Wl = Wh + SBS * X_STRIDE;
     float* pmx = reinterpret_cast<float*>(smem + S_HDR);   // the W m exchange at the end, over the same bytes
 
     const int B = a.B, N = a.N, d = a.d, T = a.T;
@@ -158,7 +111,6 @@ __global__ __launch_bounds__(TILE_THREADS, 2) void nw_bwd_values_support_kernel(
     const int nc = min(NCH, nkt - kc0);                 // 32-column chunks of this slab
     const int qt_begin = chunk * a.tpc, qt_end = min(a.n_qtiles, qt_begin + a.tpc);
     const int rb = wave & 3, hf = wave >> 2;          // the third product: rows 16 rb .. + 15, chunks hf, hf + 2, ...
-    const bool windowed = a.win_lo != nullptr;
     const bool weighted = a.row_logw != nullptr;
     const bool exclude = a.exclude != 0;
     const bool want_pm = a.want_glogw != 0 && slab == 0;
@@ -191,23 +143,10 @@ __global__ __launch_bounds__(TILE_THREADS, 2) void nw_bwd_values_support_kernel(
 
         if (wave < NCONS) {
             // ================================ consumers: W, its m sums, its halves to LDS ================================
-            using SF = ScoreFactors<KIND>;
             const int qrow = 16 * wave + i;
-            const int b = q0 + qrow, bb = b < B ? b : B - 1;
-            const float lse = a.lse[bb];
-            // a dead query and a lane past B: W = 2^(u - inf) = 0 in every row
-            const float lsev = (lse == -INFINITY || b >= B) ? INFINITY : lse * L2E;
-            const float mq = a.ws.mb[bb];
-            int lo = 0, hi = N;
-            if (windowed) lo = min(max(a.win_lo[bb], 0), N), hi = min(max(a.win_hi[bb], 0), N);   // never used as addresses
-            const unsigned width = hi > lo ? (unsigned)(hi - lo) : 0u;
-            const float qn = NEED_NORM ? qn2[qrow] : 0.f;
-            float Cq, Bq;
-            SF::query(qn, qsc_s[qrow], scale, Cq, Bq);
-            // the window's rule of the forward (fused_impl.h, OUT_WIN): a pair the window leaves whole skips the comparisons
-            const bool whole = !windowed || (exclude ? (width == 0u || hi <= s0 || lo >= tile_end) : (lo <= s0 && hi >= tile_end));
-            const bool check = !whole || tile_end < s0 + SBS || b >= B;
-            const int rel = s0 + 4 * g - lo;
+            const SupQuery Q = sup_query<KIND>(a.lse, a.win_lo, a.win_hi, exclude, B, N, q0, qrow, g, s0, tile_end,
+                                               NEED_NORM ? qn2[qrow] : 0.f, qsc_s[qrow], scale);
+            const float mq = a.ws.mb[Q.bb];
 #pragma unroll
             for (int r = 0; r < SRS; ++r) {
                 float4 n4 = make_float4(0.f, 0.f, 0.f, 0.f);
@@ -218,62 +157,17 @@ __global__ __launch_bounds__(TILE_THREADS, 2) void nw_bwd_values_support_kernel(
                 const float aw[4] = {a4.x, a4.y, a4.z, a4.w};
 #pragma unroll
                 for (int e = 0; e < 4; ++e) {
-                    float K, Base;
-                    SF::support(nn[e], ss[e], K, Base);
-                    const float u = SF::finish(__builtin_fmaf(acc[r][e], K * Cq, Base + Bq));   // base-2 units, as the forward
-                    float W = __builtin_amdgcn_exp2f(__builtin_fmaf(aw[e], L2E, u) - lsev);
-                    if (check) {
-                        const int t = 16 * r + e;
-                        bool keep = s0 + 4 * g + t < N && b < B;
-                        if (windowed) keep = keep && (((unsigned)(rel + t) < width) != exclude);
-                        W = keep ? W : 0.f;
-                    }
+                    float u;
+                    const float W = sup_weight<KIND>(Q, acc[r][e], nn[e], ss[e], aw[e], 16 * r + e, B, N, u);
                     pm[r][e] = __builtin_fmaf(W, mq, pm[r][e]);
-                    const float x = __builtin_amdgcn_fmed3f(W * (float)(1 << W_SHIFT), 0.f, HALF_MAX);
-                    const _Float16 h = (_Float16)x;
-                    const int row = 16 * r + 4 * g + e;
-                    Wh[row * W_STRIDE + qrow] = h;
-                    Wl[row * W_STRIDE + qrow] = (_Float16)(x - (float)h);
+                    sup_put_halves(Wh, Wl, 16 * r + 4 * g + e, qrow, W, (float)(1 << W_SHIFT), 0.f);
                 }
             }
         }
         __syncthreads();   // W is in LDS
 
         // ================================ all waves: gV tile += W^T G ================================
-        {
-            half8 Ah[2], Al[2];
-#pragma unroll
-            for (int ks = 0; ks < 2; ++ks) {
-                Ah[ks] = *reinterpret_cast<const half8*>(Wh + (16 * rb + i) * W_STRIDE + 32 * ks + 8 * g);
-                Al[ks] = *reinterpret_cast<const half8*>(Wl + (16 * rb + i) * W_STRIDE + 32 * ks + 8 * g);
-            }
-            auto mm = [](const half8& x, const half8& y, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x32_f16(x, y, c, 0, 0, 0); };
-            const half8* gq = a.ws.gpack + (size_t)qt * ncb * 256 + lane;
-#pragma unroll
-            for (int cc = 0; cc < NCC; ++cc) {
-                const int c = 2 * cc + hf;
-                if (c < nc) {
-                    half8 Gf[2][2][2];   // [column block][step][h, l]
-#pragma unroll
-                    for (int nb = 0; nb < 2; ++nb)
-#pragma unroll
-                        for (int ks = 0; ks < 2; ++ks)
-#pragma unroll
-                            for (int hl = 0; hl < 2; ++hl)
-                                Gf[nb][ks][hl] = gq[((size_t)(2 * (kc0 + c) + nb) * 2 + ks) * 128 + hl * 64];
-                    // small terms first, the dominant h*h product last; the two column blocks alternate
-#pragma unroll
-                    for (int ks = 0; ks < 2; ++ks) {
-                        gacc[cc][0] = mm(Al[ks], Gf[0][ks][0], gacc[cc][0]);
-                        gacc[cc][1] = mm(Al[ks], Gf[1][ks][0], gacc[cc][1]);
-                        gacc[cc][0] = mm(Ah[ks], Gf[0][ks][1], gacc[cc][0]);
-                        gacc[cc][1] = mm(Ah[ks], Gf[1][ks][1], gacc[cc][1]);
-                        gacc[cc][0] = mm(Ah[ks], Gf[0][ks][0], gacc[cc][0]);
-                        gacc[cc][1] = mm(Ah[ks], Gf[1][ks][0], gacc[cc][1]);
-                    }
-                }
-            }
-        }
+        sup_mfma_tile<NCC>(gacc, Wh, Wl, a.ws.gpack, qt, ncb, kc0, nc, rb, hf, lane);
         __syncthreads();   // the ring is free for the next tile
     }
 
@@ -313,20 +207,7 @@ __global__ __launch_bounds__(TILE_THREADS, 2) void nw_bwd_values_support_kernel(
             if (i == 0)
                 a.ws.glp[((size_t)chunk * a.nslabs * 2 + 2 * slab + hf) * npad + s0 + 16 * rb + 4 * g + e] = v;
         }
-        if (want_pm) {   // (uniform over the workgroup)
-            if (wave < NCONS) {
-#pragma unroll
-                for (int r = 0; r < SRS; ++r)
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) pmx[(16 * wave + i) * SBS + 16 * r + 4 * g + e] = pm[r][e];
-            }
-            __syncthreads();
-            if (tid < SBS) {
-                float v = 0.f;
-                for (int k = 0; k < BQ; ++k) v += pmx[k * SBS + tid];   // the tile's 64 query slots in order
-                a.ws.pmp[(size_t)chunk * npad + s0 + tid] = v;
-            }
-        }
+        if (want_pm) sup_row_sums(pm, pmx, a.ws.pmp + (size_t)chunk * npad + s0, tid, wave);   // (uniform over the workgroup)
     }
 }
 
@@ -355,61 +236,21 @@ __global__ __launch_bounds__(256) void nw_bwd_values_support_finish_kernel(const
     *reinterpret_cast<float4*>(gvalues + idx * 4) = v;
 }
 
-inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
-
-// Slab width: the narrow one when it takes all of T.  Query chunks: one when the support tiles and slabs alone fill the
-// chip, otherwise as many as do (at most the query tiles); a positive query_chunks is taken, clamped to the query tiles.
-SupPlan sup_plan(int64_t B, int64_t N, int64_t T, int query_chunks) {
-    const int64_t n_stiles = (N + SBS - 1) / SBS, n_qtiles = (B + BQ - 1) / BQ, nkt = T / BK;
-    const int nch = nkt <= S_NCH_MIN ? S_NCH_MIN : S_NCH_MAX;
-    const int64_t nslabs = (nkt + nch - 1) / nch;
-    int64_t want;
-    if (query_chunks > 0) {
-        want = query_chunks;
-    } else {
-        const int64_t wgs = n_stiles * nslabs;
-        want = wgs >= S_CUS ? 1 : (S_CUS + wgs - 1) / wgs;
-    }
-    if (want > n_qtiles) want = n_qtiles;
-    if (want < 1) want = 1;
-    const int64_t tpc = (n_qtiles + want - 1) / want, nchunks = (n_qtiles + tpc - 1) / tpc;
-    return {(int)n_stiles, (int)n_qtiles, nch, (int)nslabs, (int)nchunks, (int)tpc};
-}
-
 // mb | gmax | gexp | gpack | glp | pmp | part
 size_t sup_layout(int64_t B, int64_t N, int64_t T, const SupPlan& p, bool want_gvalues, char* base, SupWs* ws) {
-    size_t off = 0;
-    auto take = [&](size_t bytes) {
-        char* ptr = base ? base + off : nullptr;
-        off += align256(bytes);
-        return ptr;
-    };
+    SupCarve ws_{base};
     const size_t npad = (size_t)p.n_stiles * SBS;
     SupWs w;
-    w.mb = reinterpret_cast<float*>(take((size_t)B * 4));
-    w.gmax = reinterpret_cast<float*>(take((size_t)B * 4));
-    w.gexp = reinterpret_cast<int*>(take(4));
-    w.gpack = reinterpret_cast<half8*>(take((size_t)p.n_qtiles * BQ * T * 4));
+    w.mb = ws_.take<float>((size_t)B * 4);
+    w.gmax = ws_.take<float>((size_t)B * 4);
+    w.gexp = ws_.take<int>(4);
+    w.gpack = ws_.take<half8>((size_t)p.n_qtiles * BQ * T * 4);
     // (the weights' partial sums are laid out whether or not glogw is asked for: the size depends on the shape alone)
-    w.glp = reinterpret_cast<float*>(take((size_t)p.nchunks * p.nslabs * 2 * npad * 4));
-    w.pmp = reinterpret_cast<float*>(take((size_t)p.nchunks * npad * 4));
-    w.part = reinterpret_cast<float*>(take(want_gvalues && p.nchunks > 1 ? (size_t)p.nchunks * N * T * 4 : 0));
+    w.glp = ws_.take<float>((size_t)p.nchunks * p.nslabs * 2 * npad * 4);
+    w.pmp = ws_.take<float>((size_t)p.nchunks * npad * 4);
+    w.part = ws_.take<float>(want_gvalues && p.nchunks > 1 ? (size_t)p.nchunks * N * T * 4 : 0);
     if (ws) *ws = w;
-    return off;
-}
-
-template <int KIND, int NCH>
-int launch_sup_kernel(const SupArgs& a, unsigned grid, hipStream_t st) {
-    static const bool attr = hipFuncSetAttribute(reinterpret_cast<const void*>(nw_bwd_values_support_kernel<KIND, NCH>),
-                                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)S_LDS) == hipSuccess;
-    if (!attr) return NW_ERR_LAUNCH;
-    hipLaunchKernelGGL((nw_bwd_values_support_kernel<KIND, NCH>), dim3(grid), dim3(TILE_THREADS), S_LDS, st, a);
-    return NW_OK;
-}
-template <int KIND>
-int launch_sup_kind(const SupArgs& a, int nch, unsigned grid, hipStream_t st) {
-    if (nch == S_NCH_MAX) return launch_sup_kernel<KIND, S_NCH_MAX>(a, grid, st);
-    return launch_sup_kernel<KIND, S_NCH_MIN>(a, grid, st);
+    return ws_.off;
 }
 
 }  // namespace
@@ -426,25 +267,23 @@ int launch_bwd_values_support(const BwdValuesSupportCall& c) {
     const size_t need = sup_layout(c.B, c.N, c.T, p, c.gvalues != nullptr, static_cast<char*>(c.workspace), &ws);
     if (!c.workspace || c.workspace_bytes < need) return NW_ERR_WORKSPACE;
     const int64_t wgs = (int64_t)p.n_stiles * p.nslabs * p.nchunks;
-    const int64_t npack = (int64_t)p.n_qtiles * (c.T / 16) * 128, total4 = c.N * c.T / 4;
+    const int64_t npack = sup_pack_threads(p, c.T), total4 = c.N * c.T / 4;
     if (wgs > 0x7fffffffLL || (npack + 255) / 256 > 0x7fffffffLL || (total4 + 255) / 256 > 0x7fffffffLL) return NW_ERR_UNSUPPORTED;
     hipLaunchKernelGGL(nw_bwd_values_support_prologue_kernel, dim3((unsigned)c.B), dim3(256), 0, st, c.out, c.gout, ws.mb, ws.gmax,
                        c.T);
-    hipLaunchKernelGGL(nw_bwd_values_support_gexp_kernel, dim3(1), dim3(256), 0, st, ws.gmax, ws.gexp, c.B);
-    hipLaunchKernelGGL(nw_bwd_values_support_pack_kernel, dim3((unsigned)((npack + 255) / 256)), dim3(256), 0, st, c.gout, ws.gexp,
-                       ws.gpack, c.B, c.T, npack);
+    launch_sup_pack(c.gout, ws.gmax, ws.gexp, ws.gpack, c.B, c.T, p, st);
     float* gv_out = c.gvalues ? (p.nchunks > 1 ? ws.part : c.gvalues) : nullptr;
     const SupArgs a = {c.q, c.s_split, c.s_scale, c.s_norm2, c.v_rows, c.row_lo, c.row_hi, c.lse, c.logit_scale_dev, c.row_logw,
                        gv_out, ws, c.glogw != nullptr, c.row_lo && c.exclude != 0, (int)c.B, (int)c.N, (int)c.d, (int)c.T,
                        p.n_stiles, p.n_qtiles, p.nslabs, p.nchunks, p.tpc};
-    int rc;
-    switch (c.kind) {
-        case NW_SCORE_EUCLIDEAN: rc = launch_sup_kind<NW_SCORE_EUCLIDEAN>(a, p.nch, (unsigned)wgs, st); break;
-        case NW_SCORE_HYPERSPHERE: rc = launch_sup_kind<NW_SCORE_HYPERSPHERE>(a, p.nch, (unsigned)wgs, st); break;
-        case NW_SCORE_COSINE: rc = launch_sup_kind<NW_SCORE_COSINE>(a, p.nch, (unsigned)wgs, st); break;
-        case NW_SCORE_DOT: rc = launch_sup_kind<NW_SCORE_DOT>(a, p.nch, (unsigned)wgs, st); break;
-        default: rc = launch_sup_kind<NW_SCORE_CLIP>(a, p.nch, (unsigned)wgs, st); break;
-    }
+    int rc = NW_ERR_UNSUPPORTED;   // (the entry admits the five kinds alone)
+#define NW_KIND_CASE(K)                                                                                               \
+    case K:                                                                                                           \
+        rc = launch_sup_kind<nw_bwd_values_support_kernel<K, S_NCH_MAX>, nw_bwd_values_support_kernel<K, S_NCH_MIN>>( \
+            a, S_LDS, p.nch, (unsigned)wgs, st);                                                                      \
+        break;
+    switch (c.kind) { NW_FOR_EACH_KIND(NW_KIND_CASE) }
+#undef NW_KIND_CASE
     if (rc != NW_OK) return rc;
     if (c.gvalues && p.nchunks > 1)
         hipLaunchKernelGGL(nw_bwd_values_support_finish_kernel, dim3((unsigned)((total4 + 255) / 256)), dim3(256), 0, st, ws.part,

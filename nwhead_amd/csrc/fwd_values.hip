@@ -297,8 +297,6 @@ __global__ __launch_bounds__(256) void nw_fwd_values_finish_kernel(const float* 
     *reinterpret_cast<float4*>(out + idx * 4) = v;
 }
 
-inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
-
 // Slab width and chunk count, by bwd_query_plan's model with T in d's place for the second product: per support tile a
 // workgroup costs 3 d/32 for the scores (every slab recomputes them) + 4 per 32 columns of its slab; the grid runs in
 // ceil(workgroups / CUs) rounds.  The library's own choice keeps the partial tiles, nchunks B T 4 bytes, below 0.85 B N

@@ -45,6 +45,7 @@ int launch_rownorm2(const float* x, float* n2, int64_t rows, int64_t d, hipStrea
 struct Area {
     size_t off, bytes;
 };
+inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
 // The K-split of one product of the backward: nchunks partial tiles of k_chunk each (gemm_plan in backward.hip for the
 // fp32 matrix cores, xgemm_plan for the split route); chosen once per call by plan_bwd and handed to the launcher.
 struct KSplit {

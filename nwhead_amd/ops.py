@@ -1328,17 +1328,52 @@ def bank_update_refusal(*, split, packed, sorted_copy, shape, pad, width, R):
     return None
 
 
+def _bank_node_save(ctx, qc, lse, out, ls, window, exclude, kind_id, operands, bank, logw, logw_src, values=None):
+    """What the autograd nodes of the heads over a resident bank keep for their backward.  Saved tensors: the queries, lse,
+    out, a clip scale and the window -- nothing of size B x N.  Beside them the constants the backward recomputes the scores
+    from, each with what tells a write: the bank's ``operands`` and its ``writes`` count (SplitBank.update_rows writes them
+    in place), the weights as the kernels read them with the caller's tensor and its version (an in-place write bumps it),
+    the value head's BankValues."""
+    ctx.save_for_backward(qc, lse, out, *([ls] if ls is not None else []), *(window if window is not None else []))
+    ctx.bank = operands
+    ctx.bank_writes = (bank, bank.writes)
+    ctx.logw = None if logw is None else (logw, logw_src, logw_src._version)
+    ctx.values = values
+    ctx.meta = (kind_id, ls is not None, window is not None, exclude)
+
+
+def _bank_node_load(ctx, entry):
+    """-> (q, lse, out, clip scale or None, lo, hi, weights or None, kind_id, exclude) as _bank_node_save recorded them, after
+    the refusal of a constant written since the forward (RuntimeError; ``entry``: the public name in front)."""
+    kind_id, has_ls, windowed, exclude = ctx.meta
+    saved = list(ctx.saved_tensors)
+    qc, lse, out = saved[:3]
+    ls = saved[3] if has_ls else None
+    lo, hi = saved[-2:] if windowed else (None, None)
+    if ctx.bank_writes[0].writes != ctx.bank_writes[1]:
+        raise RuntimeError(f"{entry}: the bank was written (SplitBank.update_rows) between this forward and its "
+                           "backward, which recomputes the scores from the bank: call backward() first, then update")
+    if ctx.logw is not None and ctx.logw[1]._version != ctx.logw[2]:
+        raise RuntimeError(f"{entry}: row_logw was written in place between this forward and its backward, which "
+                           "recomputes the weighted scores from it: call backward() first, then change the weights")
+    if ctx.values is not None and ctx.values.stale():
+        raise RuntimeError(f"{entry}: the tensor the BankValues was prepared from was written between this forward "
+                           "and its backward (the prepared rows no longer stand for it): build a new ops.BankValues")
+    return qc, lse, out, ls, lo, hi, ctx.logw and ctx.logw[0], kind_id, exclude
+
+
 class _NWHeadBankFn(torch.autograd.Function):
-    """autograd node of nw_head_bank: today's inference call forward, nw_bwd_query_f32 backward (with support weights
-    nw_bwd_query_weighted_f32, or nw_bwd_query_logw_f32 when the weights need a gradient too: it goes to the 10th input, the
-    caller's tensor).  Saves the queries, lse, out and the window: nothing of size B x N."""
+    """autograd node of nw_head_bank: today's inference call forward.  Backward: ONE query / weights call when q, the clip
+    scale or row_logw needs it -- nw_bwd_query_f32, with support weights nw_bwd_query_weighted_f32, or nw_bwd_query_logw_f32
+    when the weights need a gradient too (it goes to the last input, the caller's tensor; without gq when only they learn) --
+    and, with ``support_grad``, nw_bwd_bank_support_f32 for the bank rows `s`, the third input.  Nothing of size B x N."""
 
     @staticmethod
-    def forward(ctx, q, logit_scale, call, n_classes, kind_id, window, exclude, bank=None, logw=None, logw_src=None):
-        """``call``: the _Call nw_head_bank resolved (``q`` is its queries, an argument of its own for autograd);
-        ``window``: None or (lo, hi) int32; ``bank``: the SplitBank the call reads, whose ``writes`` the backward checks;
-        ``logw``: None or the (N,) fp32 support weights as the kernels read them (_row_logw), ``logw_src`` the caller's tensor
-        they came from (the same one, or what a conversion copied), whose version the backward checks likewise."""
+    def forward(ctx, q, logit_scale, s, call, n_classes, kind_id, window, exclude, bank, logw=None, logw_src=None):
+        """``s``: the bank rows when their gradient is wanted, else None; ``call``: the _Call nw_head_bank resolved (``q`` is
+        its queries, an argument of its own for autograd); ``window``: None or (lo, hi) int32; ``bank``: the SplitBank the
+        call reads; ``logw``: None or the (N,) fp32 support weights as the kernels read them (_row_logw), ``logw_src`` the
+        caller's tensor they came from (the same one, or what a conversion copied)."""
         _, sc, syc, sn2, ssplit, sscale, opts = call
         lib = _lib.load()
         qc = _f32c(q)
@@ -1357,35 +1392,30 @@ class _NWHeadBankFn(torch.autograd.Function):
                                           st), "nw_fwd_f32")
         else:
             _bank_head_fwd(qc, call, syc, logw, lo, hi, exclude, out, lse, kind_id, ls)
-        ctx.save_for_backward(qc, lse, out, *([ls] if ls is not None else []), *([lo, hi] if window is not None else []))
-        # the backward recomputes the scores from these: SplitBank.update_rows writes them in place and counts in `writes`
-        ctx.bank = (ssplit, sscale, sn2, syc)
-        ctx.bank_writes = (bank, bank.writes) if bank is not None else None
-        # ... and the weights, a constant of this node: the tensor itself and its version (an in-place write bumps it)
-        ctx.logw = None if logw is None else (logw, logw_src, logw_src._version)
-        ctx.meta = (kind_id, ls is not None, window is not None, exclude)
+        _bank_node_save(ctx, qc, lse, out, ls, window, exclude, kind_id, (ssplit, sscale, sn2, syc), bank, logw, logw_src)
+        # the fp32 rows the bank's forms were prepared from, at the bank's width (read for the 2 r s term), and what `s` is
+        ctx.s_rows = None if s is None else (bank.rows if bank.rows is not None else _f32c(s), s.shape[1], s.dtype)
         return out
 
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, gout):
-        kind_id, has_ls, windowed, exclude = ctx.meta
-        saved = list(ctx.saved_tensors)
-        qc, lse, out = saved[:3]
-        ls = saved[3] if has_ls else None
-        lo, hi = saved[-2:] if windowed else (None, None)
-        if ctx.bank_writes is not None and ctx.bank_writes[0].writes != ctx.bank_writes[1]:
-            raise RuntimeError("nw_head_bank: the bank was written (SplitBank.update_rows) between this forward and its "
-                               "backward, which recomputes the scores from the bank: call backward() first, then update")
-        if ctx.logw is not None and ctx.logw[1]._version != ctx.logw[2]:
-            raise RuntimeError("nw_head_bank: row_logw was written in place between this forward and its backward, which "
-                               "recomputes the weighted scores from it: call backward() first, then change the weights")
-        # the weights' gradient as well: then without gq (no second pass over the bank) when only the weights learn
-        want_glogw = ctx.logw is not None and ctx.needs_input_grad[9]
-        want_gq = not want_glogw or ctx.needs_input_grad[0] or (has_ls and ctx.needs_input_grad[1])
-        gq, gls, ga = _bank_head_bwd(qc, ctx.bank, ctx.logw and ctx.logw[0], lo, hi, exclude, lse, out, _f32c(gout), kind_id, ls,
-                                     want_gq, want_glogw)
-        return gq, gls, None, None, None, None, None, None, None, ga if ga is None else ga.to(ctx.logw[1].dtype)
+        qc, lse, out, ls, lo, hi, logw, kind_id, exclude = _bank_node_load(ctx, "nw_head_bank")
+        g = _f32c(gout)
+        want_glogw = logw is not None and ctx.needs_input_grad[10]
+        need_q = ctx.needs_input_grad[0] or (ls is not None and ctx.needs_input_grad[1])
+        gq = gls = ga = gs = None
+        if want_glogw or need_q:      # without gq (no second pass over the bank) when only the weights (and the rows) learn
+            gq, gls, ga = _bank_head_bwd(qc, ctx.bank, logw, lo, hi, exclude, lse, out, g, kind_id, ls,
+                                         not want_glogw or need_q, want_glogw)
+        if ctx.s_rows is not None and ctx.needs_input_grad[2]:
+            s_rows, width, dtype = ctx.s_rows
+            gs = _bank_support_bwd(qc, s_rows, ctx.bank, logw, lo, hi, exclude, lse, out, g, kind_id, ls)
+            if width != gs.shape[1]:
+                gs = gs[:, :width]
+            gs = gs.to(dtype)
+        return (gq if ctx.needs_input_grad[0] else None, gls if ls is not None and ctx.needs_input_grad[1] else None, gs, None,
+                None, None, None, None, None, None, ga if ga is None else ga.to(ctx.logw[1].dtype))
 
 
 def _bank_support_bwd(q, s_rows, operands, logw, lo, hi, exclude, lse, out, gout, kind_id, ls, query_chunks=0):
@@ -1403,51 +1433,6 @@ def _bank_support_bwd(q, s_rows, operands, logw, lo, hi, exclude, lse, out, gout
                                                _ptr(ws), ws_bytes, B, N, d, C, kind_id, _ptr(ls), int(query_chunks), _stream(q)),
                    "nw_bwd_bank_support_f32")
     return gs
-
-
-class _NWHeadBankSupportFn(torch.autograd.Function):
-    """autograd node of nw_head_bank(..., support_grad=True): _NWHeadBankFn with the bank rows `s` a third input.  Forward:
-    that node's.  Backward: its one query / weights call when q, the clip scale or row_logw needs it -- the same arguments,
-    the same bits -- and none otherwise, plus nw_bwd_bank_support_f32 for the rows.  Nothing of size B x N."""
-
-    @staticmethod
-    def forward(ctx, q, logit_scale, s, call, n_classes, kind_id, window, exclude, bank, logw=None, logw_src=None):
-        out = _NWHeadBankFn.forward(ctx, q, logit_scale, call, n_classes, kind_id, window, exclude, bank, logw, logw_src)
-        # the fp32 rows the bank's forms were prepared from, at the bank's width (read for the 2 r s term), and what `s` is
-        ctx.s_rows = bank.rows if bank.rows is not None else _f32c(s)
-        ctx.s_meta = (s.shape[1], s.dtype)
-        return out
-
-    @staticmethod
-    @torch.autograd.function.once_differentiable
-    def backward(ctx, gout):
-        kind_id, has_ls, windowed, exclude = ctx.meta
-        saved = list(ctx.saved_tensors)
-        qc, lse, out = saved[:3]
-        ls = saved[3] if has_ls else None
-        lo, hi = saved[-2:] if windowed else (None, None)
-        if ctx.bank_writes[0].writes != ctx.bank_writes[1]:
-            raise RuntimeError("nw_head_bank: the bank was written (SplitBank.update_rows) between this forward and its "
-                               "backward, which recomputes the scores from the bank: call backward() first, then update")
-        if ctx.logw is not None and ctx.logw[1]._version != ctx.logw[2]:
-            raise RuntimeError("nw_head_bank: row_logw was written in place between this forward and its backward, which "
-                               "recomputes the weighted scores from it: call backward() first, then change the weights")
-        g = _f32c(gout)
-        logw = ctx.logw and ctx.logw[0]
-        want_glogw = ctx.logw is not None and ctx.needs_input_grad[10]
-        need_q = ctx.needs_input_grad[0] or (has_ls and ctx.needs_input_grad[1])
-        gq = gls = ga = gs = None
-        if want_glogw or need_q:      # _NWHeadBankFn's call: without gq when only the weights (and the rows) learn
-            gq, gls, ga = _bank_head_bwd(qc, ctx.bank, logw, lo, hi, exclude, lse, out, g, kind_id, ls,
-                                         not want_glogw or need_q, want_glogw)
-        if ctx.needs_input_grad[2]:
-            gs = _bank_support_bwd(qc, ctx.s_rows, ctx.bank, logw, lo, hi, exclude, lse, out, g, kind_id, ls)
-            width, dtype = ctx.s_meta
-            if width != gs.shape[1]:
-                gs = gs[:, :width]
-            gs = gs.to(dtype)
-        return (gq if ctx.needs_input_grad[0] else None, gls if has_ls and ctx.needs_input_grad[1] else None, gs, None, None,
-                None, None, None, None, None, ga if ga is None else ga.to(ctx.logw[1].dtype))
 
 
 def nw_head_bank(q, s, sy, n_classes, bank, kind="euclidean", logit_scale=None, row_window=None, exclude=False, row_logw=None,
@@ -1490,9 +1475,8 @@ def nw_head_bank(q, s, sy, n_classes, bank, kind="euclidean", logit_scale=None, 
     if not isinstance(bank, SplitBank):
         raise TypeError("nw_head_bank runs over a prepared bank: pass ops.SplitBank(support)")
     grad = torch.is_grad_enabled()
-    if support_grad and grad and s.requires_grad:
-        return _head_bank_support(q, s, sy, n_classes, bank, kind, logit_scale, row_window, exclude, row_logw)
-    if grad and s.requires_grad:
+    grad_s = bool(support_grad and grad and s.requires_grad)
+    if grad and s.requires_grad and not grad_s:
         raise ValueError("nw_head_bank: the bank is a constant here and `s` requires grad; nw_head(q, s, sy, ..., "
                          "support_cache=bank) is the call for support gradients")
     _need_hip(q, s, sy, logit_scale)
@@ -1502,14 +1486,17 @@ def nw_head_bank(q, s, sy, n_classes, bank, kind="euclidean", logit_scale=None, 
     if kid == SCORE_KINDS["clip"] and logit_scale is None:
         raise ValueError("clip kernel needs logit_scale")
     grad_logw = grad and torch.is_tensor(row_logw) and row_logw.requires_grad
-    if not (grad and (q.requires_grad or (logit_scale is not None and logit_scale.requires_grad) or grad_logw)):
+    if not (grad_s or (grad and (q.requires_grad or (logit_scale is not None and logit_scale.requires_grad) or grad_logw))):
         return nw_head(q, s, sy, n_classes, kind, logit_scale, support_cache=bank, row_window=row_window, exclude=exclude,
                        row_logw=row_logw)
     C = int(n_classes)
     _check_label_range(None, bank.label_max, C)
     logw = None if row_logw is None else _row_logw(row_logw, s.shape[0], q.device, "nw_head_bank")
-    why = head_bank_refusal(split=bank.split is not None, sorted_copy=bank.sorted_rows is not None, shape=bank.shape,
-                            pad=bank.pad, width=q.shape[1], B=q.shape[0], n_classes=C)
+    facts = dict(split=bank.split is not None, sorted_copy=bank.sorted_rows is not None, shape=bank.shape, pad=bank.pad,
+                 width=q.shape[1], B=q.shape[0], n_classes=C)
+    why = None if grad_s else head_bank_refusal(**facts)
+    if grad_s and head_bank_support_route(window=row_window is not None, weights=logw is not None, **facts) == "matrix":
+        return nw_head(q, s, sy, C, kind, logit_scale, support_cache=bank)
     if why is not None:
         if grad_logw:
             raise NWHipError(f"nw_head_bank(row_logw=...) has no route for the gradient to the weights here: {why}.  Without "
@@ -1521,40 +1508,14 @@ def nw_head_bank(q, s, sy, n_classes, bank, kind="euclidean", logit_scale=None, 
             return nw_head(q, s, sy, C, kind, logit_scale, support_cache=bank)
         raise NWHipError(f"nw_head_bank(row_window=...) has no gradient route here: {why}")
     if row_window is None and logw is None:
-        call = _resolve(bank, q, s, sy, C, False, False, False, 0, None, False)       # nw_head's inference call
+        # nw_head's inference call over the bank (the rows are the bank's: a learnable `s` is not handed to the graph here)
+        call = _resolve(bank, q, s.detach() if grad_s else s, sy, C, False, False, False, 0, None, False)
         window = None
     else:
         call = _resolve_scores(bank, q)._replace(sy=_i64c(sy))
         window = None if row_window is None else tuple(_row_window(row_window, q.shape[0], q.device))
-    out = _NWHeadBankFn.apply(call.q, logit_scale, call, C, kid, window, bool(exclude), bank, logw, row_logw)
-    return out
-
-
-def _head_bank_support(q, s, sy, n_classes, bank, kind, logit_scale, row_window, exclude, row_logw):
-    """nw_head_bank(..., support_grad=True) with an `s` that requires grad: nw_head_bank's checks, then
-    head_bank_support_route's answer."""
-    _need_hip(q, s, sy, logit_scale)
-    if s.dim() != 2 or sy.dim() != 1 or sy.shape[0] != s.shape[0] or not bank.matches(s):
-        raise ValueError("nw_head_bank: `s` (N,d) must be the tensor the bank was prepared from and `sy` its (N,) labels")
-    kid = _kind_id(kind)
-    if kid == SCORE_KINDS["clip"] and logit_scale is None:
-        raise ValueError("clip kernel needs logit_scale")
-    C = int(n_classes)
-    _check_label_range(None, bank.label_max, C)
-    logw = None if row_logw is None else _row_logw(row_logw, s.shape[0], q.device, "nw_head_bank")
-    route = head_bank_support_route(split=bank.split is not None, sorted_copy=bank.sorted_rows is not None, shape=bank.shape,
-                                    pad=bank.pad, width=q.shape[1], B=q.shape[0], n_classes=C, window=row_window is not None,
-                                    weights=logw is not None)
-    if route == "matrix":
-        return nw_head(q, s, sy, C, kind, logit_scale, support_cache=bank)
-    if row_window is None and logw is None:
-        # nw_head's inference call over the bank (the rows are the bank's: `s` is not handed to the graph here)
-        call = _resolve(bank, q, s.detach(), sy, C, False, False, False, 0, None, False)
-        window = None
-    else:
-        call = _resolve_scores(bank, q)._replace(sy=_i64c(sy))
-        window = None if row_window is None else tuple(_row_window(row_window, q.shape[0], q.device))
-    return _NWHeadBankSupportFn.apply(call.q, logit_scale, s, call, C, kid, window, bool(exclude), bank, logw, row_logw)
+    return _NWHeadBankFn.apply(call.q, logit_scale, s if grad_s else None, call, C, kid, window, bool(exclude), bank, logw,
+                               row_logw)
 
 
 def head_values_grad_route(*, split, sorted_copy, shape, pad, width, B, T):
@@ -1617,64 +1578,26 @@ def _values_head_matrix(q, s, bank, vals, kind, logit_scale, logw, lo, hi, exclu
     return torch.softmax(x.masked_fill(dead, 0.0), dim=1).masked_fill(dead, 0.0) @ vals
 
 
-class _NWValuesBankFn(torch.autograd.Function):
-    """autograd node of nw_head_values_bank on the fused route: the inference launches forward (_values_head_fwd: the lse pass,
-    nw_fwd_values_f32), ONE call of nw_bwd_values_query_f32 backward.  Returns the padded (B, values.width) raw output; the
-    slice to T and the logarithm are torch ops behind it.  Saves the queries, lse, out and the window: nothing of size B x N."""
-
-    @staticmethod
-    def forward(ctx, q, logit_scale, call, bank, values, kind_id, window, exclude, logw=None, logw_src=None):
-        """``call``: _resolve_scores' _Call (``q`` is its queries, an argument of its own for autograd); ``values``: the
-        BankValues; ``window``: None or (lo, hi) int32; ``logw`` / ``logw_src``: as in _NWHeadBankFn."""
-        qc = _f32c(q)
-        if qc.data_ptr() % 16:
-            qc = qc.clone()
-        ls = None if logit_scale is None else _f32c(logit_scale)
-        lo, hi = window if window is not None else (None, None)
-        out, lse = _values_head_fwd(call._replace(q=qc), bank, values, logw, lo, hi, exclude, kind_id, ls)
-        ctx.save_for_backward(qc, lse, out, *([ls] if ls is not None else []), *([lo, hi] if window is not None else []))
-        # the backward recomputes the scores and c from these: constants of this node, each with what tells a write
-        ctx.bank = (call.operand, call.scale, call.norm2)
-        ctx.bank_writes = (bank, bank.writes)
-        ctx.values = values
-        ctx.logw = None if logw is None else (logw, logw_src, logw_src._version)
-        ctx.meta = (kind_id, ls is not None, window is not None, exclude)
-        return out
-
-    @staticmethod
-    @torch.autograd.function.once_differentiable
-    def backward(ctx, gout):
-        kind_id, has_ls, windowed, exclude = ctx.meta
-        saved = list(ctx.saved_tensors)
-        qc, lse, out = saved[:3]
-        ls = saved[3] if has_ls else None
-        lo, hi = saved[-2:] if windowed else (None, None)
-        if ctx.bank_writes[0].writes != ctx.bank_writes[1]:
-            raise RuntimeError("nw_head_values_bank: the bank was written (SplitBank.update_rows) between this forward and its "
-                               "backward, which recomputes the scores from the bank: call backward() first, then update")
-        if ctx.logw is not None and ctx.logw[1]._version != ctx.logw[2]:
-            raise RuntimeError("nw_head_values_bank: row_logw was written in place between this forward and its backward, which "
-                               "recomputes the weighted scores from it: call backward() first, then change the weights")
-        if ctx.values.stale():
-            raise RuntimeError("nw_head_values_bank: the tensor the BankValues was prepared from was written between this forward "
-                               "and its backward (the prepared rows no longer stand for it): build a new ops.BankValues")
-        lib = _lib.load()
-        ssplit, sscale, sn2 = ctx.bank
-        logw = ctx.logw and ctx.logw[0]
-        (B, d), N, Tp, dev = qc.shape, ssplit.shape[0], out.shape[1], qc.device
-        g = _f32c(gout)
-        if g.data_ptr() % 16:
-            g = g.clone()
-        gq = torch.empty_like(qc)
-        gls = torch.empty((), dtype=torch.float32, device=dev) if ls is not None else None
-        ws_bytes = lib.nw_bwd_values_query_workspace_bytes(B, N, d, Tp, 0)
-        ws = _workspace(ws_bytes, dev)
-        with _OnDevice(dev):
-            _lib.check(lib.nw_bwd_values_query_f32(_ptr(qc), _ptr(ssplit), _ptr(sscale), _ptr(sn2), _ptr(ctx.values.split),
-                                                   _ptr(ctx.values.scale), _ptr(logw), _ptr(lo), _ptr(hi), int(bool(exclude)),
-                                                   _ptr(lse), _ptr(out), _ptr(g), _ptr(gq), _ptr(gls), _ptr(ws), ws_bytes, B, N, d,
-                                                   Tp, kind_id, _ptr(ls), 0, _stream(qc)), "nw_bwd_values_query_f32")
-        return gq, gls, None, None, None, None, None, None, None, None
+def _values_query_bwd(qc, operands, values, logw, lo, hi, exclude, lse, out, gout, kind_id, ls):
+    """ONE call of nw_bwd_values_query_f32 -> (gq, glogit_scale or None).  ``operands``: the bank's (split rows, scales,
+    norms); ``values``: the BankValues; ``gout``: the upstream gradient, copied where it is not fp32, contiguous and 16-byte
+    aligned."""
+    lib = _lib.load()
+    ssplit, sscale, sn2 = operands
+    (B, d), N, Tp, dev = qc.shape, ssplit.shape[0], out.shape[1], qc.device
+    g = _f32c(gout)
+    if g.data_ptr() % 16:
+        g = g.clone()
+    gq = torch.empty_like(qc)
+    gls = torch.empty((), dtype=torch.float32, device=dev) if ls is not None else None
+    ws_bytes = lib.nw_bwd_values_query_workspace_bytes(B, N, d, Tp, 0)
+    ws = _workspace(ws_bytes, dev)
+    with _OnDevice(dev):
+        _lib.check(lib.nw_bwd_values_query_f32(_ptr(qc), _ptr(ssplit), _ptr(sscale), _ptr(sn2), _ptr(values.split),
+                                               _ptr(values.scale), _ptr(logw), _ptr(lo), _ptr(hi), int(bool(exclude)),
+                                               _ptr(lse), _ptr(out), _ptr(g), _ptr(gq), _ptr(gls), _ptr(ws), ws_bytes, B, N, d,
+                                               Tp, kind_id, _ptr(ls), 0, _stream(qc)), "nw_bwd_values_query_f32")
+    return gq, gls
 
 
 def _values_support_bwd(qc, operands, values, logw, lo, hi, exclude, lse, out, g, kind_id, ls, want_gvalues, want_glogw,
@@ -1698,124 +1621,49 @@ def _values_support_bwd(qc, operands, values, logw, lo, hi, exclude, lse, out, g
     return gv, ga
 
 
-class _NWValuesSupportFn(torch.autograd.Function):
-    """autograd node of nw_head_values_bank(support_grad=True) on the fused route: _NWValuesBankFn's forward (the inference
-    launches as they are); backward nw_bwd_values_query_f32 when the queries or a clip scale need it (the same call, the same
-    bits) and ONE call of nw_bwd_values_support_f32 for the values' source tensor (3rd input) and the caller's row_logw (last
-    input), each in its dtype.  When only the weights learn nothing of size N x T is allocated.  Saves what _NWValuesBankFn
-    saves: nothing of size B x N."""
+class _NWValuesBankFn(torch.autograd.Function):
+    """autograd node of nw_head_values_bank on the fused route: the inference launches forward (_values_head_fwd: the lse pass,
+    nw_fwd_values_f32).  Backward: ONE call of nw_bwd_values_query_f32 when the queries or a clip scale need it and, with
+    ``support_grad``, ONE call of nw_bwd_values_support_f32 for the values' source tensor (3rd input) and the caller's row_logw
+    (last input), each in its dtype; when only the weights learn nothing of size N x T is allocated.  Returns the padded
+    (B, values.width) raw output; the slice to T and the logarithm are torch ops behind it.  Nothing of size B x N is saved."""
 
     @staticmethod
     def forward(ctx, q, logit_scale, vsrc, call, bank, values, kind_id, window, exclude, logw=None, logw_src=None):
+        """``vsrc``: the tensor the values were prepared from when its gradient is wanted, else None; ``call``:
+        _resolve_scores' _Call (``q`` is its queries, an argument of its own for autograd); ``values``: the BankValues;
+        ``window``: None or (lo, hi) int32; ``logw`` / ``logw_src``: as in _NWHeadBankFn."""
         qc = _f32c(q)
         if qc.data_ptr() % 16:
             qc = qc.clone()
         ls = None if logit_scale is None else _f32c(logit_scale)
         lo, hi = window if window is not None else (None, None)
         out, lse = _values_head_fwd(call._replace(q=qc), bank, values, logw, lo, hi, exclude, kind_id, ls)
-        ctx.save_for_backward(qc, lse, out, *([ls] if ls is not None else []), *([lo, hi] if window is not None else []))
-        ctx.bank = (call.operand, call.scale, call.norm2)
-        ctx.bank_writes = (bank, bank.writes)
-        ctx.values = values
+        _bank_node_save(ctx, qc, lse, out, ls, window, exclude, kind_id, (call.operand, call.scale, call.norm2), bank, logw,
+                        logw_src, values)
         ctx.vsrc = None if vsrc is None else (vsrc.dtype, tuple(vsrc.shape))
-        ctx.logw = None if logw is None else (logw, logw_src, logw_src._version)
-        ctx.meta = (kind_id, ls is not None, window is not None, exclude)
         return out
 
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, gout):
-        kind_id, has_ls, windowed, exclude = ctx.meta
-        saved = list(ctx.saved_tensors)
-        qc, lse, out = saved[:3]
-        ls = saved[3] if has_ls else None
-        lo, hi = saved[-2:] if windowed else (None, None)
-        if ctx.bank_writes[0].writes != ctx.bank_writes[1]:
-            raise RuntimeError("nw_head_values_bank: the bank was written (SplitBank.update_rows) between this forward and its "
-                               "backward, which recomputes the scores from the bank: call backward() first, then update")
-        if ctx.logw is not None and ctx.logw[1]._version != ctx.logw[2]:
-            raise RuntimeError("nw_head_values_bank: row_logw was written in place between this forward and its backward, which "
-                               "recomputes the weighted scores from it: call backward() first, then change the weights")
-        if ctx.values.stale():
-            raise RuntimeError("nw_head_values_bank: the tensor the BankValues was prepared from was written between this forward "
-                               "and its backward (the prepared rows no longer stand for it): build a new ops.BankValues")
-        lib = _lib.load()
-        ssplit, sscale, sn2 = ctx.bank
-        logw = ctx.logw and ctx.logw[0]
-        (B, d), N, Tp, dev = qc.shape, ssplit.shape[0], out.shape[1], qc.device
+        qc, lse, out, ls, lo, hi, logw, kind_id, exclude = _bank_node_load(ctx, "nw_head_values_bank")
         g = _f32c(gout)
         if g.data_ptr() % 16:
             g = g.clone()
-        gq = gls = None
-        if ctx.needs_input_grad[0] or (has_ls and ctx.needs_input_grad[1]):
-            gq = torch.empty_like(qc)
-            gls = torch.empty((), dtype=torch.float32, device=dev) if ls is not None else None
-            ws_bytes = lib.nw_bwd_values_query_workspace_bytes(B, N, d, Tp, 0)
-            ws = _workspace(ws_bytes, dev)
-            with _OnDevice(dev):
-                _lib.check(lib.nw_bwd_values_query_f32(_ptr(qc), _ptr(ssplit), _ptr(sscale), _ptr(sn2), _ptr(ctx.values.split),
-                                                       _ptr(ctx.values.scale), _ptr(logw), _ptr(lo), _ptr(hi), int(bool(exclude)),
-                                                       _ptr(lse), _ptr(out), _ptr(g), _ptr(gq), _ptr(gls), _ptr(ws), ws_bytes, B, N,
-                                                       d, Tp, kind_id, _ptr(ls), 0, _stream(qc)), "nw_bwd_values_query_f32")
+        gq = gls = gv = ga = None
+        if ctx.needs_input_grad[0] or (ls is not None and ctx.needs_input_grad[1]):
+            gq, gls = _values_query_bwd(qc, ctx.bank, ctx.values, logw, lo, hi, exclude, lse, out, g, kind_id, ls)
         want_gv = ctx.vsrc is not None and ctx.needs_input_grad[2]
-        want_ga = ctx.logw is not None and ctx.needs_input_grad[10]
-        gv = ga = None
+        want_ga = logw is not None and ctx.needs_input_grad[10]
         if want_gv or want_ga:
             gv, ga = _values_support_bwd(qc, ctx.bank, ctx.values, logw, lo, hi, exclude, lse, out, g, kind_id, ls, want_gv, want_ga)
         if gv is not None:
-            T = ctx.vsrc[1][1]
+            T, Tp = ctx.vsrc[1][1], out.shape[1]
             gv = (gv if T == Tp else gv[:, :T]).to(ctx.vsrc[0])
         if ga is not None:
             ga = ga.to(ctx.logw[1].dtype)
         return gq, gls, gv, None, None, None, None, None, None, None, ga
-
-
-def _values_support_entry(q, s, bank, values, kind, logit_scale, row_window, exclude, row_logw, log, grad_v, grad_a):
-    """nw_head_values_bank(support_grad=True) with something on the support side requiring grad."""
-    if s.dim() != 2 or not bank.matches(s):
-        raise ValueError("nw_head_values_bank: `s` (N,d) must be the tensor the bank was prepared from")
-    if torch.is_tensor(values):
-        vsrc, values = values, BankValues(values, bank)
-    elif isinstance(values, BankValues):
-        vsrc = values.source()
-        if grad_v and vsrc is None:
-            raise NWHipError("nw_head_values_bank(support_grad=True): the tensor this BankValues was prepared from is gone, so "
-                             "there is nothing for the gradient to the values to go to; build a new ops.BankValues")
-    else:
-        raise TypeError("nw_head_values_bank: values is an ops.BankValues or an (N,T) float tensor")
-    N, T = s.shape[0], values.T
-    if values.rows.shape[0] != N or values.rows.device != q.device:
-        raise ValueError(f"nw_head_values_bank: the values hold {values.rows.shape[0]} rows on {values.rows.device} for a bank of "
-                         f"{N} rows and queries on {q.device}")
-    if values.stale():
-        raise ValueError("nw_head_values_bank: the tensor this BankValues was prepared from was written since; build a new "
-                         "ops.BankValues (or BankValues.refresh())")
-    if q.dtype != torch.float32:
-        q = q.float()
-    B = q.shape[0]
-    window = None if row_window is None else tuple(_row_window(row_window, B, q.device))
-    logw = None if row_logw is None else _row_logw(row_logw, N, q.device, "nw_head_values_bank")
-    kid = _kind_id(kind)
-    if kid == SCORE_KINDS["clip"] and logit_scale is None:
-        raise ValueError("clip kernel needs logit_scale")
-    route = head_values_grad_route(split=bank.split is not None, sorted_copy=bank.sorted_rows is not None, shape=bank.shape,
-                                   pad=bank.pad, width=q.shape[1], B=B, T=T)
-    if route == "fused":
-        call = _resolve_scores(bank, q, s)
-        out = _NWValuesSupportFn.apply(call.q, logit_scale, vsrc if grad_v else None, call, bank, values, kid, window,
-                                       bool(exclude), logw, row_logw)
-        if values.width != T:
-            out = out[:, :T]
-    else:
-        # the matrix composition differentiates in the graph tensors themselves
-        vals = vsrc.float() if grad_v else values.rows[:, :T]
-        a = row_logw.float() if grad_a else logw
-        if B == 0 or N == 0:
-            out = torch.zeros(B, T, dtype=torch.float32, device=q.device) + 0.0 * (vals.sum() + (a.sum() if grad_a else 0.0))
-        else:
-            lo, hi = window if window is not None else (None, None)
-            out = _values_head_matrix(q, s, bank, vals, kind, logit_scale, a, lo, hi, bool(exclude))
-    return torch.log(out + 1e-12) if log else out
 
 
 def nw_head_values_bank(q, s, bank, values, kind="euclidean", logit_scale=None, row_window=None, exclude=False, row_logw=None,
@@ -1861,24 +1709,26 @@ def nw_head_values_bank(q, s, bank, values, kind="euclidean", logit_scale=None, 
     if grad and s.requires_grad:
         raise ValueError("nw_head_values_bank: the bank is a constant here and `s` requires grad")
     raw = values if torch.is_tensor(values) else None
-    if grad and support_grad:
-        grad_v = bool(raw.requires_grad if raw is not None else getattr(values, "requires_grad", False))
-        grad_a = torch.is_tensor(row_logw) and row_logw.requires_grad
-        if grad_v or grad_a:
-            _need_hip(values if raw is not None else None, row_logw if torch.is_tensor(row_logw) else None)
-            return _values_support_entry(q, s, bank, values, kind, logit_scale, row_window, exclude, row_logw, log, grad_v, grad_a)
-    if grad and ((raw.requires_grad if raw is not None else getattr(values, "requires_grad", False))
-                 or (torch.is_tensor(row_logw) and row_logw.requires_grad)):
+    grad_v = bool(grad and (raw.requires_grad if raw is not None else getattr(values, "requires_grad", False)))
+    grad_a = bool(grad and torch.is_tensor(row_logw) and row_logw.requires_grad)
+    if (grad_v or grad_a) and not support_grad:
         raise NWHipError("nw_head_values_bank differentiates in the queries and a clip scale alone and does not detach silently: "
                          "values or row_logw requires grad.  The composition nw_scores + softmax + matmul differentiates in them")
-    if not (grad and (q.requires_grad or (logit_scale is not None and logit_scale.requires_grad))):
+    if grad_v or grad_a:
+        _need_hip(raw, row_logw if torch.is_tensor(row_logw) else None)
+    elif not (grad and (q.requires_grad or (logit_scale is not None and logit_scale.requires_grad))):
         return nw_head_values(q, s, bank, values, kind, logit_scale, row_window=row_window, exclude=exclude, row_logw=row_logw,
                               log=log)
     if s.dim() != 2 or not bank.matches(s):
         raise ValueError("nw_head_values_bank: `s` (N,d) must be the tensor the bank was prepared from")
     if raw is not None:
-        values = BankValues(raw, bank)
-    elif not isinstance(values, BankValues):
+        vsrc, values = raw, BankValues(raw, bank)
+    elif isinstance(values, BankValues):
+        vsrc = values.source()
+        if grad_v and vsrc is None:
+            raise NWHipError("nw_head_values_bank(support_grad=True): the tensor this BankValues was prepared from is gone, so "
+                             "there is nothing for the gradient to the values to go to; build a new ops.BankValues")
+    else:
         raise TypeError("nw_head_values_bank: values is an ops.BankValues or an (N,T) float tensor")
     N, T = s.shape[0], values.T
     if values.rows.shape[0] != N or values.rows.device != q.device:
@@ -1886,7 +1736,7 @@ def nw_head_values_bank(q, s, bank, values, kind="euclidean", logit_scale=None, 
                          f"{N} rows and queries on {q.device}")
     if values.stale():
         raise ValueError("nw_head_values_bank: the tensor this BankValues was prepared from was written since; build a new "
-                         "ops.BankValues")
+                         "ops.BankValues" + (" (or BankValues.refresh())" if grad_v or grad_a else ""))
     if q.dtype != torch.float32:
         q = q.float()
     B = q.shape[0]
@@ -1899,14 +1749,20 @@ def nw_head_values_bank(q, s, bank, values, kind="euclidean", logit_scale=None, 
                                    pad=bank.pad, width=q.shape[1], B=B, T=T)
     if route == "fused":
         call = _resolve_scores(bank, q, s)                      # (queries padded by a torch op: autograd slices gq back)
-        out = _NWValuesBankFn.apply(call.q, logit_scale, call, bank, values, kid, window, bool(exclude), logw, row_logw)
+        out = _NWValuesBankFn.apply(call.q, logit_scale, vsrc if grad_v else None, call, bank, values, kid, window,
+                                    bool(exclude), logw, row_logw)
         if values.width != T:
             out = out[:, :T]
-    elif B == 0 or N == 0:
-        out = torch.zeros(B, T, dtype=torch.float32, device=q.device) + 0.0 * q.sum()
     else:
-        lo, hi = window if window is not None else (None, None)
-        out = _values_head_matrix(q, s, bank, values.rows[:, :T], kind, logit_scale, logw, lo, hi, bool(exclude))
+        # the matrix composition differentiates in the graph tensors themselves
+        vals = vsrc.float() if grad_v else values.rows[:, :T]
+        a = row_logw.float() if grad_a else logw
+        if B == 0 or N == 0:     # nothing to compute: zeros, tied to whatever requires grad
+            out = torch.zeros(B, T, dtype=torch.float32, device=q.device) + 0.0 * sum(
+                t.sum() for t, on in ((q, q.requires_grad), (vals, grad_v), (a, grad_a)) if on)
+        else:
+            lo, hi = window if window is not None else (None, None)
+            out = _values_head_matrix(q, s, bank, vals, kind, logit_scale, a, lo, hi, bool(exclude))
     return torch.log(out + 1e-12) if log else out
 
 
