@@ -578,6 +578,42 @@ int nw_bwd_bank_support_f32(const float *q, const float *s, const float *s_split
                             float *gs, void *workspace, size_t workspace_bytes,
                             int64_t B, int64_t N, int64_t d, int64_t C, int kind, const float *logit_scale_dev,
                             int query_chunks, void *stream);
+/* Gradient of the VALUE head over a resident split bank w.r.t. the BANK ROWS, without a (B,N) matrix (bwd_values_bank.hip):
+ * learnable keys of a key-value memory (prototypes with regression targets, a condensed support set with soft labels).  With
+ * g = gout and the values and the weights constants,
+ *   c_bj = g_b . v_j,   m_b = g_b . out_b,   dS_bj = W_bj (c_bj - m_b),   W_bj = exp(score_bj + a_j - lse_b),
+ *   gs_j = sum_b A_bj q_b + 2 (sum_b r_bj) s_j,  (A_bj, r_bj) the per-pair coefficients of nw_bwd_query_f32 (df/ddot and
+ *   df/d|s|^2 times dS_bj, the derivative taken at the RAW score, W carrying row_logw):
+ * nw_bwd_bank_support_f32 with c_bj - m_b in the place of dP_b[y_j] - t_b; c is a second product of the scores' kind over
+ * (gout, v_split, T), recomputed per 64-query x 64-row tile as in nw_bwd_values_query_f32.
+ *   q (B,d), s (N,d) the fp32 rows the split forms were prepared from (read for the 2 r s term only), s_split / s_scale /
+ *   s_norm2, v_split / v_scale, row_logw (or NULL), row_lo / row_hi / exclude: nw_fwd_values_f32's operands;
+ *   lse (B,), out (B,T): what that forward read and wrote for the same operands, window and weights (the RAW output);
+ *   gout (B,T) fp32, 16-byte aligned: the upstream gradient w.r.t. out, zero in the padding columns of T;
+ *   T: the padded width, a multiple of 32 within nw_bwd_values_support_f32's range;
+ *   gs (N,d) fp32, 16-byte aligned;
+ *   query_chunks: as in nw_bwd_bank_support_f32.
+ * EVERY element of gs[0..N) x [0..d) is written by a successful call with B > 0, nothing past it; the padded columns of a
+ * padded bank get zeros.  A row at a = -inf, a row no query's window admits and the share of a dead query (lse = -inf) are
+ * exactly +0.0 in every column.  Every value must be finite, in every row: c of a pair that takes no part is multiplied with
+ * W = 0.  Scaling gout by a power of two scales gs exactly.  No float atomics: two calls with the same arguments give the
+ * same bits.
+ * Accuracy: nw_bwd_bank_support_f32's bound for the contraction, with Amax the tile's largest |A|,
+ *   |error of gs[j,k]| <~ (2^-21 + B 2^-24) sum_b |A_bj| |q_bk| + 2^-38 (Amax sum_b |q_bk| + max|q| sum_b |A_bj|),
+ * on top of the error of dS: c - m cancels, and the error of c is ~2.4e-7 sum_t |g_t v_jt| whatever the spread of the values
+ * among the rows, so value columns with a large common offset lose that many bits of the gradient: centre such columns.
+ * Regime, alignment, order of the checks, status codes and refusals before anything is launched are
+ * nw_bwd_values_support_f32's, for s and gs nw_bwd_bank_support_f32's.  workspace:
+ * nw_bwd_values_bank_support_workspace_bytes(B, N, d, T, query_chunks) -- nothing of size B x N or N x T --, 0 for a shape
+ * outside the regime; short or NULL: NW_ERR_WORKSPACE.  B == 0: NW_OK and NOTHING is touched. */
+size_t nw_bwd_values_bank_support_workspace_bytes(int64_t B, int64_t N, int64_t d, int64_t T, int query_chunks);
+int nw_bwd_values_bank_support_f32(const float *q, const float *s, const float *s_split, const float *s_scale,
+                                   const float *s_norm2, const float *v_split, const float *v_scale, const float *row_logw,
+                                   const int32_t *row_lo, const int32_t *row_hi, int exclude,
+                                   const float *lse, const float *out, const float *gout,
+                                   float *gs, void *workspace, size_t workspace_bytes,
+                                   int64_t B, int64_t N, int64_t d, int64_t T, int kind, const float *logit_scale_dev,
+                                   int query_chunks, void *stream);
 /* support_influence (util/metric.py:23-50) of k SELECTED supports per query, from the head's own outputs:
  *   vals (B,k) fp32 raw scores and rows (B,k) int64 bank rows (a search's val_out / idx_out),
  *   sy (N,) int64, qy (B,) int64, out (B,C) log-probabilities and lse (B,) of nw_fwd_f32 over the same bank;

@@ -69,6 +69,9 @@ SIGNATURES = {
     "nw_bwd_bank_support_workspace_bytes": (_sz, [_i64, _i64, _i64, _i64, _int]),
     "nw_bwd_bank_support_f32": (_int, [_p, _p, _p, _p, _p, _p, _p, _p, _p, _int, _p, _p, _p, _p, _p, _sz, _i64, _i64, _i64, _i64,
                                        _int, _p, _int, _p]),
+    "nw_bwd_values_bank_support_workspace_bytes": (_sz, [_i64, _i64, _i64, _i64, _int]),
+    "nw_bwd_values_bank_support_f32": (_int, [_p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _int, _p, _p, _p, _p, _p, _sz, _i64, _i64, _i64,
+                                              _i64, _int, _p, _int, _p]),
     "nw_influence_select_f32":(_int, [_p] * 8 + [_i64, _i64, _i64, _i64, _p]),
     "nw_knn_f16_workspace_bytes": (_sz, [_i64, _i64, _i64, _i64]),
     "nw_knn_f16": (_int, [_p, _p, _p, _p, _p, _p, _p, _sz, _i64, _i64, _i64, _i64, _int, _p, _p, _p]),

@@ -1,13 +1,15 @@
-// bwd_support_core.h -- the skeleton the two SUPPORT-SIDE gradient kernels over a resident split bank share:
-// bwd_values_support.hip (the value head: gradients to the values and the row weights) and bwd_support.hip (the class
-// head: gradient to the bank rows).  Both contract, over the QUERIES, a (B, N) matrix X that is recomputed tile by tile with
+// bwd_support_core.h -- the skeleton the three SUPPORT-SIDE gradient kernels over a resident split bank share:
+// bwd_values_support.hip (the value head: gradients to the values and the row weights), bwd_support.hip (the class
+// head: gradient to the bank rows) and bwd_values_bank.hip (the value head: gradient to the bank rows).  All contract, over the QUERIES, a (B, N) matrix X that is recomputed tile by tile with
 // an operand of width `width` (gout, T columns; q, d columns): a workgroup owns one 64-row support tile, a slab of 32 * NCH
 // operand columns and a contiguous chunk of the 64-query tiles.  What is the same in both is here once: the plan, the
 // operand's one exponent and its pack in MFMA lane order, the consumer lane's window rule and weight W, the h + l write of
 // X to LDS, tile += X^T operand on v_mfma_f32_16x16x32_f16 in the order lh + hl + hh, the exchange of the per-row sums at
-// the end, and the launch of the main kernel.  Each file keeps its numerics (its header comment), its prologue and finish
-// kernels, its workspace layout and what turns W into X.  Every piece is __forceinline__: the kernels' code is what it was
-// with the pieces written out (the Makefile's resource rules hold for both units).
+// the end, and the launch of the main kernel.  Each file keeps its numerics (its header comment), its prologue, its own
+// workspace areas and what turns W into X.  The two gradients to the BANK ROWS (operand q, X the signed coefficient A) share
+// more, at the end of the file: the workspace areas behind their own, the workgroup's running exponent, the store of the
+// still-scaled tile and the finish kernel.  Every device piece is __forceinline__: the kernels' code is what it was with the
+// pieces written out (the Makefile's resource rules hold for every unit).
 #pragma once
 #include "nw_internal.h"
 #include "tile_dma.h"
@@ -246,6 +248,107 @@ template <auto KERNEL_MAX, auto KERNEL_MIN, typename Args>
 int launch_sup_kind(const Args& a, size_t lds, int nch, unsigned grid, hipStream_t st) {
     if (nch == S_NCH_MAX) return launch_sup_kernel<KERNEL_MAX>(a, lds, grid, st);
     return launch_sup_kernel<KERNEL_MIN>(a, lds, grid, st);
+}
+
+// ---- what the gradients to the BANK ROWS share beyond the skeleton (bwd_support.hip, bwd_values_bank.hip):
+//      gs_j = sum_b A_bj q_b + 2 (sum_b r_bj) s_j with A signed and unbounded, scaled by the workgroup's running exponent.
+
+// The workspace areas of both, behind the file's own (its prologue's results): qmax | qexp | qpack | rp | esc | part
+struct SupRowsWs {
+    float* qmax;       // [query]: max_k |q_bk|
+    int* qexp;
+    half8* qpack;      // [query tile][16-column block][32-query step][h, l][lane]: 8 halves each
+    float* rp;         // [chunk][row]: rows padded to the tile
+    int* esc;          // [chunk][support tile]: the exponent that unscales the chunk's tile
+    float* part;       // [chunk][N][d], only with more than one chunk
+};
+inline void sup_rows_layout(SupCarve& c, int64_t B, int64_t N, int64_t d, const SupPlan& p, SupRowsWs& w) {
+    const size_t npad = (size_t)p.n_stiles * SBS;
+    w.qmax = c.take<float>((size_t)B * 4);
+    w.qexp = c.take<int>(4);
+    w.qpack = c.take<half8>((size_t)p.n_qtiles * BQ * d * 4);
+    w.rp = c.take<float>((size_t)p.nchunks * npad * 4);
+    w.esc = c.take<int>((size_t)p.nchunks * p.n_stiles * 4);
+    w.part = c.take<float>(p.nchunks > 1 ? (size_t)p.nchunks * N * d * 4 : 0);
+}
+
+// The workgroup's exponent, from the consumer waves' largest |A| of the query tile (wmx[NCONS], behind a barrier): raised
+// (a smaller E) when this query tile holds a larger coefficient than any before.  Returns the power of two every accumulator
+// of the workgroup is multiplied with before the tile is added (1: none).  Uniform over the workgroup.
+__device__ __forceinline__ float sup_running_exponent(const float* wmx, int& Erun, bool& have) {
+    static_assert(NCONS == 4, "the four maxima are read as one float4");
+    float factor = 1.f;
+    const float4 m4 = *reinterpret_cast<const float4*>(wmx);
+    const float tmax = fmaxf(fmaxf(m4.x, m4.y), fmaxf(m4.z, m4.w));
+    if (tmax > 0.f && tmax < INFINITY) {
+        const int En = split_exponent(tmax);
+        if (!have || En < Erun) {
+            if (have) factor = __builtin_ldexpf(1.f, En - Erun);   // (before: the accumulators are all zero)
+            Erun = En;
+            have = true;
+        }
+    }
+    return factor;
+}
+
+// The chunk's tile, still scaled: gacc[cc][nb][e] of lane (i, g) = gs'[row 16 rb + 4g + e][column 32 (kc0 + 2 cc + hf) + 16 nb + i]
+// -> dst (N, d), the chunk's own.
+template <int NCC>
+__device__ __forceinline__ void sup_rows_store(const f32x4 (&gacc)[NCC][2], float* __restrict__ dst, int N, int d, int s0,
+                                               int kc0, int nc, int rb, int hf, int lane) {
+    const int i = lane & 15, g = lane >> 4;
+#pragma unroll
+    for (int cc = 0; cc < NCC; ++cc) {
+        const int c = 2 * cc + hf;
+        if (c < nc) {
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                const int row = s0 + 16 * rb + 4 * g + e;
+                if (row < N) {
+                    float* at = dst + (size_t)row * d + (size_t)(kc0 + c) * BK + i;
+                    at[0] = gacc[cc][0][e];
+                    at[16] = gacc[cc][1][e];
+                }
+            }
+        }
+    }
+}
+
+// gs[j,k] = sum_chunks part[c][j,k] 2^esc[c][tile of j] + 2 (sum_chunks rp[c][j]) s[j,k], chunks in ascending order from +0
+// (k in float4s).  With one chunk `part` is gs itself: a thread reads and writes its own four floats.
+__global__ __launch_bounds__(256) void nw_bwd_support_rows_finish_kernel(const float* part, const int* __restrict__ esc,
+                                                                          const float* __restrict__ rp, const float* __restrict__ s,
+                                                                          float* gs, int nchunks, int n_stiles, int64_t N, int64_t d) {
+    const int64_t total4 = N * d / 4;
+    const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (idx >= total4) return;
+    const int64_t j = (idx * 4) / d, npad = (int64_t)n_stiles * SBS;
+    float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+    float r = 0.f;
+    for (int c = 0; c < nchunks; ++c) {
+        const float4 w = *reinterpret_cast<const float4*>(part + ((int64_t)c * total4 + idx) * 4);
+        const int e = esc[(int64_t)c * n_stiles + j / SBS];   // a power of two: exact
+        v.x += __builtin_ldexpf(w.x, e); v.y += __builtin_ldexpf(w.y, e);
+        v.z += __builtin_ldexpf(w.z, e); v.w += __builtin_ldexpf(w.w, e);
+        r += rp[(int64_t)c * npad + j];
+    }
+    const float r2 = 2.f * r;
+    const float4 x = *reinterpret_cast<const float4*>(s + idx * 4);
+    v.x = __builtin_fmaf(r2, x.x, v.x); v.y = __builtin_fmaf(r2, x.y, v.y);
+    v.z = __builtin_fmaf(r2, x.z, v.z); v.w = __builtin_fmaf(r2, x.w, v.w);
+    *reinterpret_cast<float4*>(gs + idx * 4) = v;
+}
+
+// whether the grids of a call fit: the main kernel's, the pack's, the finish's
+inline bool sup_rows_grids_ok(const SupPlan& p, int64_t N, int64_t d) {
+    const int64_t wgs = (int64_t)p.n_stiles * p.nslabs * p.nchunks;
+    return wgs <= 0x7fffffffLL && (sup_pack_threads(p, d) + 255) / 256 <= 0x7fffffffLL && (N * d / 4 + 255) / 256 <= 0x7fffffffLL;
+}
+inline void launch_sup_rows_finish(const float* part, const SupRowsWs& w, const float* s, float* gs, const SupPlan& p, int64_t N,
+                                   int64_t d, hipStream_t st) {
+    const int64_t total4 = N * d / 4;
+    hipLaunchKernelGGL(nw_bwd_support_rows_finish_kernel, dim3((unsigned)((total4 + 255) / 256)), dim3(256), 0, st, part, w.esc,
+                       w.rp, s, gs, p.nchunks, p.n_stiles, N, d);
 }
 
 }  // namespace

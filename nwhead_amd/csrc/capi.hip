@@ -477,6 +477,36 @@ extern "C" int nw_bwd_bank_support_f32(const float* q, const float* s, const flo
                                         static_cast<hipStream_t>(stream)});
 }
 
+// The value head's gradient w.r.t. the bank rows (bwd_values_bank.hip): nw_bwd_values_support_f32's rule, in its order, with
+// nw_bwd_bank_support_f32's for the fp32 rows and gs.
+extern "C" size_t nw_bwd_values_bank_support_workspace_bytes(int64_t B, int64_t N, int64_t d, int64_t T, int query_chunks) {
+    if (B <= 0 || N < 0 || d < 0 || T < 0 || query_chunks < 0) return 0;
+    return nw::bwd_values_bank_support_workspace_bytes(B, N, d, T, query_chunks);
+}
+
+extern "C" int nw_bwd_values_bank_support_f32(const float* q, const float* s, const float* s_split, const float* s_scale,
+                                              const float* s_norm2, const float* v_split, const float* v_scale,
+                                              const float* row_logw, const int32_t* row_lo, const int32_t* row_hi, int exclude,
+                                              const float* lse, const float* out, const float* gout, float* gs, void* workspace,
+                                              size_t workspace_bytes, int64_t B, int64_t N, int64_t d, int64_t T, int kind,
+                                              const float* logit_scale_dev, int query_chunks, void* stream) {
+    if (B < 0 || N < 0 || d < 0 || T < 0 || query_chunks < 0) return NW_ERR_INVALID_ARG;
+    if ((row_lo != nullptr) != (row_hi != nullptr)) return NW_ERR_INVALID_ARG;
+    if (bad_kind(kind)) return NW_ERR_UNSUPPORTED;
+    if (!nw::fwd_values_shape_ok(B, N, d, T)) return NW_ERR_UNSUPPORTED;
+    if (B == 0) return NW_OK;         // before any pointer is looked at: nothing is touched, gs included
+    if (!q || !s || !s_split || !s_scale || !s_norm2 || !v_split || !v_scale || !lse || !out || !gout || !gs)
+        return NW_ERR_INVALID_ARG;
+    if (kind == NW_SCORE_CLIP && !logit_scale_dev) return NW_ERR_INVALID_ARG;
+    if ((addr(q) | addr(s) | addr(s_split) | addr(v_split) | addr(gout) | addr(gs) | addr(row_logw)) & 15) return NW_ERR_UNSUPPORTED;
+    const size_t need = nw::bwd_values_bank_support_workspace_bytes(B, N, d, T, query_chunks);
+    if (!workspace || workspace_bytes < need) return NW_ERR_WORKSPACE;
+    if (addr(workspace) & 15) return NW_ERR_UNSUPPORTED;
+    return nw::launch_bwd_values_bank_support({q, s, s_split, s_scale, s_norm2, v_split, v_scale, row_logw, row_lo, row_hi, exclude,
+                                               lse, out, gout, gs, workspace, workspace_bytes, B, N, d, T, kind, logit_scale_dev,
+                                               query_chunks, static_cast<hipStream_t>(stream)});
+}
+
 extern "C" int nw_fwd_partial_f32(const float* q, const float* s, const int64_t* sy,
                                   const float* s_norm2, const float* s_split, const float* s_scale,
                                   float* m, float* den, float* num, void* workspace, size_t workspace_bytes,

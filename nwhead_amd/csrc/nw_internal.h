@@ -183,6 +183,28 @@ struct BwdBankSupportCall {
 size_t bwd_bank_support_workspace_bytes(int64_t B, int64_t N, int64_t d, int64_t C, int query_chunks);
 int launch_bwd_bank_support(const BwdBankSupportCall& c);
 
+// bwd_values_bank.hip: the value head's gradient w.r.t. the bank rows, bwd_support.hip's contraction over the queries with
+// bwd_values.hip's second product in the labels' place, no (B,N) matrix (nw_bwd_values_bank_support_f32)
+struct BwdValuesBankSupportCall {
+    const float *q, *s;               // (B,d) queries; (N,d) the fp32 bank rows, read for the 2 r s term only
+    const float *s_split, *s_scale, *s_norm2;
+    const float *v_split, *v_scale;   // (N,T), (N,): nw_split_rows_f16x2 of the values
+    const float* row_logw;            // (N,) log-weights of the bank rows, or null
+    const int32_t *row_lo, *row_hi;   // both or neither
+    int exclude;
+    const float *lse, *out, *gout;    // (B,), (B,T) the forward's raw output, (B,T) the upstream gradient
+    float* gs;                        // (N,d)
+    void* workspace;
+    size_t workspace_bytes;
+    int64_t B, N, d, T;
+    int kind;
+    const float* logit_scale_dev;
+    int query_chunks;
+    hipStream_t st;
+};
+size_t bwd_values_bank_support_workspace_bytes(int64_t B, int64_t N, int64_t d, int64_t T, int query_chunks);
+int launch_bwd_values_bank_support(const BwdValuesBankSupportCall& c);
+
 // Options of the forward call in progress on this thread (nw_fwd_opts of the ABI, set for the duration of the call by
 // the entry point): explicit arguments, not process state.
 struct FwdOpts {

@@ -324,8 +324,10 @@ class NWNet(nn.Module):
         ``support_bank``, which shares ``full_feat``'s storage -- in parameters() and state_dict() from this call on, not
         before; rebuild the optimizer's parameter group.  forward_bank then passes the parameter with its graph
         (ops.nw_head_bank(support_grad=True): no (B, N) matrix), so a loss on its output puts a gradient on
-        ``support_bank``, with ``leave_out`` too.  After the optimizer wrote the rows, every entry point that reads the bank
-        re-prepares it in place first (ops.SplitBank.refresh: no rebuild, no allocation); predict('full'), predict_loo,
+        ``support_bank``, with ``leave_out`` too.  forward_values does the same for the value head
+        (ops.nw_head_values_bank(support_grad=True)): the rows are then the learnable KEYS of a key-value
+        memory, beside learnable values (``support_targets``) and weights or on their own.  After the optimizer wrote the
+        rows, every entry point that reads the bank re-prepares it in place first (ops.SplitBank.refresh: no rebuild, no allocation); predict('full'), predict_loo,
         get_neighbors and explain read the rows detached, and refresh_bank keeps working (it writes in place).  Cleared by
         precompute() and by ``set_bank_learnable(False)``, like ``support_logw``.  A sharded bank, a missing bank and a custom
         kernel module are refused (NWHipError) as for forward_bank; a full_precision="fp16" bank or one whose labels are not
@@ -593,7 +595,8 @@ class NWNet(nn.Module):
         the bank row of each query or -1 for none (a leave-one-out regression loss over the bank's own samples).  ``log``:
         log(out + 1e-12), for soft labels under a KL or cross-entropy loss.  Honours return_mask.
 
-        The bank and the values are CONSTANTS here, as in forward_bank: ``bank_features`` keeps the batch's features,
+        The bank and the values are CONSTANTS here (unless made learnable, below), as in forward_bank: ``bank_features``
+        keeps the batch's features,
         detached, for refresh_bank(rows).  Support weights (set_support_weights) are honoured as a constant; LEARNABLE
         weights are read detached -- no gradient reaches ``support_logw`` from this head.  Value columns with a large
         common offset lose that many bits of the gradient (ops.nw_head_values_bank): centre them.  A sharded bank, a missing
@@ -602,7 +605,12 @@ class NWNet(nn.Module):
         LEARNABLE values (set_support_values(..., learnable=True)) are passed with their graph: a loss on the output puts a
         gradient on ``support_targets``.  ``weights_grad=True`` passes learnable support weights with their graph as well,
         so that ``support_logw`` learns from this head too; the default keeps the detached read described above.  Both go
-        through ops.nw_head_values_bank(support_grad=True) (no (B, N) matrix)."""
+        through ops.nw_head_values_bank(support_grad=True) (no (B, N) matrix).
+
+        LEARNABLE BANK ROWS: after set_bank_learnable() the parameter ``support_bank`` is passed with its graph, as
+        forward_bank does, and a loss on the output puts a gradient on it (DESIGN 4.8n: no (B, N) matrix on the fused route;
+        the matrix composition elsewhere) -- with ``leave_out``, and beside learnable ``support_targets`` and
+        ``weights_grad=True``.  After an optimizer step on the rows the next call re-prepares the bank in place."""
         what = WHAT["forward_values"]
         self._served("forward_values", early_only=True)    # (a sharded or missing bank: no featurizer pass)
         vals = self._values()
@@ -612,10 +620,12 @@ class NWNet(nn.Module):
         self.bank_features = qfeat.detach()
         sfeat, _sy, cache = self._resident_bank("forward_values", qfeat.device)
         window = None if leave_out is None else self._leave_out_window(leave_out, qfeat, what)
-        support = {"support_grad": True} if weights_grad or self._parameters.get('support_targets') is not None else {}
-        out = ops.nw_head_values_bank(qfeat, sfeat, cache, vals, self.kernel.kind, self.kernel._logit_scale(), row_window=window,
-                                      exclude=window is not None, row_logw=self._weights(graph=bool(weights_grad)), log=log,
-                                      **support)
+        rows = self._parameters.get('support_bank')     # learnable rows: the parameter with its graph
+        learn = weights_grad or rows is not None or self._parameters.get('support_targets') is not None
+        support = {"support_grad": True} if learn else {}
+        out = ops.nw_head_values_bank(qfeat, sfeat if rows is None else rows, cache, vals, self.kernel.kind,
+                                      self.kernel._logit_scale(), row_window=window, exclude=window is not None,
+                                      row_logw=self._weights(graph=bool(weights_grad)), log=log, **support)
         return self._result(out)
 
     def predict_loo_values(self, rows=None, batch_size=256, log=False):

@@ -568,6 +568,8 @@ class SplitBank:
 
     * the gradient to the bank rows (nw_head_bank(support_grad=True); head_bank_support_route): fused on the same terms as the
       query gradient, else nw_head's route without a window and weights and a refusal with either.
+    * the value head's gradient to the bank rows (nw_head_values_bank(support_grad=True); head_values_grad_route): fused
+      exactly where the value head is, else the matrix composition, windows and weights included.
 
     The bank's tensors are written again only by ``update_rows``, which replaces rows of the support and of every prepared
     form in place and keeps the bank matching its tensor, and by ``refresh``, which re-prepares every row in place after
@@ -1526,11 +1528,35 @@ def head_values_grad_route(*, split, sorted_copy, shape, pad, width, B, T):
     return head_values_route(split=split, sorted_copy=sorted_copy, shape=shape, pad=pad, width=width, B=B, T=T)
 
 
+def _scores_support_grad(q, s, sc, g, kind_id, scale=None):
+    """Gradient of the (B, N) score matrix ``sc`` = scores(q, s) w.r.t. the SUPPORT rows `s` under the upstream gradient `g`
+    -> (N, d): the transposes of _ScoresFn.backward's closed forms for the queries (bwd_coeff.h), in plain torch ops on
+    whatever device and float dtype the arguments have.  The same conventions: no gradient passes at a distance of exactly 0
+    (the euclidean kinds), and a row F.normalize's clamp holds (|s_j| <= 1e-12) gets no share through its norm.  ``scale``:
+    exp(logit_scale), clip alone."""
+    if kind_id == SCORE_KINDS["dotproduct"]:
+        return g.t() @ q
+    if kind_id == SCORE_KINDS["euclidean"]:
+        a = torch.where(sc == 0, torch.zeros_like(g), g / -sc)
+        return a.t() @ q - a.sum(0)[:, None] * s
+    nq, ns = q.norm(dim=1, keepdim=True).clamp_min(1e-12), s.norm(dim=1, keepdim=True)
+    nsc = ns.clamp_min(1e-12)
+    if kind_id == SCORE_KINDS["hypersphere_euclidean"]:
+        gc, c = torch.where(sc == 0, torch.zeros_like(g), g / -sc), 1.0 - 0.5 * sc * sc
+    elif kind_id == SCORE_KINDS["cosine"]:
+        gc, c = g, sc
+    else:
+        gc, c = g * scale, sc / scale
+    through_norm = torch.where(ns > 1e-12, (gc * c).sum(0)[:, None], torch.zeros_like(ns))   # (the clamp passes none)
+    return (gc.t() @ (q / nq) - through_norm * (s / nsc)) / nsc
+
+
 class _ScoresFn(torch.autograd.Function):
-    """``nw_scores`` with a gradient to the queries and to a clip ``logit_scale``, the supports a constant: the score matrix
-    of the "matrix" route of nw_head_values_bank.  Forward: nw_scores, as it is.  Backward: the closed forms of bwd_coeff.h in
+    """``nw_scores`` with a gradient to the queries, to a clip ``logit_scale`` and to the supports: the score matrix of the
+    "matrix" route of nw_head_values_bank.  Forward: nw_scores, as it is.  Backward: the closed forms of bwd_coeff.h in
     torch ops over the saved (B, N) scores -- a = g df/ddot, gq = a @ s + 2 rq q -- two (B, N) x (N, d) products; the
-    zero sub-gradient at distance 0 and F.normalize's clamp are those of the kernels."""
+    zero sub-gradient at distance 0 and F.normalize's clamp are those of the kernels.  The supports' gradient
+    (_scores_support_grad: the transposes) is computed only when `s` needs it."""
 
     @staticmethod
     def forward(ctx, q, logit_scale, s, kind, bank):
@@ -1543,12 +1569,17 @@ class _ScoresFn(torch.autograd.Function):
     @torch.autograd.function.once_differentiable
     def backward(ctx, g):
         q, s, sc = ctx.saved_tensors[:3]
+        sdtype = s.dtype
         q, s, kid, gls = q.float(), s.float(), ctx.kind, None
+        scale = ctx.saved_tensors[3].float().exp() if kid == SCORE_KINDS["clip"] else None
+        gs = _scores_support_grad(q, s, sc, g, kid, scale).to(sdtype) if ctx.needs_input_grad[2] else None
+        if not (ctx.needs_input_grad[0] or (scale is not None and ctx.needs_input_grad[1])):
+            return None, None, gs, None, None
         if kid == SCORE_KINDS["dotproduct"]:
-            return g @ s, None, None, None, None
+            return g @ s, None, gs, None, None
         if kid == SCORE_KINDS["euclidean"]:
             a = torch.where(sc == 0, torch.zeros_like(g), g / -sc)
-            return a @ s - a.sum(1, keepdim=True) * q, None, None, None, None
+            return a @ s - a.sum(1, keepdim=True) * q, None, gs, None, None
         nq, ns = q.norm(dim=1, keepdim=True), s.norm(dim=1, keepdim=True).clamp_min(1e-12)
         nqc = nq.clamp_min(1e-12)
         if kid == SCORE_KINDS["hypersphere_euclidean"]:
@@ -1556,10 +1587,9 @@ class _ScoresFn(torch.autograd.Function):
         elif kid == SCORE_KINDS["cosine"]:
             gc, c = g, sc
         else:
-            scale = ctx.saved_tensors[3].float().exp()
             gc, c, gls = g * scale, sc / scale, (g * sc).sum().to(ctx.saved_tensors[3].dtype)
         through_norm = torch.where(nq > 1e-12, (gc * c).sum(1, keepdim=True), torch.zeros_like(nq))   # (the clamp passes none)
-        return (gc @ (s / ns) - through_norm * (q / nqc)) / nqc, gls, None, None, None
+        return (gc @ (s / ns) - through_norm * (q / nqc)) / nqc, gls, gs, None, None
 
 
 def _values_head_matrix(q, s, bank, vals, kind, logit_scale, logw, lo, hi, exclude):
@@ -1621,18 +1651,40 @@ def _values_support_bwd(qc, operands, values, logw, lo, hi, exclude, lse, out, g
     return gv, ga
 
 
+def _values_bank_support_bwd(qc, s_rows, operands, values, logw, lo, hi, exclude, lse, out, g, kind_id, ls, query_chunks=0):
+    """ONE call of nw_bwd_values_bank_support_f32 -> gs (N, d) fp32, the value head's gradient w.r.t. the bank rows.
+    ``s_rows``: the fp32 rows the bank's forms were prepared from, at the bank's width (read for the 2 r s term); the rest
+    as _values_query_bwd."""
+    lib = _lib.load()
+    ssplit, sscale, sn2 = operands
+    (B, d), N, Tp, dev = qc.shape, ssplit.shape[0], out.shape[1], qc.device
+    gs = torch.empty(N, d, dtype=torch.float32, device=dev)
+    ws_bytes = lib.nw_bwd_values_bank_support_workspace_bytes(B, N, d, Tp, int(query_chunks))
+    ws = _workspace(ws_bytes, dev)
+    with _OnDevice(dev):
+        _lib.check(lib.nw_bwd_values_bank_support_f32(_ptr(qc), _ptr(s_rows), _ptr(ssplit), _ptr(sscale), _ptr(sn2),
+                                                      _ptr(values.split), _ptr(values.scale), _ptr(logw), _ptr(lo), _ptr(hi),
+                                                      int(bool(exclude)), _ptr(lse), _ptr(out), _ptr(g), _ptr(gs), _ptr(ws),
+                                                      ws_bytes, B, N, d, Tp, kind_id, _ptr(ls), int(query_chunks), _stream(qc)),
+                   "nw_bwd_values_bank_support_f32")
+    return gs
+
+
 class _NWValuesBankFn(torch.autograd.Function):
     """autograd node of nw_head_values_bank on the fused route: the inference launches forward (_values_head_fwd: the lse pass,
     nw_fwd_values_f32).  Backward: ONE call of nw_bwd_values_query_f32 when the queries or a clip scale need it and, with
     ``support_grad``, ONE call of nw_bwd_values_support_f32 for the values' source tensor (3rd input) and the caller's row_logw
-    (last input), each in its dtype; when only the weights learn nothing of size N x T is allocated.  Returns the padded
-    (B, values.width) raw output; the slice to T and the logarithm are torch ops behind it.  Nothing of size B x N is saved."""
+    (11th input), each in its dtype; when only the weights learn nothing of size N x T is allocated.  With the bank rows `s`
+    as the last input, ONE call of nw_bwd_values_bank_support_f32 for them; when only the rows learn, no other call.  Returns
+    the padded (B, values.width) raw output; the slice to T and the logarithm are torch ops behind it.  Nothing of size
+    B x N is saved."""
 
     @staticmethod
-    def forward(ctx, q, logit_scale, vsrc, call, bank, values, kind_id, window, exclude, logw=None, logw_src=None):
+    def forward(ctx, q, logit_scale, vsrc, call, bank, values, kind_id, window, exclude, logw=None, logw_src=None, s=None):
         """``vsrc``: the tensor the values were prepared from when its gradient is wanted, else None; ``call``:
         _resolve_scores' _Call (``q`` is its queries, an argument of its own for autograd); ``values``: the BankValues;
-        ``window``: None or (lo, hi) int32; ``logw`` / ``logw_src``: as in _NWHeadBankFn."""
+        ``window``: None or (lo, hi) int32; ``logw`` / ``logw_src``: as in _NWHeadBankFn; ``s``: the bank rows when their
+        gradient is wanted, else None."""
         qc = _f32c(q)
         if qc.data_ptr() % 16:
             qc = qc.clone()
@@ -1642,6 +1694,8 @@ class _NWValuesBankFn(torch.autograd.Function):
         _bank_node_save(ctx, qc, lse, out, ls, window, exclude, kind_id, (call.operand, call.scale, call.norm2), bank, logw,
                         logw_src, values)
         ctx.vsrc = None if vsrc is None else (vsrc.dtype, tuple(vsrc.shape))
+        # the fp32 rows the bank's forms were prepared from, at the bank's width (read for the 2 r s term), and what `s` is
+        ctx.s_rows = None if s is None else (bank.rows if bank.rows is not None else _f32c(s), s.shape[1], s.dtype)
         return out
 
     @staticmethod
@@ -1663,7 +1717,14 @@ class _NWValuesBankFn(torch.autograd.Function):
             gv = (gv if T == Tp else gv[:, :T]).to(ctx.vsrc[0])
         if ga is not None:
             ga = ga.to(ctx.logw[1].dtype)
-        return gq, gls, gv, None, None, None, None, None, None, None, ga
+        gs = None
+        if ctx.s_rows is not None and ctx.needs_input_grad[11]:
+            s_rows, width, dtype = ctx.s_rows
+            gs = _values_bank_support_bwd(qc, s_rows, ctx.bank, ctx.values, logw, lo, hi, exclude, lse, out, g, kind_id, ls)
+            if width != gs.shape[1]:
+                gs = gs[:, :width]
+            gs = gs.to(dtype)
+        return gq, gls, gv, None, None, None, None, None, None, None, ga, gs
 
 
 def nw_head_values_bank(q, s, bank, values, kind="euclidean", logit_scale=None, row_window=None, exclude=False, row_logw=None,
@@ -1684,7 +1745,8 @@ def nw_head_values_bank(q, s, bank, values, kind="euclidean", logit_scale=None, 
     class-sorted copy, N <= 25, widths that do not pad, T > 16384) "matrix": nw_scores over the bank, + row_logw, the
     window's mask, torch.softmax and a matmul, through torch autograd and three (B, N) matrices -- no shape is refused.
 
-    Constants: `s` must not require grad (ValueError); ``values`` or ``row_logw`` that requires grad raises NWHipError (no
+    Constants: `s` must not require grad (ValueError; ``support_grad=True`` below lifts it); ``values`` or ``row_logw``
+    that requires grad raises NWHipError (no
     gradient to either is computed here: the composition nw_scores + softmax + matmul differentiates in them through the
     (B, N) matrix).  On the fused route a bank written (SplitBank.update_rows), a ``row_logw`` written in place, or a
     BankValues gone stale between forward and backward is refused at backward (RuntimeError).
@@ -1701,12 +1763,25 @@ def nw_head_values_bank(q, s, bank, values, kind="euclidean", logit_scale=None, 
     queries or the clip scale need it (gq's bits are those of the call without ``support_grad``) and ONE call of
     nw_bwd_values_support_f32, gvalues_j = sum_b W_bj gout_b and glogw_j = gvalues_j . values_j - sum_b W_bj (gout_b . out_b):
     no (B, N) buffer; when only the weights learn, nothing of size N x T either.  Matrix route: the graph tensors go through
-    the composition.  With nothing on the support side requiring grad the keyword changes nothing."""
+    the composition.  With nothing on the support side requiring grad the keyword changes nothing.
+
+    LEARNABLE BANK ROWS: with ``support_grad=True`` and ``s.requires_grad`` -- `s` still the tensor the bank
+    was prepared from -- the gradient flows to `s` as well, in its dtype (on a padded bank: the caller's columns): the keys
+    of a key-value memory, prototypes with regression targets, a condensed support set with soft labels.  Fused route: ONE
+    more call, nw_bwd_values_bank_support_f32, gs_j = sum_b A_bj q_b + 2 (sum_b r_bj) s_j with (A, r) the query gradient's
+    per-pair coefficients of dS = W (c - gout . out), recomputed tile by tile and contracted with the queries: no (B, N)
+    buffer, nothing of size N x T; a row at -inf and a row no query admits get exactly 0.  The forward and the gradients to
+    q, the clip scale, the values and row_logw are those of the call without a learnable `s`, bit for bit; when only the
+    rows learn no other backward call is made.  The accuracy note above holds for gs too.  After the optimizer wrote `s`
+    the bank must be brought up to date (``SplitBank.refresh``); a refresh or update_rows between forward and backward is
+    refused at backward (RuntimeError).  Matrix route: nw_scores differentiates in `s` too (the transposed closed forms),
+    windows and weights included.  Without the keyword an `s` that requires grad is refused as before."""
     _need_hip(q, s, logit_scale)
     if not isinstance(bank, SplitBank):
         raise TypeError("nw_head_values_bank runs over a prepared bank: pass ops.SplitBank(support)")
     grad = torch.is_grad_enabled()
-    if grad and s.requires_grad:
+    grad_s = bool(support_grad and grad and s.requires_grad)
+    if grad and s.requires_grad and not grad_s:
         raise ValueError("nw_head_values_bank: the bank is a constant here and `s` requires grad")
     raw = values if torch.is_tensor(values) else None
     grad_v = bool(grad and (raw.requires_grad if raw is not None else getattr(values, "requires_grad", False)))
@@ -1716,7 +1791,7 @@ def nw_head_values_bank(q, s, bank, values, kind="euclidean", logit_scale=None, 
                          "values or row_logw requires grad.  The composition nw_scores + softmax + matmul differentiates in them")
     if grad_v or grad_a:
         _need_hip(raw, row_logw if torch.is_tensor(row_logw) else None)
-    elif not (grad and (q.requires_grad or (logit_scale is not None and logit_scale.requires_grad))):
+    elif not (grad_s or (grad and (q.requires_grad or (logit_scale is not None and logit_scale.requires_grad)))):
         return nw_head_values(q, s, bank, values, kind, logit_scale, row_window=row_window, exclude=exclude, row_logw=row_logw,
                               log=log)
     if s.dim() != 2 or not bank.matches(s):
@@ -1748,9 +1823,11 @@ def nw_head_values_bank(q, s, bank, values, kind="euclidean", logit_scale=None, 
     route = head_values_grad_route(split=bank.split is not None, sorted_copy=bank.sorted_rows is not None, shape=bank.shape,
                                    pad=bank.pad, width=q.shape[1], B=B, T=T)
     if route == "fused":
-        call = _resolve_scores(bank, q, s)                      # (queries padded by a torch op: autograd slices gq back)
+        # (queries padded by a torch op: autograd slices gq back; the rows of the call are the bank's: a learnable `s` goes to
+        # the node as an input of its own)
+        call = _resolve_scores(bank, q, s.detach() if grad_s else s)
         out = _NWValuesBankFn.apply(call.q, logit_scale, vsrc if grad_v else None, call, bank, values, kid, window,
-                                    bool(exclude), logw, row_logw)
+                                    bool(exclude), logw, row_logw, s if grad_s else None)
         if values.width != T:
             out = out[:, :T]
     else:
@@ -1759,7 +1836,7 @@ def nw_head_values_bank(q, s, bank, values, kind="euclidean", logit_scale=None, 
         a = row_logw.float() if grad_a else logw
         if B == 0 or N == 0:     # nothing to compute: zeros, tied to whatever requires grad
             out = torch.zeros(B, T, dtype=torch.float32, device=q.device) + 0.0 * sum(
-                t.sum() for t, on in ((q, q.requires_grad), (vals, grad_v), (a, grad_a)) if on)
+                t.sum() for t, on in ((q, q.requires_grad), (vals, grad_v), (a, grad_a), (s, grad_s)) if on)
         else:
             lo, hi = window if window is not None else (None, None)
             out = _values_head_matrix(q, s, bank, vals, kind, logit_scale, a, lo, hi, bool(exclude))
